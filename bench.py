@@ -11,11 +11,12 @@ groundwater arrays.  `--config` picks the BASELINE.json configuration (default 3
   4  1e6 LHS samples x hourly 10 yr in total, sample-sharded over the N GPUs, gather of [N, 9]     strong
   5  64 synthetic catchments x 1e4 samples x hourly 10 yr in total, catchment-sharded              strong
 
-Rank 0 prints ONE JSON line; DESIGN.md section 5 explains every field.  At N = 1 the line also carries, measured in
-the same run: `parity` (GPU against the CPU oracle on the rows the cpu_baseline leg simulates anyway),
+Rank 0 prints ONE JSON line; DESIGN.md section 5 explains every field.  A plain run sets up, warms up, times the K
+steps, writes the outputs of the last step when `--dump-outputs DIR` asks for them, and prints the line.  Everything
+else is behind `--full`: `roofline`, `parity` (rows of the timed launch on every rank, and at N = 1 the rows the
+cpu_baseline leg simulates anyway, against the CPU oracle), `cpu_baseline`, `strong_1e6` and the legs --
 `flat_forcing` (the same workload with forcing that varies inside the day: the step loop instead of the interval
-engine), `objectives_only` (the same runs without the stored discharge matrix, the Monte-Carlo default) and
-`cpu_baseline`.
+engine), `objectives_only` (the same runs without the stored discharge matrix, the Monte-Carlo default) and the rest.
 """
 import argparse
 import hashlib
@@ -475,6 +476,36 @@ def daily_leg(so, n, device, steps, from_fixture=False):
     return leg
 
 
+DUMP_BYTES = {'objectives_gw': 24 * 10 ** 6, 'discharge': 40 * 10 ** 6}     # --dump-outputs: 64 MB in all at most
+DUMP_SEED = 4242
+
+
+def dump_rows(n_rows, row_bytes, max_bytes):
+    """Rows of an [n_rows, ...] output that --dump-outputs writes: all of them when they fit into max_bytes, else a fixed
+    seeded sample of as many as fit, in ascending order."""
+    keep = max_bytes // row_bytes
+    if n_rows <= keep:
+        return np.arange(n_rows)
+    return np.sort(np.random.default_rng(DUMP_SEED).choice(n_rows, size=keep, replace=False))
+
+
+def dump_outputs(out_dir, gathered, result):
+    """What the timed path handed its caller in its last step: the gathered [N, 9] (config 5: [C, N, 9], written as
+    [C * N, 9]) block of objective functions + groundwater ratio, and rank 0's stored discharge [N, R] where the launch
+    stores it -- float64, rows sampled by dump_rows() where the whole array would not fit.  -> {name: shape written}"""
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {'objectives_gw': gathered.reshape(-1, gathered.shape[-1]), 'discharge': result.discharge}
+    written = {}
+    for name, t in arrays.items():
+        if t is None:
+            continue
+        rows = dump_rows(t.shape[0], t[0].numel() * t.element_size(), DUMP_BYTES[name])
+        a = t[torch.as_tensor(rows, device=t.device)].cpu().numpy().astype(np.float64, copy=False)
+        np.save(os.path.join(out_dir, name + '.npy'), a)
+        written[name] = {'shape': list(a.shape), 'rows_of': int(t.shape[0])}
+    return written
+
+
 def timed_steps(step, n_steps, n_warmup, device):
     """W untimed steps, then K steps between barrier + synchronize on both sides.  Returns (wall seconds, max over
     ranks; mean HIP-event milliseconds of a step on the stream the kernels are launched on)."""
@@ -594,7 +625,15 @@ def main():
     ap.add_argument('--obs-from-fixture', action='store_true',
                     help='observations from tests/golden/bench_truth.npz instead of a run of the oracle (automatic when '
                          'the oracle cannot be built: a box without gcc)')
+    ap.add_argument('--full', action='store_true',
+                    help='everything beyond the headline figure: roofline, the checks against the oracle (parity), '
+                         'cpu_baseline, strong_1e6 and the legs (the --no-* options above pick among them)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the last step computed as DIR/<name>.npy (float64, 64 MB '
+                         'in all at most: a fixed seeded sample of the rows of a larger output)')
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error('--steps must be at least 1 and --warmup at least 0')
 
     if args.gpus > 1 and 'WORLD_SIZE' not in os.environ:    # started bare: this process becomes the launcher
         raise SystemExit(spawn_ranks(args.gpus, sys.argv[1:]))
@@ -626,7 +665,7 @@ def main():
         truth, obs_source = truth_discharge(so, forcing, dt, T, W, gap, hourly, args.obs_from_fixture)
         obs = synthetic_observations(truth, rng, R)
     obs = sdist.broadcast_matrix(obs if rank == 0 else np.empty(0), src=0)
-    if rank != 0:       # (behind the broadcast: rank 0 has built the library, the others only load it)
+    if rank != 0 and args.full:     # (behind the broadcast: rank 0 has built the library, the others only load it)
         so, no_oracle = load_oracle()
 
     store = not args.no_discharge and cfg in (2, 3)     # configs 4 and 5 gather objective functions only
@@ -672,18 +711,20 @@ def main():
     res = res if again is None else again
     assert bool(torch.isfinite(res[..., :7]).all())
     ranks = rank_evidence(device, launch_ms)
-    # every rank, on rows of the job it has just timed (cfg 5: four of its catchments)
-    if cfg == 5:
+    dumped = dump_outputs(args.dump_outputs, res, job.prepared.result()) if args.dump_outputs and rank == 0 else None
+    # --full: every rank, on rows of the job it has just timed (cfg 5: four of its catchments)
+    timed = {}
+    if args.full and cfg == 5:
         timed = timed_launch_parity(so, no_oracle, job, 'catchments', params, lambda c: synthetic_forcing(c, True)[0],
                                     lambda c: float(areas[c]), obs, W, gap, dt)
-    else:
+    elif args.full:
         timed = timed_launch_parity(so, no_oracle, job, 'samples', params[lo:hi] if cfg == 4 else params,
                                     lambda c: forcing, lambda c: AREA, obs, W, gap, dt)
 
     # config 4's strong-scaled figure in the same line (SURVEY.md 7.3-3 asks for both series from the driver's runs):
     # 1e6 samples IN TOTAL, cut by rows over the ranks, objective functions only, one all-gather
     strong = None
-    if cfg == 3 and not args.no_strong and args.math == 'fast':
+    if args.full and cfg == 3 and not args.no_strong and args.math == 'fast':
         n_total = 1000000
         p_all = latin_hypercube(n_total, ranges, seed=2718)
         lo, hi = sdist.shard_bounds(n_total, world, rank)
@@ -716,6 +757,30 @@ def main():
         flops_per_step = 105.0 + 121.0 * w                        # literal operation count
         bytes_per_step = (8.0 / gap * T / (W + T) if store else 0.0) + 16.0 / max(n_local, 1) \
             + (80.0 + 64.0 + 8.0) / (W + T)
+        line = {
+            'metric': 'MC sample-timesteps/sec/GPU; 1e5 LHS x hourly 10-yr forcing',
+            'value': value, 'unit': 'sample-timesteps/s', 'n_gpus': world, 'steps': args.steps,
+            'warmup': args.warmup, 'ms_per_step': elapsed / args.steps * 1e3, 'higher_is_better': True,
+            'scaling': scaling, 'vs_baseline': None, 'dtype': 'f64', 'data': 'synthetic',
+            'config': {'workload': 'configs[%d]: %s (T=%d + warm-up %d steps), summary report gap %d, objective '
+                                   'functions fused, discharge %s; forcing constant within each report interval '
+                                   '(daily values spread over the steps of the day, the reference\'s own input format)'
+                                   % (cfg - 1, what, T, W, gap, 'stored [R,N]' if store else 'not stored'),
+                       'runs_total': n_runs_total, 'runs_per_gpu': n_local, 'n_steps': T, 'n_warm': W,
+                       'math_mode': args.math, 'wet_fraction': w, 'parallelism': shard},
+            'per_gpu': value / world,
+            # which scaling series this line belongs to; north_star's ">= 7x at 8 GPUs" reads on `value` for the weak
+            # series (per-GPU work fixed) and on strong_1e6.value for the strong one (1e6 samples in total, configs[3])
+            'series': {'value': '%s: %s' % (scaling, 'configs[%d]' % (cfg - 1)),
+                       'strong_1e6': 'strong: configs[3], 1e6 samples in total over the %d GPU(s)' % world,
+                       'target': '>= 7x the n_gpus=1 figure of the same series at n_gpus=8 (BASELINE.json north_star)'},
+            'ranks': ranks,
+            # SURVEY.md 8(d): the same rate counting the simulated steps only (the warm-up replays W of them)
+            'value_without_warmup': n_runs_total * T * args.steps / elapsed,
+        }
+        if dumped is not None:
+            line['outputs'] = dumped
+    if rank == 0 and args.full:
         kern_s = launch_ms * 1e-3
         kernels = job.prepared.describe()
         pmc_key = 'config%d:runs_per_gpu=%d:discharge=%d:math=%s' % (cfg, n_local, int(store), args.math)
@@ -787,28 +852,7 @@ def main():
                     'frac': units_per_launch * bytes_per_step / kern_s / 1e9 / HBM_PEAK_GBS,
                     'bytes_per_sample_step': bytes_per_step},
         }
-        line = {
-            'metric': 'MC sample-timesteps/sec/GPU; 1e5 LHS x hourly 10-yr forcing',
-            'value': value, 'unit': 'sample-timesteps/s', 'n_gpus': world, 'steps': args.steps,
-            'warmup': args.warmup, 'ms_per_step': elapsed / args.steps * 1e3, 'higher_is_better': True,
-            'scaling': scaling, 'vs_baseline': None, 'dtype': 'f64', 'data': 'synthetic',
-            'config': {'workload': 'configs[%d]: %s (T=%d + warm-up %d steps), summary report gap %d, objective '
-                                   'functions fused, discharge %s; forcing constant within each report interval '
-                                   '(daily values spread over the steps of the day, the reference\'s own input format)'
-                                   % (cfg - 1, what, T, W, gap, 'stored [R,N]' if store else 'not stored'),
-                       'runs_total': n_runs_total, 'runs_per_gpu': n_local, 'n_steps': T, 'n_warm': W,
-                       'math_mode': args.math, 'wet_fraction': w, 'parallelism': shard},
-            'per_gpu': value / world,
-            # which scaling series this line belongs to; north_star's ">= 7x at 8 GPUs" reads on `value` for the weak
-            # series (per-GPU work fixed) and on strong_1e6.value for the strong one (1e6 samples in total, configs[3])
-            'series': {'value': '%s: %s' % (scaling, 'configs[%d]' % (cfg - 1)),
-                       'strong_1e6': 'strong: configs[3], 1e6 samples in total over the %d GPU(s)' % world,
-                       'target': '>= 7x the n_gpus=1 figure of the same series at n_gpus=8 (BASELINE.json north_star)'},
-            'ranks': ranks,
-            # SURVEY.md 8(d): the same rate counting the simulated steps only (the warm-up replays W of them)
-            'value_without_warmup': n_runs_total * T * args.steps / elapsed,
-            'roofline': roofline,
-        }
+        line['roofline'] = roofline
         if world == 1 and cfg in (3, 4) and not args.no_flat and args.math == 'fast':
             # the same workload with forcing that varies inside the report interval: the step loop (smart_fast_steps)
             vary = hourly_varying_forcing(forcing)
@@ -878,7 +922,6 @@ def main():
             line.update(api_legs(forcing, obs, WARM_DAYS, device))
         if world == 1 and cfg == 3 and not args.no_daily and not args.no_flat and args.math == 'fast':
             line['daily_1e6'] = daily_leg(so, 1000000, device, max(2, args.steps // 4), args.obs_from_fixture)
-        line['observations'] = obs_source
         if args.no_cpu_baseline:
             line['parity'] = dict(timed)
         elif so is None:
@@ -888,7 +931,10 @@ def main():
             # rank 0's host cores and rank 0's GPU, whatever the world size
             line['cpu_baseline'], line['parity'] = cpu_baseline_and_parity(so, forcing, W, gap, dt, device)
             line['parity'].update(timed)
+    if rank == 0:
+        line['observations'] = obs_source
         print(json.dumps(line), flush=True)
+    if rank == 0 and args.full:
         bad = [k for k in ('ok',) if line['parity'].get(k) is False]
         if line['parity'].get('timed_launch') and not line['parity']['timed_launch']['ok']:
             bad.append('timed_launch')

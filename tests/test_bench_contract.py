@@ -97,8 +97,8 @@ def test_bench_bare_command_with_two_gpus_spawns_two_ranks():
 
 @pytest.mark.gpu
 def test_bench_prints_one_json_line_with_the_contract_fields():
-    out = subprocess.check_output([sys.executable, os.path.join(ROOT, 'bench.py'), '--steps', '2', '--warmup', '1',
-                                   '--samples', '20000'], cwd=ROOT, stderr=subprocess.DEVNULL).decode()
+    out = subprocess.check_output([sys.executable, os.path.join(ROOT, 'bench.py'), '--full', '--steps', '2', '--warmup',
+                                   '1', '--samples', '20000'], cwd=ROOT, stderr=subprocess.DEVNULL).decode()
     lines = [ln for ln in out.splitlines() if ln.startswith('{')]
     assert len(lines) == 1
     d = json.loads(lines[0])
@@ -150,6 +150,56 @@ def test_bench_prints_one_json_line_with_the_contract_fields():
     assert d['value'] > 50 * c['value']          # sanity: the GPU path is orders of magnitude ahead of the host cores
 
 
+def test_dump_rows_are_all_rows_or_a_fixed_sample_within_the_budget():
+    """--dump-outputs: an output that fits is written whole; a larger one as the same seeded rows in every run."""
+    import bench
+    assert np.array_equal(bench.dump_rows(100, 72, 7200), np.arange(100))
+    rows = bench.dump_rows(1000000, 72, bench.DUMP_BYTES['objectives_gw'])
+    assert len(rows) * 72 <= bench.DUMP_BYTES['objectives_gw'] and np.all(np.diff(rows) > 0) and rows[-1] < 1000000
+    assert np.array_equal(rows, bench.dump_rows(1000000, 72, bench.DUMP_BYTES['objectives_gw']))
+    assert sum(bench.DUMP_BYTES.values()) <= 64 * 10 ** 6
+
+
+@pytest.mark.gpu
+def test_a_plain_run_prints_the_headline_only_and_dumps_what_the_last_step_computed(tmp_path):
+    """Without --full: the headline figure and nothing that needs runs or checks of its own.  --dump-outputs DIR: the
+    gathered objective functions + groundwater ratios of every run and a seeded sample of the stored discharge rows,
+    float64, 64 MB at most -- the discharge rows are the oracle's within the bench's parity gate."""
+    out_dir = tmp_path / 'outputs'
+    out = subprocess.check_output([sys.executable, os.path.join(ROOT, 'bench.py'), '--steps', '3', '--warmup', '1',
+                                   '--samples', '20000', '--dump-outputs', str(out_dir)], cwd=ROOT,
+                                  stderr=subprocess.DEVNULL).decode()
+    lines = [ln for ln in out.splitlines() if ln.startswith('{')]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    assert d['steps'] == 3 and d['warmup'] == 1 and d['dtype'] == 'f64' and d['higher_is_better'] is True
+    assert d['unit'] == 'sample-timesteps/s' and d['metric'].startswith('MC sample-timesteps/sec/GPU')
+    assert abs(d['value'] - 20000 * 96432 / (d['ms_per_step'] * 1e-3)) < 1e-6 * d['value']
+    for key in ('roofline', 'parity', 'cpu_baseline', 'strong_1e6', 'flat_forcing', 'objectives_only', 'daily_1e6',
+                'simulate_ms'):
+        assert key not in d, key
+    files = sorted(os.listdir(out_dir))
+    assert files == ['discharge.npy', 'objectives_gw.npy']
+    assert sum(os.path.getsize(out_dir / f) for f in files) <= 64 * 10 ** 6
+    fn, dis = np.load(out_dir / 'objectives_gw.npy'), np.load(out_dir / 'discharge.npy')
+    assert fn.dtype == dis.dtype == np.float64 and fn.shape == (20000, 9) and np.isfinite(fn[:, :7]).all()
+    import bench
+    rows = bench.dump_rows(20000, 3653 * 8, bench.DUMP_BYTES['discharge'])
+    assert dis.shape == (len(rows), 3653) and d['outputs']['discharge'] == {'shape': list(dis.shape), 'rows_of': 20000}
+    from oracle import smart_oracle as so
+    from smartpy_amd.parameters import Parameters
+    from smartpy_amd.sampling import latin_hypercube
+    forcing, _ = bench.synthetic_forcing(0, hourly=True)
+    params = latin_hypercube(20000, Parameters().ranges, seed=2718)
+    pick = rows[::max(1, len(rows) // 4)][:4]
+    want, want_gw, _ = so.run_batch(bench.AREA, 3600.0, forcing.shape[0], 8760, np.ascontiguousarray(forcing[:, 0]),
+                                    np.ascontiguousarray(forcing[:, 1]), np.ascontiguousarray(params[pick]), bench.EXTRA,
+                                    so.REPORT_SUMMARY, 24, want_discharge=True)
+    got = dis[np.searchsorted(rows, pick)]
+    assert np.max(np.abs(got - want) / np.maximum(np.abs(want), 1e-300)) <= bench.PARITY_GATE
+    assert np.max(np.abs(fn[pick, 8] - want_gw)) <= bench.PARITY_GATE
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize('config, samples', [(3, 20000), (4, 40000), (5, 1000)])
 def test_bench_with_two_ranks_launched_the_way_the_driver_does(config, samples):
@@ -163,8 +213,8 @@ def test_bench_with_two_ranks_launched_the_way_the_driver_does(config, samples):
     env = dict(os.environ, SMART_DIST_BACKEND='gloo')
     out = subprocess.check_output(
         [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '2', '--master-addr',
-         '127.0.0.1', '--master-port', str(port), os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--steps', '2',
-         '--warmup', '1', '--config', str(config), '--samples', str(samples), '--no-flat'] +
+         '127.0.0.1', '--master-port', str(port), os.path.join(ROOT, 'bench.py'), '--full', '--gpus', '2', '--steps',
+         '2', '--warmup', '1', '--config', str(config), '--samples', str(samples), '--no-flat'] +
         ([] if config == 3 else ['--no-cpu-baseline']),       # config 3: the whole line, cpu_baseline and parity included
         cwd=ROOT, env=env, stderr=subprocess.DEVNULL, timeout=900).decode()
     lines = [ln for ln in out.splitlines() if ln.startswith('{')]
@@ -213,8 +263,8 @@ def test_bench_with_eight_ranks_launched_the_way_the_driver_does(config, samples
     env = {k: v for k, v in os.environ.items() if k != 'SMART_DIST_BACKEND'}
     out = subprocess.check_output(
         [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '8', '--master-addr',
-         '127.0.0.1', '--master-port', str(port), os.path.join(ROOT, 'bench.py'), '--gpus', '8', '--steps', '2',
-         '--warmup', '1', '--config', str(config), '--samples', str(samples), '--no-flat', '--no-strong',
+         '127.0.0.1', '--master-port', str(port), os.path.join(ROOT, 'bench.py'), '--full', '--gpus', '8', '--steps',
+         '2', '--warmup', '1', '--config', str(config), '--samples', str(samples), '--no-flat', '--no-strong',
          '--no-cpu-baseline'], cwd=ROOT, env=env, stderr=subprocess.DEVNULL, timeout=1200).decode()
     lines = [ln for ln in out.splitlines() if ln.startswith('{')]
     assert len(lines) == 1
@@ -244,8 +294,8 @@ def test_bench_without_a_checker_still_prints_its_line():
     """A box without gcc and without a built oracle (round 5: no line at all): the observations come from the committed
     fixture, the throughput line stands, `cpu_baseline` and `parity.timed_launch` are null with the reason."""
     env = dict(os.environ, SMART_BENCH_NO_ORACLE='1')
-    out = subprocess.check_output([sys.executable, os.path.join(ROOT, 'bench.py'), '--steps', '2', '--warmup', '1',
-                                   '--samples', '20000', '--no-flat', '--no-strong'], cwd=ROOT, env=env,
+    out = subprocess.check_output([sys.executable, os.path.join(ROOT, 'bench.py'), '--full', '--steps', '2', '--warmup',
+                                   '1', '--samples', '20000', '--no-flat', '--no-strong'], cwd=ROOT, env=env,
                                   stderr=subprocess.DEVNULL).decode()
     d = json.loads([ln for ln in out.splitlines() if ln.startswith('{')][0])
     assert d['value'] > 1e11 and d['cpu_baseline'] is None and d['observations'].startswith('fixture')

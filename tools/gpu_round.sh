@@ -35,6 +35,7 @@ suite)
     timeout 3000 python -m pytest tests -m gpu -x -q > gpurun_out/suite_pytest.log 2>&1; tail -15 gpurun_out/suite_pytest.log
     ;;
 bench)
+    set -- --full "$@"      # the digest reads the legs
     python bench.py --steps 20 --warmup 5 "$@" > gpurun_out/bench_round.log 2>&1
     grep '^{' gpurun_out/bench_round.log | python tools/bench_digest.py
     ;;
@@ -60,7 +61,7 @@ soak)
 slices) # slice counts at the loads where the hand-over is the only HBM traffic (configs 4 and 5 on one GPU)
     for cfg in 4 5; do for rep in 1 2; do for k in default 4 8 16; do
         if [ $k = default ]; then unset SMART_TIME_SLICES; else export SMART_TIME_SLICES=$k; fi
-        echo -n "config $cfg slices $k: "; timeout 600 python bench.py --config $cfg --steps 4 --warmup 1 --no-cpu-baseline --no-flat 2>/dev/null | tail -1 | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('%.3f ms  %s' % (d['roofline']['launch_ms'], d['roofline']['kernel']))"
+        echo -n "config $cfg slices $k: "; timeout 600 python bench.py --full --config $cfg --steps 4 --warmup 1 --no-cpu-baseline --no-flat 2>/dev/null | tail -1 | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('%.3f ms  %s' % (d['roofline']['launch_ms'], d['roofline']['kernel']))"
     done; done; done 2>&1 | tee gpurun_out/slices_round.log
     ;;
 final)
@@ -107,14 +108,14 @@ slices-flat)
     ;;
 slices-headline)
     for rep in 1 2; do for k in 12 16 20 24 32; do
-      echo -n "headline slices $k: "; SMART_TIME_SLICES=$k python bench.py --steps 12 --warmup 3 --no-cpu-baseline --no-flat --no-strong 2>/dev/null | tail -1 | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('%.3f ms' % d['roofline']['launch_ms'])"
+      echo -n "headline slices $k: "; SMART_TIME_SLICES=$k python bench.py --full --steps 12 --warmup 3 --no-cpu-baseline --no-flat --no-strong 2>/dev/null | tail -1 | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('%.3f ms' % d['roofline']['launch_ms'])"
       echo -n "runs6 slices $k: "; SMART_TIME_SLICES=$k python tools/debug/runs_only.py 100000 6 2>/dev/null | grep " ms" | sort -n | head -3 | tr '\n' ' '; echo
     done; done 2>&1 | tee gpurun_out/slices_headline.log
     ;;
 slices-legs)
     for rep in 1 2 3; do for k in default 16; do
       if [ $k = default ]; then unset SMART_TIME_SLICES; else export SMART_TIME_SLICES=$k; fi
-      echo -n "slices $k: "; python bench.py --steps 10 --warmup 2 --no-cpu-baseline --no-strong 2>/dev/null | tail -1 | python tools/bench_digest.py | grep " ms" | awk '{printf "%s %s | ", $1, $2}'; echo
+      echo -n "slices $k: "; python bench.py --full --steps 10 --warmup 2 --no-cpu-baseline --no-strong 2>/dev/null | tail -1 | python tools/bench_digest.py | grep " ms" | awk '{printf "%s %s | ", $1, $2}'; echo
     done; done 2>&1 | tee gpurun_out/slices_ab.log
     ;;
 phases-every)
@@ -128,7 +129,7 @@ phases-every)
 turns)
     for rep in 1 2 3 4; do for f in default $(ls tools/variants/libsmart_amd_*.so); do
       if [ $f = default ]; then unset SMART_AMD_LIB; else export SMART_AMD_LIB=$PWD/$f; fi
-      echo -n "$(basename $f .so | sed s/libsmart_amd_//): "; python bench.py --steps 12 --warmup 3 --no-cpu-baseline --no-strong 2>/dev/null | tail -1 | python tools/bench_digest.py | grep " ms" | awk '{printf "%s %s | ", $1, $2}'; echo
+      echo -n "$(basename $f .so | sed s/libsmart_amd_//): "; python bench.py --full --steps 12 --warmup 3 --no-cpu-baseline --no-strong 2>/dev/null | tail -1 | python tools/bench_digest.py | grep " ms" | awk '{printf "%s %s | ", $1, $2}'; echo
     done; done 2>&1 | tee gpurun_out/wet_ab.log
     ;;
 icache) # instruction-cache requests / misses of the time-loop kernels (the pair blocks are 84 KB of code an instance)

@@ -2,7 +2,7 @@
 # rocprofv3 evidence for the bench command: kernel-trace stats, then PMC passes (each in its own run).
 # usage: bash tools/profile.sh <tag> [bench args...]
 TAG=${1:-r01}; shift
-ARGS=${@:---steps 20 --warmup 5 --no-cpu-baseline --no-flat}     # the driver's own K / W
+ARGS=${@:---full --steps 20 --warmup 5 --no-cpu-baseline --no-flat}     # the driver's own K / W
 export TMPDIR=/tmp
 OUT=$PWD/gpurun_out/prof_$TAG
 mkdir -p $OUT
