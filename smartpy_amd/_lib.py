@@ -4,6 +4,7 @@ The library is the product: there is no CPU fallback.  If the shared object is m
 cannot be loaded, importing the engine fails loudly with instructions, and every compute entry point
 returns SMART_E_NO_DEVICE when no HIP device is visible.
 """
+import contextlib
 import ctypes
 import os
 
@@ -89,36 +90,21 @@ def _apply_lint_verdict():
     stands (A/B builds: tools/variants)."""
     import warnings
     from . import isa_lint
-    ok, pairs, reason = isa_lint.verdict_for(LIB_PATH)
-    unrecorded = isa_lint.read_sidecar(LIB_PATH) is None or 'another build' in reason
-    if ok and not pairs and unrecorded and os.path.exists(isa_lint.OBJDUMP):
+    report = None
+    if isa_lint.record_state(LIB_PATH) != 'this-build' and os.path.exists(isa_lint.OBJDUMP):
         # no record, or one for another file (a library that travelled without it, or was rebuilt by something else): look
         # at the code now (~6 s) and leave the record for the next load.  ONE process of a job does it -- the others wait
-        # at the lock and read what it wrote (round 5: the N ranks of a launch each disassembled the library: advisor)
-        lock = None
-        try:
-            import fcntl
-            lock = open(LIB_PATH + '.lint.lock', 'w')
-            fcntl.flock(lock, fcntl.LOCK_EX)
-        except (ImportError, OSError):
-            lock = None         # (a read-only tree: every process looks for itself, as before)
-        try:
-            ok, pairs, reason = isa_lint.verdict_for(LIB_PATH)
-            if ok and not pairs and (isa_lint.read_sidecar(LIB_PATH) is None or 'another build' in reason):
-                report = isa_lint.check_library(LIB_PATH)
-                report['stamp'] = isa_lint.library_stamp(LIB_PATH)
-                try:
-                    isa_lint.write_sidecar(report, LIB_PATH)
-                except OSError:
-                    pass
-                if report['checked']:
-                    if report['handover'] is False or report['rows'] is False:
-                        ok, pairs, reason = False, False, '; '.join(report['problems'])
-                    else:
-                        ok, pairs, reason = True, bool(report['pair_blocks']), '; '.join(report['problems'])
-        finally:
-            if lock is not None:
-                lock.close()
+        # at the lock and read what it wrote
+        with contextlib.ExitStack() as held:
+            try:
+                import fcntl
+                fcntl.flock(held.enter_context(open(LIB_PATH + '.lint.lock', 'w')), fcntl.LOCK_EX)
+            except (ImportError, OSError):
+                pass            # (a read-only tree: every process looks for itself)
+            if isa_lint.record_state(LIB_PATH) != 'this-build':
+                report = isa_lint.lint_and_record(LIB_PATH)
+    # (the report in hand rather than the record: in a read-only tree none was written)
+    ok, pairs, reason = isa_lint.verdict_of(report, report['sha256']) if report else isa_lint.verdict_for(LIB_PATH)
     if not ok:
         raise ImportError("smartpy_amd: %s failed the code lints of smartpy_amd.isa_lint (%s); rebuild it with "
                           "`python -m smartpy_amd.build --force`" % (LIB_PATH, reason))

@@ -65,40 +65,23 @@ def build(force=False, verbose=False, extra_flags=(), lib_path=LIB):
                 print(' '.join(cmd))
         with ThreadPoolExecutor(max_workers=min(len(jobs), os.cpu_count() or 1)) as pool:
             list(pool.map(subprocess.check_call, jobs))
-    if force or _stale(lib_path, objs):
-        # linked under a name of this process's own, then renamed onto the library: a process that loads it meanwhile sees
-        # the old file or the new one, never half of one
-        tmp = '%s.%d.tmp' % (lib_path, os.getpid())
-        cmd = [cc, '-shared', '-fPIC', '-pthread', '--offload-arch=' + ARCH, '-o', tmp] + objs
-        if verbose:
-            print(' '.join(cmd))
-        try:
-            subprocess.check_call(cmd)
-            from . import isa_lint
-            report = lint(tmp, verbose)
-            # the verdict on the pair blocks goes INTO the file (a caller of the C ABI reads no record next to it), then
-            # the record is written for the file as it now is
-            isa_lint.stamp_library(tmp, bool(report['pair_blocks']))
-            report['sha256'] = isa_lint.sha256_of(tmp)
-            report['stamp'] = isa_lint.library_stamp(tmp)
-            os.replace(tmp, lib_path)
-            isa_lint.write_sidecar(report, lib_path)
-        finally:
-            if os.path.exists(tmp):
-                os.remove(tmp)
-    elif lint_missing(lib_path):
-        # a library without a record of its own (copied here, or its record lost): looked at now, stamped in a copy that
-        # then takes its place (a process that has the old file loaded keeps it)
-        from . import isa_lint
-        report = lint(lib_path, verbose)
+    from . import isa_lint
+    relink = force or _stale(lib_path, objs)
+    if relink or isa_lint.record_state(lib_path) != 'this-build':
+        # linked (or, for a library without a record of its own -- copied here, or its record lost -- copied) under a name
+        # of this process's own, looked at, stamped with the verdict on its pair blocks, then renamed onto the library: a
+        # process that loads it meanwhile sees the old file or the new one, never half of one
         tmp = '%s.%d.tmp' % (lib_path, os.getpid())
         try:
-            shutil.copy(lib_path, tmp)
-            isa_lint.stamp_library(tmp, bool(report['pair_blocks']))
-            report['sha256'] = isa_lint.sha256_of(tmp)
-            report['stamp'] = isa_lint.library_stamp(tmp)
+            if relink:
+                cmd = [cc, '-shared', '-fPIC', '-pthread', '--offload-arch=' + ARCH, '-o', tmp] + objs
+                if verbose:
+                    print(' '.join(cmd))
+                subprocess.check_call(cmd)
+            else:
+                shutil.copy(lib_path, tmp)
+            isa_lint.lint_and_record(tmp, record_for=lib_path, stamp=True, check=lambda path: lint(path, verbose))
             os.replace(tmp, lib_path)
-            isa_lint.write_sidecar(report, lib_path)
         finally:
             if os.path.exists(tmp):
                 os.remove(tmp)
@@ -107,12 +90,6 @@ def build(force=False, verbose=False, extra_flags=(), lib_path=LIB):
 
 class BuildLintError(RuntimeError):
     pass
-
-
-def lint_missing(lib_path):
-    from . import isa_lint
-    rep = isa_lint.read_sidecar(lib_path)
-    return rep is None or rep.get('sha256') != isa_lint.sha256_of(lib_path)
 
 
 def lint(path, verbose=False):

@@ -10,13 +10,13 @@ correctness rests on where hipcc's assembler put an instruction.
                 hipcc's hazard recogniser, so the two wait states gfx950 wants between a vector write of a register
                 and a DPP read of it are the source's own business
 
-Round 4 ran the first two from the test suite only.  Now smartpy_amd.build runs all three on every library it links
-(check_library) and writes the outcome next to it (<lib>.lint.json, with `hipcc --version` and the library's
-sha256); smartpy_amd._lib reads that file when it loads the library: a library whose pair blocks failed the lint -- or
-that is not the one the lint looked at, e.g. rebuilt by another hipcc on another box -- runs the threaded chunks
-(SMART_PAIR_BLOCKS=0: the same arithmetic without computed jumps) behind a warning; a library whose hand-over or row
-chains failed is refused.  The tests (tests/test_pair_blocks_isa.py, test_handover_isa.py, test_lanes_isa.py) call
-the same functions.
+smartpy_amd.build runs all three on every library it links (lint_and_record): the verdict on the pair blocks goes into
+the file itself (stamp_library) and the whole outcome next to it (<lib>.lint.json, with `hipcc --version` and the
+library's sha256).  smartpy_amd._lib reads that record when it loads the library: a library whose pair blocks failed
+the lint -- or that is not the one the lint looked at, e.g. rebuilt by another hipcc on another box -- runs the threaded
+chunks (SMART_PAIR_BLOCKS=0: the same arithmetic without computed jumps) behind a warning; a library whose hand-over
+or row chains failed is refused.  The tests (tests/test_pair_blocks_isa.py, test_handover_isa.py, test_lanes_isa.py)
+call the same functions.
 
 llvm-objdump of the ROCm toolchain is needed; without it check_library() says so and nothing is claimed.
 """
@@ -25,14 +25,13 @@ import json
 import os
 import re
 import shutil
+import struct
 import subprocess
 import tempfile
 
 
-
 def _find_objdump():
-    """llvm-objdump of the ROCm toolchain: $ROCM_PATH, the usual place, or whatever the PATH holds (round 5 knew one
-    hard-coded path: advisor)."""
+    """llvm-objdump of the ROCm toolchain: $ROCM_PATH, the usual place, or whatever the PATH holds"""
     roots = [os.environ.get('ROCM_PATH'), os.environ.get('ROCM_HOME'), '/opt/rocm']
     for root in roots:
         if root:
@@ -44,32 +43,60 @@ def _find_objdump():
 
 OBJDUMP = _find_objdump()
 
+# smart_capi.hip: the exported `char smart_lint_stamp[40]`.  The verdict on the pair blocks is written INTO the library
+# file there: a caller of the C ABI, who reads no record next to it, gets the computed jumps only from code that was looked at
+STAMP_SYMBOL, STAMP_SIZE = b'smart_lint_stamp', 40
 STAMP_UNCHECKED = b'SMART_LINT_STAMP=unchecked'
-STAMP_PAIRS_OK = b'SMART_LINT_STAMP=pairs-ok\0'          # (same length: written over the other in the file)
+STAMP_PAIRS_OK = b'SMART_LINT_STAMP=pairs-ok\0'          # (same length: the one written over the other)
 
 
-def stamp_library(path, pairs_ok):
-    """The lint's verdict on the pair blocks INTO the library file (smart_capi.hip: smart_lint_stamp), so that a caller of
-    the C ABI who never sees the record next to the file gets the computed jumps only from a library whose code was looked
-    at.  -> True if the stamp was found (once) and written."""
+def _stamp_offset(path):
+    """Where in the file smart_lint_stamp lies, by the dynamic symbol table of an ELF64 little-endian library (None for
+    any other file, and without the symbol).  Its text is NOT searched for: the same text may stand elsewhere in the
+    image, as a constant of the code that compares it."""
     with open(path, 'rb') as fh:
         blob = fh.read()
-    assert len(STAMP_PAIRS_OK) == len(STAMP_UNCHECKED)
-    if blob.count(STAMP_UNCHECKED) != 1:
-        return False
-    if pairs_ok:
-        with open(path, 'wb') as fh:
-            fh.write(blob.replace(STAMP_UNCHECKED, STAMP_PAIRS_OK))
-    return True
+    try:
+        if blob[:6] != b'\x7fELF\x02\x01':
+            return None
+        shoff, = struct.unpack_from('<Q', blob, 0x28)
+        shentsize, shnum = struct.unpack_from('<HH', blob, 0x3a)
+        # (name, type, flags, addr, offset, size, link, info, addralign, entsize) of every section
+        sections = [struct.unpack_from('<IIQQQQIIQQ', blob, shoff + i * shentsize) for i in range(shnum)]
+        for _, _, _, _, offset, size, link, _, _, entsize in [sec for sec in sections if sec[1] == 11]:     # SHT_DYNSYM
+            strings = sections[link][4]
+            for sym in range(offset, offset + size, entsize):
+                name, _, _, shndx, value, length = struct.unpack_from('<IBBHQQ', blob, sym)
+                if blob[strings + name:blob.index(b'\0', strings + name)] == STAMP_SYMBOL and length == STAMP_SIZE:
+                    at = value - sections[shndx][3] + sections[shndx][4]
+                    return at if 0 <= at <= len(blob) - STAMP_SIZE else None
+    except (struct.error, ValueError, IndexError):
+        pass                        # (a truncated or doctored file)
+    return None
 
 
 def library_stamp(path):
     """'pairs-ok' | 'unchecked' | None (no stamp in the file)"""
+    at = _stamp_offset(path)
+    if at is None:
+        return None
     with open(path, 'rb') as fh:
-        blob = fh.read()
-    if STAMP_PAIRS_OK.rstrip(b'\0') in blob:
-        return 'pairs-ok'
-    return 'unchecked' if STAMP_UNCHECKED in blob else None
+        fh.seek(at)
+        text = fh.read(STAMP_SIZE).split(b'\0')[0]
+    return {STAMP_PAIRS_OK.rstrip(b'\0'): 'pairs-ok', STAMP_UNCHECKED: 'unchecked'}.get(text)
+
+
+def stamp_library(path, pairs_ok):
+    """Write the verdict on the pair blocks into the library file, whatever stood there.  -> was the stamp found?"""
+    at = _stamp_offset(path)
+    if at is None:
+        return False
+    with open(path, 'r+b') as fh:
+        fh.seek(at)
+        fh.write((STAMP_PAIRS_OK if pairs_ok else STAMP_UNCHECKED).ljust(STAMP_SIZE, b'\0'))
+    return True
+
+
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB = os.path.join(HERE, 'csrc', 'libsmart_amd.so')
 FP64 = ('v_fma_f64', 'v_fmac_f64', 'v_add_f64', 'v_mul_f64', 'v_min_f64', 'v_max_f64', 'v_ldexp_f64')
@@ -82,6 +109,7 @@ ROWS = ['smart_fast_illcond', 'smart_ensemble_literal_rows']
 
 KINDS = 'CDR'          # smart_device.h: step_kind -- 0 calm, 1 dry, 2 rain
 FIRST = {'C': 'v_cmp_lt_f64', 'D': 'v_mul_f64', 'R': 'v_mov_b64'}      # how the three arms begin
+PAIRS = [k0 + k1 for k0 in KINDS for k1 in KINDS]       # a pair of steps: the nine patterns, in the order of their blocks
 
 
 class LintError(Exception):
@@ -195,10 +223,37 @@ def _entries(insts):
     return [i for i, x in enumerate(insts) if x['op'] == 's_getpc_b64' and 's[78:79]' in x['args']]
 
 
-def _check_pair_instance(insts, at, i, stride):
+def _walk_blocks(insts, i, stride, names, count, what='block'):
+    """The blocks of the streaming loop behind the entry at instruction i: block n, `stride` bytes behind block n - 1, runs
+    steps of the kinds names[n].  Each must be what the code words assume: it starts on an instruction -- a block that
+    begins with the rain arm is entered 4 bytes in (pair_code adds 4), so an s_nop stands on its boundary --, with the
+    first instruction of its first arm, and its main path reaches the computed jump inside its room.  Yields, per block,
+    (n, names[n], index of its s_setpc_b64, {prefix: instructions of the main path that begin with it} for `count`)."""
+    at = {x['addr']: k for k, x in enumerate(insts)}
+    base = _block_base(insts, i)
+    _need(base % 64 == 0, '%s 0 at %#x is not on a 64-byte line' % (what, base))
+    for n, kinds in enumerate(names):
+        where, b = '%s %d (%s)' % (what, n, kinds), base + n * stride
+        _need(b in at, '%s does not start on an instruction' % where)
+        k = at[b]
+        if kinds[0] == 'R':
+            _need(insts[k]['op'] == 's_nop' and insts[k]['size'] == 4, '%s: no s_nop on the boundary' % where)
+            k += 1
+        _need(insts[k]['op'].startswith(FIRST[kinds[0]]), '%s begins with %s' % (where, insts[k]['op']))
+        seen = dict.fromkeys(count, 0)
+        while insts[k]['op'] != 's_setpc_b64':
+            _need(insts[k]['addr'] < b + stride, '%s outgrew its %d bytes' % (where, stride))
+            for prefix in count:
+                seen[prefix] += insts[k]['op'].startswith(prefix)
+            k += 1
+        yield n, kinds, k, seen
+
+
+def _check_pair_instance(insts, i, stride):
+    """SMART_A_PAIRS_STRETCH: 36 pair blocks (buffer 0: first pair, second pair; buffer 1: first, second; nine patterns
+    each), then 4 of a whole chunk (four calm, four dry steps; per buffer)"""
     _need(insts[i + 1]['op'] == 's_add_u32' and insts[i + 1]['args'].startswith('s78, s78,'), 'entry without its s_add_u32')
     base = _block_base(insts, i)
-    _need(base % 64 == 0, 'block 0 at %#x is not on a 64-byte line' % base)
     # the entry (the second form has two: a stretch may start in either buffer) ends with the jump to the first block,
     # nothing falls into the blocks
     j, last = i, insts[i]
@@ -209,66 +264,29 @@ def _check_pair_instance(insts, at, i, stride):
         j -= 1
         last = insts[j - 1]
     _need(last['op'] == 's_setpc_b64', 'the entry falls into block 0 (%s in front of it)' % last['op'])
-
-    def block(n, names, tail_loads):
-        b = base + n * stride
-        _need(b in at, 'block %d does not start on an instruction' % n)
-        k = at[b]
-        if names[0] == 'R':         # entered 4 bytes in (pair_code adds 4): an s_nop on the boundary
-            _need(insts[k]['op'] == 's_nop' and insts[k]['size'] == 4, 'block %d (%s): no s_nop on the boundary' % (n, names))
-            k += 1
-        _need(insts[k]['op'].startswith(FIRST[names[0]]), 'block %d (%s) begins with %s' % (n, names, insts[k]['op']))
-        loads = 0
-        while insts[k]['op'] != 's_setpc_b64':          # the main path: up to the computed jump
-            _need(insts[k]['addr'] < b + stride, 'block %d (%s) outgrew its %d bytes' % (n, names, stride))
-            loads += insts[k]['op'].startswith('s_load_dwordx16')
-            k += 1
-        _need(insts[k]['args'].strip() == 's[76:77]', 'block %d (%s): jump through %s' % (n, names, insts[k]['args']))
-        _need(loads == tail_loads, 'block %d (%s) requests %d chunks' % (n, names, loads))
+    for n, kinds, k, seen in _walk_blocks(insts, i, stride, PAIRS * 4 + ['CCCC', 'DDDD'] * 2, ('s_load_dwordx16',)):
+        _need(insts[k]['args'].strip() == 's[76:77]', 'block %d (%s): jump through %s' % (n, kinds, insts[k]['args']))
+        # a first pair's tail requests nothing; a second pair's, and a whole chunk's, the chunk after next
+        _need(seen['s_load_dwordx16'] == (n // 9 % 2 if n < 36 else 1),
+              'block %d (%s) requests %d chunks' % (n, kinds, seen['s_load_dwordx16']))
         # what follows the jump (out-of-line cascades) stays inside the block's room and ends with a branch back
+        room = base + (n + 1) * stride
         end = insts[k]['addr'] + 4
         m = k + 1
-        while m < len(insts) and insts[m]['addr'] < b + stride:
+        while m < len(insts) and insts[m]['addr'] < room:
             if insts[m]['op'].startswith(('v_', 's_branch', 's_cbranch')):
                 end = insts[m]['addr'] + insts[m]['size']
             m += 1
-        _need(end <= b + stride or n == 39, 'block %d (%s): its out-of-line code outgrew the room' % (n, names))
-
-    n = 0
-    for pos in range(4):                    # buffer 0: first pair, second pair; buffer 1: first, second
-        for k0 in KINDS:
-            for k1 in KINDS:
-                block(n, k0 + k1, tail_loads=pos % 2)       # the second pair's tail requests the chunk after next
-                n += 1
-    for _ in range(2):                      # whole chunks: four calm, four dry steps
-        for k0 in 'CD':
-            block(n, k0 * 4, tail_loads=1)
-            n += 1
+        _need(end <= room or n == 39, 'block %d (%s): its out-of-line code outgrew the room' % (n, kinds))
 
 
-def _check_gap_stream(insts, at, i, stride):
-    """54 blocks: 2 buffers x 3 variants (no report in the pair / behind its first arm / behind its second) x 9 patterns;
-    every main path ends with the computed jump inside the block's room, requests one pair, and holds the report's
-    row-pointer move exactly where its variant says"""
-    base = _block_base(insts, i)
-    _need(base % 64 == 0, 'stream block 0 at %#x is not on a 64-byte line' % base)
-    for n in range(54):
-        variant, pattern = (n % 27) // 9, n % 9
-        names = KINDS[pattern // 3] + KINDS[pattern % 3]
-        b = base + n * stride
-        _need(b in at, 'stream block %d does not start on an instruction' % n)
-        k = at[b]
-        if names[0] == 'R':
-            _need(insts[k]['op'] == 's_nop' and insts[k]['size'] == 4, 'stream block %d: no s_nop on the boundary' % n)
-            k += 1
-        _need(insts[k]['op'].startswith(FIRST[names[0]]), 'stream block %d (%s) begins with %s' % (n, names, insts[k]['op']))
-        loads = reports = 0
-        while insts[k]['op'] != 's_setpc_b64':
-            _need(insts[k]['addr'] < b + stride, 'stream block %d (%s) outgrew its %d bytes' % (n, names, stride))
-            loads += insts[k]['op'].startswith('s_load_dwordx16')
-            reports += insts[k]['op'] == 'v_lshl_add_u64'
-            k += 1
-        _need(loads == 1 and reports == (variant != 0), 'stream block %d (%s): %d loads, %d reports' % (n, names, loads, reports))
+def _check_gap_stream(insts, i, stride):
+    """SMART_A_GAP_STREAM: 54 blocks, 2 buffers x 3 variants (no report in the pair / behind its first arm / behind its
+    second) x 9 patterns; every main path requests one pair and holds the report's row-pointer move exactly where its
+    variant says"""
+    for n, kinds, _, seen in _walk_blocks(insts, i, stride, PAIRS * 6, ('s_load_dwordx16', 'v_lshl_add_u64'), 'stream block'):
+        loads, reports = seen['s_load_dwordx16'], seen['v_lshl_add_u64']
+        _need(loads == 1 and reports == (n % 27 >= 9), 'stream block %d (%s): %d loads, %d reports' % (n, kinds, loads, reports))
 
 
 def lint_pair_blocks(lib=None, kernel=None):
@@ -279,18 +297,17 @@ def lint_pair_blocks(lib=None, kernel=None):
         stride = _define('SMART_PS_STRIDE' if split else 'SMART_P_STRIDE')
         _need(stride % 64 == 0, 'stride %d is no multiple of 64' % stride)
         insts = dis.kernel(name)
-        at = {x['addr']: i for i, x in enumerate(insts)}
         entries = _entries(insts)
         # the stream of records (SMART_A_GAP_STREAM) loads ONE code word per pair, the pair blocks two per chunk
         pairs = [i for i in entries if not any(x['op'] == 's_load_dword' for x in insts[i:i + 12])]
         _need(len(pairs) == 2, '%s: %d instances of the stretch asm (two: even / any number of chunks)' % (name, len(pairs)))
         try:
             for i in pairs:
-                _check_pair_instance(insts, at, i, stride)
+                _check_pair_instance(insts, i, stride)
             streams = [i for i in entries if i not in pairs]
             _need(len(streams) == (0 if split else 1), '%s: %d streams of records' % (name, len(streams)))
             if streams:
-                _check_gap_stream(insts, at, streams[0], _define('SMART_E_STRIDE'))
+                _check_gap_stream(insts, streams[0], _define('SMART_E_STRIDE'))
         except LintError as e:
             raise LintError('%s: %s' % (name, e))
     if kernel is None or kernel == 'smart_fast_steps_every':
@@ -300,38 +317,24 @@ def lint_pair_blocks(lib=None, kernel=None):
 def lint_every_stream(lib=None):
     """SMART_A_EVERY_STREAM (a report every step): four instances in smart_fast_steps_every (matrix stored or not,
     observations or not), each 2 x 9 blocks SMART_E_STRIDE bytes apart; every block's main path -- arm, report, arm,
-    report, loop control -- ends with the computed jump inside the block's room and requests exactly one pair of steps"""
+    report, loop control -- requests exactly one pair of steps, and the two instances that store the matrix store it in
+    every arm"""
     dis = _disassembly(lib)
     stride = _define('SMART_E_STRIDE')
     _need(stride % 64 == 0, 'stride %d is no multiple of 64' % stride)
     insts = dis.kernel('smart_fast_steps_every')
-    at = {x['addr']: i for i, x in enumerate(insts)}
     entries = _entries(insts)
-    _need(len(entries) == 4, 'smart_fast_steps_every: %d instances of the stream (four)' % len(entries))
-    stores = []
-    for i in entries:
-        base = _block_base(insts, i)
-        _need(base % 64 == 0, 'smart_fast_steps_every: block 0 at %#x is not on a 64-byte line' % base)
-        n_store = 0
-        for n in range(18):
-            names = KINDS[(n % 9) // 3] + KINDS[n % 3]
-            b = base + n * stride
-            _need(b in at, 'smart_fast_steps_every: block %d does not start on an instruction' % n)
-            k = at[b]
-            if names[0] == 'R':
-                _need(insts[k]['op'] == 's_nop' and insts[k]['size'] == 4, 'smart_fast_steps_every: block %d: no s_nop' % n)
-                k += 1
-            _need(insts[k]['op'].startswith(FIRST[names[0]]),
-                  'smart_fast_steps_every: block %d (%s) begins with %s' % (n, names, insts[k]['op']))
-            loads = 0
-            while insts[k]['op'] != 's_setpc_b64':
-                _need(insts[k]['addr'] < b + stride, 'smart_fast_steps_every: block %d (%s) outgrew its %d bytes' % (n, names, stride))
-                loads += insts[k]['op'].startswith('s_load_dwordx16')
-                n_store += insts[k]['op'] == 'global_store_dwordx2'
-                k += 1
-            _need(loads == 1, 'smart_fast_steps_every: block %d (%s) requests %d pairs' % (n, names, loads))
-        stores.append(n_store)
-    _need(sorted(stores) == [0, 0, 36, 36], 'smart_fast_steps_every: stores per instance %r' % (stores,))
+    try:
+        _need(len(entries) == 4, '%d instances of the stream (four)' % len(entries))
+        stores = []
+        for i in entries:
+            stores.append(0)
+            for n, kinds, _, seen in _walk_blocks(insts, i, stride, PAIRS * 2, ('s_load_dwordx16', 'global_store_dwordx2')):
+                _need(seen['s_load_dwordx16'] == 1, 'block %d (%s) requests %d pairs' % (n, kinds, seen['s_load_dwordx16']))
+                stores[-1] += seen['global_store_dwordx2']
+        _need(sorted(stores) == [0, 0, 36, 36], 'stores per instance %r' % (stores,))
+    except LintError as e:
+        raise LintError('smart_fast_steps_every: %s' % e)
 
 
 # ---- hand-over ------------------------------------------------------------------------------------------------------
@@ -528,21 +531,51 @@ def read_sidecar(lib=LIB):
         return None
 
 
+def record_state(lib=LIB):
+    """Is there a record next to the library that counts for it?  'none' | 'other-build' (written for another file: the
+    library was rebuilt by something else, or the record travelled alone) | 'this-build'"""
+    rep = read_sidecar(lib)
+    if rep is None:
+        return 'none'
+    return 'this-build' if rep.get('sha256') == sha256_of(lib) else 'other-build'
+
+
+def verdict_of(report, sha256):
+    """What smartpy_amd._lib does with a library of that sha256, given a report of check_library
+    -> (ok_to_load, pair_blocks_ok, reason).  A report counts only for the very file it was made for."""
+    if report.get('sha256') != sha256:
+        return True, False, 'the lint record next to the library was written for another build of it'
+    if not report.get('checked'):
+        return True, False, 'the library was built without llvm-objdump at hand: its code was not looked at'
+    if report.get('handover') is False or report.get('rows') is False:
+        return False, False, '; '.join(report.get('problems', []))
+    if not report.get('pair_blocks'):
+        return True, False, '; '.join(report.get('problems', []))
+    return True, True, ''
+
+
 def verdict_for(lib=LIB):
-    """What smartpy_amd._lib does with the library it is about to load -> (ok_to_load, pair_blocks_ok, reason).
-    The sidecar counts only for the very file it was written for (sha256)."""
+    """verdict_of the record next to the library"""
     rep = read_sidecar(lib)
     if rep is None:
         return True, False, 'no lint record next to the library (%s): not built by smartpy_amd.build' % os.path.basename(sidecar_path(lib))
-    if rep.get('sha256') != sha256_of(lib):
-        return True, False, 'the lint record next to the library was written for another build of it'
-    if not rep.get('checked'):
-        return True, False, 'the library was built without llvm-objdump at hand: its code was not looked at'
-    if rep.get('handover') is False or rep.get('rows') is False:
-        return False, False, '; '.join(rep.get('problems', []))
-    if not rep.get('pair_blocks'):
-        return True, False, '; '.join(rep.get('problems', []))
-    return True, True, ''
+    return verdict_of(rep, sha256_of(lib))
+
+
+def lint_and_record(path, record_for=None, stamp=False, check=check_library):
+    """Look at the library at `path`, stamp it if asked (the build does, on a file nobody has mapped yet; the loader never
+    rewrites the file it is about to map) and leave the report, for the file as it now is, next to `record_for`: the
+    name the library is installed under, `path` by default.  -> the report (all there is of it in a read-only tree)."""
+    report = check(path)
+    if stamp:
+        stamp_library(path, bool(report['pair_blocks']))
+        report['sha256'] = sha256_of(path)
+    report['stamp'] = library_stamp(path)
+    try:
+        write_sidecar(report, record_for or path)
+    except OSError:
+        pass
+    return report
 
 
 if __name__ == '__main__':

@@ -36,8 +36,9 @@ VALU_CLASSES = ('fp64', 'vcmp', 'vmov', 'lane', 'valu')
 
 
 def disassemble(lib, kernel):
-    """-> (address of the kernel's first instruction, its mangled name, llvm-objdump's text of it)"""
-    return Disassembly(lib).raw(kernel)
+    """-> (address of the kernel's first instruction, its mangled name, llvm-objdump's text of it); `lib` is a library's
+    path, or its Disassembly where more than one kernel is wanted"""
+    return (lib if isinstance(lib, Disassembly) else Disassembly(lib)).raw(kernel)
 
 
 def blocks_and_loops(insts):

@@ -3,25 +3,20 @@
 command line): an edit that is meant to leave a kernel's code alone shows here whether it did."""
 import hashlib
 import os
-import re
 import sys
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import isa_report as R      # noqa: E402
+from smartpy_amd import isa_lint      # noqa: E402  (isa_report put the repository's root on the path)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def kernel_names():
-    text = open(os.path.join(ROOT, 'smartpy_amd', 'csrc', 'smart_capi.hip')).read()
-    table = re.search(r'kFastKernelNames\[kNumFastKernels\] = \{(.*?)\};', text, re.S).group(1)
-    return re.findall(r'"(smart_fast_\w+)"', table)
-
-
 def main():
     lib = sys.argv[1] if len(sys.argv) > 1 else os.path.join(ROOT, 'smartpy_amd', 'csrc', 'libsmart_amd.so')
-    for k in kernel_names():
-        start, sym, body = R.disassemble(lib, k)
+    dis = isa_lint.Disassembly(lib)         # (once: llvm-objdump of the whole library)
+    for k in isa_lint.fast_kernel_names():
+        start, sym, body = R.disassemble(dis, k)
         ins = R.parse(start, body)
         h = hashlib.sha256('\n'.join(x['op'] + ' ' + x['args'] for x in ins).encode()).hexdigest()[:12]
         print('%-30s %6d instructions  %s' % (k, len(ins), h))
