@@ -4,6 +4,7 @@ PyTorch is plumbing here (device memory, streams, torch.distributed); all arithm
 smartpy_amd/csrc/*.hip behind include/smart_amd.h.  Nothing in this module computes model steps on the CPU
 and nothing imports the test oracle.
 """
+import collections
 import ctypes
 import math
 import threading
@@ -68,6 +69,19 @@ def extra_vector(extra):
     return [float(extra['aar']), float(extra['r-o_ratio'])] + [float(v) for v in extra['r-o_split']]
 
 
+def _per_catchment(x, device, C, tail=()):
+    """An input with a catchment axis, on the device: a scalar (tail == ()) or an array of shape `tail` that the
+    catchments share -> contiguous [C, *tail]; an array that has one entry per catchment -> reshaped to [C, *tail]."""
+    if x is None:
+        return None
+    if not tail:
+        return as_device(np.full(C, x, dtype=np.float64) if np.ndim(x) == 0 else x, device, (C,))
+    x = as_device(x, device)
+    if x.numel() == math.prod(tail):
+        return x.reshape((1,) + tail).expand((C,) + tail).contiguous()
+    return x.reshape((C,) + tail)
+
+
 class EnsembleResult(object):
     """Outputs of one launch.  discharge is a [C, N, R] *view* of the sample-minor buffer the kernel writes."""
 
@@ -99,14 +113,14 @@ def n_reports(n_steps, gap, report_type):
 
 
 def variant_classes(params, delta_sec, initial=None, area=None):
-    """Which arithmetic variant of the fast kernels a parameter row needs -- the rules of wave_class() in
-    csrc/smart_fast_model.h: 0 regular, 1 stiff (some k*3600 < dt: clamps / river rule reachable), 2 guarded
-    (S outside [0, 0.5], C < 0 or Z <= 0), 3 ill-conditioned (dt / (RK*3600) > 2, the river: literal arithmetic) --
-    and any row with a NaN or an infinite parameter, or a share or a residence time that is none (D or H outside [0, 1], T < 0, a k <= 0), for the
-    literal arithmetic to decide what comes of it; likewise a
-    row whose INITIAL states (initial [C, N, 12] or [N, 12], with the catchments' areas) hold a NaN, an infinity, a
-    negative volume, or soil so far above its capacity that S * sum(levels) / Z starts beyond 0.5 or H * sum(levels) / Z
-    beyond 1 (in any catchment)."""
+    """Which arithmetic variant of the fast kernels each row of params [N, 10] needs at a step of delta_sec seconds --
+    the rules of wave_class() in csrc/smart_fast_model.h: 0 regular, 1 stiff (some k*3600 < dt: clamps / river rule
+    reachable), 2 guarded (S outside [0, 0.5], C < 0 or Z <= 0), 3 ill-conditioned (dt / (RK*3600) > 2, the river:
+    literal arithmetic).  Class 3 as well, for the literal arithmetic to decide what comes of it: a row with a NaN or an
+    infinite parameter, or a share or a residence time that is none (D or H outside [0, 1], T < 0, a k <= 0); and, when
+    initial ([C, N, 12] or [N, 12] states) is given with area (the catchments' areas, scalar or [C]), a row whose
+    initial states hold a NaN, an infinity, a negative volume, or soil so far above its capacity that
+    S * sum(levels) / Z starts beyond 0.5 or H * sum(levels) / Z beyond 1 (in any catchment).  -> int64 [N]"""
     k = params[:, 6:10] * 3600.0
     cls = torch.zeros(params.shape[0], dtype=torch.int64, device=params.device)
     cls[~(k >= delta_sec).all(dim=1)] = 1
@@ -140,6 +154,7 @@ def _variant_grouping(params, delta_sec, sort_rows=False, initial=None, area=Non
     arithmetic (and cost) independent of its neighbours, rows are grouped by variant before the launch, each group
     padded to whole wavefronts with copies of its last row.  Returns (gather [N_run], inverse [N]) or None when the
     matrix needs no reordering (one variant only -- always the case for hourly steps with the default ranges).
+    params, delta_sec, initial and area are those of variant_classes(), which decides the variants.
 
     sort_rows: within a variant, order the rows so that the 64 samples of a wavefront behave alike -- by T (the
     rainfall correction factor) in 64 bins, then by S * Z.  Wet or dry is decided by the sign of rain * T - peva, so a
@@ -170,50 +185,67 @@ def _variant_grouping(params, delta_sec, sort_rows=False, initial=None, area=Non
     return gather, inverse
 
 
+_MemoEntry = collections.namedtuple('_MemoEntry', 'refs versions key value')
+
+
 class _Memo(object):
-    """What has been worked out about a (params, forcing) pair: the variant grouping of the rows and the launch plan
-    (which kernels the rows and the forcing need, smart_plan_ensemble).  Entries are tied to the tensor OBJECTS the
-    caller passed (weak references) and their in-place version counters, never to addresses: a fresh tensor that
-    happens to reuse a freed address starts from nothing.  One list for the process, guarded by a lock (the C side
-    is thread-aware as well: DeviceCtx::mu)."""
+    """One prepare_ensemble() call's handle on what has been worked out about its (params, forcing) pair: the variant
+    grouping of the rows and the launch plan (which kernels the rows and the forcing need, smart_plan_ensemble).  What
+    is remembered is tied to the tensor OBJECTS the caller passed (weak references), their in-place version counters at
+    the time and the key (everything else the two depend on), never to addresses: a fresh tensor that happens to reuse
+    a freed address starts from nothing.  Nothing is remembered (`applies` is False) outside fast mode, with initial
+    states (the rows' classes depend on them as well) or when an input was converted on the way in (anything but a
+    tensor on the device: a fresh object is classified afresh); lookup(), store() and forget() then do nothing, as they
+    do once one of the tensors is gone.  One list of entries for the process, at most SIZE, guarded by a lock (the C
+    side is thread-aware as well: DeviceCtx::mu)."""
     _entries = []
     _lock = threading.Lock()
     SIZE = 8
 
-    @classmethod
-    def _matches(cls, ent, kind, tensors, key, refs):
-        return (ent[0] == kind and ent[3] == key and len(refs) == len(tensors)
-                and all(r is t for r, t in zip(refs, tensors)))
+    def __init__(self, inputs, key, device, initial=None, fast=True):
+        on = [t for t in inputs if isinstance(t, torch.Tensor) and t.device.type == device.type]
+        self.applies = fast and initial is None and len(on) == len(inputs)
+        self.refs, self.key = [weakref.ref(t) for t in on], key
+        self.refresh()
 
-    @classmethod
-    def lookup(cls, kind, tensors, key):
-        with cls._lock:
-            alive = []
-            hit = None
-            for ent in cls._entries:
-                refs = [r() for r in ent[1]]
-                if any(t is None for t in refs):
-                    continue
-                alive.append(ent)
-                if cls._matches(ent, kind, tensors, key, refs) and ent[2] == tuple(t._version for t in tensors):
-                    hit = ent
-            cls._entries[:] = alive
-            return None if hit is None else hit[4]
+    def refresh(self):
+        """Take the version counters again (None: the tensor is gone): what is stored next describes the tensors as
+        they are now."""
+        self.versions = tuple(None if r() is None else r()._version for r in self.refs)
 
-    @classmethod
-    def store(cls, kind, tensors, key, value):
-        with cls._lock:
-            cls._entries.append((kind, [weakref.ref(t) for t in tensors], tuple(t._version for t in tensors), key,
-                                 (value,)))
-            del cls._entries[:-cls.SIZE]
+    def _is_about(self, ent):
+        return (self.applies and ent.key == self.key and len(ent.refs) == len(self.refs)
+                and all(r() is not None and r() is mine() for r, mine in zip(ent.refs, self.refs)))
 
-    @classmethod
-    def forget(cls, kind, tensors, key):
+    def lookup(self):
+        """The value stored last for these objects at these versions under this key, or None.  Entries whose tensors
+        have died are dropped on the way."""
+        with self._lock:
+            self._entries[:] = [ent for ent in self._entries if all(r() is not None for r in ent.refs)]
+            hits = [ent.value for ent in self._entries if self._is_about(ent) and ent.versions == self.versions]
+        return hits[-1] if hits else None
+
+    def store(self, value):
+        if self.applies and None not in self.versions:
+            with self._lock:
+                self._entries.append(_MemoEntry(self.refs, self.versions, self.key, value))
+                del self._entries[:-self.SIZE]
+
+    def forget(self):
         """Drop what is remembered about these tensors: it turned out stale without a version bump (a write through
         ctypes, a foreign kernel, `.data`), and would be handed out again to the next prepare_ensemble()."""
-        with cls._lock:
-            cls._entries[:] = [ent for ent in cls._entries
-                               if not cls._matches(ent, kind, tensors, key, [r() for r in ent[1]])]
+        with self._lock:
+            self._entries[:] = [ent for ent in self._entries if not self._is_about(ent)]
+
+
+def _compose_plan(planned, keep=0, row_class=None):
+    """The plan word of a launch from what smart_plan_ensemble answered: that the rows were ordered is carried over
+    from `keep`, the word being replaced.  With row_class, the plan of a call of ONE row of that class instead: valid,
+    the kinds of forcing that `planned` (the plan in force) names, the kernel of that class and no other."""
+    if row_class is not None:
+        forcing = _lib.PLAN_FORCING_PIECEWISE | _lib.PLAN_FORCING_VARYING | _lib.PLAN_FORCING_RUNS
+        return _lib.PLAN_VALID | (planned & forcing) | _lib.PLAN_CLASS_BITS[row_class]
+    return planned | (keep & _lib.PLAN_ROWS_ORDERED)
 
 
 class PreparedEnsemble(object):
@@ -223,6 +255,21 @@ class PreparedEnsemble(object):
     Build one with prepare_ensemble()."""
 
     repeated = False    # did the last verify() have to repeat the launch?
+
+    def __init__(self, e, device, n_samples, squeeze, outputs, workspace, grouping, caller_out, keep, memo):
+        self._e = e                     # the filled SmartEnsemble struct; it points into everything below
+        self.device, self.n_samples, self._squeeze = device, n_samples, squeeze
+        self._dis, self._gw, self._objfn, self._fin = outputs       # [C, R, ld] or None, [C, N_run], [C, N_run, 8], ...
+        self._ws = workspace            # the library's scratch (None: the call needs none)
+        self._grouping = grouping       # None, or (gather [N_run], inverse [N]): the rows run in another order
+        self._caller_out = caller_out   # the caller's discharge buffer, when the rows had to be permuted behind it
+        self._keep = keep               # the inputs on the device: alive for as long as the struct points at them
+        self._memo = memo               # the _Memo of the caller's (params, forcing)
+
+    @property
+    def has_status(self):
+        """Does a launch leave a status word for status() and verify()?  (The fast kernels do, in the workspace.)"""
+        return self._ws is not None and self._e.math_mode == MATH_FAST
 
     def enqueue(self):
         """The kernels onto torch's current stream of the device, nothing else: no result object is built, nothing is
@@ -280,25 +327,29 @@ class PreparedEnsemble(object):
         if word & _lib.STATUS_SLICE_TIMEOUT:
             self._e.time_slices = 1
         if word & _lib.STATUS_STALE_PLAN:
-            ordered = self._e.plan & _lib.PLAN_ROWS_ORDERED
-            self._e.plan = 0
-            self._e.plan = self._make_plan() | ordered
-            if self._memo_of is not None:      # what was remembered about these tensors is what went stale
-                tensors, key = self._memo_of
-                _Memo.forget('fast', tensors, key)
-                _Memo.store('fast', tensors, key, (self._grouping, int(self._e.plan)))
+            self._memo.forget()      # what was remembered about these tensors is what went stale
+            self._memo.refresh()
+            self._plan()
+            self._memo.store((self._grouping, int(self._e.plan)))
         self.enqueue()
         word = self.status()
         if word != 0:
             raise SmartEngineError(-6, "smartpy_amd: the repeated launch reports status %#x as well" % word)
         return self._result()
 
-    def _make_plan(self):
-        plan = ctypes.c_int32(0)
+    def _plan(self, ordered=0):
+        """Ask the library which kernels the rows and the forcing need (smart_plan_ensemble: synchronises) and make
+        that the plan of the launches to come; that the rows were ordered stays on record across a re-plan."""
+        keep, word = self._e.plan | ordered, ctypes.c_int32(0)
+        self._e.plan = 0
         with torch.cuda.device(self.device):
             self._e.stream = torch.cuda.current_stream(self.device).cuda_stream
-            _lib.check(_lib.lib().smart_plan_ensemble(ctypes.byref(self._e), ctypes.byref(plan)))
-        return int(plan.value)
+            _lib.check(_lib.lib().smart_plan_ensemble(ctypes.byref(self._e), ctypes.byref(word)))
+        self._e.plan = _compose_plan(int(word.value), keep)
+
+    def aim_at(self, row_class):
+        """A call of ONE row: the plan names the kernel of that row's class and no other (the forcing stays as planned)."""
+        self._e.plan = _compose_plan(self._e.plan, row_class=row_class)
 
     def _result(self):
         dis, gw, objfn, fin = self._dis, self._gw, self._objfn, self._fin
@@ -316,33 +367,23 @@ class PreparedEnsemble(object):
         return EnsembleResult(dis, gw, objfn, fin, self.n_samples, self._squeeze)
 
 
-def prepare_ensemble(params, forcing, area_m2, delta_sec, n_warm, report_gap, report='summary', extra=None,
-                     initial=None, obs=None, gw_obs=None, math_mode='fast', want_discharge=True, want_objfn=None,
-                     want_final=False, device=None, discharge_out=None, group_variants=True, time_slices=0,
-                     literal_form='auto'):
-    """Everything of run_ensemble() short of the launch: see PreparedEnsemble.  Arguments as run_ensemble()."""
-    L = _lib.lib()
+def _normalise_inputs(params, forcing, report, math_mode, device):
+    """Step 1 of prepare_ensemble(): both inputs on the device, the forcing as [C, T, 2], report type and math mode as codes."""
     device = torch.device(device) if device is not None else (
         params.device if isinstance(params, torch.Tensor) and params.is_cuda else default_device())
-    params_in, forcing_in = params, forcing
+    forcing_in = forcing
     params = as_device(params, device)
     forcing = as_device(forcing, device)
     squeeze = forcing.dim() == 2
     if squeeze:
         forcing = forcing.unsqueeze(0)
-    C, T = forcing.shape[0], forcing.shape[1]
     if forcing.shape[2] != 2:
         raise Exception("forcing must be [T, 2] or [C, T, 2] (rain, peva)")
-    if params.dim() == 2:
-        pstride = 0
-        N = params.shape[0]
-    else:
-        if params.shape[0] != C:
-            raise Exception("params [C, N, 10] must have one block per catchment")
-        N = params.shape[1]
-        pstride = N * 10
+    if params.dim() != 2 and params.shape[0] != forcing.shape[0]:
+        raise Exception("params [C, N, 10] must have one block per catchment")
     if params.shape[-1] != 10:
         raise Exception("params must have 10 columns (T, C, H, D, S, Z, SK, FK, GK, RK)")
+    pstride = 0 if params.dim() == 2 else params.shape[1] * 10
     rtype = report_code(report)
     try:
         mmode = _MATH[math_mode]
@@ -355,99 +396,96 @@ def prepare_ensemble(params, forcing, area_m2, delta_sec, n_warm, report_gap, re
     if mmode == MATH_FAST and not (isinstance(forcing_in, torch.Tensor) and forcing_in.is_cuda):
         if not bool(np.isfinite(np.asarray(forcing_in, dtype=np.float64)).all()):
             mmode = MATH_LITERAL
-    R = n_reports(T, report_gap, rtype)
+    return device, params, forcing, squeeze, pstride, rtype, mmode
 
-    area = as_device(np.full(C, area_m2, dtype=np.float64) if np.ndim(area_m2) == 0 else area_m2, device, (C,))
-    if isinstance(extra, dict):
-        extra = extra_vector(extra)
-    if extra is not None:
-        extra = as_device(extra, device)
-        extra = extra.reshape(1, 7).expand(C, 7).contiguous() if extra.numel() == 7 else extra.reshape(C, 7)
-    if initial is not None:
-        initial = as_device(initial, device)
-        initial = initial.reshape(1, N, 12).expand(C, N, 12).contiguous() if initial.numel() == N * 12 \
-            else initial.reshape(C, N, 12)
-    if want_objfn is None:
-        want_objfn = obs is not None
-    if obs is not None:
-        obs = as_device(obs, device)
-        obs = obs.reshape(1, R).expand(C, R).contiguous() if obs.numel() == R else obs.reshape(C, R)
-    elif want_objfn:
-        raise Exception("objective functions need observations")
-    if gw_obs is not None:
-        gw_obs = as_device(np.full(C, gw_obs, dtype=np.float64) if np.ndim(gw_obs) == 0 else gw_obs, device, (C,))
 
-    # what is already known about these very tensors (only when the caller handed over device tensors: anything
-    # converted above is a fresh object, and a fresh object is classified afresh)
-    memo_on = [t for t in (params_in, forcing_in) if isinstance(t, torch.Tensor) and t.is_cuda]
-    sort_rows = not want_discharge and discharge_out is None
-    memo_key = (float(delta_sec), int(report_gap), rtype, C, N, T, bool(group_variants), sort_rows)
-    if initial is not None:
-        memo_on = []          # the rows' classes depend on the initial states as well: nothing is remembered across calls
-    memo = _Memo.lookup('fast', memo_on, memo_key) if len(memo_on) == 2 and mmode == MATH_FAST else None
-
-    # rows grouped by arithmetic variant (fast mode, one shared [N, 10] matrix spanning more than one wavefront)
-    p = PreparedEnsemble()
-    p.device, p.n_samples, p._squeeze = device, N, squeeze
-    p._grouping, p._caller_out = None, None
-    p._memo_of = (memo_on, memo_key) if len(memo_on) == 2 and mmode == MATH_FAST else None
-    if group_variants and mmode == MATH_FAST and pstride == 0 and N > 64:
-        p._grouping = memo[0][0] if memo else _variant_grouping(params, float(delta_sec), sort_rows, initial, area)
-        if p._grouping is not None:
-            gather = p._grouping[0]
-            params = params[gather].contiguous()
-            if initial is not None:
-                initial = initial[:, gather].contiguous()
-            N = gather.numel()
-    if p._grouping is not None and discharge_out is not None:
-        p._caller_out, discharge_out, want_discharge = discharge_out, None, True
-
-    ld = N
-    dis = None
-    if discharge_out is not None:
-        dis = discharge_out
+def _allocate_outputs(C, R, N, device, want_discharge, want_objfn, want_final, discharge_out):
+    """Step 3: (discharge [C, R, ld >= N] or None, gw [C, N], objfn [C, N, 8] or None, final_vars [C, N, 19] or None)."""
+    dis = discharge_out
+    if dis is not None:
         assert dis.is_contiguous() and dis.dtype == torch.float64 and dis.shape[:2] == (C, R) and dis.shape[2] >= N
-        ld = dis.shape[2]
     elif want_discharge:
-        dis = torch.empty((C, R, ld), dtype=torch.float64, device=device)
-    p._dis = dis
-    p._gw = torch.empty((C, N), dtype=torch.float64, device=device)
-    p._objfn = torch.empty((C, N, 8), dtype=torch.float64, device=device) if want_objfn else None
-    p._fin = torch.empty((C, N, 19), dtype=torch.float64, device=device) if want_final else None
+        dis = torch.empty((C, R, N), dtype=torch.float64, device=device)
+    return (dis, torch.empty((C, N), dtype=torch.float64, device=device),
+            torch.empty((C, N, 8), dtype=torch.float64, device=device) if want_objfn else None,
+            torch.empty((C, N, 19), dtype=torch.float64, device=device) if want_final else None)
 
+
+def _fill_struct(inputs, outputs, pstride, n_warm, report_gap, rtype, mmode, delta_sec, time_slices, literal_form):
+    """Step 4: the SmartEnsemble of include/smart_amd.h, pointing at the inputs (area, forcing, params, extra, initial,
+    obs, gw_obs) and the outputs of step 3."""
     def ptr(t):
         return None if t is None else t.data_ptr()
 
-    e = p._e = _lib.SmartEnsemble()
-    e.n_catchments, e.n_samples, e.n_steps, e.n_warm, e.report_gap = C, N, T, int(n_warm), int(report_gap)
-    e.report_type, e.math_mode, e.delta_sec = rtype, mmode, float(delta_sec)
-    e.area_m2, e.forcing, e.params, e.params_catchment_stride = ptr(area), ptr(forcing), ptr(params), pstride
-    e.extra, e.initial, e.obs, e.gw_obs = ptr(extra), ptr(initial), ptr(obs), ptr(gw_obs)
-    e.discharge, e.discharge_ld, e.gw, e.objfn = ptr(dis), ld, ptr(p._gw), ptr(p._objfn)
-    e.final_vars = ptr(p._fin)
-    e.time_slices = int(time_slices)
+    forcing, params, dis = inputs[1], inputs[2], outputs[0]
+    e = _lib.SmartEnsemble()
+    e.n_catchments, e.n_samples, e.n_steps, e.n_warm = forcing.shape[0], params.shape[-2], forcing.shape[1], int(n_warm)
+    e.report_gap, e.report_type, e.math_mode, e.delta_sec = int(report_gap), rtype, mmode, float(delta_sec)
+    e.area_m2, e.forcing, e.params, e.extra, e.initial, e.obs, e.gw_obs = [ptr(t) for t in inputs]
+    e.discharge, e.gw, e.objfn, e.final_vars = [ptr(t) for t in outputs]
+    e.discharge_ld = params.shape[-2] if dis is None else dis.shape[2]
+    e.params_catchment_stride, e.time_slices = pstride, int(time_slices)
     try:
         e.literal_form = _LITERAL_FORMS[literal_form]
     except KeyError:
         raise Exception("literal_form '{}' unknown ('auto', 'rows' or 'lanes').".format(literal_form))
-    # the caller of the C ABI owns every buffer, the library's scratch included: header, observation statistics,
-    # slice hand-over
+    return e
+
+
+def _size_workspace(e, device):
+    """Step 5: the caller of the C ABI owns every buffer, the library's scratch included (header, observation statistics,
+    slice hand-over); with it in place the library checks the whole struct."""
     with torch.cuda.device(device):
-        n_ws = int(L.smart_workspace_bytes(ctypes.byref(e)))
-    p._ws = torch.empty((n_ws + 7) // 8, dtype=torch.float64, device=device) if n_ws > 0 else None
-    e.workspace, e.workspace_bytes = ptr(p._ws), n_ws
-    _lib.check(L.smart_check_ensemble(ctypes.byref(e)))
-    if mmode == MATH_FAST and p._ws is not None:
-        ordered = _lib.PLAN_ROWS_ORDERED if (sort_rows and p._grouping is not None) else 0
-        if memo:
-            e.plan = memo[0][1]
-        elif torch.cuda.is_current_stream_capturing():
-            e.plan = 0      # planning synchronises: inside a graph capture every kernel the call could need is launched
-        else:
-            e.plan = p._make_plan() | ordered
-            if len(memo_on) == 2:
-                _Memo.store('fast', memo_on, memo_key, (p._grouping, int(e.plan)))
-    p._keep = (area, forcing, params, extra, initial, obs, gw_obs)     # alive for as long as the struct points at them
+        n_ws = int(_lib.lib().smart_workspace_bytes(ctypes.byref(e)))
+    ws = torch.empty((n_ws + 7) // 8, dtype=torch.float64, device=device) if n_ws > 0 else None
+    e.workspace, e.workspace_bytes = (None if ws is None else ws.data_ptr()), n_ws
+    _lib.check(_lib.lib().smart_check_ensemble(ctypes.byref(e)))
+    return ws
+
+
+def prepare_ensemble(params, forcing, area_m2, delta_sec, n_warm, report_gap, report='summary', extra=None,
+                     initial=None, obs=None, gw_obs=None, math_mode='fast', want_discharge=True, want_objfn=None,
+                     want_final=False, device=None, discharge_out=None, group_variants=True, time_slices=0,
+                     literal_form='auto'):
+    """Everything of run_ensemble() short of the launch: see PreparedEnsemble.  Arguments as run_ensemble()."""
+    _lib.lib()      # (a library that cannot be loaded is reported before anything else)
+    inputs_in = (params, forcing)
+    device, params, forcing, squeeze, pstride, rtype, mmode = _normalise_inputs(params, forcing, report, math_mode, device)
+    C, T, N = forcing.shape[0], forcing.shape[1], params.shape[-2]
+    R = n_reports(T, report_gap, rtype)
+    area = _per_catchment(area_m2, device, C)
+    extra = _per_catchment(extra_vector(extra) if isinstance(extra, dict) else extra, device, C, (7,))
+    initial = _per_catchment(initial, device, C, (N, 12))
+    if want_objfn is None:
+        want_objfn = obs is not None
+    if want_objfn and obs is None:
+        raise Exception("objective functions need observations")
+    obs = _per_catchment(obs, device, C, (R,))
+    gw_obs = _per_catchment(gw_obs, device, C)
+
+    sort_rows = not want_discharge and discharge_out is None
+    memo = _Memo(inputs_in, (float(delta_sec), int(report_gap), rtype, C, N, T, bool(group_variants), sort_rows),
+                 device, initial, mmode == MATH_FAST)
+    known = memo.lookup()               # (grouping, plan) of an earlier call with these very tensors, or None
+    grouping, caller_out = None, None
+    if group_variants and mmode == MATH_FAST and pstride == 0 and N > 64:     # one shared matrix, more than a wavefront
+        grouping = known[0] if known else _variant_grouping(params, float(delta_sec), sort_rows, initial, area)
+    if grouping is not None:            # the rows run in that order
+        params = params[grouping[0]].contiguous()
+        initial = None if initial is None else initial[:, grouping[0]].contiguous()
+    if grouping is not None and discharge_out is not None:
+        caller_out, discharge_out, want_discharge = discharge_out, None, True     # permuted into it by result()
+    outputs = _allocate_outputs(C, R, params.shape[-2], device, want_discharge, want_objfn, want_final, discharge_out)
+    inputs = (area, forcing, params, extra, initial, obs, gw_obs)
+    e = _fill_struct(inputs, outputs, pstride, n_warm, report_gap, rtype, mmode, delta_sec, time_slices, literal_form)
+    p = PreparedEnsemble(e, device, N, squeeze, outputs, _size_workspace(e, device), grouping, caller_out, inputs, memo)
+    if p.has_status:
+        if known:
+            e.plan = known[1]
+        elif not torch.cuda.is_current_stream_capturing():
+            # (planning synchronises: inside a graph capture the plan stays 0 and every kernel the call could need runs)
+            p._plan(_lib.PLAN_ROWS_ORDERED if (sort_rows and grouping is not None) else 0)
+            memo.store((grouping, int(e.plan)))
     return p
 
 
@@ -477,10 +515,8 @@ def run_ensemble(params, forcing, area_m2, delta_sec, n_warm, report_gap, report
                          discharge_out=discharge_out, group_variants=group_variants, time_slices=time_slices,
                          literal_form=literal_form)
     p.enqueue()
-    if verify and p._ws is not None and p._e.math_mode == MATH_FAST and not torch.cuda.is_current_stream_capturing():
-        out = p.verify()        # (builds the result once: after the status word has been read)
-    else:
-        out = p.result()
+    # (verify() builds the result once: after the status word has been read)
+    out = p.verify() if verify and p.has_status and not torch.cuda.is_current_stream_capturing() else p.result()
     out._prepared = p       # the result's tensors live in the prepared call's buffers
     return out
 
@@ -491,8 +527,7 @@ class SingleRun(object):
     (montecarlo.py:179-186) -- made ready once: the forcing on the device, a [1, 10] parameter buffer, the outputs, the
     workspace and what smart_plan_ensemble found out about the forcing all live here.  run(params) then copies 80
     bytes to the device, enqueues the one kernel the row's class needs, and brings [R] + 1 doubles back; nothing is
-    allocated, the forcing is not touched, no planning kernel runs.  (Round 4 gave the smartcpp hook this treatment and
-    left the package's own single-run entry stacking, uploading and planning on every call.)"""
+    allocated, the forcing is not touched, no planning kernel runs."""
 
     def __init__(self, forcing, area_m2, delta_sec, n_warm, report_gap, report='summary', extra=None, device=None,
                  math_mode='fast'):
@@ -505,7 +540,6 @@ class SingleRun(object):
         self._args = (area_m2, delta_sec, n_warm, report_gap)
         self._kw = dict(report=report, extra=extra, math_mode=math_mode, device=self.device)
         self._prep = None
-        self._forcing_bits = 0
 
     def run(self, params):
         """params: the ten values (T, C, H, D, S, Z, SK, FK, GK, RK).  -> (discharge ndarray [R], gw float)."""
@@ -515,20 +549,14 @@ class SingleRun(object):
         self.params.copy_(self._host, non_blocking=True)        # the 80 bytes of this call
         h2d_bytes += 80
         if self._prep is None:
-            # the first call plans: which kinds of forcing the series holds comes back once and is kept
+            # the first call plans: which kinds of forcing the series holds comes back once and stays in the plan
             self._prep = prepare_ensemble(self.params, self.forcing, *self._args, **self._kw)
-            self._forcing_bits = self._prep._e.plan & (_lib.PLAN_FORCING_PIECEWISE | _lib.PLAN_FORCING_VARYING |
-                                                       _lib.PLAN_FORCING_RUNS)
         p = self._prep
-        if p._e.math_mode == MATH_FAST and p._ws is not None:
+        if p.has_status:
             # the row's class on the host (ten numbers, the rules of wave_class): the plan names its kernel and no other
-            cls = int(_lib.lib().smart_row_class(row.ctypes.data, self.delta_sec, None, 0.0))
-            p._e.plan = _lib.PLAN_VALID | self._forcing_bits | _lib.PLAN_CLASS_BITS[cls]
-            p.enqueue()
-            out = p.verify()
-        else:
-            p.enqueue()
-            out = p.result()
+            p.aim_at(int(_lib.lib().smart_row_class(row.ctypes.data, self.delta_sec, None, 0.0)))
+        p.enqueue()
+        out = p.verify() if p.has_status else p.result()
         return np.ascontiguousarray(out.discharge.cpu().numpy()[0]), float(out.gw.cpu().numpy()[0])
 
 

@@ -743,3 +743,144 @@ def test_reciprocal_correction_step_gives_the_bits_of_the_division():
             checked += 1
     assert checked > 140000
     print('inexact remainders', inexact, 'of', checked)
+
+
+# ---- the engine's host side: the memo behind its handle, the plan word, broadcasting over catchments --------------
+def _memo_pair():
+    import torch
+    return torch.zeros(4, 10, dtype=torch.float64), torch.zeros(6, 2, dtype=torch.float64)
+
+
+@pytest.fixture
+def memo():
+    """engine._Memo with an empty process-wide list (restored afterwards)."""
+    from smartpy_amd import engine
+    kept = list(engine._Memo._entries)
+    engine._Memo._entries[:] = []
+    yield engine._Memo
+    engine._Memo._entries[:] = kept
+
+
+def test_memo_hits_on_the_same_objects_at_the_same_versions_only(memo):
+    """What prepare_ensemble() remembers is tied to the two tensor OBJECTS and their in-place version counters: the
+    same objects come back -> hit; an in-place write to either, a fresh tensor with equal contents, another key -> miss."""
+    import torch
+    cpu = torch.device('cpu')
+    p, f = _memo_pair()
+    assert memo((p, f), 'key', cpu).lookup() is None
+    memo((p, f), 'key', cpu).store(('grouping', 0x123))
+    assert memo((p, f), 'key', cpu).lookup() == ('grouping', 0x123)
+    assert memo((p, f), 'other key', cpu).lookup() is None
+    assert memo((p.clone(), f), 'key', cpu).lookup() is None and memo((p, f.clone()), 'key', cpu).lookup() is None
+    assert memo((f, p), 'key', cpu).lookup() is None
+    for written in (p, f):
+        a, b = _memo_pair()
+        memo((a, b), 'key', cpu).store('before')
+        (a if written is p else b)[0, 0] = 1.0
+        assert memo((a, b), 'key', cpu).lookup() is None
+        memo((a, b), 'key', cpu).store('after')              # the newest entry for the objects at their versions wins
+        assert memo((a, b), 'key', cpu).lookup() == 'after'
+    assert memo((p, f), 'key', cpu).lookup() == ('grouping', 0x123)
+
+
+def test_memo_forget_removes_exactly_that_entry_and_refresh_takes_the_new_versions(memo):
+    import torch
+    cpu = torch.device('cpu')
+    p, f = _memo_pair()
+    q, g = _memo_pair()
+    h = memo((p, f), 'key', cpu)
+    h.store('mine')
+    memo((p, f), 'other key', cpu).store('other key')
+    memo((q, g), 'key', cpu).store('other tensors')
+    p[0, 0] = 2.0               # forget() goes by objects and key, not by version: what went stale is what it drops
+    h.forget()
+    assert [ent.value for ent in memo._entries] == ['other key', 'other tensors']
+    h.store('stale versions')   # what verify() does after a stale plan: forget, refresh, re-plan, store
+    assert memo((p, f), 'key', cpu).lookup() is None
+    h.forget()
+    h.refresh()
+    h.store('fresh')
+    assert memo((p, f), 'key', cpu).lookup() == 'fresh' and len(memo._entries) == 3
+
+
+def test_memo_keeps_eight_entries_and_drops_those_whose_tensor_died(memo):
+    import gc
+    import torch
+    cpu = torch.device('cpu')
+    assert memo.SIZE == 8
+    pairs = [_memo_pair() for _ in range(9)]
+    for i, pair in enumerate(pairs):
+        memo(pair, 'key', cpu).store(i)
+    assert len(memo._entries) == 8 and memo(pairs[0], 'key', cpu).lookup() is None           # the oldest went out
+    assert [memo(pair, 'key', cpu).lookup() for pair in pairs[1:]] == list(range(1, 9))
+    h = memo(pairs[3], 'key', cpu)
+    del pairs[3:5]
+    gc.collect()
+    assert memo(pairs[1], 'key', cpu).lookup() == 1
+    assert sorted(ent.value for ent in memo._entries) == [1, 2, 5, 6, 7, 8]                 # pruned by that lookup
+    h.refresh()
+    h.store('about dead tensors')
+    h.forget()
+    assert h.lookup() is None and len(memo._entries) == 6                                    # ... which nothing touches
+
+
+def test_memo_does_not_apply_to_converted_inputs_initial_states_or_literal_mode(memo):
+    """An input that is not a tensor on the device is converted on the way in (a fresh object each call); with initial
+    states the rows' classes depend on them too; the plan belongs to fast mode.  Then nothing is stored or found."""
+    import torch
+    cpu = torch.device('cpu')
+    p, f = _memo_pair()
+    assert memo((p, f), 'key', cpu).applies
+    for h in (memo((p.numpy(), f), 'key', cpu), memo((p, f.tolist()), 'key', cpu), memo((p, f), 'key', torch.device('meta')),
+              memo((p, f), 'key', cpu, initial=torch.zeros(4, 12)), memo((p, f), 'key', cpu, fast=False)):
+        assert not h.applies
+        h.store('never')
+        assert h.lookup() is None and memo._entries == []
+    memo((p, f), 'key', cpu).store('kept')
+    memo((p, f), 'key', cpu, fast=False).forget()
+    assert memo((p, f), 'key', cpu).lookup() == 'kept'
+
+
+def test_plan_word_keeps_the_row_order_mark_and_aims_at_one_class():
+    """engine._compose_plan: a re-plan carries PLAN_ROWS_ORDERED over from the word it replaces (and nothing else of
+    it); the plan of a single row is PLAN_VALID, the forcing bits of the plan in force and the kernel of its class."""
+    from smartpy_amd import engine, _lib
+    forcing = (_lib.PLAN_FORCING_PIECEWISE, _lib.PLAN_FORCING_VARYING, _lib.PLAN_FORCING_RUNS)
+    old = _lib.PLAN_VALID | _lib.PLAN_ROWS_ORDERED | _lib.PLAN_CLASS_BITS[1] | _lib.PLAN_FORCING_VARYING
+    new = _lib.PLAN_VALID | _lib.PLAN_CLASS_BITS[0] | _lib.PLAN_FORCING_RUNS | (5 << _lib.PLAN_ILLCOND_BLOCKS_SHIFT)
+    assert engine._compose_plan(new, old) == new | _lib.PLAN_ROWS_ORDERED
+    assert engine._compose_plan(new, old & ~_lib.PLAN_ROWS_ORDERED) == new and engine._compose_plan(new) == new
+    assert engine._compose_plan(new, _lib.PLAN_ROWS_ORDERED) == new | _lib.PLAN_ROWS_ORDERED
+    for cls in range(4):
+        for bits in (0, forcing[0], forcing[1] | forcing[2], forcing[0] | forcing[1] | forcing[2]):
+            in_force = new | _lib.PLAN_ROWS_ORDERED | _lib.PLAN_CLASS_BITS[3] | bits
+            assert engine._compose_plan(in_force, row_class=cls) == _lib.PLAN_VALID | (in_force & sum(forcing)) | \
+                _lib.PLAN_CLASS_BITS[cls]
+    assert engine._compose_plan(new, row_class=2) == _lib.PLAN_VALID | _lib.PLAN_FORCING_RUNS | _lib.PLAN_CLASS_BITS[2]
+
+
+def test_inputs_are_broadcast_over_the_catchments():
+    """engine._per_catchment: a scalar or an array the catchments share -> contiguous [C, ...]; one entry per catchment
+    -> reshaped; the bytes that cross to a device are counted by as_device as before (none on the host)."""
+    import torch
+    from smartpy_amd import engine
+    cpu, C = torch.device('cpu'), 3
+    assert engine._per_catchment(None, cpu, C) is None and engine._per_catchment(None, cpu, C, (7,)) is None
+    area = engine._per_catchment(175.46e6, cpu, C)
+    assert area.shape == (C,) and area.dtype == torch.float64 and area.tolist() == [175.46e6] * C
+    assert engine._per_catchment([1.0, 2.0, 3.0], cpu, C).tolist() == [1.0, 2.0, 3.0]
+    assert engine._per_catchment(np.float32(0.5), cpu, 1).tolist() == [0.5]
+    with pytest.raises(RuntimeError):
+        engine._per_catchment([1.0, 2.0], cpu, C)
+    seven = np.arange(7.0)
+    shared = engine._per_catchment(seven, cpu, C, (7,))
+    assert shared.shape == (C, 7) and shared.is_contiguous() and all(np.array_equal(r.numpy(), seven) for r in shared)
+    own = engine._per_catchment(np.arange(21.0), cpu, C, (7,))
+    assert own.shape == (C, 7) and own.is_contiguous() and np.array_equal(own.numpy().ravel(), np.arange(21.0))
+    init = engine._per_catchment(torch.arange(5 * 12, dtype=torch.float64), cpu, C, (5, 12))
+    assert init.shape == (C, 5, 12) and init.is_contiguous() and torch.equal(init[2], init[0])
+    assert engine._per_catchment(np.zeros((C, 5, 12)), cpu, C, (5, 12)).shape == (C, 5, 12)
+    obs = engine._per_catchment(np.arange(4.0), cpu, 1, (4,))
+    assert obs.shape == (1, 4) and obs.is_contiguous()
+    with pytest.raises(RuntimeError):
+        engine._per_catchment(np.arange(5.0), cpu, C, (4,))

@@ -12,7 +12,7 @@ f = torch.as_tensor(bench.synthetic_forcing(0, True)[0], device=dev)
 T, W = f.shape[0], 8760
 obs = torch.rand(T // 24, dtype=torch.float64, device=dev) + 0.5
 engine_sort = engine._variant_grouping
-engine._variant_grouping = lambda params, dt, sort_rows=False: engine_sort(params, dt, False)
+engine._variant_grouping = lambda params, dt, sort_rows=False, initial=None, area=None: engine_sort(params, dt, False, initial, area)
 
 
 def binned(p, bins, second):
