@@ -745,8 +745,8 @@ static int decide(const SmartEnsemble *e, const DeviceCtx *d, const Workspace &w
     if (x.n_seg > 1 && (!w.slices || w.slice_room < slice_bytes(e->n_samples, e->n_catchments)))
         x.n_seg = 1;
     // Early exits inside every step of the interval engine (FastModel::kExits) cost a wavefront a taken branch where
-    // they trigger; the straight-line kernels run their wet intervals in two modes instead (SMART_WET_MODES: one
-    // taken branch per interval) and keep the asm loop.  The exits win once a SIMD holds three waves whose scalar
+    // they trigger; the straight-line kernels run their wet intervals as two kinds of step instead (SMART_A_WET_INTERVAL:
+    // one taken branch per interval) and keep the asm loop.  The exits win once a SIMD holds three waves whose scalar
     // work and branches hide behind each other's vector work -- by 1.5 to 2.5 % from 3 blocks per SIMD on (3.05,
     // 4.6, 15: config 4 on one GPU, config 5), level at 2.44, and lose 6 % at 1.9 and 1.53; rows ordered or not
     // (tools/gpu_r03_l.sh, gpu_r03_n.sh: profiles/r03_ab_exits_modes.txt).

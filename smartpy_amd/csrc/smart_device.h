@@ -7,6 +7,16 @@
 // loads (s_load, address uniform in blockIdx.y and the time index), report means / groundwater sums /
 // objective-function moments are accumulated in registers, and the only per-step-scale HBM traffic is
 // one coalesced 512-byte discharge store per wavefront per report step.
+//
+// Macros that a build may still set with -D (everything else in these headers is plain code; the tuning switches of
+// rounds 2-6 are folded in at the value that won, their measurements are under profiles/):
+//   SMART_STEP_ARMS=0    hipcc's step loop instead of the asm arms   tests/test_gpu_parity.py::test_asm_loops_are_bit_identical_to_the_compiled_ones
+//   SMART_WET_ASM=0      hipcc's wet-interval loop (smart_fast_model.h)   the same test
+//   SMART_NO_ILLCOND     no row counts as ill-conditioned (wave_class, smart_fast_model.h)   tools/debug/illcond_err.py
+//   SMART_LANES_COUNT    instruction counters in smart_literal_lanes.h   tools/microbench/lanes.hip
+//   SMART_P_STRIDE, SMART_PS_STRIDE, SMART_E_STRIDE    block strides of the computed jumps: smartpy_amd/isa_lint.py reads
+//                        them from the `#define NAME <int>` lines below; tools/gpu_round.sh strides builds variants
+//   SMART_STEPS_PHASE, SMART_EVERY_PHASE    loop placement   tools/gpu_round.sh phases-every
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -79,17 +89,6 @@ __device__ __forceinline__ void raise_status(const KArgs &a, int bit)
         __hip_atomic_fetch_or(a.hdr + kHdrStatus, bit, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
-
-#ifndef SMART_NT_STORE
-#define SMART_NT_STORE 1
-#endif
-#ifndef SMART_IV_DEFER
-#define SMART_IV_DEFER 0 // interval / run engine: 1 = a dry interval defers its evaporation demand to the next wet one (measured:
-                         // no gain at any load, and its extra live value costs the kernel with exits its third wave per SIMD)
-#endif
-#ifndef SMART_CHUNK_THREADED
-#define SMART_CHUNK_THREADED 1 // the four steps of a chunk as one threaded asm (0: four single-step asms; A/B builds)
-#endif
 // code placement of a hot loop: onto a 64-byte line, `phase` dwords (s_nop) behind it
 #define SMART_NOPS_0 ""
 #define SMART_NOPS_1 "s_nop 0\n\t"
@@ -112,9 +111,6 @@ __device__ __forceinline__ void raise_status(const KArgs &a, int bit)
 #define SMART_PLACE_LOOP(phase) asm volatile(".p2align 6\n\t" SMART_NOPS(phase))
 #ifndef SMART_STEPS_PHASE
 #define SMART_STEPS_PHASE 1
-#endif
-#ifndef SMART_PAIR_BLOCKS
-#define SMART_PAIR_BLOCKS 1 // the streaming step loop as pair blocks behind computed jumps (0: the threaded chunks; A/B builds)
 #endif
 #ifndef SMART_PS_STRIDE
 #define SMART_PS_STRIDE 2368 // ... of the SPLIT models (two more reservoirs in every arm)
@@ -235,10 +231,7 @@ __device__ __forceinline__ bool same_bits(double x, double y)
 // Walk n time steps of one catchment's forcing.  The forcing of a step is the same for all 64 lanes, so it is
 // fetched with scalar loads into SGPRs: kChunk steps (one 64-byte line) per s_load_dwordx16, and the next chunk is
 // requested before the current one is consumed, so the load latency hides behind kChunk model steps.
-#ifndef SMART_CHUNK
-#define SMART_CHUNK 4
-#endif
-constexpr int kChunk = SMART_CHUNK;
+constexpr int kChunk = 4;
 
 // does the model want to look at a chunk before its steps (LiteralModelT<true>::begin_chunk)?
 template <class Model, class = void>
@@ -384,14 +377,8 @@ __device__ __forceinline__ void time_loop_arms(Model &m, const double2 *__restri
 #pragma unroll
         for (int j = 0; j < kChunk; ++j)
             nxt[j] = f[pre + j];
-#if SMART_CHUNK_THREADED
         static_assert(kChunk == 4, "SMART_A_CHUNK threads four steps");
         m.template chunk_arms<QUICK, LAST>(cur, acc);
-#else
-#pragma unroll
-        for (int j = 0; j < kChunk; ++j)
-            m.template step_arms<QUICK, LAST>(cur[j], acc);
-#endif
         chunk_end();
 #pragma unroll
         for (int j = 0; j < kChunk; ++j)
@@ -482,10 +469,8 @@ __device__ __forceinline__ void arm_intervals(Model &m, const double2 *__restric
 {
     const int cpi = (int)(gap / kChunk);
     long n_stream = 0;
-#if SMART_CHUNK_THREADED
     if (gap % (2 * kChunk) == 0 && n_iv > 0) // (an even number of chunks per interval: the two buffers swap roles)
         n_stream = ends_at_array_end ? n_iv - 1 : n_iv;
-#endif
     if (n_stream > 0) {
         double2 cur[kChunk], nxt[kChunk];
 #pragma unroll
@@ -640,11 +625,7 @@ struct Reporter {
     __device__ __forceinline__ void emit(const KArgs &a, const LaneCtx &x, long r, double val)
     {
         if (a.discharge && x.live)
-#if SMART_NT_STORE
             __builtin_nontemporal_store(val, &a.discharge[(x.c * a.R + r) * a.ld + x.n]);
-#else
-            a.discharge[(x.c * a.R + r) * a.ld + x.n] = val;
-#endif
         if (want_obj) {
             const double e = obs[r];
             if (r == 0)
@@ -683,11 +664,7 @@ struct Reporter {
         const double e = e_nx, w = w_nx;
         prime(a, r + 1);
         if (a.discharge && x.live)
-#if SMART_NT_STORE
             __builtin_nontemporal_store(val, &a.discharge[(x.c * a.R + r) * a.ld + x.n]);
-#else
-            a.discharge[(x.c * a.R + r) * a.ld + x.n] = val;
-#endif
         if (want_obj && r == 0)
             shift = val;
         if (want_obj && !is_nan_bits(e)) { // montecarlo.py:195-196
@@ -816,11 +793,8 @@ __device__ __forceinline__ void run_ensemble(const KArgs &a, const double2 *__re
         // sample (lane_ctx) and store its value to its address, the same bits.  Same-box A/B, every output bit equal
         // (profiles/r06_ab_lean_every.txt): smart_fast_stiff 1.30 -> 1.12 ms on config 2's stiff rows (21 scalar
         // instructions and 6 branches a step beside 85 vector ones before), smart_fast_illcond_lanes 4.12 -> 3.95 ms,
-        // the daily ensemble of 1e6 samples 11.28 -> 10.97 ms.  SMART_LEAN_EVERY=0 builds the old form (A/B).
-#ifndef SMART_LEAN_EVERY
-#define SMART_LEAN_EVERY 1
-#endif
-        constexpr bool kLean = kAhead || (SMART_LEAN_EVERY && !Model::kBalanceSums);
+        // the daily ensemble of 1e6 samples 11.28 -> 10.97 ms.
+        constexpr bool kLean = kAhead || !Model::kBalanceSums;
         if constexpr (kLean) {
             // The row form's wavefront is alone on its SIMD: every instruction of the report is four to five cycles of
             // the step.  The PMC counters of config 2 (profiles/r05_config2.md) had 54 scalar instructions per wave-step
@@ -851,11 +825,7 @@ __device__ __forceinline__ void run_ensemble(const KArgs &a, const double2 *__re
                 // for every x, the zeros and a NaN included
                 const double val = m.q_out + zero;
                 if (store) {
-#if SMART_NT_STORE
                     __builtin_nontemporal_store(val, row);
-#else
-                    *row = val;
-#endif
                     row += stride;
                 }
                 if (obj) {
@@ -1051,10 +1021,7 @@ __device__ __forceinline__ int forcing_kind(const KArgs &a, int flags)
 
 // Walk the report intervals of a piecewise-constant forcing: one (rain, peva) pair per interval, fetched with scalar
 // loads kGroup intervals ahead (a dry interval takes ~100 cycles, far less than a load's latency).
-#ifndef SMART_IV_GROUP
-#define SMART_IV_GROUP 4
-#endif
-constexpr int kGroup = SMART_IV_GROUP;
+constexpr int kGroup = 4;
 
 template <class Body>
 __device__ __forceinline__ void interval_loop(const double2 *__restrict__ f, long i0, long i1, long gap, Body &&body)
@@ -1117,9 +1084,7 @@ __device__ __forceinline__ void interval_loop_obs(const double2 *__restrict__ f,
 // and poisons its chain (negative flag), so that no number computed from a missing hand-over can pass for a result;
 // the host reads the status word and repeats the launch unsliced (engine.py).  The arithmetic is that of the
 // unsliced run, bit for bit.
-#ifndef SMART_POLL_SLEEP
-#define SMART_POLL_SLEEP 100
-#endif
+constexpr int kPollSleep = 100;             // s_sleep argument between two looks at the flag: one poll is ~3 us
 constexpr long kDefaultMaxPolls = 1000000; // x ~3 us = three seconds; a slice takes ~1 ms and waits for one predecessor
 
 // the piece of work of this workgroup: block of 64 samples, catchment, time slice
@@ -1156,7 +1121,7 @@ __device__ __forceinline__ bool wait_for_slice(const KArgs &a, long slot, int se
     long polls = 0;
     int v;
     while ((v = __hip_atomic_load(flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) > -seg && v < seg) {
-        __builtin_amdgcn_s_sleep(SMART_POLL_SLEEP);
+        __builtin_amdgcn_s_sleep(kPollSleep);
         if (++polls > a.max_polls) {
             raise_status(a, kStatusSliceTimeout);
             return false;
@@ -1239,10 +1204,6 @@ __device__ __forceinline__ void run_ensemble_merged(const KArgs &a, const double
         if constexpr (piecewise && Model::kWetAsm) {
             if (quick && __builtin_bit_cast(unsigned long long, v.x) == 0) {
                 if (__builtin_bit_cast(unsigned long long, v.y) == 0) {
-#if SMART_IV_DEFER
-                    if (__builtin_amdgcn_ballot_w64(m.pend > 0.0) != 0)
-                        m.flush_pending();
-#endif
                     m.calm_interval(run_len, acc);
                 } else {
                     m.dry_interval(-v.y, run_len, acc);
@@ -1254,12 +1215,6 @@ __device__ __forceinline__ void run_ensemble_merged(const KArgs &a, const double
         if (ex < 0.0) {
             m.dry_interval(ex, run_len, acc);
         } else {
-#if SMART_IV_DEFER
-            // what the lane's dry intervals since its last wet one have added to `pend` is taken from the layers now
-            // (FastModel::dry_interval): one cascade per dry spell instead of one per dry interval
-            if (m.pend > 0.0)
-                m.flush_pending();
-#endif
             if constexpr (piecewise && Model::kWetAsm)
                 m.wet_interval(ex, run_len, acc, num, den, fits);
             else
@@ -1363,7 +1318,7 @@ __device__ __forceinline__ void run_ensemble_merged(const KArgs &a, const double
     auto park_state = [&]() {
         if constexpr (Model::kSplit) {
             m.save_state(park, 1);
-            if constexpr (!piecewise || SMART_IV_DEFER)
+            if constexpr (!piecewise)
                 park[15] = m.pend;
         }
     };
@@ -1373,9 +1328,7 @@ __device__ __forceinline__ void run_ensemble_merged(const KArgs &a, const double
     double s0 = 0.0, s1 = 0.0, s2 = 0.0;
     const double inv_gap = 1.0 / (double)gap;
     const bool starts_run = ra == 0 && (rb > 0 || last);
-    constexpr bool deferring = !piecewise || SMART_IV_DEFER; // is an evaporation demand carried in `pend`?
-    if constexpr (piecewise && deferring)
-        m.pend = seg > 0 ? hand[15 * kWave] : 0.0; // evaporation demand not yet taken from the layers (dry_interval)
+    constexpr bool deferring = !piecewise; // is an evaporation demand carried in `pend`?  (the step loop's lazy dry steps)
     if constexpr (runs) {
         // `per` runs make a report interval; the walk is over runs, the report falls on every per-th of them
         const long per = gap / run_len;
@@ -1533,7 +1486,6 @@ __device__ __forceinline__ void run_ensemble_merged(const KArgs &a, const double
                                                                 report_every(store_tag, obs_tag, e, w);
                                                             });
                             };
-#if SMART_PAIR_BLOCKS
                             // whole groups of four steps, from a multiple of four on: the stream of SMART_A_EVERY_STREAM
                             if constexpr (Q && !Model::kSplit) {
                                 const unsigned pc_lo = (unsigned)__builtin_amdgcn_s_getpc(); // (see arm_intervals)
@@ -1555,7 +1507,6 @@ __device__ __forceinline__ void run_ensemble_merged(const KArgs &a, const double
                                     }
                                 }
                             }
-#endif
                             each(first, i1 - first);
                         };
                         if (row && rep.want_obj)
@@ -1569,7 +1520,6 @@ __device__ __forceinline__ void run_ensemble_merged(const KArgs &a, const double
                     }
                 } else {
                     long done = 0;
-#if SMART_PAIR_BLOCKS
                     // The pair blocks (FastModel::stream_stretch: the whole stretch, reports included, in one asm): report
                     // gaps of whole pairs of chunks, the kinds of the steps from smart_forcing_scan's code words.  The last
                     // interval of the forcing array stays with the loop below (the asm requests two chunks ahead).  Its
@@ -1640,7 +1590,6 @@ __device__ __forceinline__ void run_ensemble_merged(const KArgs &a, const double
                             done = n_stream;
                         }
                     }
-#endif
                     arm_intervals<Q, REPORT == kReportLast>(m, f + (i0 + done) * gap, i1 - i0 - done, gap, i1 * gap == a.T,
                                                             acc, [&]() __attribute__((always_inline)) {
                                                                 if (stretch == 1)

@@ -10,7 +10,7 @@
 //                               instructions, no EXEC change, no filling;
 //   rain > 0              RAIN  the general step: excess per lane, wet lanes under EXEC, filling, leaks -- 84, of
 //                               which 17 (the filling below the top layer) are skipped when the top layer takes the
-//                               excess of every wet lane (SMART_RAIN_FILL_EXIT: 59 % of the rainy steps).
+//                               excess of every wet lane (SMART_A_FILL_QUICK: 59 % of the rainy steps).
 // The deferred evaporation cascade (FastModel::flush_pending) is due in the calm and the rain arm when a wet lane has
 // a demand pending -- read from `pend` itself (lanes with something pending are exactly the lanes with pend > 0; the
 // lane mask step_lazy() carries says the same, but an SGPR pair that lives across `asm` statements is taken for
@@ -116,10 +116,6 @@
 // ... with a way out behind the top layer: when no lane has excess left there (59 % of the rainy steps of the
 // flat-forcing workload) the other five layers see  t = l + 0; l = min(t, z); t - l = 0  -- the identity as long as
 // no layer is above its capacity (QUICK waves only) -- and the saturation excess is zero (v_cmp_nle: a NaN goes on)
-#ifndef SMART_RAIN_FILL_EXIT
-#define SMART_RAIN_FILL_EXIT 1
-#endif
-#if SMART_RAIN_FILL_EXIT
 #define SMART_A_FILL_QUICK(drain)                                                                                      \
     "v_mul_f64 %[eh], %[hz], %[ex]\n\t"                                                                                \
     "v_fma_f64 %[xf], -%[eh], %[tot], %[ex]\n\t" SMART_A_FILL1("l0", "xf") "v_mul_f64 %[xs], %[eh], %[tot]\n\t"        \
@@ -129,9 +125,6 @@
         SMART_A_FILL1("l3", "t1") SMART_A_FILL1("l4", "t1") SMART_A_FILL1("l5", "t1")                                  \
             "v_fma_f64 %[xf], -%[pd], %[t1], %[xf]\n\t"                                                                \
             "v_fma_f64 %[xs], %[pd], %[t1], %[xs]\n\t" drain "6:\n\t"
-#else
-#define SMART_A_FILL_QUICK(drain) SMART_A_FILL(drain)
-#endif
 // s', s'^2 and s'^3 live in the registers of three temporaries that are dead by the time the leaks start (the excess,
 // e_h and the routing / cascade temporary): 6 VGPRs less
 #define SMART_S1 "ex"
@@ -223,22 +216,11 @@
 #define SMART_A_RAIN_SPLIT                                                                                             \
     "v_fma_f64 %[yd], %[yd], %[ds], %[xd]\n\t"                                                                         \
     "v_fma_f64 %[ydg], %[ydg], %[dg], %[dp]\n\t"
-// the cascade hook of an arm and its out-of-line block; `id`: digits that make the two labels unique in the asm.
-// SMART_ARM_OOL 0 keeps the cascade in line, skipped by a taken branch when it is not due (A/B: tools/gpu_r03_*.sh)
-#ifndef SMART_ARM_OOL
-#define SMART_ARM_OOL 1
-#endif
-#if SMART_ARM_OOL
+// the cascade hook of an arm and its out-of-line block; `id`: digits that make the two labels unique in the asm
 #define SMART_A_CASC_CALM(id) "s_cbranch_vccnz 3" id "0f\n\t3" id "1:\n\t"
 #define SMART_A_CASC_CALM_OOL(id) "3" id "0:\n\t" SMART_A_CASCADE "s_branch 3" id "1b\n\t"
 #define SMART_A_CASC_RAIN(id) "s_cbranch_scc1 4" id "0f\n\t4" id "1:\n\t"
 #define SMART_A_CASC_RAIN_OOL(id) "4" id "0:\n\t" SMART_A_CASCADE "s_branch 4" id "1b\n\t"
-#else
-#define SMART_A_CASC_CALM(id) "s_cbranch_vccz 3" id "1f\n\t" SMART_A_CASCADE "3" id "1:\n\t"
-#define SMART_A_CASC_CALM_OOL(id) ""
-#define SMART_A_CASC_RAIN(id) "s_cbranch_scc0 4" id "1f\n\t" SMART_A_CASCADE "4" id "1:\n\t"
-#define SMART_A_CASC_RAIN_OOL(id) ""
-#endif
 
 // ---- one step ---------------------------------------------------------------------------------------------------
 // dispatch, calm arm (entered by falling through), rain arm, dry arm (left by falling through): one taken branch per
@@ -425,14 +407,7 @@
 #define SMART_P_REPORT(value, after) SMART_P_REPORT_X(value, after, "s[80:81]", "s[82:83]", "s83")
 // (the discharge matrix is written once and read by another kernel, if at all: `nt` keeps it from displacing what the L2
 // holds for the loop -- 1 % of a leg, profiles/r04_ab_store_and_icache.txt)
-#ifndef SMART_STORE_NT
-#define SMART_STORE_NT 1
-#endif
-#if SMART_STORE_NT
 #define SMART_STORE_MOD " nt"
-#else
-#define SMART_STORE_MOD ""
-#endif
 #define SMART_P_REPORT_X(value, after, e, w, whi)                                                                      \
     "s_cmp_eq_u32 %[rep], 0\n\t"                                                                                       \
     "s_cbranch_scc1 96f\n\t" value "s_cmp_eq_u32 s85, 0\n\t"                                                           \
@@ -661,182 +636,82 @@
 // hipcc's own loop over the same arithmetic carries 5 to 8 more per step (a 64-bit counter, a constant rebuilt in
 // every turn, s_waitcnt's for loads that were long in) -- and a lone wavefront issues ONE instruction of any kind
 // per turn of its SIMD.  s', s'^2, s'^3 in registers of their own here: `ex` and `eh` live across the steps.
-// SMART_WET_E32 (round 6).  A wavefront that has its SIMD (nearly) to itself is fed by the instruction fetch: an 8-byte
-// encoding costs it 5.6 cycles, a 4-byte one 4.7 (profiles/r05_microbench_lanes.txt, `probe`) -- and every fp64
-// instruction is a VOP3 of 8 bytes except ONE: v_fmac_f64_e32  dst = src0 * src1 + dst, no modifiers.  22 of the wet
-// step's 73 instructions are of that shape once the powers carry the sign (n_i = -s'^i: l = l * n_i + l is the leak
-// fma(-l, s'^i, l), the same bits -- a product's magnitude does not depend on its factors' signs) and -D sits in a
-// register of its own: the two products of the routing sum, the saturation excess' two shares, and the eighteen leaks.
-// They come in runs of even length, so every 8-byte instruction starts where it did (SMART_A_WET_INTERVAL has the parities).
-// The second leak pass forms its five factors first (four scratch registers more) and then leaks six times in a row.
-#ifndef SMART_WET_E32
-#define SMART_WET_E32 0
-#endif
-#if SMART_WET_E32
-#define SMART_A_ROUTE_W                                                                                                \
-    "v_mul_f64 %[t0], %[cg], %[yg]\n\t"                                                                                \
-    "v_fmac_f64_e32 %[t0], %[cf], %[yf]\n\t"                                                                           \
-    "v_fmac_f64_e32 %[t0], %[cs], %[ys]\n\t"                                                                           \
-    "v_add_f64 %[acc], %[acc], %[riv]\n\t"                                                                             \
-    "v_fma_f64 %[riv], %[riv], %[oma], %[t0]\n\t"
-#define SMART_A_SAT_SHARES                                                                                             \
-    "v_fmac_f64_e32 %[xf], %[npd], %[t1]\n\t"                                                                          \
-    "v_fmac_f64_e32 %[xs], %[pd], %[t1]\n\t"
-#define SMART_A_LEAK_N(l, p) "v_fmac_f64_e32 %[" l "], %[" l "], %[" p "]\n\t"
-// s1 .. p6 hold -s', -s'^2, ... -s'^6 here
-#define SMART_A_LEAKS_W                                                                                                \
-    "v_mul_f64 %[s1], -%[sz], %[tot]\n\t"                                                                              \
-    "v_mul_f64 %[p2], %[s1], -%[s1]\n\t"                                                                               \
-    "v_mul_f64 %[p3], %[p2], -%[s1]\n\t"                                                                               \
-    "v_mul_f64 %[p4], %[p2], -%[p2]\n\t"                                                                               \
-    "v_mul_f64 %[p5], %[p4], -%[s1]\n\t"                                                                               \
-    "v_mul_f64 %[p6], %[p3], -%[p3]\n\t" SMART_A_LEAK_N("l0", "s1") SMART_A_LEAK_N("l1", "p2")                         \
-        SMART_A_LEAK_N("l2", "p3") SMART_A_LEAK_N("l3", "p4") SMART_A_LEAK_N("l4", "p5") SMART_A_LEAK_N("l5", "p6")    \
-            SMART_A_LSUM("ai") "v_mul_f64 %[t1], %[s1], 0.5\n\t"                                                       \
-                               "v_mul_f64 %[t0], %[s1], %[k3]\n\t"                                                     \
-                               "v_ldexp_f64 %[xg], %[s1], -2\n\t"                                                      \
-                               "v_mul_f64 %[q1], %[s1], %[k5]\n\t"                                                     \
-                               "v_mul_f64 %[q2], %[s1], %[k6]\n\t" SMART_A_LEAK_N("l0", "s1") SMART_A_LEAK_N("l1", "t1") \
-                SMART_A_LEAK_N("l2", "t0") SMART_A_LEAK_N("l3", "xg") SMART_A_LEAK_N("l4", "q1")                       \
-                    SMART_A_LEAK_N("l5", "q2") SMART_A_LEAK_N("l0", "p6") SMART_A_LEAK_N("l1", "p5")                   \
-                        SMART_A_LEAK_N("l2", "p4") SMART_A_LEAK_N("l3", "p3") SMART_A_LEAK_N("l4", "p2")               \
-                            SMART_A_LEAK_N("l5", "s1")
-#else
-#define SMART_A_ROUTE_W SMART_A_ROUTE
-#define SMART_A_SAT_SHARES                                                                                             \
-    "v_fma_f64 %[xf], -%[pd], %[t1], %[xf]\n\t"                                                                        \
-    "v_fma_f64 %[xs], %[pd], %[t1], %[xs]\n\t"
-#define SMART_A_LEAKS_W SMART_A_LEAKS_("s1", "p2", "p3", "")
-#endif
-#define SMART_A_WET_HEAD SMART_A_ROUTE_W "v_fma_f64 %[xf], -%[eh], %[tot], %[ex]\n\t" SMART_A_FILL1("l0", "xf")
+// (v_fmac_f64_e32, the one 4-byte fp64 encoding, for the 22 instructions of the step that can take its shape: built and
+// measured in round 6, no gain -- profiles/r06_ab_wet_e32.txt)
+#define SMART_A_WET_HEAD SMART_A_ROUTE "v_fma_f64 %[xf], -%[eh], %[tot], %[ex]\n\t" SMART_A_FILL1("l0", "xf")
 #define SMART_A_WET_FILL_TAIL                                                                                          \
     SMART_A_FILL1("l1", "t1") SMART_A_FILL1("l2", "t1") SMART_A_FILL1("l3", "t1") SMART_A_FILL1("l4", "t1")            \
-        SMART_A_FILL1("l5", "t1") "v_mul_f64 %[xs], %[eh], %[tot]\n\t" SMART_A_SAT_SHARES
+        SMART_A_FILL1("l5", "t1") "v_mul_f64 %[xs], %[eh], %[tot]\n\t"                                                 \
+                                  "v_fma_f64 %[xf], -%[pd], %[t1], %[xf]\n\t"                                          \
+                                  "v_fma_f64 %[xs], %[pd], %[t1], %[xs]\n\t"
 #define SMART_A_WET_REST                                                                                               \
-    SMART_A_LEAKS_W "v_add_f64 %[t1], %[tot], -%[ai]\n\t"                                                              \
+    SMART_A_LEAKS_("s1", "p2", "p3", "") "v_add_f64 %[t1], %[tot], -%[ai]\n\t"                                                            \
                     "v_add_f64 %[xf], %[xf], %[t1]\n\t" SMART_A_TOT_XG                                                 \
                     "v_fma_f64 %[ys], %[ys], %[ds], %[xs]\n\t"                                                         \
                     "v_fma_f64 %[yf], %[yf], %[df], %[xf]\n\t"                                                         \
                     "v_fma_f64 %[yg], %[yg], %[dg], %[xg]\n\t"                                                         \
                     "v_add_f64 %[xgs], %[xgs], %[xg]\n\t"
 #define SMART_A_WET_STEP SMART_A_WET_HEAD SMART_A_WET_FILL_TAIL SMART_A_WET_REST
-// SMART_WET_MODES 0: every step fills all six layers (round 3's first form, kept for the A/B).
-// 1 / 2: two loops.  While the rain excess of every lane fits into the TOP layer -- 39 % of the wet wave-steps of the
+// Two kinds of step.  While the rain excess of every lane fits into the TOP layer -- 39 % of the wet wave-steps of the
 // headline workload, 58 % of those of 6-hourly forcing, and within an interval a prefix of its steps: the top layer
 // fills up, it does not empty under rain -- the other five layers see  t = l + 0; l = min(t, z); t - l = 0,  the
 // identity as long as no layer is above its capacity (`ok`, wave-uniform, known at the start of the launch: nothing
-// but a caller's initial state puts a layer there), and the saturation excess is zero: 15 instructions for a compare
-// and a branch that is NOT taken.  The first step that leaves something over in any lane (or meets a NaN: v_cmp_nle)
-// jumps into the middle of the loop of full steps and the interval ends there: one taken branch per interval, where
-// an exit inside every step (the kernels with exits, FastModel::kExits) costs a lone wavefront one per step.
-// Bit-identical to mode 0 (tools/debug/steps_bits.py).  2: both loops unrolled twice.
-#ifndef SMART_WET_MODES
-#define SMART_WET_MODES 3
-#endif
+// but a caller's initial state puts a layer there), and the saturation excess is zero: an ABSORBED step spends a
+// compare and a branch that is NOT taken instead of those 15 instructions.  The first step that leaves something over
+// in any lane (or meets a NaN: v_cmp_nle) jumps into the middle of the same step of the FULL kind, which fills all six
+// layers, and the interval ends in full steps: one taken branch per interval, where an exit inside every step (the
+// kernels with exits, FastModel::kExits) costs a lone wavefront one per step.  Same instructions per layer that is
+// filled, same bits as filling all six in every step (tools/debug/steps_bits.py, profiles/r03_steps_bits.txt).
 #define SMART_A_WET_ABSORBED(fix)                                                                                      \
     SMART_A_WET_HEAD "v_cmp_nle_f64 vcc, %[t1], 0\n\t"                                                                 \
                      "s_cbranch_vccnz " fix "f\n\t"                                                                    \
                      "v_mul_f64 %[xs], %[eh], %[tot]\n\t" SMART_A_WET_REST
 #define SMART_A_WET_FULL(fix) SMART_A_WET_HEAD fix ":\n\t" SMART_A_WET_FILL_TAIL SMART_A_WET_REST
-#if SMART_WET_MODES == 0
-#define SMART_A_WET_INTERVAL                                                                                           \
-    "s_add_i32 %[cnt], %[n], 1\n\t"                                                                                    \
-    "s_lshr_b32 %[cnt], %[cnt], 1\n\t"                                                                                 \
-    "s_bitcmp1_b32 %[n], 0\n\t"                                                                                        \
-    "s_cbranch_scc1 6f\n\t"                                                                                            \
-    "5:\n\t" SMART_A_WET_STEP "6:\n\t" SMART_A_WET_STEP "s_add_i32 %[cnt], %[cnt], -1\n\t"                             \
-    "s_cmp_lg_u32 %[cnt], 0\n\t"                                                                                       \
-    "s_cbranch_scc1 5b\n\t"
-#elif SMART_WET_MODES == 1
-// cnt counts up from -n: s_add_u32 carries out (SCC) when it reaches zero.
-// WHERE the 8-byte instructions lie counts (round 4).  Every fp64 instruction is a 64-bit encoding; one that starts at
-// 4 mod 8 straddles a 32-byte fetch line every fourth time, and a wavefront that has its SIMD to itself waits for the
-// second half (a same-instructions, same-registers shift of the step loop by 4 bytes moved its launch by 4.5 %:
-// profiles/r04_placement_phases.txt).  Scalar instructions are 4 bytes, so the parity of a run of vector instructions is
-// the parity of the number of scalar ones in front of it -- here, by hand:
-//   the asm starts on an 8-byte boundary (SMART_A_ALIGN8: at most one s_nop, once per interval);
-//   the three entry instructions put label 5 at 4 mod 8: the 10 instructions of the absorbed step's head straddle, the
-//   s_cbranch_vccnz behind them puts its other 47 on the boundary, counter and back-edge (8 bytes) keep it there;
-//   an s_nop behind `s_branch 9f` (never executed) puts label 6 -- the loop of full steps, 73 instructions and 8 bytes
-//   of scalar ones a turn -- on the boundary as a whole.  Round 3's build had it at 4 mod 8 in the run loop.
-#define SMART_A_WET_INTERVAL                                                                                           \
-    SMART_A_ALIGN8 "s_sub_u32 %[cnt], 0, %[n]\n\t"                                                                     \
-    "s_cmp_eq_u32 %[ok], 0\n\t"                                                                                        \
-    "s_cbranch_scc1 6f\n\t"                                                                                            \
-    "5:\n\t" SMART_A_WET_ABSORBED("7") "s_add_u32 %[cnt], %[cnt], 1\n\t"                                               \
-    "s_cbranch_scc0 5b\n\t"                                                                                            \
-    "s_branch 9f\n\t"                                                                                                  \
-    "s_nop 0\n\t"                                                                                                      \
-    "6:\n\t" SMART_A_WET_FULL("7") "s_add_u32 %[cnt], %[cnt], 1\n\t"                                                   \
-    "s_cbranch_scc0 6b\n\t"                                                                                            \
-    "9:\n\t"
-#elif SMART_WET_MODES == 3
-// FOUR steps per turn of either loop (round 4).  What a lone wavefront pays at the end of every step of mode 1 is a taken
-// branch: 24 cycles and more (tools/microbench/lone.hip) on a step of 57 to 73 vector instructions; a branch that is not
-// taken costs it 16, so unrolling with a test between the copies (mode 2) gains next to nothing.  Here the n mod 4
-// steps that do not fill a turn come first, in mode 1's loops; the rest runs four to a turn with one counter and one
-// back-edge per turn.  The absorbed loops leave for the full ones as in mode 1: from copy k into the middle of copy k.
-// Same instructions per step, same bits.  Parities as in mode 1: an absorbed step starts at 4 mod 8 and ends on the
-// boundary -- an s_nop between the copies of a turn (4 cycles against eleven straddling instructions); the full steps
-// are 64-bit encodings throughout and start on the boundary.
-#ifndef SMART_WET_TURN
-#define SMART_WET_TURN 4 // steps per turn: 4 or 8
-#endif
-#if SMART_WET_TURN == 8
-#define SMART_A_WET_SHIFT "3"
-#define SMART_A_WET_MASK "7"
-#define SMART_A_WET_ABS_MORE                                                                                           \
-    "s_nop 0\n\t" SMART_A_WET_ABSORBED("75") "s_nop 0\n\t" SMART_A_WET_ABSORBED("76") "s_nop 0\n\t" SMART_A_WET_ABSORBED("77") \
-    "s_nop 0\n\t" SMART_A_WET_ABSORBED("78")
-#define SMART_A_WET_FULL_MORE SMART_A_WET_FULL("75") SMART_A_WET_FULL("76") SMART_A_WET_FULL("77") SMART_A_WET_FULL("78")
-#else
-#define SMART_A_WET_SHIFT "2"
-#define SMART_A_WET_MASK "3"
-#define SMART_A_WET_ABS_MORE ""
-#define SMART_A_WET_FULL_MORE ""
-#endif
+// SMART_A_WET_INTERVAL: a loop of absorbed steps (labels 5, 25) and one of full steps (6, 31; entered at 40 when a layer
+// may be above its capacity, `ok` == 0).  Each takes the n mod 4 steps that do not fill a turn first, one step per
+// turn (5, 6: cnt counts up from -(n mod 4), s_add_u32 carries out -- SCC -- when it reaches zero), then n / 4 turns of
+// FOUR steps with one counter and one back-edge per turn (25, 31): a taken branch costs a lone wavefront 24 cycles and
+// more (tools/microbench/lone.hip) on a step of 57 to 73 vector instructions, one that is not taken 16, so a test
+// between the copies would gain next to nothing (profiles/r04_ab_wet_turns.txt; eight steps per turn: no better).  An
+// absorbed step leaves for the full ones from copy k into the middle of copy k (labels 7, 71 .. 74).
+// WHERE the 8-byte instructions lie counts.  Every fp64 instruction is a 64-bit encoding; one that starts at 4 mod 8
+// straddles a 32-byte fetch line every fourth time, and a wavefront that has its SIMD to itself waits for the second
+// half (a same-instructions, same-registers shift of the step loop by 4 bytes moved its launch by 4.5 %:
+// profiles/r04_placement_phases.txt).  Scalar instructions are 4 bytes, so the parity of a run of vector instructions
+// is the parity of the number of scalar ones in front of it -- here, by hand: the asm starts on an 8-byte boundary
+// (SMART_A_ALIGN8: at most one s_nop, once per interval); five scalar instructions put label 5, and so every absorbed
+// step, at 4 mod 8: the 10 instructions of its head straddle, the s_cbranch_vccnz behind them puts its other 47 on the
+// boundary, and counter and back-edge (8 bytes) -- in a turn of four, an s_nop (4 cycles) between the copies -- put
+// the next step where this one was.  The full steps are 64-bit encodings throughout and start on the boundary: label 6
+// by itself, label 31 behind an s_nop.
 #define SMART_A_WET_GROUPS                                                                                             \
-    "s_lshr_b32 %[cnt], %[n], " SMART_A_WET_SHIFT "\n\t"                                                               \
+    "s_lshr_b32 %[cnt], %[n], 2\n\t"                                                                                  \
     "s_sub_u32 %[cnt], 0, %[cnt]\n\t"                                                                                  \
     "s_cbranch_scc0 9f\n\t"
 #define SMART_A_WET_INTERVAL                                                                                           \
     SMART_A_ALIGN8 "s_cmp_eq_u32 %[ok], 0\n\t"                                                                         \
     "s_cbranch_scc1 40f\n\t"                                                                                           \
-    "s_and_b32 %[cnt], %[n], " SMART_A_WET_MASK "\n\t"                                                                 \
+    "s_and_b32 %[cnt], %[n], 3\n\t"                                                                                  \
     "s_cbranch_scc0 20f\n\t"                                                                                           \
     "s_sub_u32 %[cnt], 0, %[cnt]\n\t"                                                                                  \
     "5:\n\t" SMART_A_WET_ABSORBED("7") "s_add_u32 %[cnt], %[cnt], 1\n\t"                                               \
     "s_cbranch_scc0 5b\n\t"                                                                                            \
     "20:\n\t" SMART_A_WET_GROUPS "25:\n\t" SMART_A_WET_ABSORBED("71") "s_nop 0\n\t" SMART_A_WET_ABSORBED("72")         \
-    "s_nop 0\n\t" SMART_A_WET_ABSORBED("73") "s_nop 0\n\t" SMART_A_WET_ABSORBED("74") SMART_A_WET_ABS_MORE                   \
+    "s_nop 0\n\t" SMART_A_WET_ABSORBED("73") "s_nop 0\n\t" SMART_A_WET_ABSORBED("74")                        \
     "s_add_u32 %[cnt], %[cnt], 1\n\t"                                                                                  \
     "s_cbranch_scc0 25b\n\t"                                                                                           \
     "s_branch 9f\n\t"                                                                                                  \
     "40:\n\t"                                                                                                          \
-    "s_and_b32 %[cnt], %[n], " SMART_A_WET_MASK "\n\t"                                                                 \
+    "s_and_b32 %[cnt], %[n], 3\n\t"                                                                                  \
     "s_cbranch_scc0 30f\n\t"                                                                                           \
     "s_sub_u32 %[cnt], 0, %[cnt]\n\t"                                                                                  \
     "6:\n\t" SMART_A_WET_FULL("7") "s_add_u32 %[cnt], %[cnt], 1\n\t"                                                   \
     "s_cbranch_scc0 6b\n\t"                                                                                            \
     "30:\n\t" SMART_A_WET_GROUPS "s_nop 0\n\t"                                                                         \
     "31:\n\t" SMART_A_WET_FULL("71") SMART_A_WET_FULL("72") SMART_A_WET_FULL("73") SMART_A_WET_FULL("74")              \
-    SMART_A_WET_FULL_MORE "s_add_u32 %[cnt], %[cnt], 1\n\t"                                                                                  \
+    "s_add_u32 %[cnt], %[cnt], 1\n\t"                                                                                  \
     "s_cbranch_scc0 31b\n\t"                                                                                           \
     "9:\n\t"
-#else
-#define SMART_A_WET_INTERVAL                                                                                           \
-    "s_sub_u32 %[cnt], 0, %[n]\n\t"                                                                                    \
-    "s_cmp_eq_u32 %[ok], 0\n\t"                                                                                        \
-    "s_cbranch_scc1 6f\n\t"                                                                                            \
-    "5:\n\t" SMART_A_WET_ABSORBED("7") "s_add_u32 %[cnt], %[cnt], 1\n\t"                                               \
-    "s_cbranch_scc1 9f\n\t" SMART_A_WET_ABSORBED("8") "s_add_u32 %[cnt], %[cnt], 1\n\t"                                \
-    "s_cbranch_scc0 5b\n\t"                                                                                            \
-    "s_branch 9f\n\t"                                                                                                  \
-    "6:\n\t" SMART_A_WET_FULL("7") "s_add_u32 %[cnt], %[cnt], 1\n\t"                                                   \
-    "s_cbranch_scc1 9f\n\t" SMART_A_WET_FULL("8") "s_add_u32 %[cnt], %[cnt], 1\n\t"                                    \
-    "s_cbranch_scc0 6b\n\t"                                                                                            \
-    "9:\n\t"
-#endif
 // ... and the calm interval: `n` wet steps with ZERO excess (no rain, no evaporation: the night block of sub-daily
 // data) need no filling -- with no layer above capacity it is the identity, as in the calm arm of the step loop: 51
 // instructions a step instead of 73.

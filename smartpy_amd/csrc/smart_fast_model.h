@@ -39,35 +39,12 @@
 // dt / k <= 2), so the discharge stays within ~1e-12 relative of the reference (measured 1.5e-12 at most over 256 LHS
 // rows x 10 years hourly, median 2.5e-14; gate in tests: 1e-9; contract: 1e-6).
 //
-// Tuning knobs (macros) are kept so that tools/ab_variants.sh can A/B them on one box; the defaults are the
-// measured winners.  Tried and not kept: see DESIGN.md section 4.1.
+// The macros a build may still set with -D are listed at the top of smart_device.h.  Tried and not kept: see
+// DESIGN.md section 4.1.
 #pragma once
 
 #include "smart_device.h"
 #include "smart_fast_arms.h"
-
-#ifndef SMART_FAST_EARLY_EXIT
-#define SMART_FAST_EARLY_EXIT 1
-#endif
-#ifndef SMART_FAST_DRY_EXIT2
-#define SMART_FAST_DRY_EXIT2 1
-#endif
-#ifndef SMART_FAST_INTERVALS
-#define SMART_FAST_INTERVALS 1
-#endif
-#ifndef SMART_FAST_BALANCE_SUMS
-#define SMART_FAST_BALANCE_SUMS 1
-#endif
-#ifndef SMART_FAST_LEAK_BALANCE
-#define SMART_FAST_LEAK_BALANCE 1
-#endif
-#ifndef SMART_FILL_EXITS
-#define SMART_FILL_EXITS 2 // exits after the first and after the second layer of the filling cascade (kExits kernels)
-#endif
-#ifndef SMART_WET_UNROLL
-#define SMART_WET_UNROLL 1
-#endif
-
 
 namespace smart {
 
@@ -331,10 +308,7 @@ struct FastModel {
         const double of = hp * ex;
         ex = fma(-hp, ex, ex);
         fill(l0, ex, z);
-#if SMART_FAST_EARLY_EXIT
-        if (excess_left(ex))
-#endif
-        {
+        if (excess_left(ex)) {
             fill(l1, ex, z);
             fill(l2, ex, z);
             fill(l3, ex, z);
@@ -380,7 +354,7 @@ struct FastModel {
     // groundwater total after 7,680 steps).  Fine for a total that is millimetres; not for the deep part on its own,
     // which SPLIT therefore sums directly (deep_leak).  Filling as t = l + ex; l = min(t, z); ex = t - l (3 instead
     // of 4 per layer).
-    static constexpr bool kLeakBalance = SMART_FAST_LEAK_BALANCE && MERGE && !GUARD;
+    static constexpr bool kLeakBalance = MERGE && !GUARD;
     static_assert(kLeakBalance || !SPLIT, "SPLIT is implemented in wet_balance()");
 
     // Wave-uniform early exits in the filling cascade of a wet step (no lane has excess left after the top layer: 32 %
@@ -419,15 +393,11 @@ struct FastModel {
         fill3(l0, rem, z);
         if (!kExits || excess_left(rem)) {
             fill3(l1, rem, z);
-            if (!kExits || SMART_FILL_EXITS < 2 || excess_left(rem)) {
+            if (!kExits || excess_left(rem)) { // two exits: behind the first and behind the second layer
                 fill3(l2, rem, z);
-                if (!kExits || SMART_FILL_EXITS < 3 || excess_left(rem)) {
-                    fill3(l3, rem, z);
-                    if (!kExits || SMART_FILL_EXITS < 4 || excess_left(rem)) {
-                        fill3(l4, rem, z);
-                        fill3(l5, rem, z);
-                    }
-                }
+                fill3(l3, rem, z);
+                fill3(l4, rem, z);
+                fill3(l5, rem, z);
             }
         }
         const double p2 = s1 * s1, p3 = p2 * s1, p4 = p2 * p2, p5 = p4 * s1, p6 = p3 * p3;
@@ -475,7 +445,7 @@ struct FastModel {
 #ifndef SMART_WET_ASM
 #define SMART_WET_ASM 1
 #endif
-    static constexpr bool kWetAsm = SMART_WET_ASM && kLeakBalance && !kExits && !SPLIT && SMART_FAST_BALANCE_SUMS && !STIFF;
+    static constexpr bool kWetAsm = SMART_WET_ASM && kLeakBalance && !kExits && !SPLIT && !STIFF;
 
     // `n` wet steps with ZERO excess for every lane (rain == 0 and peva == 0 over the run: wave-uniform, decided by the
     // caller on the scalar unit; never when a layer may be above its capacity): no overland flow, nothing to fill
@@ -498,7 +468,7 @@ struct FastModel {
     }
 
     // `n` wet steps with the same rain excess: the layer sum is handed from step to step
-    // `fits`: no layer of this wavefront is above its capacity (wave-uniform; SMART_WET_MODES in smart_fast_arms.h)
+    // `fits`: no layer of this wavefront is above its capacity (wave-uniform; SMART_A_WET_INTERVAL in smart_fast_arms.h)
     __device__ __forceinline__ void wet_interval(double ex, long n, double &acc, double &num, double &den,
                                                  const bool fits = false)
     {
@@ -509,23 +479,6 @@ struct FastModel {
             double tot = layer_sum();
             double t0, t1, xs, xf, xg, w_s1, w_p2, w_p3, w_p4, w_p5, w_p6, w_ai;
             int cnt;
-#if SMART_WET_E32
-            // (the powers carry the sign here -- n_i = -s'^i -- so the second pass's factors are +1/2 ... +1/6 of -s', and
-            // -D sits in a register: smart_fast_arms.h, SMART_WET_E32)
-            double w_q1, w_q2;
-            asm volatile(SMART_A_WET_INTERVAL
-                         : [l0] "+v"(l0), [l1] "+v"(l1), [l2] "+v"(l2), [l3] "+v"(l3), [l4] "+v"(l4), [l5] "+v"(l5),
-                           [ys] "+v"(u_ove), [yf] "+v"(u_int), [yg] "+v"(u_sgw), [riv] "+v"(u_riv), [acc] "+v"(acc),
-                           [tot] "+v"(tot), [xgs] "+v"(xg_sum), [t0] "=&v"(t0), [t1] "=&v"(t1), [xs] "=&v"(xs),
-                           [xf] "=&v"(xf), [xg] "=&v"(xg), [s1] "=&v"(w_s1), [p2] "=&v"(w_p2), [p3] "=&v"(w_p3),
-                           [p4] "=&v"(w_p4), [p5] "=&v"(w_p5), [p6] "=&v"(w_p6), [ai] "=&v"(w_ai), [q1] "=&v"(w_q1),
-                           [q2] "=&v"(w_q2), [cnt] "=&s"(cnt)
-                         : [cs] "v"(car_s), [cf] "v"(car_f), [cg] "v"(car_g), [oma] "v"(om_ar), [ds] "v"(dec_s),
-                           [df] "v"(dec_f), [dg] "v"(dec_g), [sz] "v"(sz), [z] "v"(z), [pd] "v"(pD), [npd] "v"(-pD),
-                           [ex] "v"(ex), [eh] "v"(e_h), [k3] "s"(1.0 / 3.0), [k5] "s"(0.2), [k6] "s"(1.0 / 6.0),
-                           [n] "s"((int)n), [ok] "s"(__builtin_amdgcn_readfirstlane((int)fits))
-                         : "scc", "vcc");
-#else
             asm volatile(SMART_A_WET_INTERVAL
                          : [l0] "+v"(l0), [l1] "+v"(l1), [l2] "+v"(l2), [l3] "+v"(l3), [l4] "+v"(l4), [l5] "+v"(l5),
                            [ys] "+v"(u_ove), [yf] "+v"(u_int), [yg] "+v"(u_sgw), [riv] "+v"(u_riv), [acc] "+v"(acc),
@@ -537,14 +490,13 @@ struct FastModel {
                            [eh] "v"(e_h), [k3] "s"(-(1.0 / 3.0)), [k5] "s"(-0.2), [k6] "s"(-(1.0 / 6.0)),
                            [n] "s"((int)n), [ok] "s"(__builtin_amdgcn_readfirstlane((int)fits))
                          : "scc", "vcc");
-#endif
         } else if (kLeakBalance) {
             const double e_h = ex * hz;
             double tot = layer_sum();
-            // unrolled: a taken branch costs a wavefront that has its SIMD (nearly) to itself about as much as a
-            // dozen vector instructions (profiles/r01_microbench_valu_salu_branch.txt), and the loop's back-edge
-            // is one per 74
-#pragma unroll SMART_WET_UNROLL
+            // not unrolled: a taken branch costs a wavefront that has its SIMD (nearly) to itself about as much as a
+            // dozen vector instructions (profiles/r01_microbench_valu_salu_branch.txt), but the loop's back-edge is
+            // one per 74 and hidden already (unrolled 2 / 4 / 8 times: +-0.5 %)
+#pragma unroll 1
             for (long k = 0; k < n; ++k) {
                 route_and_sum(acc, num, den);
                 wet_balance(ex, e_h, tot);
@@ -566,17 +518,11 @@ struct FastModel {
         // negative C (GUARD) hands a NEGATIVE demand down, which the next layer takes as an addition
         // (structure.py:410-413: `if lvl >= deficit` holds for any negative deficit), so there only an exact zero ends it
         auto handed_down = [](double x) { return GUARD ? x != 0.0 : x > 0.0; };
-#if SMART_FAST_EARLY_EXIT
         // the demand is met by the top layer for every lane of the wave on 57 % of the dry steps, by the top two on
         // 77 %, and reaches the bottom on 11 % (64 random LHS rows, synthetic hourly forcing): two exits, then all
-        if (__builtin_amdgcn_ballot_w64(handed_down(d)) != 0)
-#endif
-        {
+        if (__builtin_amdgcn_ballot_w64(handed_down(d)) != 0) {
             dry(l1, d, pC);
-#if SMART_FAST_EARLY_EXIT && SMART_FAST_DRY_EXIT2
-            if (__builtin_amdgcn_ballot_w64(handed_down(d)) != 0)
-#endif
-            {
+            if (__builtin_amdgcn_ballot_w64(handed_down(d)) != 0) {
                 dry(l2, d, pC);
                 dry(l3, d, pC);
                 dry(l4, d, pC);
@@ -671,7 +617,7 @@ struct FastModel {
     //   river  U' = U + (q_in - U) a_r        =>  sum_t q_in = sum_t U(t) + (U(T) - U(0)) / a_r,  sum_t U(t) = sum of Q_out
     //   gw     G' = G (1 - a_g) + x cq_g      =>  sum_t G(t) = (G(0) - G(T) + cq_g sum_t x(t)) / a_g
     // so the step only adds the groundwater inflow on wet steps; num / den are assembled once at the end.
-    static constexpr bool kBalanceSums = SMART_FAST_BALANCE_SUMS && MERGE;
+    static constexpr bool kBalanceSums = MERGE;
     double g0, r0, xg_sum;
 
     __device__ void begin_run()
@@ -1149,13 +1095,6 @@ struct FastModel {
         // the two differ by the rounding of n subtractions).  Every lane does the same thing, so a sample's
         // arithmetic does not depend on its wave neighbours; the early exits only skip identity operations.
         double d = -ex * (double)n;
-#if SMART_IV_DEFER
-        // ... and, by the same argument, the demands of CONSECUTIVE dry intervals add up as well: nothing looks at the
-        // layers before the lane's next wet interval, so the demand only joins `pend` here and the cascade runs once
-        // per dry spell, in front of that wet interval (run_ensemble_merged) -- 13 instead of 36 vector instructions
-        // for a dry interval.  `pend` travels in the slice hand-over like the states.
-        pend += d;
-#else
         dry(l0, d, pC);
         if (!kExits || __builtin_amdgcn_ballot_w64(d > 0.0) != 0) {
             dry(l1, d, pC);
@@ -1166,7 +1105,6 @@ struct FastModel {
                 dry(l5, d, pC);
             }
         }
-#endif
         acc += fma(B_r, u_riv, fma(B_q, u_ove, fma(B_i, u_int, B_g * u_sgw)));
         u_riv = fma(P_r, u_riv, fma(A_q, u_ove, fma(A_i, u_int, A_g * u_sgw)));
         u_ove *= P_q;
@@ -1284,12 +1222,7 @@ __device__ inline int wave_class(const KArgs &a, long block, long catchment)
             // below zero -- where its guard `leak < level` lets nothing leak and the fast arithmetic's unguarded leaks
             // would (round 4; the same hole the fuzzer found in the reciprocal path, smart_literal_model.h)
             const double h_init = p[2] * fill;
-#ifdef SMART_NO_HINIT // measurement builds only: what the fast arithmetic makes of such a start
-            wild = is_nan_bits(s_init) || !(s_init <= 0.5);
-            (void)h_init;
-#else
             wild = is_nan_bits(s_init) || !(s_init <= 0.5) || is_nan_bits(h_init) || !(h_init <= 1.0);
-#endif
         }
     }
     const bool any_stiff = __builtin_amdgcn_ballot_w64(stiff) != 0;

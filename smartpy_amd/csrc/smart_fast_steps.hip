@@ -5,14 +5,9 @@
 
 namespace smart {
 
-// SMART_STEPS_WAVES (A/B builds, round 6): ask hipcc for an allocation that lets that many wavefronts of smart_fast_steps
-// share a SIMD (3: <= 168 VGPRs where it takes 170 by itself; profiles/r06_ab_steps_third_wave.txt has what that buys)
-#ifdef SMART_STEPS_WAVES
-#define SMART_STEPS_OCC __attribute__((amdgpu_waves_per_eu(SMART_STEPS_WAVES, SMART_STEPS_WAVES)))
-#else
-#define SMART_STEPS_OCC
-#endif
-SMART_STEPS_OCC SMART_FAST_KERNEL(smart_fast_steps) { merged_kernel<FastModel<false, false, true>, kForcingVarying>(a, forcing, obs, ws); }
+// (170 VGPRs: two wavefronts per SIMD.  An allocation bounded at 168 for a third was measured in round 6 and not kept:
+// profiles/r06_ab_steps_third_wave.txt)
+SMART_FAST_KERNEL(smart_fast_steps) { merged_kernel<FastModel<false, false, true>, kForcingVarying>(a, forcing, obs, ws); }
 
 SMART_FAST_KERNEL(smart_fast_steps_states) { merged_kernel<FastModel<false, false, true, true, true>, kForcingVarying>(a, forcing, obs, ws); }
 

@@ -116,9 +116,6 @@ struct LiteralModelT {
     __device__ __forceinline__ static bool in_range(double x)
     {
         const unsigned long long u = __builtin_bit_cast(unsigned long long, x);
-#ifdef SMART_RECIP_RANGE_R03 // (debug builds only: round 3's [2^-800, 2^800))
-        return u == 0 || u - 0x0df0000000000000ull < 0x6400000000000000ull;
-#endif
         return u == 0 || u - 0x26f0000000000000ull < 0x3200000000000000ull;
     }
 

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """How often the rain excess of a wet step fits into the TOP soil layer for every lane of a wavefront -- the path
-frequencies behind SMART_WET_MODES / SMART_RAIN_FILL_EXIT (smart_fast_arms.h), which tools/isa_model.py weighs the
+frequencies behind SMART_A_WET_INTERVAL / SMART_A_FILL_QUICK (smart_fast_arms.h), which tools/isa_model.py weighs the
 instruction counts with.  A numpy walk of the soil layers alone (structure.py:339-419 as restated in SURVEY.md
 App. A: filling, the three leak passes, the evaporation cascade) over the bench workloads, for the first 2,048 rows
 (32 wavefronts of 64 consecutive rows) of the 1e5-row LHS matrix the bench draws.  Depends on the workload only, not on

@@ -20,7 +20,7 @@
 #   slices-headline    slice counts on the headline run and the run engine
 #   slices-legs        the default slice count against 16 on every bench leg
 #   phases-every       placement of the every-step loop (variants e*: -DSMART_EVERY_PHASE=N), then slices-flat
-#   turns              library variants in tools/variants/ against the default on every bench leg, five interleaved rounds (the wet interval's turns, the lean report)
+#   turns              library variants in tools/variants/ against the default on every bench leg, five interleaved rounds (it settled the wet interval's four steps per turn and the lean report, both plain code now)
 # Everything a stage prints also lands in gpurun_out/<stage>_*.log.
 export TMPDIR=/tmp
 mkdir -p gpurun_out

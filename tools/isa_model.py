@@ -250,7 +250,7 @@ def steps_model(out):
     rain_soil = hist(soil_ops)
     report.append('- of a rain arm, the soil half under EXEC (skipped when no lane is wet): %s' % fmt(rain_soil))
     # ... and of that half, the five lower layers of the filling cascade with the saturation excess (skipped by
-    # s_cbranch_vccz when the top layer takes the excess of every lane: SMART_RAIN_FILL_EXIT)
+    # s_cbranch_vccz when the top layer takes the excess of every lane: SMART_A_FILL_QUICK)
     fill_tail = hist(soil_ops[soil_ops.index('s_cbranch_vccz') + 1:soil_ops.index('s_cbranch_vccz') + 18])
     assert fill_tail['VALU'] == 17 and fill_tail['scalar'] == 0, fill_tail
     report.append('- of that half, the filling below the top layer (skipped when the top layer takes every lane\'s '
@@ -409,7 +409,7 @@ def intervals_model(out):
     assert wet, 'no wet-interval asm found'
     seg = segments(wet[0][2])
     # 5: the loop of steps whose excess the top layer takes in every lane, 6: head of a full step, 7: where the first step
-    # that leaves something over joins it; 9: end.  SMART_WET_MODES 3 (round 4): these two loops take the n mod 4 steps
+    # that leaves something over joins it; 9: end.  SMART_A_WET_INTERVAL (round 4): these two loops take the n mod 4 steps
     # that do not fill a turn; 25 / 31 = the same steps four to a turn (71 ... 74 the joins), one counter and one back-edge
     # per turn, an s_nop between the absorbed copies; 20 / 30 / 40: the group counts
     four = '25' in seg and '31' in seg
