@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """The workflow of the reference's examples/api_usage_example.ipynb on the GPU engine: one simulation with the
-shipped parameter set, then a Latin-hypercube calibration and the two second stages (GLUE, Best).
+shipped parameter set, then a Latin-hypercube calibration and the two second stages (GLUE with its prediction bounds, Best).
 
     python examples/calibrate_example.py [sample_size] [root]
 
@@ -73,11 +73,16 @@ def main():
                 sampling=lhs)
     glue.model.extra = EXTRA
     glue.run()
+    # what a GLUE analysis is run for: the likelihood-weighted prediction bounds of the behavioural ensemble at every
+    # report step (one launch of its own; the [R, N] matrix stays on the GPU, only the [3, R] bounds come back)
+    bounds = glue.prediction_bounds(quantiles=(0.05, 0.5, 0.95), likelihood='NSE', write=True)
     top = Best('Catchment', root, 'csv', 'csv', target='KGE', nb_best=10, constraining={'GW': ('equal', (1.0,))})
     top.model.extra = EXTRA
     top.run()
     if rank == 0:
         print('GLUE: %d behavioural sets -> %s' % (len(glue.behavioural_params), glue.db_file))
+        print('      5 / 50 / 95 %% prediction bounds hold %.1f %% of the observations -> %s'
+              % (100 * bounds.containment, bounds.file))
         print('Best: 10 best KGE among the sets meeting the groundwater constraint -> %s' % top.db_file)
     distributed.finish()        # (several ranks: leave the process group -- without waiting for a communicator that never answered)
 

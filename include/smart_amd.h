@@ -256,6 +256,42 @@ int smart_objfn_hip(int64_t n_samples, int64_t n_reports, const double *sim, int
                     const double *gw_sim, double gw_obs, double *objfn, void *stream);
 
 /*
+ * Weighted quantiles of an existing discharge matrix along the SAMPLE axis, per report step: the GLUE prediction
+ * bounds (likelihood-weighted 5 / 50 / 95 % of the behavioural ensemble).  For one report step with values x_n and
+ * weights w_n >= 0 (n < n_samples), W = sum of w_n, and a probability 0 < q <= 1:
+ *     Q(q) = the smallest value v among the x_n with   sum of w_n over { n : x_n <= v }  >=  q * W.
+ * No interpolation: numpy.quantile(..., method='inverted_cdf', weights=w); with equal weights the plain inverted CDF.
+ * Ties need no tie-break (the sum runs over x_n <= v); a sample with w_n == 0 never decides a result; a NaN value sorts
+ * above +inf, as in numpy.sort, and a quantile that reaches it is NaN; W == 0 gives NaN for every quantile of the step;
+ * -0.0 and +0.0 are the same value.  The weights MUST be finite and >= 0: a precondition, not checked on the device.
+ *   sim[R][ld] sample-minor (the layout smart_run_ensemble_hip writes), weights[N] or NULL = equal weights: device
+ *   pointers; probs[n_probs]: HOST pointer, read before the call returns, each in (0, 1],
+ *   n_probs <= SMART_QUANTILES_MAX_PROBS; out[n_probs][R]: device.  Asynchronous on stream; allocates nothing.
+ * One workgroup per report step, in one of two forms (smartpy_amd/csrc/smart_quantiles.hip) that answer alike:
+ *   SMART_QUANTILES_SORT    the step's values sorted in LDS, the weights scanned in that order, a binary search per
+ *                           probability; n_samples <= smart_quantiles_sort_capacity(), else SMART_E_SIZE
+ *   SMART_QUANTILES_SELECT  any n_samples: no sort, the probabilities bisect the 64-bit key space together
+ *   SMART_QUANTILES_AUTO    sort within its capacity, select beyond
+ * Deterministic: no floating-point atomics, every sum has one association for a given (n_samples, form), so two
+ * launches give the same bits.  The two forms add in different orders: they agree exactly where the partial sums of the
+ * weights are exact, and to the rounding of those sums otherwise.
+ * Errors (all found before the device is touched): SMART_E_NULL sim, probs or out missing; SMART_E_SIZE a size < 1,
+ * ld < n_samples, n_reports >= 2^31, a probability outside (0, 1] or NaN, too many probabilities, the sort form beyond
+ * its capacity; SMART_E_MODE unknown method; then SMART_E_NO_DEVICE without a HIP device.
+ */
+#define SMART_QUANTILES_AUTO 0
+#define SMART_QUANTILES_SORT 1
+#define SMART_QUANTILES_SELECT 2
+#define SMART_QUANTILES_MAX_PROBS 16
+int smart_weighted_quantiles_hip(int64_t n_samples, int64_t n_reports, const double *sim, int64_t ld,
+                                 const double *weights, const double *probs, int32_t n_probs, double *out,
+                                 int32_t method, void *stream);
+
+/* The largest n_samples SMART_QUANTILES_SORT takes: what the LDS of a gfx950 compute unit (160 KiB, all of it open to
+ * one workgroup) holds at 18 bytes per sorted element, rounded down to a power of two -- 8192.  Needs no device. */
+int64_t smart_quantiles_sort_capacity(void);
+
+/*
  * Sampling database, CSV flavour -- the rows MonteCarlo.save writes one by one (montecarlo.py:211-231): every value
  * cast to float32 and printed '%.6e', comma separated, one '\n'-terminated line per sample.  HOST pointers, no
  * device involved.  Appends n_rows lines of n_cols values (row-major float32 table: objective functions, parameters,

@@ -27,6 +27,9 @@ UNITS = {
     # ... except where the literal model lives inside the fast mode (the ill-conditioned rows and rows with NaN or
     # infinite parameters): NaNs honoured -- what a NaN does in the reference's compares is part of what it reproduces
     'smart_fast_guarded.hip': ['-ffp-contract=fast-honor-pragmas'],
+    # the ensemble's weighted quantiles per report step (GLUE prediction bounds): default flags, NaNs honoured -- a
+    # NaN value has a place in the order (above +inf)
+    'smart_quantiles.hip': [],
     'smart_capi.hip': [],
     'smart_hostio.cpp': ['-pthread'],      # host only: the sampling-database writer
 }

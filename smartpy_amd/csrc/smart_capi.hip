@@ -15,6 +15,10 @@ namespace smart {
 void launch_literal(const KArgs &a, dim3 grid, size_t lds_bytes, hipStream_t s, bool rows);
 void launch_onestep(long n, const double *in, double *out, hipStream_t s);
 void launch_river(long n, const double *in, double *out, hipStream_t s);
+long quantiles_sort_capacity();     // smart_quantiles.hip
+int quantiles_max_probs();
+void launch_quantiles(long N, long R, const double *sim, long ld, const double *weights, const double *probs, int K,
+                      double *out, bool sort, hipStream_t s);
 
 static_assert(kStatusSliceTimeout == SMART_STATUS_SLICE_TIMEOUT && kStatusStalePlan == SMART_STATUS_STALE_PLAN,
               "status bits of smart_device.h and include/smart_amd.h");
@@ -1359,6 +1363,45 @@ int smart_objfn_hip(int64_t n_samples, int64_t n_reports, const double *sim, int
     g_err[0] = 0;
     return SMART_OK;
 }
+
+int smart_weighted_quantiles_hip(int64_t n_samples, int64_t n_reports, const double *sim, int64_t ld,
+                                 const double *weights, const double *probs, int32_t n_probs, double *out,
+                                 int32_t method, void *stream)
+{
+    static_assert(SMART_QUANTILES_MAX_PROBS == 16, "QuantileProbs of smart_quantiles.hip");
+    if (!sim || !probs || !out)
+        return fail(SMART_E_NULL, "smart_weighted_quantiles_hip: sim, probs and out are required");
+    if (n_samples < 1 || n_reports < 1 || n_probs < 1 || ld < n_samples)
+        return fail(SMART_E_SIZE, "smart_weighted_quantiles_hip: need n_samples, n_reports, n_probs >= 1 and "
+                                  "ld >= n_samples");
+    if (n_reports > 0x7fffffffll)
+        return fail(SMART_E_SIZE, "smart_weighted_quantiles_hip: n_reports %lld is more than one launch takes (2^31 - 1)",
+                    (long long)n_reports);
+    if (n_probs > SMART_QUANTILES_MAX_PROBS || n_probs > quantiles_max_probs())
+        return fail(SMART_E_SIZE, "smart_weighted_quantiles_hip: %d probabilities, at most %d per call", (int)n_probs,
+                    SMART_QUANTILES_MAX_PROBS);
+    for (int32_t k = 0; k < n_probs; ++k)
+        if (!(probs[k] > 0.0 && probs[k] <= 1.0))
+            return fail(SMART_E_SIZE, "smart_weighted_quantiles_hip: probability %d is %g, outside (0, 1]", (int)k,
+                        probs[k]);
+    if (method != SMART_QUANTILES_AUTO && method != SMART_QUANTILES_SORT && method != SMART_QUANTILES_SELECT)
+        return fail(SMART_E_MODE, "smart_weighted_quantiles_hip: method '%d' unknown.", (int)method);
+    if (method == SMART_QUANTILES_SORT && n_samples > quantiles_sort_capacity())
+        return fail(SMART_E_SIZE, "smart_weighted_quantiles_hip: the sort form takes at most %lld samples, not %lld",
+                    (long long)quantiles_sort_capacity(), (long long)n_samples);
+    int rc = device_ready();
+    if (rc)
+        return rc;
+    const bool sort = method == SMART_QUANTILES_SORT ||
+                      (method == SMART_QUANTILES_AUTO && n_samples <= quantiles_sort_capacity());
+    launch_quantiles((long)n_samples, (long)n_reports, sim, (long)ld, weights, probs, (int)n_probs, out, sort,
+                     (hipStream_t)stream);
+    HIP_TRY(hipGetLastError());
+    g_err[0] = 0;
+    return SMART_OK;
+}
+
+int64_t smart_quantiles_sort_capacity(void) { return quantiles_sort_capacity(); }
 
 int smart_row_class(const double *params, double delta_sec, const double *initial12, double area_m2)
 {

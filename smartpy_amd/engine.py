@@ -581,6 +581,49 @@ def objective_functions(discharge_report_major, obs, gw_sim=None, gw_obs=None):
     return out
 
 
+_QUANTILE_METHODS = {'auto': _lib.QUANTILES_AUTO, 'sort': _lib.QUANTILES_SORT, 'select': _lib.QUANTILES_SELECT}
+
+
+def quantiles_sort_capacity():
+    """The largest number of samples the sort form of weighted_quantiles takes (no device needed)."""
+    return int(_lib.lib().smart_quantiles_sort_capacity())
+
+
+def weighted_quantiles(discharge_report_major, probs, weights=None, method='auto'):
+    """Weighted quantiles over the samples of a stored [R, N] discharge matrix, per report step -> device tensor
+    [K, R] float64 (the GLUE prediction bounds).  Q(q) is the smallest value v of the step with
+    sum(w[x <= v]) >= q * sum(w): numpy's method='inverted_cdf' with weights=, no interpolation; NaN sorts last; a step
+    whose weights sum to zero gives NaN.  probs: K <= 16 probabilities in (0, 1]; weights: [N], finite and >= 0, or
+    None for equal weights; method: 'auto' (by size), 'sort' (N <= quantiles_sort_capacity()) or 'select'."""
+    L = _lib.lib()
+    try:
+        code = _QUANTILE_METHODS[method]
+    except KeyError:
+        raise SmartEngineError(-7, "weighted_quantiles: method '{}' unknown.".format(method))
+    sim = discharge_report_major
+    if not (isinstance(sim, torch.Tensor) and sim.is_cuda):
+        sim = as_device(sim, default_device())
+    if sim.stride(-1) != 1:
+        sim = sim.contiguous()
+    R, N = sim.shape
+    ld = sim.stride(0) if R > 1 else N
+    q = np.ascontiguousarray(np.atleast_1d(np.asarray(probs, dtype=np.float64)))
+    if weights is not None:
+        weights = as_device(weights, sim.device, (N,))
+        bad = int((~(torch.isfinite(weights) & (weights >= 0))).sum())
+        if bad:
+            raise SmartEngineError(-2, "weighted_quantiles: {} of the {} weights are negative or not finite."
+                                   .format(bad, N))
+    out = torch.empty((q.size, R), dtype=torch.float64, device=sim.device)
+    with torch.cuda.device(sim.device):
+        _lib.check(L.smart_weighted_quantiles_hip(N, R, sim.data_ptr(), ld,
+                                                  None if weights is None else weights.data_ptr(),
+                                                  q.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), q.size,
+                                                  out.data_ptr(), code,
+                                                  torch.cuda.current_stream(sim.device).cuda_stream))
+    return out
+
+
 def allsteps(area_m2, delta_sec, length_simu, nd_rain, nd_peva, nd_parameters, nd_initial, report_type, report_gap):
     """smartcpp.allsteps: same arguments and results as run_all_steps (structure.py:149-152,197); host arrays."""
     L = _lib.lib()

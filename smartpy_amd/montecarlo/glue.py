@@ -1,7 +1,24 @@
 """GLUE conditioning run (counterpart of smartpy/montecarlo/glue.py): keep the behavioural sets of a previous
-LHS sampling, re-simulate them (typically on another period)."""
+LHS sampling, re-simulate them (typically on another period) -- and, beyond the reference, hand out what a GLUE
+analysis is run for: the likelihood-weighted prediction bounds of the behavioural ensemble (prediction_bounds)."""
+from csv import writer
+
+import numpy as np
+
 from .montecarlo import MonteCarlo
 from .selection import condition_mask, check_shapes, SecondStage
+from .. import distributed as sdist
+
+
+class PredictionBounds(object):
+    """What GLUE.prediction_bounds returns: `quantiles` (the K probabilities), `bounds` (numpy [K, R] float64, row k
+    the weighted quantile quantiles[k] of the behavioural ensemble's discharge at every report step), `datetime`
+    (the R report stamps, model.timeseries_report[1:]), `containment` (the share of the non-missing observations o_r
+    with bounds[0, r] <= o_r <= bounds[-1, r]; NaN without observations) and `file` (the path written, or None)."""
+
+    def __init__(self, quantiles, bounds, stamps, containment, file=None):
+        self.quantiles, self.bounds, self.datetime = quantiles, bounds, stamps
+        self.containment, self.file = containment, file
 
 
 class GLUE(SecondStage, MonteCarlo):
@@ -25,10 +42,16 @@ class GLUE(SecondStage, MonteCarlo):
             keep = condition_mask(self._device_obj_fns[:, self.objective_fn_indices], self.conditions_values,
                                   self.conditions_types)
             self.behavioural_params = self._rows_as_stored(keep)
+            keep = keep.cpu().numpy()
         else:
             self.behavioural_params = self._get_behavioural_sets(
                 self.sampled_params, self.sampled_obj_fns[:, self.objective_fn_indices],
                 self.conditions_values, self.conditions_types)
+            keep = condition_mask(self.sampled_obj_fns[:, self.objective_fn_indices], self.conditions_values,
+                                  self.conditions_types)
+        #: the sampling run's objective functions of the behavioural rows (float32 [N_behavioural, 7|8], as the
+        #: database keeps them): the numbers the sets were selected on, and the likelihoods prediction_bounds weighs with
+        self.behavioural_obj_fns = self.sampled_obj_fns[keep, :]
         self._set_sample(self.behavioural_params)
 
     @staticmethod
@@ -36,3 +59,64 @@ class GLUE(SecondStage, MonteCarlo):
         """glue.py:222-289 -> the rows of params (float32, possibly none) that meet every condition."""
         check_shapes(params, obj_fns, conditions_val, conditions_typ, 'objective')
         return params[condition_mask(obj_fns, conditions_val, conditions_typ), :]
+
+    # ---- prediction bounds ------------------------------------------------------------------------------
+    def _likelihood_weights(self, likelihood):
+        """None (equal weights) | the name of an objective function (its values in the sampling run, for the
+        behavioural rows) | an array [N_behavioural] -> float64 [N_behavioural] or None.  Nothing is clipped."""
+        n = self._sample.shape[0]
+        if likelihood is None:
+            return None
+        if isinstance(likelihood, str):
+            if likelihood not in self.obj_fn_names:
+                raise Exception("The likelihood '{}' is not one of the objective functions of the sampling run "
+                                "({}).".format(likelihood, ', '.join(self.obj_fn_names)))
+            weights = self.behavioural_obj_fns[:, self.obj_fn_names.index(likelihood)].astype(np.float64)
+        else:
+            weights = np.asarray(likelihood, dtype=np.float64)
+            if weights.shape != (n,):
+                raise Exception("The likelihood array has shape {} where one value per behavioural set ({}) is "
+                                "expected.".format(weights.shape, n))
+        bad = int(np.count_nonzero(~(np.isfinite(weights) & (weights >= 0.0))))
+        if bad:
+            raise Exception("{} of the {} likelihood values are negative or not finite: they cannot be used as "
+                            "weights (shift or select them first, nothing is clipped here).".format(bad, n))
+        return weights
+
+    def prediction_bounds(self, quantiles=(0.05, 0.5, 0.95), likelihood=None, write=False):
+        """The GLUE prediction bounds: at every report step the likelihood-weighted quantiles of the behavioural
+        ensemble's discharge -- Q(q) = the smallest simulated value v with sum(w[x <= v]) >= q * sum(w), no
+        interpolation (engine.weighted_quantiles).  One launch of its own over the behavioural rows; the [R, N] matrix
+        stays on the device and only the [K, R] bounds come back.  likelihood: None = equal weights, the name of an
+        objective function = its values in the sampling run (behavioural_obj_fns), or an array [N_behavioural];
+        negative or non-finite weights raise.  write=True also writes `<out>/<catchment>.SMART.glue.bounds` (CSV:
+        DateTime,q<p>,... with the dates and the '%e' of the modelled flow file).  Under torch.distributed every rank
+        that calls this computes all rows itself (no collective); rank 0 alone writes.  -> PredictionBounds"""
+        import torch
+        from .. import engine
+        q = np.atleast_1d(np.asarray(quantiles, dtype=np.float64))
+        stamps = self.model.timeseries_report[1:]
+        weights = self._likelihood_weights(likelihood)
+        n = self._sample.shape[0]
+        if n == 0:      # no behavioural set: nothing to launch
+            bounds, containment = np.full((q.size, len(stamps)), np.nan), float('nan')
+        else:
+            rows = self._device_sample if self._device_sample is not None else self._sample
+            out = self.model.simulate_ensemble(rows, save_discharge=True, math_mode=self.math_mode)
+            on_device = engine.weighted_quantiles(out.discharge_report_major, q, weights)
+            containment = float('nan')
+            obs = self.model._device_cache[2]       # the observations the launch has left on the device, or None
+            if obs is not None:
+                there = ~torch.isnan(obs)
+                inside = there & (on_device[0] <= obs) & (obs <= on_device[-1])
+                if int(there.sum()) > 0:
+                    containment = float(inside.sum()) / float(there.sum())
+            bounds = on_device.cpu().numpy()
+        path = None
+        if write and sdist.rank_world()[0] == 0:
+            path = '{}{}.SMART.glue.bounds'.format(self.model.out_f, self.model.catchment)
+            with open(path, 'w', newline='', encoding='utf8') as f:
+                w = writer(f, delimiter=',')
+                w.writerow(['DateTime'] + ['q%g' % p for p in q])
+                w.writerows([dt] + ['%e' % v for v in column] for dt, column in zip(stamps, bounds.T))
+        return PredictionBounds(q, bounds, stamps, containment, path)
