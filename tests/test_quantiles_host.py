@@ -53,7 +53,183 @@ def band_violations(x, w, q, v):
     return problems
 
 
+def statement_rows(matrix, w, probs):
+    """statement, all rows at once (for a matrix of very many short rows): the same stable order, the same left-to-right
+    sums, the same single product q * W and the same `cum >= q * W` -> [K, R]."""
+    x = np.asarray(matrix, dtype=np.float64)
+    w = np.ones(x.shape[1]) if w is None else np.asarray(w, dtype=np.float64)
+    order = np.argsort(x, axis=1, kind='stable')
+    cum = np.cumsum(w[order], axis=1)
+    ranked = np.take_along_axis(x, order, axis=1)
+    out = np.full((len(probs), x.shape[0]), np.nan)
+    live = cum[:, -1] > 0.0
+    for k, q in enumerate(probs):
+        first = (cum < (q * cum[:, -1])[:, None]).sum(axis=1)          # cum is non-decreasing: the count IS the position
+        out[k, live] = ranked[live, first[live]]
+    return out
+
+
+# ---- inputs whose thresholds are known to the bit (tests/test_gpu_quantiles.py launches them) -------------------------
+def power_of_two_weights(rng, n):
+    """n weights, integer multiples of 2**-10, all > 0, whose sum W is an exact power of two: integers in [1, 2**10), the
+    last one raised until the total is a power of two, all divided by 1024.  Every partial sum is exact in any order
+    (an integer below 2**34 times 2**-10), W / 2**m is exact, and so is cum / W."""
+    units = rng.integers(1, 2 ** 10, size=n)
+    total = int(units.sum())
+    units[-1] += (1 << (total - 1).bit_length()) - total
+    return units.astype(np.float64) / 1024.0
+
+
+def is_power_of_two(v):
+    m, _ = math.frexp(v)
+    return v > 0.0 and m == 0.5
+
+
+def threshold_probs(x, w, positions):
+    """For a row x of DISTINCT values, weights with exact partial sums and a power-of-two total W, and sorted positions
+    j: the probabilities p_j = cum[j] / W (exact), nextafter(p_j, 2) and nextafter(p_j, 0), and what the definition
+    gives for them -- x_sorted[j]; the next element of POSITIVE weight (x_sorted[j + 1] unless that one weighs nothing:
+    p * W is then above cum[j] by less than one weight unit, and an element of weight zero does not move cum); and
+    x_sorted[j] again (p * W is below cum[j] by less than a unit, so above cum[j - 1]).
+    Every position must carry weight, lie before the last one (j < n - 1) and have weight after it (p_j < 1), so that
+    all probabilities stay inside (0, 1].  -> (probs [3 * len(positions)], values [3 * len(positions)])."""
+    x, w = np.asarray(x, dtype=np.float64), np.asarray(w, dtype=np.float64)
+    order = np.argsort(x, kind='stable')
+    ranked, wr = x[order], w[order]
+    assert np.all(ranked[1:] > ranked[:-1]), 'the values of the row must be distinct'
+    cum = np.cumsum(wr)
+    W = cum[-1]
+    assert is_power_of_two(W)
+    probs, values = [], []
+    for j in positions:
+        assert 0 <= j < x.size - 1 and wr[j] > 0.0 and cum[j] < W, j
+        p = cum[j] / W
+        assert p * W == cum[j]
+        after = j + 1
+        while wr[after] == 0.0:
+            after += 1
+        probs += [p, np.nextafter(p, 2.0), np.nextafter(p, 0.0)]
+        values += [ranked[j], ranked[after], ranked[j]]
+    assert all(0.0 < p <= 1.0 for p in probs)
+    return tuple(float(p) for p in probs), np.array(values)
+
+
+def distinct_rows(rng, R, n):
+    """R independent random permutations of n distinct values."""
+    return np.stack([rng.permutation(n).astype(np.float64) * 0.25 - n / 8.0 for _ in range(R)])
+
+
+def weightless_successor(x, w, rng):
+    """Take the weight off one element of the row x (not its largest, not its smallest) and give it to the row's largest
+    element, so the total stays what it was -> (weights, j): sorted position j is followed by an element of weight zero."""
+    order = np.argsort(x, kind='stable')
+    j = int(rng.integers(0, x.size - 2))
+    w = w.copy()
+    w[order[-1]] += w[order[j + 1]]
+    w[order[j + 1]] = 0.0
+    return w, j
+
+
+# the NaNs a row may hold: quiet and signalling, either sign, with and without a payload
+NAN_BITS = np.array([0x7ff8000000000000, 0xfff8000000000000, 0x7ff8000000000abc, 0xfff8000000000001,
+                     0x7ff0000000000001, 0xfff4000000000000, 0x7fffffffffffffff, 0xffffffffffffffff], dtype=np.uint64)
+NAN_SHARE = 0.4
+
+
+def mixed_nans(rng, size):
+    return rng.choice(NAN_BITS, size=size).view(np.float64)
+
+
+def many_nan_rows(rng, x):
+    """Puts NaNs of every kind on ceil(NAN_SHARE * N) random places of every row of x (its own places per row)."""
+    R, N = x.shape
+    count = math.ceil(NAN_SHARE * N)
+    for r in range(R):
+        x[r, rng.permutation(N)[:count]] = mixed_nans(rng, count)
+    return x
+
+
 # ---- the statement itself -----------------------------------------------------------------------------------------
+THRESHOLD_SIZES = (65, 1025, 2048, 2049, 4096, 4097, 8192)
+SUBNORMAL, HUGE = 2.0 ** -1060, 2.0 ** 900
+
+
+@pytest.mark.parametrize('n', THRESHOLD_SIZES)
+def test_threshold_constructions_are_sound(n):
+    """power_of_two_weights and threshold_probs against the statement: the three probabilities around sixteen partial
+    sums give exactly the values the construction names (also where the successor weighs nothing), and a power-of-two
+    scale of the weights changes nothing.  With 2**-1060 every weight and W itself are subnormal: the partial sums stay
+    exact (multiples of 2**-1070), and so does q * W for a dyadic q; for a q one ulp off a partial sum the product
+    rounds ONTO that sum down there, so the ulp-neighbours are scaled up only."""
+    rng = np.random.default_rng(4000 + n)
+    w = power_of_two_weights(rng, n)
+    assert w.shape == (n,) and (w > 0).all() and np.array_equal(w * 1024.0, np.round(w * 1024.0))
+    assert is_power_of_two(w.sum()) and is_power_of_two(math.fsum(w)) and w.sum() == math.fsum(w)
+    x = distinct_rows(rng, 1, n)[0]
+    positions = rng.choice(n - 1, size=16, replace=False)
+    probs, values = threshold_probs(x, w, positions)
+    assert len(probs) == 48 and len(set(probs)) == 48
+    got = statement([x], w, probs)[:, 0]
+    assert np.array_equal(got, values), (n, positions)
+    ranked = np.sort(x)
+    at = np.searchsorted(ranked, values)
+    assert np.array_equal(at[0::3], positions) and np.array_equal(at[1::3], positions + 1)
+    assert np.array_equal(at[2::3], positions)
+    # ... the successor of one position without weight: one ulp above skips it
+    w0, j = weightless_successor(x, w, rng)
+    assert is_power_of_two(w0.sum()) and w0.sum() == w.sum() and np.count_nonzero(w0 == 0.0) == 1
+    p0, v0 = threshold_probs(x, w0, [j])
+    assert v0.tolist() == [ranked[j], ranked[j + 2], ranked[j]]
+    assert np.array_equal(statement([x], w0, p0)[:, 0], v0)
+    # ... the scale of the weights
+    assert (w * SUBNORMAL > 0).all() and (w * SUBNORMAL < 2.0 ** -1022).all() and w.sum() * SUBNORMAL < 2.0 ** -1022
+    assert np.array_equal(w * SUBNORMAL / SUBNORMAL, w) and np.array_equal(w * HUGE / HUGE, w)
+    rows = rng.normal(size=(2, n))
+    want = statement(rows, w, DYADIC)
+    assert same_bits(statement(rows, w * SUBNORMAL, DYADIC), want) and same_bits(statement(rows, w * HUGE, DYADIC), want)
+    assert not np.isnan(want).any()
+    assert np.array_equal(statement([x], w * HUGE, probs)[:, 0], values)
+    assert np.array_equal(statement([x], w0 * HUGE, p0)[:, 0], v0)
+
+
+def same_bits(a, b):
+    return a.shape == b.shape and np.array_equal(a.view(np.int64), b.view(np.int64))
+
+
+def test_statement_on_rows_where_nans_decide():
+    """numpy sorts every NaN last, whatever its sign and payload: with two fifths of a row NaN (and weights that give
+    them between a sixteenth and a half of the total) the upper quantiles are NaN and the lower ones are not."""
+    assert np.isnan(NAN_BITS.view(np.float64)).all() and len(set(NAN_BITS.tolist())) == len(NAN_BITS)
+    assert np.signbit(NAN_BITS.view(np.float64)).sum() == 4
+    rng = np.random.default_rng(99)
+    for n in (64, 65, 1025, 8192, 8257):
+        x = many_nan_rows(rng, rng.normal(size=(5, n)))
+        assert (np.isnan(x).sum(axis=1) == math.ceil(NAN_SHARE * n)).all() and np.isnan(x).mean() > 1 / 3
+        assert len(set(x[np.isnan(x)].view(np.uint64).tolist())) == len(NAN_BITS)
+        assert np.isnan(np.sort(x, axis=1)[:, -int(NAN_SHARE * n):]).all()
+        w = rng.integers(1, 2 ** 20, size=n).astype(np.float64) / 1024.0
+        want = statement(x, w, DYADIC)                                   # DYADIC = (0.0625, 0.5, 0.9375, 1.0)
+        assert np.isnan(want[2:]).all() and not np.isnan(want[:2]).any(), n
+        assert np.array_equal(want, statement(np.where(np.isnan(x), np.nan, x), w, DYADIC), equal_nan=True)
+        assert np.isnan(statement(mixed_nans(rng, (2, n)), w, DYADIC)).all()
+        # without weight the NaNs decide nothing: the row without them answers the same
+        x[:] = rng.normal(size=(5, n))
+        cols = rng.permutation(n)[:int(NAN_SHARE * n)]
+        w[cols] = 0.0
+        want = statement(np.delete(x, cols, axis=1), np.delete(w, cols), DYADIC)
+        x[:, cols] = mixed_nans(rng, (5, cols.size))
+        assert same_bits(statement(x, w, DYADIC), want) and not np.isnan(want).any()
+
+
+def test_statement_rows_is_the_statement():
+    rng = np.random.default_rng(12)
+    for n, w in ((1, None), (3, np.array([0.25, 0.5, 0.25])), (3, np.zeros(3)), (7, rng.integers(0, 4, size=7) / 4.0)):
+        x = rng.integers(0, 5, size=(50, n)).astype(np.float64)
+        x[rng.random(size=x.shape) < 0.1] = np.nan
+        probs = (0.0625, 0.5, 0.75, 1.0)
+        assert same_bits(statement_rows(x, w, probs), statement(x, w, probs)), n
+
+
 def test_statement_is_numpys_inverted_cdf_with_weights():
     rng = np.random.default_rng(20240607)
     for n in (1, 2, 7, 64, 65, 301):
