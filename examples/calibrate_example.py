@@ -76,6 +76,10 @@ def main():
     # what a GLUE analysis is run for: the likelihood-weighted prediction bounds of the behavioural ensemble at every
     # report step (one launch of its own; the [R, N] matrix stays on the GPU, only the [3, R] bounds come back)
     bounds = glue.prediction_bounds(quantiles=(0.05, 0.5, 0.95), likelihood='NSE', write=True)
+    # split-sample and low-flow scores of the behavioural sets: KGE per hydrological year and the NSE of ln(Q + eps), one
+    # launch each; the [W, N, 7] values stay on the GPU (per_year.device_values) for conditioning on every year
+    per_year = glue.window_objective_functions('hydro_year', write=True)
+    low_flow = glue.window_objective_functions('all', transform='log')
     top = Best('Catchment', root, 'csv', 'csv', target='KGE', nb_best=10, constraining={'GW': ('equal', (1.0,))})
     top.model.extra = EXTRA
     top.run()
@@ -83,6 +87,11 @@ def main():
         print('GLUE: %d behavioural sets -> %s' % (len(glue.behavioural_params), glue.db_file))
         print('      5 / 50 / 95 %% prediction bounds hold %.1f %% of the observations -> %s'
               % (100 * bounds.containment, bounds.file))
+        if len(glue.behavioural_params):
+            print('      KGE per hydrological year, median over the sets: %s -> %s'
+                  % (', '.join('%s: %.3f' % (y, np.nanmedian(per_year.values[w][:, 1])) for w, y in enumerate(per_year.labels)),
+                     per_year.file))
+            print('      NSE of ln(Q + %.3g): best %.4f' % (low_flow.eps, np.nanmax(low_flow.values[0][:, 0])))
         print('Best: 10 best KGE among the sets meeting the groundwater constraint -> %s' % top.db_file)
     distributed.finish()        # (several ranks: leave the process group -- without waiting for a communicator that never answered)
 

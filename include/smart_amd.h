@@ -292,6 +292,41 @@ int smart_weighted_quantiles_hip(int64_t n_samples, int64_t n_reports, const dou
 int64_t smart_quantiles_sort_capacity(void);
 
 /*
+ * Objective functions of an existing discharge matrix PER WINDOW of report steps and on TRANSFORMED flows: split-sample
+ * scores (per hydrological year, season, calibration / evaluation period) and low-flow scores, for every sample.
+ *   sim[R][ld] sample-minor (the layout smart_run_ensemble_hip writes), obs[R] (NaN = missing), window[R] int32 with
+ *   -1 = the report step belongs to no window, else 0 .. n_windows-1 (any other value is a broken PRECONDITION, not
+ *   checked on the device), objfn[n_windows][N][SMART_OBJFN_WINDOW_COLS]: device pointers.  Asynchronous on stream;
+ *   allocates nothing.
+ * For window w and sample n let rows = { r : window[r] == w and obs[r] is not NaN }, e = f(obs[rows]) and
+ * s = f(sim[rows, n]) with f the transform; the seven values NSE, KGE, KGEc, KGEa, KGEb, PBias, RMSE are the formulas
+ * of montecarlo.py:193-209 (smart_objfn_hip's) applied to (s, e).  GW does not depend on a window and has no column.
+ * Two rules of this entry's own:
+ *   - fewer than two rows in a window: NaN in all seven columns, for every sample of that window;
+ *   - a transformed value that is not finite (a negative flow under sqrt or ln, x + eps == 0, a NaN or an infinity in
+ *     the matrix): NaN in all seven columns of that (window, sample); a non-finite f(obs[r]) does it for every sample of
+ *     the window.  (numpy answers with a mixture of NaN and +-inf there.)  A sum of finite transformed values that
+ *     overflows counts as not finite.
+ * Rows of no window are not read, and every element of a row that belongs to a window is loaded once.  Deterministic: no
+ * floating-point atomics, every sum has one association for a given (n_samples, n_reports, window array), so two
+ * launches give the same bits.  n_windows <= smart_objfn_max_windows(): every window walks window[] once more.
+ * Errors (all found before the device is touched): SMART_E_NULL sim, obs, window or objfn missing; SMART_E_SIZE a size
+ * < 1, ld < n_samples, n_reports >= 2^31, n_windows > smart_objfn_max_windows(), eps negative or not finite;
+ * SMART_E_MODE unknown transform; then SMART_E_NO_DEVICE without a HIP device.
+ */
+#define SMART_TRANSFORM_NONE 0     /* f(x) = x            */
+#define SMART_TRANSFORM_SQRT 1     /* f(x) = sqrt(x)      */
+#define SMART_TRANSFORM_LOG 2      /* f(x) = ln(x + eps)  */
+#define SMART_TRANSFORM_INVERSE 3  /* f(x) = 1 / (x + eps) */
+#define SMART_OBJFN_WINDOW_COLS 7  /* NSE, KGE, KGEc, KGEa, KGEb, PBias, RMSE -- GW does not depend on a window */
+int smart_objfn_windows_hip(int64_t n_samples, int64_t n_reports, const double *sim, int64_t ld, const double *obs,
+                            const int32_t *window, int32_t n_windows, int32_t transform, double eps,
+                            double *objfn, void *stream);
+
+/* The largest n_windows smart_objfn_windows_hip takes in one call (1024).  Needs no device. */
+int32_t smart_objfn_max_windows(void);
+
+/*
  * Sampling database, CSV flavour -- the rows MonteCarlo.save writes one by one (montecarlo.py:211-231): every value
  * cast to float32 and printed '%.6e', comma separated, one '\n'-terminated line per sample.  HOST pointers, no
  * device involved.  Appends n_rows lines of n_cols values (row-major float32 table: objective functions, parameters,

@@ -24,6 +24,8 @@ LITERAL_FORM_AUTO, LITERAL_FORM_ROWS, LITERAL_FORM_LANES = 0, 1, 2
 STATUS_SLICE_TIMEOUT, STATUS_STALE_PLAN, STATUS_NONFINITE_FORCING = 0x1, 0x2, 0x4
 QUANTILES_AUTO, QUANTILES_SORT, QUANTILES_SELECT = 0, 1, 2
 QUANTILES_MAX_PROBS = 16
+TRANSFORMS = {'none': 0, 'sqrt': 1, 'log': 2, 'inverse': 3}     # SMART_TRANSFORM_*
+OBJFN_WINDOW_COLS = 7
 
 _dp = ctypes.c_void_p   # device or host address, passed as an integer
 
@@ -63,6 +65,9 @@ SYMBOLS = {
                                                     ctypes.POINTER(ctypes.c_double), ctypes.c_int32, _dp,
                                                     ctypes.c_int32, _dp]),
     'smart_quantiles_sort_capacity': (ctypes.c_int64, []),
+    'smart_objfn_windows_hip': (ctypes.c_int, [ctypes.c_int64, ctypes.c_int64, _dp, ctypes.c_int64, _dp, _dp,
+                                               ctypes.c_int32, ctypes.c_int32, ctypes.c_double, _dp, _dp]),
+    'smart_objfn_max_windows': (ctypes.c_int32, []),
     'smart_db_append_rows': (ctypes.c_int, [ctypes.c_char_p, ctypes.POINTER(ctypes.c_float), ctypes.c_int64,
                                             ctypes.c_int64, ctypes.c_int32]),
     'smart_db_parse_rows': (ctypes.c_int64, [ctypes.c_char_p, ctypes.c_int64, ctypes.c_int64,

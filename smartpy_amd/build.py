@@ -30,6 +30,9 @@ UNITS = {
     # the ensemble's weighted quantiles per report step (GLUE prediction bounds): default flags, NaNs honoured -- a
     # NaN value has a place in the order (above +inf)
     'smart_quantiles.hip': [],
+    # the objective functions per window of report steps, on transformed flows: default flags, NaNs honoured -- a NaN
+    # or an infinity that a transform makes has to reach the sums (it is how the kernel finds it)
+    'smart_objfn_windows.hip': [],
     'smart_capi.hip': [],
     'smart_hostio.cpp': ['-pthread'],      # host only: the sampling-database writer
 }

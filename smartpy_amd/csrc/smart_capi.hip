@@ -19,6 +19,9 @@ long quantiles_sort_capacity();     // smart_quantiles.hip
 int quantiles_max_probs();
 void launch_quantiles(long N, long R, const double *sim, long ld, const double *weights, const double *probs, int K,
                       double *out, bool sort, hipStream_t s);
+int objfn_max_windows();            // smart_objfn_windows.hip
+void launch_objfn_windows(long N, long R, const double *sim, long ld, const double *obs, const int *window, int W,
+                          int transform, double eps, double *objfn, hipStream_t s);
 
 static_assert(kStatusSliceTimeout == SMART_STATUS_SLICE_TIMEOUT && kStatusStalePlan == SMART_STATUS_STALE_PLAN,
               "status bits of smart_device.h and include/smart_amd.h");
@@ -1402,6 +1405,41 @@ int smart_weighted_quantiles_hip(int64_t n_samples, int64_t n_reports, const dou
 }
 
 int64_t smart_quantiles_sort_capacity(void) { return quantiles_sort_capacity(); }
+
+int smart_objfn_windows_hip(int64_t n_samples, int64_t n_reports, const double *sim, int64_t ld, const double *obs,
+                            const int32_t *window, int32_t n_windows, int32_t transform, double eps, double *objfn,
+                            void *stream)
+{
+    if (!sim || !obs || !window || !objfn)
+        return fail(SMART_E_NULL, "smart_objfn_windows_hip: sim, obs, window and objfn are required (%s is NULL)",
+                    !sim ? "sim" : (!obs ? "obs" : (!window ? "window" : "objfn")));
+    if (n_samples < 1 || n_reports < 1 || n_windows < 1)
+        return fail(SMART_E_SIZE, "smart_objfn_windows_hip: need n_samples, n_reports, n_windows >= 1 (got %lld, %lld, %d)",
+                    (long long)n_samples, (long long)n_reports, (int)n_windows);
+    if (ld < n_samples)
+        return fail(SMART_E_SIZE, "smart_objfn_windows_hip: ld %lld is less than n_samples %lld", (long long)ld,
+                    (long long)n_samples);
+    if (n_reports > 0x7fffffffll)
+        return fail(SMART_E_SIZE, "smart_objfn_windows_hip: n_reports %lld is more than one launch takes (2^31 - 1)",
+                    (long long)n_reports);
+    if (n_windows > objfn_max_windows())
+        return fail(SMART_E_SIZE, "smart_objfn_windows_hip: n_windows %d, at most %d per call", (int)n_windows,
+                    objfn_max_windows());
+    if (!(eps >= 0.0) || std::isinf(eps))
+        return fail(SMART_E_SIZE, "smart_objfn_windows_hip: eps %g must be finite and >= 0", eps);
+    if (transform < SMART_TRANSFORM_NONE || transform > SMART_TRANSFORM_INVERSE)
+        return fail(SMART_E_MODE, "smart_objfn_windows_hip: transform '%d' unknown.", (int)transform);
+    int rc = device_ready();
+    if (rc)
+        return rc;
+    launch_objfn_windows((long)n_samples, (long)n_reports, sim, (long)ld, obs, window, (int)n_windows, (int)transform, eps,
+                         objfn, (hipStream_t)stream);
+    HIP_TRY(hipGetLastError());
+    g_err[0] = 0;
+    return SMART_OK;
+}
+
+int32_t smart_objfn_max_windows(void) { return objfn_max_windows(); }
 
 int smart_row_class(const double *params, double delta_sec, const double *initial12, double area_m2)
 {

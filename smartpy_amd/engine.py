@@ -624,6 +624,65 @@ def weighted_quantiles(discharge_report_major, probs, weights=None, method='auto
     return out
 
 
+def objfn_max_windows():
+    """The largest number of windows objective_functions_windows takes in one call (no device needed)."""
+    return int(_lib.lib().smart_objfn_max_windows())
+
+
+def objective_functions_windows(discharge_report_major, obs, windows, n_windows=None, transform='none', eps=0.0):
+    """The seven objective functions NSE, KGE, KGEc, KGEa, KGEb, PBias, RMSE of every column of a stored [R, N]
+    discharge matrix, PER WINDOW of report steps and on transformed flows -> device tensor [W, N, 7] float64.
+    windows: [R] integers, -1 = the report step belongs to no window, else 0 .. n_windows-1 (n_windows defaults to
+    max + 1); transform: 'none', 'sqrt', 'log' (ln(x + eps)) or 'inverse' (1 / (x + eps)), applied to the observed and
+    to the simulated flows.  A window with fewer than two observed steps is NaN for every sample; a (window, sample)
+    that meets a transformed value that is not finite is NaN (include/smart_amd.h: smart_objfn_windows_hip)."""
+    L = _lib.lib()
+    try:
+        code = _lib.TRANSFORMS[transform]
+    except (KeyError, TypeError):
+        raise SmartEngineError(-7, "objective_functions_windows: transform '{}' unknown.".format(transform))
+    # the window ids are checked where they lie, before anything is moved or launched
+    if isinstance(windows, torch.Tensor):
+        win = windows.reshape(-1)
+        if win.dtype.is_floating_point or win.dtype == torch.bool:
+            raise SmartEngineError(-2, "objective_functions_windows: windows must be integers.")
+        top = int(win.max()) if win.numel() else -1
+    else:
+        win = np.asarray(windows).reshape(-1)
+        if win.dtype.kind not in 'iu':
+            raise SmartEngineError(-2, "objective_functions_windows: windows must be integers.")
+        top = int(win.max()) if win.size else -1
+    W = top + 1 if n_windows is None else int(n_windows)
+    if W < 1:
+        raise SmartEngineError(-2, "objective_functions_windows: no window (n_windows = {}).".format(W))
+    bad = int(((win < -1) | (win >= W)).sum())
+    if bad:
+        raise SmartEngineError(-2, "objective_functions_windows: {} of the {} window ids are outside -1 .. {}."
+                               .format(bad, len(win), W - 1))
+    sim = discharge_report_major
+    if len(sim.shape) != 2 or sim.shape[0] != len(win):
+        raise SmartEngineError(-2, "objective_functions_windows: {} window ids for a matrix of shape {}."
+                               .format(len(win), tuple(sim.shape)))
+    if not (isinstance(sim, torch.Tensor) and sim.is_cuda):
+        sim = as_device(sim, default_device())
+    if sim.stride(-1) != 1:
+        sim = sim.contiguous()
+    R, N = sim.shape
+    ld = sim.stride(0) if R > 1 else N
+    obs = as_device(obs, sim.device, (R,))
+    if not isinstance(win, torch.Tensor):
+        win = torch.from_numpy(np.ascontiguousarray(win.astype(np.int32)))
+    win = win.to(device=sim.device, dtype=torch.int32).contiguous()
+    out = torch.empty((W, N, _lib.OBJFN_WINDOW_COLS), dtype=torch.float64, device=sim.device)
+    if N == 0:
+        return out
+    with torch.cuda.device(sim.device):
+        _lib.check(L.smart_objfn_windows_hip(N, R, sim.data_ptr(), ld, obs.data_ptr(), win.data_ptr(), W, code,
+                                             float(eps), out.data_ptr(),
+                                             torch.cuda.current_stream(sim.device).cuda_stream))
+    return out
+
+
 def allsteps(area_m2, delta_sec, length_simu, nd_rain, nd_peva, nd_parameters, nd_initial, report_type, report_gap):
     """smartcpp.allsteps: same arguments and results as run_all_steps (structure.py:149-152,197); host arrays."""
     L = _lib.lib()

@@ -179,6 +179,55 @@ class MonteCarlo(object):
         elif failure is not None:
             raise failure
 
+    # ---- split-sample and low-flow scores -----------------------------------------------------------------
+    def window_objective_functions(self, windows='hydro_year', transform='none', eps=None, start_month=10, split=None,
+                                   write=False):
+        """NSE, KGE, KGEc, KGEa, KGEb, PBias and RMSE of every row of the sample PER WINDOW of report steps (per
+        hydrological year, season, period of a split-sample test ...) and on transformed flows ('sqrt', 'log' = ln(Q +
+        eps), 'inverse' = 1 / (Q + eps): low-flow scores).  windows: a `by` word of windows.evaluation_windows (with
+        start_month / split) over the report stamps, or a ready (ids, labels) pair.  eps=None: 0 for 'none' and 'sqrt',
+        one hundredth of the mean observation for 'log' and 'inverse'; the value used is on the result.  One launch of
+        its own over the sample; the [R, N] matrix stays on the device and only [W, N, 7] comes back.  write=True also
+        writes `<out>/<catchment>.SMART.<func>.windows` (one line per sample in the sample's order, the float32 '%.6e'
+        of the sampling database; header NSE@<label>,KGE@<label>,... window by window).  Under torch.distributed every
+        rank that calls this computes all rows itself (no collective); rank 0 alone writes.  -> WindowObjectives"""
+        from .. import engine, windows as swin
+        if transform not in _lib_transforms():
+            raise Exception("The flow transform '{}' is not recognised. Please choose one of: {}."
+                            .format(transform, ', '.join(_lib_transforms())))
+        if isinstance(windows, str):
+            ids, labels = swin.evaluation_windows(self.model.timeseries_report[1:], by=windows, start_month=start_month,
+                                                  split=split)
+        else:
+            ids, labels = windows
+            ids, labels = np.asarray(ids), list(labels)
+        n = self._sample.shape[0]
+        if self.model.nd_flow is None:
+            raise Exception("The observation array does not exist. Please make sure that a value is assigned "
+                            "to the gauged_area_m2 attribute of your SMART class instance.")
+        if eps is None:
+            eps = swin.default_eps(transform, self.model.nd_flow)
+        if n == 0:      # e.g. GLUE with no behavioural set: nothing to launch
+            on_device, values = None, np.empty((len(labels), 0, len(swin.OBJ_FN_NAMES)))
+        else:
+            rows = self._device_sample if self._device_sample is not None else self._sample
+            out = self.model.simulate_ensemble(rows, save_discharge=True, math_mode=self.math_mode)
+            obs = self.model._device_cache[2]       # the observations the launch has left on the device
+            on_device = engine.objective_functions_windows(out.discharge_report_major, obs, ids, n_windows=len(labels),
+                                                           transform=transform, eps=eps)
+            values = on_device.cpu().numpy()
+        path = None
+        if write and sdist.rank_world()[0] == 0:
+            path = self.windows_file
+            _write_windows_file(path, labels, transform, values)
+        return swin.WindowObjectives(labels, transform, float(eps), values, on_device, path)
+
+    @property
+    def windows_file(self):
+        """`<out>/<catchment>.SMART.<func>.windows`: beside the sampling database, whatever its format."""
+        base = self.db_file[:-3] if self.db_file.endswith('.nc') else self.db_file
+        return base + '.windows'
+
     # ---- the per-sample protocol of the reference (spotpy setup class) ------------------------------------
     def parameters(self):
         return np.array([p() for p in self.params])
@@ -218,3 +267,23 @@ class MonteCarlo(object):
 def _f64():
     import torch
     return torch.float64
+
+
+def _lib_transforms():
+    from .._lib import TRANSFORMS
+    return list(TRANSFORMS)
+
+
+def _write_windows_file(path, labels, transform, values):
+    """values [W, N, 7] -> header line + one line per sample, window by window (the sampling database's float32
+    '%.6e', formatted by the library)."""
+    import ctypes
+    from .. import _lib, windows as swin
+    with open(path, 'w', newline='', encoding='utf8') as f:
+        f.write(swin.header_line(labels, transform))
+    W, n, k = values.shape
+    if n == 0:
+        return
+    table = np.ascontiguousarray(np.transpose(values, (1, 0, 2)).reshape(n, W * k).astype(np.float32))
+    _lib.check(_lib.lib().smart_db_append_rows(path.encode('utf8'), table.ctypes.data_as(ctypes.POINTER(ctypes.c_float)),
+                                               table.shape[0], table.shape[1], 0))

@@ -1,0 +1,99 @@
+"""Evaluation windows over the report stamps: which report step belongs to which hydrological year, season, month or
+period of a split-sample test.  Pure host code; the ids go to engine.objective_functions_windows
+(MonteCarlo.window_objective_functions), which scores every sample per window on the GPU.
+"""
+from bisect import bisect_right
+from datetime import datetime
+
+import numpy as np
+
+OBJ_FN_NAMES = ['NSE', 'KGE', 'KGEc', 'KGEa', 'KGEb', 'PBias', 'RMSE']      # the seven columns of a window
+SEASONS = ['DJF', 'MAM', 'JJA', 'SON']
+_SEASON_OF_MONTH = [0, 0, 1, 1, 1, 2, 2, 2, 3, 3, 3, 0]                      # January .. December
+_BY = ('all', 'year', 'hydro_year', 'season', 'month', 'split')
+_STAMP = '%Y-%m-%d %H:%M:%S'
+
+
+def evaluation_windows(stamps, by='hydro_year', start_month=10, split=None):
+    """-> (ids: int32 ndarray [R], labels: list of str) for the R report stamps (datetimes).
+
+    by='all'         one window, 'all'
+    by='year'        the calendar year of the stamp; labelled with the year
+    by='hydro_year'  the twelve months from `start_month`; labelled with the calendar year in which it ENDS
+    by='season'      DJF, MAM, JJA, SON, in that order (the ids interleave along the run)
+    by='month'       '01' .. '12'
+    by='split'       `split` is one datetime or an ascending list of them: window k holds the stamps in
+                     [split[k-1], split[k]), open at both ends of the run; labelled '<first stamp>..<last stamp>'
+
+    Only windows that occur are numbered, in ascending label order (seasons in the order above, periods in time).  A
+    stamp decides its window as it is written in the flow files: nothing is shifted."""
+    if by not in _BY:
+        raise Exception("The kind of evaluation windows '{}' is not recognised. Please choose one of: {}."
+                        .format(by, ', '.join(_BY)))
+    stamps = list(stamps)
+    if len(stamps) == 0:
+        raise Exception("Evaluation windows need at least one report stamp.")
+    if not (isinstance(start_month, (int, np.integer)) and 1 <= start_month <= 12):
+        raise Exception("The first month of the hydrological year must be between 1 and 12, not {}.".format(start_month))
+    if by == 'all':
+        keys, label = [0] * len(stamps), lambda k: 'all'
+    elif by == 'year':
+        keys, label = [s.year for s in stamps], str
+    elif by == 'hydro_year':
+        keys = [s.year + (1 if start_month > 1 and s.month >= start_month else 0) for s in stamps]
+        label = str
+    elif by == 'season':
+        keys, label = [_SEASON_OF_MONTH[s.month - 1] for s in stamps], lambda k: SEASONS[k]
+    elif by == 'month':
+        keys, label = [s.month for s in stamps], lambda k: '%02d' % k
+    else:
+        if split is None:
+            raise Exception("Evaluation windows by 'split' need the date(s) to split at (split=...).")
+        bounds = [split] if isinstance(split, datetime) else list(split)
+        if len(bounds) == 0:
+            raise Exception("Evaluation windows by 'split' need the date(s) to split at (split=...).")
+        if any(b <= a for a, b in zip(bounds, bounds[1:])):
+            raise Exception("The dates to split the evaluation windows at must be in ascending order.")
+        keys = [bisect_right(bounds, s) for s in stamps]
+        ends = {}
+        for k, s in zip(keys, stamps):
+            lo, hi = ends.get(k, (s, s))
+            ends[k] = (min(lo, s), max(hi, s))
+
+        def label(k):
+            return '{}..{}'.format(ends[k][0].strftime(_STAMP), ends[k][1].strftime(_STAMP))
+    present = sorted(set(keys))
+    number = {k: i for i, k in enumerate(present)}
+    return np.array([number[k] for k in keys], dtype=np.int32), [label(k) for k in present]
+
+
+def header_columns(labels, transform='none', names=OBJ_FN_NAMES):
+    """The column names of a `.windows` file: NSE@<label>, KGE@<label>, ... window by window, with ':<transform>' behind
+    the function's name when the flows were transformed (NSE:log@1994)."""
+    tag = '' if transform == 'none' else ':' + transform
+    return ['{}{}@{}'.format(name, tag, label) for label in labels for name in names]
+
+
+def header_line(labels, transform='none', names=OBJ_FN_NAMES):
+    return ','.join(header_columns(labels, transform, names)) + '\n'
+
+
+def default_eps(transform, obs):
+    """0 for 'none' and 'sqrt'; for 'log' and 'inverse' one hundredth of the mean of the non-missing observations
+    (Pushpalatha et al. 2012, J. Hydrol. 420-421)."""
+    if transform in ('none', 'sqrt'):
+        return 0.0
+    obs = np.asarray(obs, dtype=np.float64)
+    return float(np.mean(obs[~np.isnan(obs)])) / 100.0
+
+
+class WindowObjectives(object):
+    """What MonteCarlo.window_objective_functions returns: `names` (the seven objective functions), `labels` (one per
+    window), `transform`, `eps` (the value used), `values` (numpy [W, N, 7] float64, in the order of the sample's
+    rows), `device_values` (the same as a device tensor, or None for an empty sample: device_values[w][:, [0]] goes to
+    selection.condition_mask as it is) and `file` (the path written, or None)."""
+
+    def __init__(self, labels, transform, eps, values, device_values, file=None):
+        self.names = list(OBJ_FN_NAMES)
+        self.labels, self.transform, self.eps = list(labels), transform, eps
+        self.values, self.device_values, self.file = values, device_values, file
