@@ -80,6 +80,9 @@ def main():
     # launch each; the [W, N, 7] values stay on the GPU (per_year.device_values) for conditioning on every year
     per_year = glue.window_objective_functions('hydro_year', write=True)
     low_flow = glue.window_objective_functions('all', transform='log')
+    # the flow duration curve of every behavioural set (Q5, Q50, Q95) and the fit of its top 2 %: one launch each
+    fdc = glue.flow_duration_curves(exceedance=(0.05, 0.5, 0.95), windows='all', write=True)
+    high_flow = glue.flow_duration_curves(exceedance=(0.05,), windows='all', segment=(0.98, 1.0))
     top = Best('Catchment', root, 'csv', 'csv', target='KGE', nb_best=10, constraining={'GW': ('equal', (1.0,))})
     top.model.extra = EXTRA
     top.run()
@@ -92,6 +95,10 @@ def main():
                   % (', '.join('%s: %.3f' % (y, np.nanmedian(per_year.values[w][:, 1])) for w, y in enumerate(per_year.labels)),
                      per_year.file))
             print('      NSE of ln(Q + %.3g): best %.4f' % (low_flow.eps, np.nanmax(low_flow.values[0][:, 0])))
+            print('      Q5 / Q50 / Q95, median over the sets: %s (observed %s) -> %s'
+                  % (', '.join('%.3g' % v for v in np.nanmedian(fdc.curves[0], axis=1)),
+                     ', '.join('%.3g' % v for v in fdc.observed[0]), fdc.file))
+            print('      volume bias of the top 2 %% of the curve: smallest |PBias| %.2f %%' % np.nanmin(np.abs(high_flow.values[0][:, 5])))
         print('Best: 10 best KGE among the sets meeting the groundwater constraint -> %s' % top.db_file)
     distributed.finish()        # (several ranks: leave the process group -- without waiting for a communicator that never answered)
 

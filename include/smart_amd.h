@@ -327,6 +327,64 @@ int smart_objfn_windows_hip(int64_t n_samples, int64_t n_reports, const double *
 int32_t smart_objfn_max_windows(void);
 
 /*
+ * Flow duration curves of an existing discharge matrix: order statistics ALONG TIME, per sample and per window of report
+ * steps -- the direction smart_weighted_quantiles_hip (across the samples, per report step) does not take -- and the
+ * objective functions of the sorted simulation against the sorted observations, beside smart_objfn_windows_hip.
+ *   sim[R][ld] sample-minor (the layout smart_run_ensemble_hip writes), obs[R] or NULL (NaN = missing), window[R] int32
+ *   or NULL with the convention of smart_objfn_windows_hip (-1 = no window, else 0 .. n_windows-1; NULL = one window
+ *   holding every report step, n_windows must be 1), quant[n_windows][n_probs][N] (sample-minor: the stores coalesce),
+ *   objfn[n_windows][N][SMART_OBJFN_WINDOW_COLS] or NULL, workspace: device pointers; probs[n_probs]: HOST pointer, read
+ *   before the call returns, each in [0, 1], n_probs <= SMART_QUANTILES_MAX_PROBS.  Asynchronous on stream; allocates
+ *   nothing: the workspace is the caller's, smart_flow_duration_workspace_bytes says how much (0 without objfn).
+ * For window w and sample n let rows = { r : window[r] == w, and obs[r] is not NaN where obs is given }, m = |rows| and
+ * x = sim[rows, n].
+ *   Q(q) = the k-th smallest of x, k = max(1, ceil(q * m)) with the product formed in double:
+ *   numpy.quantile(x, q, method='inverted_cdf').  No interpolation and no arithmetic on the values: an element of the
+ *   column.  A NaN sorts above +inf and counts as a value; -0.0 and +0.0 are the same value; m == 0 gives NaN.
+ *   objfn (needs obs): s = f(sort(x)) and e = f(sort(obs[rows])), both ascending and paired by the 0-based rank i, f the
+ *   transform (SMART_TRANSFORM_*, eps) applied AFTER the sort; the rank i takes part iff
+ *   seg_lo * m <= (double)i < seg_hi * m (0 <= seg_lo < seg_hi <= 1; (0, 1) = the whole curve); the seven values NSE,
+ *   KGE, KGEc, KGEa, KGEb, PBias, RMSE are the formulas of montecarlo.py:193-209 on those pairs (one-pass moments about
+ *   a shift, as smart_objfn_windows_hip).  The two rules of smart_objfn_windows_hip, on the pairs that take part:
+ *   - fewer than two pairs in the segment: NaN in all seven columns, for every sample of that window;
+ *   - a transformed value of the segment that is not finite: NaN in all seven columns of that (window, sample); a
+ *     non-finite f(obs) of the segment does it for every sample of the window.  (A NaN in a column sorts to the top: it
+ *     spoils a segment that reaches the top rank, and no other.)
+ * Two forms (smartpy_amd/csrc/smart_flow_duration.hip) that give the same bits:
+ *   SMART_FDC_SORT    n_reports <= smart_flow_duration_sort_capacity(): a workgroup sorts the window's rows of 16 .. 1
+ *                     adjacent samples in LDS (one bitonic network for all its columns) and reads the order statistics
+ *                     and the segment's moments from there; beyond the capacity SMART_E_SIZE
+ *   SMART_FDC_SELECT  any n_reports, order statistics only (objfn given: SMART_E_MODE): one lane per sample, the
+ *                     probabilities bisect the 64-bit key space together with integer counts
+ *   SMART_FDC_AUTO    sort within the capacity, select beyond -- where objfn is refused (SMART_E_SIZE): never a silent
+ *                     fallback
+ * Deterministic: no floating-point atomics, two launches give the same bits.
+ * Errors (all found before the device is touched): SMART_E_NULL sim, probs or quant missing, objfn without obs, objfn
+ * without workspace; SMART_E_SIZE a size < 1, ld < n_samples, n_reports >= 2^31, n_windows >
+ * smart_objfn_max_windows() or != 1 without a window array, n_probs > 16, a probability outside [0, 1] or not finite,
+ * eps negative or not finite, a segment that is not 0 <= seg_lo < seg_hi <= 1, workspace_bytes too small, the sort form
+ * or objfn beyond the capacity; SMART_E_MODE unknown transform or method, objfn with SMART_FDC_SELECT; then
+ * SMART_E_NO_DEVICE without a HIP device.
+ */
+#define SMART_FDC_AUTO 0
+#define SMART_FDC_SORT 1
+#define SMART_FDC_SELECT 2
+int smart_flow_duration_hip(int64_t n_samples, int64_t n_reports, const double *sim, int64_t ld, const double *obs,
+                            const int32_t *window, int32_t n_windows, const double *probs, int32_t n_probs,
+                            double *quant, int32_t transform, double eps, double seg_lo, double seg_hi, double *objfn,
+                            void *workspace, int64_t workspace_bytes, int32_t method, void *stream);
+
+/* The workspace smart_flow_duration_hip needs, in bytes: with objfn the sorted transformed observations of every window
+ * and eight statistics in front of each, (8 + n_reports) * 8 * n_windows rounded up to 256; without objfn 0.  A
+ * negative SMART_E_SIZE for sizes < 1.  Needs no device (beside smart_workspace_bytes). */
+int64_t smart_flow_duration_workspace_bytes(int64_t n_reports, int32_t n_windows, int32_t with_objfn);
+
+/* The largest n_reports SMART_FDC_SORT takes: 16,384 keys of 8 bytes are the 128 KiB a workgroup keeps in LDS (of the
+ * 160 KiB of a gfx950 compute unit), one column of that many rows in the narrowest instance.  Needs no device (beside
+ * smart_quantiles_sort_capacity). */
+int64_t smart_flow_duration_sort_capacity(void);
+
+/*
  * Sampling database, CSV flavour -- the rows MonteCarlo.save writes one by one (montecarlo.py:211-231): every value
  * cast to float32 and printed '%.6e', comma separated, one '\n'-terminated line per sample.  HOST pointers, no
  * device involved.  Appends n_rows lines of n_cols values (row-major float32 table: objective functions, parameters,

@@ -26,6 +26,7 @@ QUANTILES_AUTO, QUANTILES_SORT, QUANTILES_SELECT = 0, 1, 2
 QUANTILES_MAX_PROBS = 16
 TRANSFORMS = {'none': 0, 'sqrt': 1, 'log': 2, 'inverse': 3}     # SMART_TRANSFORM_*
 OBJFN_WINDOW_COLS = 7
+FDC_METHODS = {'auto': 0, 'sort': 1, 'select': 2}              # SMART_FDC_*
 
 _dp = ctypes.c_void_p   # device or host address, passed as an integer
 
@@ -68,6 +69,12 @@ SYMBOLS = {
     'smart_objfn_windows_hip': (ctypes.c_int, [ctypes.c_int64, ctypes.c_int64, _dp, ctypes.c_int64, _dp, _dp,
                                                ctypes.c_int32, ctypes.c_int32, ctypes.c_double, _dp, _dp]),
     'smart_objfn_max_windows': (ctypes.c_int32, []),
+    'smart_flow_duration_hip': (ctypes.c_int, [ctypes.c_int64, ctypes.c_int64, _dp, ctypes.c_int64, _dp, _dp,
+                                               ctypes.c_int32, ctypes.POINTER(ctypes.c_double), ctypes.c_int32, _dp,
+                                               ctypes.c_int32, ctypes.c_double, ctypes.c_double, ctypes.c_double, _dp,
+                                               _dp, ctypes.c_int64, ctypes.c_int32, _dp]),
+    'smart_flow_duration_workspace_bytes': (ctypes.c_int64, [ctypes.c_int64, ctypes.c_int32, ctypes.c_int32]),
+    'smart_flow_duration_sort_capacity': (ctypes.c_int64, []),
     'smart_db_append_rows': (ctypes.c_int, [ctypes.c_char_p, ctypes.POINTER(ctypes.c_float), ctypes.c_int64,
                                             ctypes.c_int64, ctypes.c_int32]),
     'smart_db_parse_rows': (ctypes.c_int64, [ctypes.c_char_p, ctypes.c_int64, ctypes.c_int64,

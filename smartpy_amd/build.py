@@ -33,11 +33,14 @@ UNITS = {
     # the objective functions per window of report steps, on transformed flows: default flags, NaNs honoured -- a NaN
     # or an infinity that a transform makes has to reach the sums (it is how the kernel finds it)
     'smart_objfn_windows.hip': [],
+    # flow duration curves (order statistics along time, per sample): default flags, NaNs honoured -- a NaN value has a
+    # place in the order, and a non-finite transformed flow has to reach the sums
+    'smart_flow_duration.hip': [],
     'smart_capi.hip': [],
     'smart_hostio.cpp': ['-pthread'],      # host only: the sampling-database writer
 }
 COMMON = ['-O3', '-fPIC', '-std=c++17', '--offload-arch=' + ARCH, '-fno-gpu-rdc', '-Wall']
-DEPS = ['smart_device.h', 'smart_literal_model.h', 'smart_literal_lanes.h', 'smart_fast_model.h', 'smart_fast_arms.h', 'smart_fast_entry.h', os.path.join('..', '..', 'include', 'smart_amd.h')]
+DEPS = ['smart_device.h', 'smart_order_keys.h', 'smart_literal_model.h', 'smart_literal_lanes.h', 'smart_fast_model.h', 'smart_fast_arms.h', 'smart_fast_entry.h', os.path.join('..', '..', 'include', 'smart_amd.h')]
 
 
 def hipcc():

@@ -22,6 +22,11 @@ void launch_quantiles(long N, long R, const double *sim, long ld, const double *
 int objfn_max_windows();            // smart_objfn_windows.hip
 void launch_objfn_windows(long N, long R, const double *sim, long ld, const double *obs, const int *window, int W,
                           int transform, double eps, double *objfn, hipStream_t s);
+long flow_duration_sort_capacity(); // smart_flow_duration.hip
+long flow_duration_workspace_bytes(long R, int W, bool with_objfn);
+void launch_flow_duration(long N, long R, const double *sim, long ld, const double *obs, const int *window, int W,
+                          const double *probs, int K, double *quant, int transform, double eps, double seg_lo,
+                          double seg_hi, double *objfn, double *ws, bool sort, hipStream_t s);
 
 static_assert(kStatusSliceTimeout == SMART_STATUS_SLICE_TIMEOUT && kStatusStalePlan == SMART_STATUS_STALE_PLAN,
               "status bits of smart_device.h and include/smart_amd.h");
@@ -1440,6 +1445,84 @@ int smart_objfn_windows_hip(int64_t n_samples, int64_t n_reports, const double *
 }
 
 int32_t smart_objfn_max_windows(void) { return objfn_max_windows(); }
+
+int smart_flow_duration_hip(int64_t n_samples, int64_t n_reports, const double *sim, int64_t ld, const double *obs,
+                            const int32_t *window, int32_t n_windows, const double *probs, int32_t n_probs,
+                            double *quant, int32_t transform, double eps, double seg_lo, double seg_hi, double *objfn,
+                            void *workspace, int64_t workspace_bytes, int32_t method, void *stream)
+{
+    if (!sim || !probs || !quant)
+        return fail(SMART_E_NULL, "smart_flow_duration_hip: sim, probs and quant are required (%s is NULL)",
+                    !sim ? "sim" : (!probs ? "probs" : "quant"));
+    if (objfn && !obs)
+        return fail(SMART_E_NULL, "smart_flow_duration_hip: objfn needs obs (obs is NULL)");
+    if (n_samples < 1 || n_reports < 1 || n_windows < 1 || n_probs < 1)
+        return fail(SMART_E_SIZE, "smart_flow_duration_hip: need n_samples, n_reports, n_windows, n_probs >= 1 (got %lld, "
+                                  "%lld, %d, %d)",
+                    (long long)n_samples, (long long)n_reports, (int)n_windows, (int)n_probs);
+    if (ld < n_samples)
+        return fail(SMART_E_SIZE, "smart_flow_duration_hip: ld %lld is less than n_samples %lld", (long long)ld,
+                    (long long)n_samples);
+    if (n_reports > 0x7fffffffll)
+        return fail(SMART_E_SIZE, "smart_flow_duration_hip: n_reports %lld is more than one launch takes (2^31 - 1)",
+                    (long long)n_reports);
+    if (n_windows > objfn_max_windows())
+        return fail(SMART_E_SIZE, "smart_flow_duration_hip: n_windows %d, at most %d per call", (int)n_windows,
+                    objfn_max_windows());
+    if (!window && n_windows != 1)
+        return fail(SMART_E_SIZE, "smart_flow_duration_hip: n_windows %d without a window array (NULL is one window)",
+                    (int)n_windows);
+    if (n_probs > SMART_QUANTILES_MAX_PROBS)
+        return fail(SMART_E_SIZE, "smart_flow_duration_hip: n_probs %d, at most %d probabilities per call", (int)n_probs,
+                    SMART_QUANTILES_MAX_PROBS);
+    for (int32_t k = 0; k < n_probs; ++k)
+        if (!(probs[k] >= 0.0 && probs[k] <= 1.0))
+            return fail(SMART_E_SIZE, "smart_flow_duration_hip: probability %d is %g, outside [0, 1]", (int)k, probs[k]);
+    if (!(eps >= 0.0) || std::isinf(eps))
+        return fail(SMART_E_SIZE, "smart_flow_duration_hip: eps %g must be finite and >= 0", eps);
+    if (!(seg_lo >= 0.0 && seg_lo < seg_hi && seg_hi <= 1.0))
+        return fail(SMART_E_SIZE, "smart_flow_duration_hip: the segment (%g, %g) is not 0 <= seg_lo < seg_hi <= 1", seg_lo,
+                    seg_hi);
+    if (transform < SMART_TRANSFORM_NONE || transform > SMART_TRANSFORM_INVERSE)
+        return fail(SMART_E_MODE, "smart_flow_duration_hip: transform '%d' unknown.", (int)transform);
+    if (method != SMART_FDC_AUTO && method != SMART_FDC_SORT && method != SMART_FDC_SELECT)
+        return fail(SMART_E_MODE, "smart_flow_duration_hip: method '%d' unknown.", (int)method);
+    if (objfn && method == SMART_FDC_SELECT)
+        return fail(SMART_E_MODE, "smart_flow_duration_hip: the select form gives order statistics only (objfn given)");
+    const long capacity = flow_duration_sort_capacity();
+    if (n_reports > capacity && (objfn || method == SMART_FDC_SORT))
+        return fail(SMART_E_SIZE, "smart_flow_duration_hip: %s at most %ld report steps (the sort capacity), not %lld",
+                    objfn ? "the objective functions of the curve take" : "the sort form takes", capacity,
+                    (long long)n_reports);
+    if (objfn) {
+        const long need = flow_duration_workspace_bytes((long)n_reports, (int)n_windows, true);
+        if (!workspace)
+            return fail(SMART_E_NULL, "smart_flow_duration_hip: objfn needs a workspace of %ld bytes (workspace is NULL)",
+                        need);
+        if (workspace_bytes < need)
+            return fail(SMART_E_SIZE, "smart_flow_duration_hip: workspace_bytes %lld, need %ld", (long long)workspace_bytes,
+                        need);
+    }
+    int rc = device_ready();
+    if (rc)
+        return rc;
+    const bool sort = method != SMART_FDC_SELECT && n_reports <= capacity;
+    launch_flow_duration((long)n_samples, (long)n_reports, sim, (long)ld, obs, window, (int)n_windows, probs, (int)n_probs,
+                         quant, (int)transform, eps, seg_lo, seg_hi, objfn, (double *)workspace, sort,
+                         (hipStream_t)stream);
+    HIP_TRY(hipGetLastError());
+    g_err[0] = 0;
+    return SMART_OK;
+}
+
+int64_t smart_flow_duration_workspace_bytes(int64_t n_reports, int32_t n_windows, int32_t with_objfn)
+{
+    if (n_reports < 1 || n_reports > 0x7fffffffll || n_windows < 1)
+        return SMART_E_SIZE;
+    return flow_duration_workspace_bytes((long)n_reports, (int)n_windows, with_objfn != 0);
+}
+
+int64_t smart_flow_duration_sort_capacity(void) { return flow_duration_sort_capacity(); }
 
 int smart_row_class(const double *params, double delta_sec, const double *initial12, double area_m2)
 {

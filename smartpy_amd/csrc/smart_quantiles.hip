@@ -4,8 +4,8 @@
 // No interpolation; NaN sorts above +inf and a quantile that reaches it is NaN; -0.0 and +0.0 are one value; W == 0
 // gives NaN.  One workgroup per report step: the matrix is sample-minor, so the step's N values are contiguous.
 //
-// Values are compared as ORDER-PRESERVING 64-BIT KEYS (value_key): unsigned order of the keys = numeric order of the
-// doubles, every NaN one key above +inf, both zeros one key.
+// Values are compared as ORDER-PRESERVING 64-BIT KEYS (value_key, smart_order_keys.h): unsigned order of the keys =
+// numeric order of the doubles, every NaN one key above +inf, both zeros one key.
 //
 // Two forms, the same definition:
 //   sort    N <= kSortCapacity.  Keys and sample indices into LDS, bitonic network there, inclusive scan of the weights
@@ -32,6 +32,7 @@
 // Weights must be finite and >= 0 (checked by the caller, not here); weights == nullptr means equal weights.
 #include <hip/hip_runtime.h>
 #include <cstdint>
+#include "smart_order_keys.h"
 
 namespace smart {
 
@@ -55,27 +56,6 @@ static_assert(kSortCapacity <= 65536, "sample indices are kept as 16-bit numbers
 struct QuantileProbs {
     double q[kQuantilesMaxProbs];
 };
-
-constexpr unsigned long long kKeyNaN = 0xfff8000000000000ull;  // above +inf (0xfff0...), below the padding
-constexpr unsigned long long kKeyPad = 0xffffffffffffffffull;
-constexpr unsigned long long kKeyZero = 0x8000000000000000ull;
-
-__device__ inline unsigned long long value_key(double x)
-{
-    if (x != x)
-        return kKeyNaN;
-    if (x == 0.0)
-        return kKeyZero;
-    const unsigned long long b = (unsigned long long)__double_as_longlong(x);
-    return (b >> 63) ? ~b : (b | kKeyZero);
-}
-
-__device__ inline double key_value(unsigned long long k)
-{
-    if (k >= kKeyNaN)
-        return __longlong_as_double(0x7ff8000000000000ll);
-    return __longlong_as_double((long long)((k >> 63) ? (k & ~kKeyZero) : ~k));
-}
 
 __device__ inline double quiet_nan() { return __longlong_as_double(0x7ff8000000000000ll); }
 

@@ -624,6 +624,29 @@ def weighted_quantiles(discharge_report_major, probs, weights=None, method='auto
     return out
 
 
+def _checked_windows(who, windows, n_windows):
+    """The window ids of a call, checked where they lie (host array or device tensor), before anything is moved or
+    launched -> (flat ids, W)."""
+    if isinstance(windows, torch.Tensor):
+        win = windows.reshape(-1)
+        if win.dtype.is_floating_point or win.dtype == torch.bool:
+            raise SmartEngineError(-2, "{}: windows must be integers.".format(who))
+        top = int(win.max()) if win.numel() else -1
+    else:
+        win = np.asarray(windows).reshape(-1)
+        if win.dtype.kind not in 'iu':
+            raise SmartEngineError(-2, "{}: windows must be integers.".format(who))
+        top = int(win.max()) if win.size else -1
+    W = top + 1 if n_windows is None else int(n_windows)
+    if W < 1:
+        raise SmartEngineError(-2, "{}: no window (n_windows = {}).".format(who, W))
+    bad = int(((win < -1) | (win >= W)).sum())
+    if bad:
+        raise SmartEngineError(-2, "{}: {} of the {} window ids are outside -1 .. {}."
+                               .format(who, bad, len(win), W - 1))
+    return win, W
+
+
 def objfn_max_windows():
     """The largest number of windows objective_functions_windows takes in one call (no device needed)."""
     return int(_lib.lib().smart_objfn_max_windows())
@@ -641,24 +664,7 @@ def objective_functions_windows(discharge_report_major, obs, windows, n_windows=
         code = _lib.TRANSFORMS[transform]
     except (KeyError, TypeError):
         raise SmartEngineError(-7, "objective_functions_windows: transform '{}' unknown.".format(transform))
-    # the window ids are checked where they lie, before anything is moved or launched
-    if isinstance(windows, torch.Tensor):
-        win = windows.reshape(-1)
-        if win.dtype.is_floating_point or win.dtype == torch.bool:
-            raise SmartEngineError(-2, "objective_functions_windows: windows must be integers.")
-        top = int(win.max()) if win.numel() else -1
-    else:
-        win = np.asarray(windows).reshape(-1)
-        if win.dtype.kind not in 'iu':
-            raise SmartEngineError(-2, "objective_functions_windows: windows must be integers.")
-        top = int(win.max()) if win.size else -1
-    W = top + 1 if n_windows is None else int(n_windows)
-    if W < 1:
-        raise SmartEngineError(-2, "objective_functions_windows: no window (n_windows = {}).".format(W))
-    bad = int(((win < -1) | (win >= W)).sum())
-    if bad:
-        raise SmartEngineError(-2, "objective_functions_windows: {} of the {} window ids are outside -1 .. {}."
-                               .format(bad, len(win), W - 1))
+    win, W = _checked_windows('objective_functions_windows', windows, n_windows)
     sim = discharge_report_major
     if len(sim.shape) != 2 or sim.shape[0] != len(win):
         raise SmartEngineError(-2, "objective_functions_windows: {} window ids for a matrix of shape {}."
@@ -681,6 +687,78 @@ def objective_functions_windows(discharge_report_major, obs, windows, n_windows=
                                              float(eps), out.data_ptr(),
                                              torch.cuda.current_stream(sim.device).cuda_stream))
     return out
+
+
+def flow_duration_sort_capacity():
+    """The largest number of report steps the sort form of flow_duration takes (no device needed)."""
+    return int(_lib.lib().smart_flow_duration_sort_capacity())
+
+
+def flow_duration(discharge_report_major, probs, obs=None, windows=None, n_windows=None, transform='none', eps=0.0,
+                  segment=(0.0, 1.0), objfn=False, method='auto'):
+    """Flow duration curves of every column of a stored [R, N] discharge matrix: order statistics ALONG TIME, per sample
+    and per window of report steps -> (quant [W, K, N], objfn [W, N, 7] or None), device tensors, float64.
+    probs: K <= 16 NON-exceedance probabilities q in [0, 1]; Q(q) is the max(1, ceil(q * m))-th smallest of the window's
+    m values of the column (numpy's method='inverted_cdf': an element of the column, NaN sorts last, m == 0 gives NaN).
+    obs: [R] or None -- report steps without an observation (NaN) are left out; windows: [R] integers as for
+    objective_functions_windows, or None for one window holding every step.  objfn=True (needs obs) adds NSE, KGE, KGEc,
+    KGEa, KGEb, PBias, RMSE of f(sorted simulation) against f(sorted observations), paired by rank, over the ranks i with
+    segment[0] * m <= i < segment[1] * m; transform / eps as for objective_functions_windows, and its two rules.
+    method: 'auto', 'sort' (R <= flow_duration_sort_capacity(); the only one that gives objfn) or 'select'.  The
+    workspace of the call is sized and owned here (include/smart_amd.h: smart_flow_duration_hip)."""
+    L = _lib.lib()
+    try:
+        code = _lib.TRANSFORMS[transform]
+    except (KeyError, TypeError):
+        raise SmartEngineError(-7, "flow_duration: transform '{}' unknown.".format(transform))
+    try:
+        how = _lib.FDC_METHODS[method]
+    except (KeyError, TypeError):
+        raise SmartEngineError(-7, "flow_duration: method '{}' unknown.".format(method))
+    if objfn and obs is None:
+        raise SmartEngineError(-1, "flow_duration: the objective functions of the curve need obs.")
+    sim = discharge_report_major
+    if windows is None:
+        win, W = None, 1
+        if n_windows is not None and int(n_windows) != 1:
+            raise SmartEngineError(-2, "flow_duration: n_windows = {} without windows.".format(n_windows))
+    else:
+        win, W = _checked_windows('flow_duration', windows, n_windows)
+        if len(sim.shape) != 2 or sim.shape[0] != len(win):
+            raise SmartEngineError(-2, "flow_duration: {} window ids for a matrix of shape {}."
+                                   .format(len(win), tuple(sim.shape)))
+    if len(sim.shape) != 2:
+        raise SmartEngineError(-2, "flow_duration: a matrix [R, N] is needed, not shape {}.".format(tuple(sim.shape)))
+    if not (isinstance(sim, torch.Tensor) and sim.is_cuda):
+        sim = as_device(sim, default_device())
+    if sim.stride(-1) != 1:
+        sim = sim.contiguous()
+    R, N = sim.shape
+    ld = sim.stride(0) if R > 1 else N
+    q = np.ascontiguousarray(np.atleast_1d(np.asarray(probs, dtype=np.float64)))
+    lo, hi = (float(x) for x in segment)
+    if obs is not None:
+        obs = as_device(obs, sim.device, (R,))
+    if win is not None:
+        if not isinstance(win, torch.Tensor):
+            win = torch.from_numpy(np.ascontiguousarray(win.astype(np.int32)))
+        win = win.to(device=sim.device, dtype=torch.int32).contiguous()
+    quant = torch.empty((W, q.size, N), dtype=torch.float64, device=sim.device)
+    scores = torch.empty((W, N, _lib.OBJFN_WINDOW_COLS), dtype=torch.float64, device=sim.device) if objfn else None
+    if N == 0:
+        return quant, scores
+    need = int(L.smart_flow_duration_workspace_bytes(R, W, 1 if objfn else 0))
+    if need < 0:
+        _lib.check(need)
+    work = torch.empty(need, dtype=torch.uint8, device=sim.device) if need else None
+    with torch.cuda.device(sim.device):
+        _lib.check(L.smart_flow_duration_hip(N, R, sim.data_ptr(), ld, None if obs is None else obs.data_ptr(),
+                                             None if win is None else win.data_ptr(), W,
+                                             q.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), q.size, quant.data_ptr(),
+                                             code, float(eps), lo, hi, None if scores is None else scores.data_ptr(),
+                                             None if work is None else work.data_ptr(), need, how,
+                                             torch.cuda.current_stream(sim.device).cuda_stream))
+    return quant, scores
 
 
 def allsteps(area_m2, delta_sec, length_simu, nd_rain, nd_peva, nd_parameters, nd_initial, report_type, report_gap):

@@ -228,6 +228,65 @@ class MonteCarlo(object):
         base = self.db_file[:-3] if self.db_file.endswith('.nc') else self.db_file
         return base + '.windows'
 
+    # ---- flow duration curves -----------------------------------------------------------------------------
+    def flow_duration_curves(self, exceedance=(0.01, 0.05, 0.1, 0.2, 0.5, 0.8, 0.9, 0.95, 0.99), windows='all',
+                             transform='none', eps=None, segment=(0.0, 1.0), start_month=10, split=None, write=False):
+        """The flow duration curve of every row of the sample PER WINDOW of report steps: the flow exceeded with
+        probability p, for each p of `exceedance` (at most 16), and the objective functions of the curve -- NSE, KGE,
+        KGEc, KGEa, KGEb, PBias, RMSE of the sorted simulation against the sorted observations, paired by rank, over the
+        `segment` (lo, hi) of the ascending ranks ((0, 1): the whole curve; (0.98, 1): the top 2 %, whose PBias is a
+        high-flow-volume bias; (0, 0.3) with transform='log': a low-flow bias).  An EXCEEDANCE probability p is turned
+        into the non-exceedance probability q = 1 - p here, on the host; the engine returns the max(1, ceil(q * m))-th
+        smallest of the window's m flows (numpy's 'inverted_cdf': a simulated value, nothing interpolated).  Report steps
+        without an observation are left out of both series.  windows / start_month / split / transform / eps as for
+        window_objective_functions.  One launch of its own over the sample; the [R, N] matrix stays on the device and
+        only [W, K, N] and [W, N, 7] come back.  write=True also writes `<out>/<catchment>.SMART.<func>.fdc` (one line
+        per sample in the sample's order, the float32 '%.6e' of the sampling database; header Q<p>@<label>,... window by
+        window, then NSE@<label>,KGE@<label>,...).  Under torch.distributed every rank that calls this computes all rows
+        itself (no collective); rank 0 alone writes.  -> FlowDuration"""
+        from .. import engine, windows as swin
+        if transform not in _lib_transforms():
+            raise Exception("The flow transform '{}' is not recognised. Please choose one of: {}."
+                            .format(transform, ', '.join(_lib_transforms())))
+        exceedance = [float(p) for p in np.atleast_1d(np.asarray(exceedance, dtype=np.float64))]
+        q = swin.non_exceedance(exceedance)
+        if isinstance(windows, str):
+            ids, labels = swin.evaluation_windows(self.model.timeseries_report[1:], by=windows, start_month=start_month,
+                                                  split=split)
+        else:
+            ids, labels = windows
+            ids, labels = np.asarray(ids), list(labels)
+        n = self._sample.shape[0]
+        if self.model.nd_flow is None:
+            raise Exception("The observation array does not exist. Please make sure that a value is assigned "
+                            "to the gauged_area_m2 attribute of your SMART class instance.")
+        if eps is None:
+            eps = swin.default_eps(transform, self.model.nd_flow)
+        W = len(labels)
+        if n == 0:      # e.g. GLUE with no behavioural set: nothing to launch
+            on_device, curves = None, np.empty((W, len(q), 0))
+            values = np.empty((W, 0, len(swin.OBJ_FN_NAMES)))
+        else:
+            rows = self._device_sample if self._device_sample is not None else self._sample
+            out = self.model.simulate_ensemble(rows, save_discharge=True, math_mode=self.math_mode)
+            obs = self.model._device_cache[2]       # the observations the launch has left on the device
+            quant, on_device = engine.flow_duration(out.discharge_report_major, q, obs=obs, windows=ids, n_windows=W,
+                                                    transform=transform, eps=eps, segment=segment, objfn=True)
+            curves, values = quant.cpu().numpy(), on_device.cpu().numpy()
+        observed = swin.observed_duration(self.model.nd_flow, ids, W, q)
+        path = None
+        if write and sdist.rank_world()[0] == 0:
+            path = self.fdc_file
+            _write_fdc_file(path, exceedance, labels, transform, curves, values)
+        return swin.FlowDuration(exceedance, labels, curves, observed, transform, float(eps), segment, values, on_device,
+                                 path)
+
+    @property
+    def fdc_file(self):
+        """`<out>/<catchment>.SMART.<func>.fdc`: beside the sampling database, whatever its format."""
+        base = self.db_file[:-3] if self.db_file.endswith('.nc') else self.db_file
+        return base + '.fdc'
+
     # ---- the per-sample protocol of the reference (spotpy setup class) ------------------------------------
     def parameters(self):
         return np.array([p() for p in self.params])
@@ -285,5 +344,22 @@ def _write_windows_file(path, labels, transform, values):
     if n == 0:
         return
     table = np.ascontiguousarray(np.transpose(values, (1, 0, 2)).reshape(n, W * k).astype(np.float32))
+    _lib.check(_lib.lib().smart_db_append_rows(path.encode('utf8'), table.ctypes.data_as(ctypes.POINTER(ctypes.c_float)),
+                                               table.shape[0], table.shape[1], 0))
+
+
+def _write_fdc_file(path, exceedance, labels, transform, curves, values):
+    """curves [W, K, N] and values [W, N, 7] -> header line + one line per sample: the K flows of every window, then
+    the seven objective functions of every window (the sampling database's float32 '%.6e', formatted by the library)."""
+    import ctypes
+    from .. import _lib, windows as swin
+    with open(path, 'w', newline='', encoding='utf8') as f:
+        f.write(swin.fdc_header_line(exceedance, labels, transform))
+    W, K, n = curves.shape
+    if n == 0:
+        return
+    table = np.concatenate([np.transpose(curves, (2, 0, 1)).reshape(n, W * K),
+                            np.transpose(values, (1, 0, 2)).reshape(n, W * values.shape[2])], axis=1)
+    table = np.ascontiguousarray(table.astype(np.float32))
     _lib.check(_lib.lib().smart_db_append_rows(path.encode('utf8'), table.ctypes.data_as(ctypes.POINTER(ctypes.c_float)),
                                                table.shape[0], table.shape[1], 0))

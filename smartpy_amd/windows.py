@@ -1,6 +1,7 @@
 """Evaluation windows over the report stamps: which report step belongs to which hydrological year, season, month or
 period of a split-sample test.  Pure host code; the ids go to engine.objective_functions_windows
-(MonteCarlo.window_objective_functions), which scores every sample per window on the GPU.
+(MonteCarlo.window_objective_functions), which scores every sample per window on the GPU, and to engine.flow_duration
+(MonteCarlo.flow_duration_curves), which sorts every sample's flows per window there.
 """
 from bisect import bisect_right
 from datetime import datetime
@@ -96,4 +97,49 @@ class WindowObjectives(object):
     def __init__(self, labels, transform, eps, values, device_values, file=None):
         self.names = list(OBJ_FN_NAMES)
         self.labels, self.transform, self.eps = list(labels), transform, eps
+        self.values, self.device_values, self.file = values, device_values, file
+
+
+# ---- flow duration curves -------------------------------------------------------------------------------------------
+def non_exceedance(exceedance):
+    """Exceedance probabilities p (the hydrologist's axis of a flow duration curve: Q1 is a high flow) -> the
+    non-exceedance probabilities q = 1 - p the engine takes, as a float64 array.  Each p must lie in [0, 1]."""
+    p = np.atleast_1d(np.asarray(exceedance, dtype=np.float64))
+    if p.ndim != 1 or p.size == 0 or not np.all((p >= 0.0) & (p <= 1.0)):
+        raise Exception("The exceedance probabilities of a flow duration curve must lie between 0 and 1.")
+    return 1.0 - p
+
+
+def observed_duration(obs, ids, n_windows, q):
+    """The rule of engine.flow_duration applied to the observations with numpy -> [W, K]: per window the
+    max(1, ceil(q * m))-th smallest of its m non-missing observations, NaN for a window without any."""
+    obs, ids = np.asarray(obs, dtype=np.float64), np.asarray(ids)
+    out = np.full((n_windows, len(q)), np.nan)
+    for w in range(n_windows):
+        x = np.sort(obs[(ids == w) & ~np.isnan(obs)])
+        if x.size:
+            out[w] = [x[max(1, int(np.ceil(qk * x.size))) - 1] for qk in q]
+    return out
+
+
+def fdc_header_line(exceedance, labels, transform='none'):
+    """The header of a `.fdc` file: Q<p>@<label> for every probability, window by window, then the columns of a
+    `.windows` file (NSE@<label>, ... with ':<transform>' behind the function's name when the flows were transformed)."""
+    quant = ['Q{:g}@{}'.format(p, label) for label in labels for p in exceedance]
+    return ','.join(quant + header_columns(labels, transform)) + '\n'
+
+
+class FlowDuration(object):
+    """What MonteCarlo.flow_duration_curves returns: `exceedance` (the K probabilities asked for), `labels` (one per
+    window), `curves` (numpy [W, K, N]: the flow of every sample exceeded with that probability), `observed` ([W, K], the
+    same rule on the observations), `names` / `values` (numpy [W, N, 7]: the objective functions of the sorted simulation
+    against the sorted observations over `segment`, on `transform`ed flows with `eps`), `device_values` (the same as a
+    device tensor, or None for an empty sample: device_values[w][:, [0]] goes to selection.condition_mask as it is) and
+    `file` (the path written, or None)."""
+
+    def __init__(self, exceedance, labels, curves, observed, transform, eps, segment, values, device_values, file=None):
+        self.names = list(OBJ_FN_NAMES)
+        self.exceedance, self.labels = [float(p) for p in exceedance], list(labels)
+        self.curves, self.observed = curves, observed
+        self.transform, self.eps, self.segment = transform, eps, (float(segment[0]), float(segment[1]))
         self.values, self.device_values, self.file = values, device_values, file
