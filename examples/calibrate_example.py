@@ -23,7 +23,7 @@ sys.path.insert(0, os.path.dirname(HERE))
 
 import smartpy_amd                                   # noqa: E402
 from smartpy_amd import distributed                  # noqa: E402
-from smartpy_amd.montecarlo import LHS, GLUE, Best   # noqa: E402
+from smartpy_amd.montecarlo import LHS, GLUE, Best, Sobol   # noqa: E402
 
 EXTRA = {'aar': 1200, 'r-o_ratio': 0.45, 'r-o_split': (0.10, 0.15, 0.15, 0.30, 0.30)}
 
@@ -86,6 +86,13 @@ def main():
     top = Best('Catchment', root, 'csv', 'csv', target='KGE', nb_best=10, constraining={'GW': ('equal', (1.0,))})
     top.model.extra = EXTRA
     top.run()
+    # which parameters does the fit depend on?  A Saltelli design of 256 x 12 rows, one launch; first-order and total Sobol
+    # indices of every objective function with bootstrap confidence intervals, and of the discharge at every report step
+    sob = Sobol('Catchment', root, 'csv', 'csv', base_size=256, seed=0)
+    sob.model.extra = EXTRA
+    sob.run()
+    sens = sob.sensitivity(targets=['NSE', 'KGE'], resamples=128, write=True)
+    in_time = sob.sensitivity_series(write=True)
     if rank == 0:
         print('GLUE: %d behavioural sets -> %s' % (len(glue.behavioural_params), glue.db_file))
         print('      5 / 50 / 95 %% prediction bounds hold %.1f %% of the observations -> %s'
@@ -99,6 +106,12 @@ def main():
                   % (', '.join('%.3g' % v for v in np.nanmedian(fdc.curves[0], axis=1)),
                      ', '.join('%.3g' % v for v in fdc.observed[0]), fdc.file))
             print('      volume bias of the top 2 %% of the curve: smallest |PBias| %.2f %%' % np.nanmin(np.abs(high_flow.values[0][:, 5])))
+        order = np.argsort(-sens.ST[0])
+        print('Sobol: total indices of NSE: %s -> %s'
+              % (', '.join('%s %.2f +- %.2f' % (sens.parameters[j], sens.ST[0, j], sens.ST_conf[0, j]) for j in order[:4]), sens.file))
+        print('       the parameter the discharge depends on most, by share of the report steps: %s -> %s'
+              % (', '.join('%s %.0f %%' % (p, 100 * np.mean(np.argmax(np.nan_to_num(in_time.ST, nan=-1.0), axis=1) == j))
+                           for j, p in enumerate(in_time.parameters)), in_time.file))
         print('Best: 10 best KGE among the sets meeting the groundwater constraint -> %s' % top.db_file)
     distributed.finish()        # (several ranks: leave the process group -- without waiting for a communicator that never answered)
 

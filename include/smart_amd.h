@@ -385,6 +385,48 @@ int64_t smart_flow_duration_workspace_bytes(int64_t n_reports, int32_t n_windows
 int64_t smart_flow_duration_sort_capacity(void);
 
 /*
+ * Sobol sensitivity indices of the rows of a matrix whose columns are a Saltelli design in block-major order
+ * (smartpy_amd.sampling.saltelli_design): first-order indices after Saltelli 2010, total indices after Jansen, and their
+ * standard deviation over bootstrap replicates.
+ *   y[n_rows][ld]: row r holds [A ; B ; AB_0 ; ... ; AB_{n_params-1}], each block n_base contiguous doubles -- a report
+ *   step of the matrix smart_run_ensemble_hip writes, or one scalar target per row; s1, st [n_rows][n_params]; moments
+ *   [n_rows][2] (mu, V); counts [n_base][n_resamples] uint16 (replicate-minor), every replicate's counts summing to
+ *   n_base; s1_std, st_std [n_rows][n_params]: device pointers.  Asynchronous on stream; allocates nothing.
+ * For one row: mu = the mean of the 2 n_base values of A and B, u = y - mu, V = their population variance,
+ *   S1_j = sum_i uB_i (yAB_j,i - yA_i) / (n_base V),    ST_j = sum_i (yA_i - yAB_j,i)^2 / (2 n_base V).
+ * Replicate b keeps mu: V_b = sum_i c_bi (uA_i^2 + uB_i^2) / 2n - (sum_i c_bi (uA_i + uB_i) / 2n)^2, and S1_bj, ST_bj are
+ * the sums above weighted by c_bi over V_b.  s1_std / st_std are the standard deviations (ddof = 1) over the n_resamples
+ * replicates: n_resamples == 0 writes nothing (counts, s1_std, st_std may be NULL), n_resamples == 1 gives NaN.
+ * Rules: a value of a row that is not finite makes every output of that row NaN (told from one sum over the row that
+ * includes the squared differences: finite values whose squared difference overflows count as not finite); V == 0 gives
+ * NaN in S1, ST and the standard deviations; a parameter the values do not depend on (yAB_j equal to yA bit for bit) gives
+ * +0.0 exactly in all four.  Deterministic: no floating-point atomics, every sum has a shape fixed by the sizes; s1, st
+ * and moments are the same bits with and without the bootstrap.
+ * Up to smart_sobol_lds_capacity() base rows a row's A and B stay in LDS and the matrix is read from HBM once; beyond, they
+ * are read again from L2 (the same sums in the same order).
+ * Errors (all found before the device is touched): SMART_E_NULL y, s1, st or moments missing, counts / s1_std / st_std
+ * missing with n_resamples > 0, workspace missing where smart_sobol_workspace_bytes is not 0; SMART_E_SIZE n_base < 1 or
+ * >= 2^31, n_params outside 1 .. SMART_SOBOL_MAX_PARAMS, n_rows < 1 or >= 2^31, ld < n_base * (n_params + 2),
+ * n_resamples < 0 or > smart_sobol_max_resamples(), workspace_bytes too small; then SMART_E_NO_DEVICE.
+ */
+#define SMART_SOBOL_MAX_PARAMS 16
+int smart_sobol_indices_hip(int64_t n_base, int32_t n_params, int64_t n_rows, const double *y, int64_t ld, double *s1,
+                            double *st, double *moments, const uint16_t *counts, int32_t n_resamples, double *s1_std,
+                            double *st_std, void *workspace, int64_t workspace_bytes, void *stream);
+
+/* The workspace smart_sobol_indices_hip needs, in bytes, for these sizes: 0 in this version (the two kernels share only the
+ * caller's moments[]); the argument is part of the entry so that a version that stages terms needs no new ABI.  A negative
+ * SMART_E_SIZE for sizes the entry refuses.  Needs no device. */
+int64_t smart_sobol_workspace_bytes(int64_t n_base, int32_t n_params, int64_t n_rows, int32_t n_resamples);
+
+/* The largest n_resamples of one call (512: one lane per replicate in a workgroup of 512).  Needs no device. */
+int32_t smart_sobol_max_resamples(void);
+
+/* The largest n_base whose A and B blocks a workgroup keeps in LDS (8,192: 16 bytes per base row, 128 KiB of the 160 KiB
+ * of a gfx950 compute unit).  Needs no device. */
+int64_t smart_sobol_lds_capacity(void);
+
+/*
  * Sampling database, CSV flavour -- the rows MonteCarlo.save writes one by one (montecarlo.py:211-231): every value
  * cast to float32 and printed '%.6e', comma separated, one '\n'-terminated line per sample.  HOST pointers, no
  * device involved.  Appends n_rows lines of n_cols values (row-major float32 table: objective functions, parameters,

@@ -27,6 +27,7 @@ QUANTILES_MAX_PROBS = 16
 TRANSFORMS = {'none': 0, 'sqrt': 1, 'log': 2, 'inverse': 3}     # SMART_TRANSFORM_*
 OBJFN_WINDOW_COLS = 7
 FDC_METHODS = {'auto': 0, 'sort': 1, 'select': 2}              # SMART_FDC_*
+SOBOL_MAX_PARAMS = 16
 
 _dp = ctypes.c_void_p   # device or host address, passed as an integer
 
@@ -75,6 +76,11 @@ SYMBOLS = {
                                                _dp, ctypes.c_int64, ctypes.c_int32, _dp]),
     'smart_flow_duration_workspace_bytes': (ctypes.c_int64, [ctypes.c_int64, ctypes.c_int32, ctypes.c_int32]),
     'smart_flow_duration_sort_capacity': (ctypes.c_int64, []),
+    'smart_sobol_indices_hip': (ctypes.c_int, [ctypes.c_int64, ctypes.c_int32, ctypes.c_int64, _dp, ctypes.c_int64, _dp,
+                                               _dp, _dp, _dp, ctypes.c_int32, _dp, _dp, _dp, ctypes.c_int64, _dp]),
+    'smart_sobol_workspace_bytes': (ctypes.c_int64, [ctypes.c_int64, ctypes.c_int32, ctypes.c_int64, ctypes.c_int32]),
+    'smart_sobol_max_resamples': (ctypes.c_int32, []),
+    'smart_sobol_lds_capacity': (ctypes.c_int64, []),
     'smart_db_append_rows': (ctypes.c_int, [ctypes.c_char_p, ctypes.POINTER(ctypes.c_float), ctypes.c_int64,
                                             ctypes.c_int64, ctypes.c_int32]),
     'smart_db_parse_rows': (ctypes.c_int64, [ctypes.c_char_p, ctypes.c_int64, ctypes.c_int64,

@@ -27,6 +27,11 @@ long flow_duration_workspace_bytes(long R, int W, bool with_objfn);
 void launch_flow_duration(long N, long R, const double *sim, long ld, const double *obs, const int *window, int W,
                           const double *probs, int K, double *quant, int transform, double eps, double seg_lo,
                           double seg_hi, double *objfn, double *ws, bool sort, hipStream_t s);
+long sobol_lds_capacity();          // smart_sobol.hip
+int sobol_max_resamples();
+long sobol_workspace_bytes();
+void launch_sobol(long n, int k, long M, const double *y, long ld, double *s1, double *st, double *moments,
+                  const unsigned short *counts, int B, double *s1_std, double *st_std, hipStream_t s);
 
 static_assert(kStatusSliceTimeout == SMART_STATUS_SLICE_TIMEOUT && kStatusStalePlan == SMART_STATUS_STALE_PLAN,
               "status bits of smart_device.h and include/smart_amd.h");
@@ -1523,6 +1528,66 @@ int64_t smart_flow_duration_workspace_bytes(int64_t n_reports, int32_t n_windows
 }
 
 int64_t smart_flow_duration_sort_capacity(void) { return flow_duration_sort_capacity(); }
+
+// the size rules of smart_sobol_indices_hip, shared with smart_sobol_workspace_bytes; 0 or the text of the refusal
+static const char *sobol_sizes(int64_t n_base, int32_t n_params, int64_t n_rows, int32_t n_resamples, char *text, size_t len)
+{
+    if (n_base < 1 || n_base > 0x7fffffffll)
+        snprintf(text, len, "n_base %lld must be in 1 .. 2^31 - 1", (long long)n_base);
+    else if (n_params < 1 || n_params > SMART_SOBOL_MAX_PARAMS)
+        snprintf(text, len, "n_params %d must be in 1 .. %d", (int)n_params, SMART_SOBOL_MAX_PARAMS);
+    else if (n_rows < 1 || n_rows > 0x7fffffffll)
+        snprintf(text, len, "n_rows %lld must be in 1 .. 2^31 - 1", (long long)n_rows);
+    else if (n_resamples < 0 || n_resamples > sobol_max_resamples())
+        snprintf(text, len, "n_resamples %d must be in 0 .. %d", (int)n_resamples, sobol_max_resamples());
+    else
+        return nullptr;
+    return text;
+}
+
+int smart_sobol_indices_hip(int64_t n_base, int32_t n_params, int64_t n_rows, const double *y, int64_t ld, double *s1,
+                            double *st, double *moments, const uint16_t *counts, int32_t n_resamples, double *s1_std,
+                            double *st_std, void *workspace, int64_t workspace_bytes, void *stream)
+{
+    if (!y || !s1 || !st || !moments)
+        return fail(SMART_E_NULL, "smart_sobol_indices_hip: y, s1, st and moments are required (%s is NULL)",
+                    !y ? "y" : (!s1 ? "s1" : (!st ? "st" : "moments")));
+    if (n_resamples > 0 && (!counts || !s1_std || !st_std))
+        return fail(SMART_E_NULL, "smart_sobol_indices_hip: n_resamples %d needs counts, s1_std and st_std (%s is NULL)",
+                    (int)n_resamples, !counts ? "counts" : (!s1_std ? "s1_std" : "st_std"));
+    char text[160];
+    if (sobol_sizes(n_base, n_params, n_rows, n_resamples, text, sizeof text))
+        return fail(SMART_E_SIZE, "smart_sobol_indices_hip: %s", text);
+    if (ld < n_base * (n_params + 2))
+        return fail(SMART_E_SIZE, "smart_sobol_indices_hip: ld %lld is less than n_base * (n_params + 2) = %lld",
+                    (long long)ld, (long long)(n_base * (n_params + 2)));
+    const long need = sobol_workspace_bytes();
+    if (need > 0 && !workspace)
+        return fail(SMART_E_NULL, "smart_sobol_indices_hip: a workspace of %ld bytes is needed (workspace is NULL)", need);
+    if (workspace_bytes < (workspace ? need : 0))
+        return fail(SMART_E_SIZE, "smart_sobol_indices_hip: workspace_bytes %lld, need %ld", (long long)workspace_bytes,
+                    need);
+    int rc = device_ready();
+    if (rc)
+        return rc;
+    launch_sobol((long)n_base, (int)n_params, (long)n_rows, y, (long)ld, s1, st, moments, counts, (int)n_resamples,
+                 s1_std, st_std, (hipStream_t)stream);
+    HIP_TRY(hipGetLastError());
+    g_err[0] = 0;
+    return SMART_OK;
+}
+
+int64_t smart_sobol_workspace_bytes(int64_t n_base, int32_t n_params, int64_t n_rows, int32_t n_resamples)
+{
+    char text[160];
+    if (sobol_sizes(n_base, n_params, n_rows, n_resamples, text, sizeof text))
+        return SMART_E_SIZE;
+    return sobol_workspace_bytes();
+}
+
+int32_t smart_sobol_max_resamples(void) { return sobol_max_resamples(); }
+
+int64_t smart_sobol_lds_capacity(void) { return sobol_lds_capacity(); }
 
 int smart_row_class(const double *params, double delta_sec, const double *initial12, double area_m2)
 {

@@ -761,6 +761,101 @@ def flow_duration(discharge_report_major, probs, obs=None, windows=None, n_windo
     return quant, scores
 
 
+def sobol_max_resamples():
+    """The largest number of bootstrap replicates of one sobol_indices call (no device needed)."""
+    return int(_lib.lib().smart_sobol_max_resamples())
+
+
+def sobol_lds_capacity():
+    """The largest base size whose A and B blocks sobol_indices keeps in LDS (no device needed)."""
+    return int(_lib.lib().smart_sobol_lds_capacity())
+
+
+def sobol_counts(n_base, resamples, seed=None):
+    """The bootstrap counts of sobol_indices -> [n_base, resamples] uint16 on the host: replicate b draws n_base base rows
+    with replacement, numpy.random.Generator(PCG64(seed)).integers(n_base, size=(resamples, n_base)), and counts[i, b] is
+    how often it drew row i (every column sums to n_base)."""
+    n, B = int(n_base), int(resamples)
+    if n < 1:
+        raise SmartEngineError(-2, "sobol_counts: n_base must be at least 1 (got {}).".format(n_base))
+    if B < 0 or B > sobol_max_resamples():
+        raise SmartEngineError(-2, "sobol_counts: {} resamples, between 0 and {} per call.".format(resamples, sobol_max_resamples()))
+    draws = np.random.Generator(np.random.PCG64(seed)).integers(n, size=(B, n))
+    counts = np.zeros((n, B), dtype=np.int64)
+    for b in range(B):
+        counts[:, b] = np.bincount(draws[b], minlength=n)
+    if counts.size and counts.max() > 65535:
+        raise SmartEngineError(-2, "sobol_counts: a count of {} does not fit the uint16 of the kernel.".format(counts.max()))
+    return np.ascontiguousarray(counts.astype(np.uint16))
+
+
+class SobolResult(object):
+    """Device tensors of one sobol_indices call: S1, ST [M, k], moments [M, 2] (mean and variance of A u B), S1_std and
+    ST_std [M, k] or None without counts."""
+
+    def __init__(self, S1, ST, moments, S1_std, ST_std):
+        self.S1, self.ST, self.moments, self.S1_std, self.ST_std = S1, ST, moments, S1_std, ST_std
+
+
+def sobol_indices(values, n_base, n_params, counts=None):
+    """First-order (Saltelli 2010) and total (Jansen) Sobol indices of every row of `values` -> SobolResult.
+    values: [M, N] or [N], host or device, N >= n_base * (n_params + 2) columns in the block-major order of
+    sampling.saltelli_design ([A ; B ; AB_0 ; ...]; a row is a report step of a stored discharge matrix, or one scalar
+    target); the leading dimension of a device matrix is honoured.  counts: [n_base, B] uint16 from sobol_counts (or a
+    device tensor of those 16-bit patterns, uint16 or int16) adds the standard deviation of both indices over the B bootstrap replicates; None leaves it out.  A row with a
+    value that is not finite, or without variance, is NaN (include/smart_amd.h: smart_sobol_indices_hip)."""
+    L = _lib.lib()
+    n, k = int(n_base), int(n_params)
+    y = values
+    if len(y.shape) == 1:
+        y = y.reshape(1, -1)
+    if len(y.shape) != 2:
+        raise SmartEngineError(-2, "sobol_indices: values [M, N] or [N] are needed, not shape {}.".format(tuple(values.shape)))
+    if n < 1 or k < 1 or k > _lib.SOBOL_MAX_PARAMS or y.shape[1] != n * (k + 2):
+        raise SmartEngineError(-2, "sobol_indices: {} columns are not n_base * (n_params + 2) with n_base = {} >= 1 and "
+                                   "n_params = {} in 1 .. {}.".format(y.shape[1], n_base, n_params, _lib.SOBOL_MAX_PARAMS))
+    B = 0
+    if counts is not None:
+        if len(counts.shape) != 2 or counts.shape[0] != n or \
+                str(counts.dtype).split('.')[-1] not in (('uint16', 'int16') if isinstance(counts, torch.Tensor) else ('uint16',)):
+            raise SmartEngineError(-2, "sobol_indices: counts must be uint16 [n_base, resamples] (engine.sobol_counts), "
+                                       "not {} {}.".format(counts.dtype, tuple(counts.shape)))
+        B = int(counts.shape[1])
+        if B > sobol_max_resamples():
+            raise SmartEngineError(-2, "sobol_indices: {} resamples, at most {} per call.".format(B, sobol_max_resamples()))
+    if not (isinstance(y, torch.Tensor) and y.is_cuda):
+        y = as_device(y, default_device())
+    if y.dtype != torch.float64:
+        y = y.to(torch.float64)
+    if y.stride(-1) != 1:
+        y = y.contiguous()
+    M, N = y.shape
+    ld = y.stride(0) if M > 1 else N
+    dev = y.device
+    S1 = torch.empty((M, k), dtype=torch.float64, device=dev)
+    ST = torch.empty((M, k), dtype=torch.float64, device=dev)
+    moments = torch.empty((M, 2), dtype=torch.float64, device=dev)
+    S1_std = ST_std = None
+    if M == 0:
+        return SobolResult(S1, ST, moments, None, None)
+    if B > 0:
+        if not isinstance(counts, torch.Tensor):
+            counts = torch.from_numpy(np.ascontiguousarray(counts).view(np.int16))     # (the same 16 bits)
+        counts = counts.to(dev).contiguous()
+        S1_std, ST_std = torch.empty_like(S1), torch.empty_like(ST)
+    need = int(L.smart_sobol_workspace_bytes(n, k, M, B))
+    if need < 0:
+        _lib.check(need)
+    work = torch.empty(need, dtype=torch.uint8, device=dev) if need else None
+    with torch.cuda.device(dev):
+        _lib.check(L.smart_sobol_indices_hip(n, k, M, y.data_ptr(), ld, S1.data_ptr(), ST.data_ptr(), moments.data_ptr(),
+                                             counts.data_ptr() if B else None, B,
+                                             S1_std.data_ptr() if B else None, ST_std.data_ptr() if B else None,
+                                             None if work is None else work.data_ptr(), need,
+                                             torch.cuda.current_stream(dev).cuda_stream))
+    return SobolResult(S1, ST, moments, S1_std, ST_std)
+
+
 def allsteps(area_m2, delta_sec, length_simu, nd_rain, nd_peva, nd_parameters, nd_initial, report_type, report_gap):
     """smartcpp.allsteps: same arguments and results as run_all_steps (structure.py:149-152,197); host arrays."""
     L = _lib.lib()
