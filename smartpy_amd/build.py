@@ -40,10 +40,13 @@ UNITS = {
     # value that is not finite has to reach the one sum that finds it
     'smart_sobol.hip': [],
     'smart_capi.hip': [],
+    # the C entries of the matrix analyses, and smart_objfn_matrix: the flags smart_capi.hip had it compiled with
+    'smart_analysis_capi.hip': [],
     'smart_hostio.cpp': ['-pthread'],      # host only: the sampling-database writer
 }
 COMMON = ['-O3', '-fPIC', '-std=c++17', '--offload-arch=' + ARCH, '-fno-gpu-rdc', '-Wall']
-DEPS = ['smart_device.h', 'smart_order_keys.h', 'smart_literal_model.h', 'smart_literal_lanes.h', 'smart_fast_model.h', 'smart_fast_arms.h', 'smart_fast_entry.h', os.path.join('..', '..', 'include', 'smart_amd.h')]
+# every header of csrc and the public one: a new header cannot be forgotten
+DEPS = sorted(f for f in os.listdir(CSRC) if f.endswith('.h')) + [os.path.join('..', '..', 'include', 'smart_amd.h')]
 
 
 def hipcc():

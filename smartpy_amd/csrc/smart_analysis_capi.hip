@@ -1,0 +1,352 @@
+// smart_analysis_capi.hip -- the C ABI of the analyses of a stored discharge matrix sim[R][ld] (include/smart_amd.h):
+// objective functions, weighted quantiles, objective functions per window, flow duration curves, Sobol indices, with
+// their capacity and workspace entries -- validation and launch -- and the one kernel among them that has no unit of its
+// own, smart_objfn_matrix.  Every refusal comes before the device is asked for; the rules the entries share are the
+// static helpers below, which take the entry's name for the text.
+#include "smart_capi_internal.h"
+#include "smart_device.h"
+
+#include <cmath>
+#include <cstdio>
+
+namespace smart {
+
+// Objective functions of a stored discharge matrix sim[R][ld] (sample-minor).  HBM-bound: the matrix is read
+// exactly once, 8 * R bytes per sample, every wavefront load one contiguous 512-byte row segment, UNROLL of them in
+// flight per lane.  Moments are taken about the observation mean (the same one-pass form as the fused path of the
+// time-loop kernel).  A workgroup is WX wavefronts wide along the samples and WR deep along the report rows:
+//   WX = 4, WR = 1 : one lane walks all rows of its sample (large N: enough wavefronts, 2 KB contiguous per row);
+//   WX = 1, WR = 8 : 8 wavefronts share 64 samples and take the rows round-robin, partial moments are reduced
+//                    through LDS in a fixed order (N ~ 1e5: 8x more wavefronts in flight).
+template <int WX, int WR, int UNROLL>
+__global__ __launch_bounds__(WX *WR *kWave) void smart_objfn_matrix(long N, long R, const double *__restrict__ sim,
+                                                                    long ld, const double *__restrict__ obs,
+                                                                    const double *__restrict__ gw_sim, double gw_obs,
+                                                                    double *__restrict__ objfn)
+{
+    __shared__ double sh[512];
+    __shared__ double st[5];
+    __shared__ double part[WR > 1 ? WR : 1][5][kWave];
+    obs_stats<false>(obs, R, st, nullptr, sh); // every thread stores the same five values to st
+    __syncthreads();
+    const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
+    const int wx = wave % WX, wr = wave / WX;
+    long n = ((long)blockIdx.x * WX + wx) * kWave + lane;
+    const bool live = n < N;
+    if (!live)
+        n = N - 1;
+    const double ebar = st[1];
+    const double *col = sim + n;
+    const double shift = col[0]; // any constant per sample works (finish_objectives); the first value keeps the digits
+    double A = 0.0, B = 0.0, C1 = 0.0, C2 = 0.0, C3 = 0.0;
+    auto add = [&](double e, double s) {
+        if (!is_nan_bits(e)) { // montecarlo.py:195-196
+            const double d = s - e, u = s - shift;
+            A += d;
+            B += d * d;
+            C1 += u;
+            C2 += u * u;
+            C3 += (e - ebar) * u;
+        }
+    };
+    long r = wr;
+    for (; r + (UNROLL - 1) * WR < R; r += UNROLL * WR) { // UNROLL independent row loads in flight
+        double s[UNROLL];
+#pragma unroll
+        for (int j = 0; j < UNROLL; ++j)
+            s[j] = col[(r + j * WR) * ld];
+#pragma unroll
+        for (int j = 0; j < UNROLL; ++j)
+            add(obs[r + j * WR], s[j]);
+    }
+    for (; r < R; r += WR)
+        add(obs[r], col[r * ld]);
+    double m[5] = {A, B, C1, C2, C3};
+    if (WR > 1) {
+#pragma unroll
+        for (int k = 0; k < 5; ++k)
+            part[wr][k][lane] = m[k];
+        __syncthreads();
+        if (wr != 0)
+            return;
+#pragma unroll
+        for (int k = 0; k < 5; ++k) {
+            double t = part[0][k][lane];
+#pragma unroll
+            for (int w = 1; w < WR; ++w)
+                t += part[w][k][lane];
+            m[k] = t;
+        }
+    }
+    if (live) {
+        double o[8];
+        finish_objectives(st, m[0], m[1], m[2], m[3], m[4], gw_sim ? gw_sim[n] : 0.0,
+                          gw_sim ? gw_obs : __builtin_nan(""), o);
+        double *op = objfn + n * 8;
+#pragma unroll
+        for (int k = 0; k < 8; ++k)
+            op[k] = o[k];
+    }
+}
+
+// ---- the rules the entries share ------------------------------------------------------------------------------------
+static int reports_fit(const char *entry, int64_t n_reports)
+{
+    if (n_reports > 0x7fffffffll)
+        return fail(SMART_E_SIZE, "%s: n_reports %lld is more than one launch takes (2^31 - 1)", entry,
+                    (long long)n_reports);
+    return SMART_OK;
+}
+
+// the sizes of a matrix read per window: every count >= 1 (n_probs where the entry has one), ld, 2^31, the window cap
+static int windowed_sizes(const char *entry, int64_t n_samples, int64_t n_reports, int64_t ld, int32_t n_windows,
+                          const int32_t *n_probs)
+{
+    if (n_probs && (n_samples < 1 || n_reports < 1 || n_windows < 1 || *n_probs < 1))
+        return fail(SMART_E_SIZE, "%s: need n_samples, n_reports, n_windows, n_probs >= 1 (got %lld, %lld, %d, %d)", entry,
+                    (long long)n_samples, (long long)n_reports, (int)n_windows, (int)*n_probs);
+    if (n_samples < 1 || n_reports < 1 || n_windows < 1)
+        return fail(SMART_E_SIZE, "%s: need n_samples, n_reports, n_windows >= 1 (got %lld, %lld, %d)", entry,
+                    (long long)n_samples, (long long)n_reports, (int)n_windows);
+    if (ld < n_samples)
+        return fail(SMART_E_SIZE, "%s: ld %lld is less than n_samples %lld", entry, (long long)ld, (long long)n_samples);
+    if (int rc = reports_fit(entry, n_reports))
+        return rc;
+    if (n_windows > objfn_max_windows())
+        return fail(SMART_E_SIZE, "%s: n_windows %d, at most %d per call", entry, (int)n_windows, objfn_max_windows());
+    return SMART_OK;
+}
+
+// every probability inside (0, 1], or [0, 1] where rank 1 has a probability of its own (a NaN is outside both)
+static int probs_inside(const char *entry, const double *probs, int32_t n_probs, bool zero_too)
+{
+    for (int32_t k = 0; k < n_probs; ++k)
+        if (!((zero_too ? probs[k] >= 0.0 : probs[k] > 0.0) && probs[k] <= 1.0))
+            return fail(SMART_E_SIZE, "%s: probability %d is %g, outside %s", entry, (int)k, probs[k],
+                        zero_too ? "[0, 1]" : "(0, 1]");
+    return SMART_OK;
+}
+
+static int eps_usable(const char *entry, double eps)
+{
+    if (!(eps >= 0.0) || std::isinf(eps))
+        return fail(SMART_E_SIZE, "%s: eps %g must be finite and >= 0", entry, eps);
+    return SMART_OK;
+}
+
+static int transform_known(const char *entry, int32_t transform)
+{
+    if (transform < SMART_TRANSFORM_NONE || transform > SMART_TRANSFORM_INVERSE)
+        return fail(SMART_E_MODE, "%s: transform '%d' unknown.", entry, (int)transform);
+    return SMART_OK;
+}
+
+// a workspace of `need` bytes: present where any are needed, and large enough
+static int workspace_fits(const char *entry, bool for_objfn, const void *workspace, int64_t workspace_bytes, long need)
+{
+    if (need > 0 && !workspace)
+        return fail(SMART_E_NULL,
+                    for_objfn ? "%s: objfn needs a workspace of %ld bytes (workspace is NULL)"
+                              : "%s: a workspace of %ld bytes is needed (workspace is NULL)",
+                    entry, need);
+    if (workspace_bytes < (workspace ? need : 0))
+        return fail(SMART_E_SIZE, "%s: workspace_bytes %lld, need %ld", entry, (long long)workspace_bytes, need);
+    return SMART_OK;
+}
+
+// the end of every entry, after its launch
+static int launched()
+{
+    HIP_TRY(hipGetLastError());
+    clear_error();
+    return SMART_OK;
+}
+
+// the size rules of smart_sobol_indices_hip, shared with smart_sobol_workspace_bytes; 0 or the text of the refusal
+static const char *sobol_sizes(int64_t n_base, int32_t n_params, int64_t n_rows, int32_t n_resamples, char *text, size_t len)
+{
+    if (n_base < 1 || n_base > 0x7fffffffll)
+        snprintf(text, len, "n_base %lld must be in 1 .. 2^31 - 1", (long long)n_base);
+    else if (n_params < 1 || n_params > SMART_SOBOL_MAX_PARAMS)
+        snprintf(text, len, "n_params %d must be in 1 .. %d", (int)n_params, SMART_SOBOL_MAX_PARAMS);
+    else if (n_rows < 1 || n_rows > 0x7fffffffll)
+        snprintf(text, len, "n_rows %lld must be in 1 .. 2^31 - 1", (long long)n_rows);
+    else if (n_resamples < 0 || n_resamples > sobol_max_resamples())
+        snprintf(text, len, "n_resamples %d must be in 0 .. %d", (int)n_resamples, sobol_max_resamples());
+    else
+        return nullptr;
+    return text;
+}
+
+} // namespace smart
+
+using namespace smart;
+
+extern "C" {
+
+int smart_objfn_hip(int64_t n_samples, int64_t n_reports, const double *sim, int64_t ld, const double *obs,
+                    const double *gw_sim, double gw_obs, double *objfn, void *stream)
+{
+    if (!sim || !obs || !objfn)
+        return fail(SMART_E_NULL, "smart_objfn_hip: sim, obs and objfn are required");
+    if (n_samples < 1 || n_reports < 1 || ld < n_samples)
+        return fail(SMART_E_SIZE, "smart_objfn_hip: need n_samples, n_reports >= 1 and ld >= n_samples");
+    if (int rc = device_ready())
+        return rc;
+    if (n_samples >= 4 * 65536) // >= 4 wavefronts per SIMD even with one lane per sample
+        hipLaunchKernelGGL((smart_objfn_matrix<4, 1, 8>), dim3((unsigned)((n_samples + 4 * kWave - 1) / (4 * kWave))),
+                           dim3(4 * kWave), 0, (hipStream_t)stream, (long)n_samples, (long)n_reports, sim, (long)ld, obs,
+                           gw_sim, gw_obs, objfn);
+    else
+        hipLaunchKernelGGL((smart_objfn_matrix<1, 8, 4>), dim3((unsigned)((n_samples + kWave - 1) / kWave)),
+                           dim3(8 * kWave), 0, (hipStream_t)stream, (long)n_samples, (long)n_reports, sim, (long)ld, obs,
+                           gw_sim, gw_obs, objfn);
+    return launched();
+}
+
+int smart_weighted_quantiles_hip(int64_t n_samples, int64_t n_reports, const double *sim, int64_t ld,
+                                 const double *weights, const double *probs, int32_t n_probs, double *out,
+                                 int32_t method, void *stream)
+{
+    static const char entry[] = "smart_weighted_quantiles_hip";
+    int rc;
+    if (!sim || !probs || !out)
+        return fail(SMART_E_NULL, "%s: sim, probs and out are required", entry);
+    if (n_samples < 1 || n_reports < 1 || n_probs < 1 || ld < n_samples)
+        return fail(SMART_E_SIZE, "%s: need n_samples, n_reports, n_probs >= 1 and ld >= n_samples", entry);
+    if ((rc = reports_fit(entry, n_reports)))
+        return rc;
+    if (n_probs > SMART_QUANTILES_MAX_PROBS)
+        return fail(SMART_E_SIZE, "%s: %d probabilities, at most %d per call", entry, (int)n_probs,
+                    SMART_QUANTILES_MAX_PROBS);
+    if ((rc = probs_inside(entry, probs, n_probs, /*zero_too=*/false)))
+        return rc;
+    if (method != SMART_QUANTILES_AUTO && method != SMART_QUANTILES_SORT && method != SMART_QUANTILES_SELECT)
+        return fail(SMART_E_MODE, "%s: method '%d' unknown.", entry, (int)method);
+    if (method == SMART_QUANTILES_SORT && n_samples > quantiles_sort_capacity())
+        return fail(SMART_E_SIZE, "%s: the sort form takes at most %lld samples, not %lld", entry,
+                    (long long)quantiles_sort_capacity(), (long long)n_samples);
+    if ((rc = device_ready()))
+        return rc;
+    const bool sort = method == SMART_QUANTILES_SORT ||
+                      (method == SMART_QUANTILES_AUTO && n_samples <= quantiles_sort_capacity());
+    launch_quantiles((long)n_samples, (long)n_reports, sim, (long)ld, weights, probs, (int)n_probs, out, sort,
+                     (hipStream_t)stream);
+    return launched();
+}
+
+int64_t smart_quantiles_sort_capacity(void) { return quantiles_sort_capacity(); }
+
+int smart_objfn_windows_hip(int64_t n_samples, int64_t n_reports, const double *sim, int64_t ld, const double *obs,
+                            const int32_t *window, int32_t n_windows, int32_t transform, double eps, double *objfn,
+                            void *stream)
+{
+    static const char entry[] = "smart_objfn_windows_hip";
+    int rc;
+    if (!sim || !obs || !window || !objfn)
+        return fail(SMART_E_NULL, "%s: sim, obs, window and objfn are required (%s is NULL)", entry,
+                    !sim ? "sim" : (!obs ? "obs" : (!window ? "window" : "objfn")));
+    if ((rc = windowed_sizes(entry, n_samples, n_reports, ld, n_windows, nullptr)) || (rc = eps_usable(entry, eps)) ||
+        (rc = transform_known(entry, transform)) || (rc = device_ready()))
+        return rc;
+    launch_objfn_windows((long)n_samples, (long)n_reports, sim, (long)ld, obs, window, (int)n_windows, (int)transform, eps,
+                         objfn, (hipStream_t)stream);
+    return launched();
+}
+
+int32_t smart_objfn_max_windows(void) { return objfn_max_windows(); }
+
+int smart_flow_duration_hip(int64_t n_samples, int64_t n_reports, const double *sim, int64_t ld, const double *obs,
+                            const int32_t *window, int32_t n_windows, const double *probs, int32_t n_probs,
+                            double *quant, int32_t transform, double eps, double seg_lo, double seg_hi, double *objfn,
+                            void *workspace, int64_t workspace_bytes, int32_t method, void *stream)
+{
+    static const char entry[] = "smart_flow_duration_hip";
+    int rc;
+    if (!sim || !probs || !quant)
+        return fail(SMART_E_NULL, "%s: sim, probs and quant are required (%s is NULL)", entry,
+                    !sim ? "sim" : (!probs ? "probs" : "quant"));
+    if (objfn && !obs)
+        return fail(SMART_E_NULL, "%s: objfn needs obs (obs is NULL)", entry);
+    if ((rc = windowed_sizes(entry, n_samples, n_reports, ld, n_windows, &n_probs)))
+        return rc;
+    if (!window && n_windows != 1)
+        return fail(SMART_E_SIZE, "%s: n_windows %d without a window array (NULL is one window)", entry, (int)n_windows);
+    if (n_probs > SMART_QUANTILES_MAX_PROBS)
+        return fail(SMART_E_SIZE, "%s: n_probs %d, at most %d probabilities per call", entry, (int)n_probs,
+                    SMART_QUANTILES_MAX_PROBS);
+    if ((rc = probs_inside(entry, probs, n_probs, /*zero_too=*/true)) || (rc = eps_usable(entry, eps)))
+        return rc;
+    if (!(seg_lo >= 0.0 && seg_lo < seg_hi && seg_hi <= 1.0))
+        return fail(SMART_E_SIZE, "%s: the segment (%g, %g) is not 0 <= seg_lo < seg_hi <= 1", entry, seg_lo, seg_hi);
+    if ((rc = transform_known(entry, transform)))
+        return rc;
+    if (method != SMART_FDC_AUTO && method != SMART_FDC_SORT && method != SMART_FDC_SELECT)
+        return fail(SMART_E_MODE, "%s: method '%d' unknown.", entry, (int)method);
+    if (objfn && method == SMART_FDC_SELECT)
+        return fail(SMART_E_MODE, "%s: the select form gives order statistics only (objfn given)", entry);
+    const long capacity = flow_duration_sort_capacity();
+    if (n_reports > capacity && (objfn || method == SMART_FDC_SORT))
+        return fail(SMART_E_SIZE, "%s: %s at most %ld report steps (the sort capacity), not %lld", entry,
+                    objfn ? "the objective functions of the curve take" : "the sort form takes", capacity,
+                    (long long)n_reports);
+    if (objfn && (rc = workspace_fits(entry, /*for_objfn=*/true, workspace, workspace_bytes,
+                                      flow_duration_workspace_bytes((long)n_reports, (int)n_windows, true))))
+        return rc;
+    if ((rc = device_ready()))
+        return rc;
+    const bool sort = method != SMART_FDC_SELECT && n_reports <= capacity;
+    launch_flow_duration((long)n_samples, (long)n_reports, sim, (long)ld, obs, window, (int)n_windows, probs, (int)n_probs,
+                         quant, (int)transform, eps, seg_lo, seg_hi, objfn, (double *)workspace, sort,
+                         (hipStream_t)stream);
+    return launched();
+}
+
+int64_t smart_flow_duration_workspace_bytes(int64_t n_reports, int32_t n_windows, int32_t with_objfn)
+{
+    if (n_reports < 1 || n_reports > 0x7fffffffll || n_windows < 1)
+        return SMART_E_SIZE;
+    return flow_duration_workspace_bytes((long)n_reports, (int)n_windows, with_objfn != 0);
+}
+
+int64_t smart_flow_duration_sort_capacity(void) { return flow_duration_sort_capacity(); }
+
+int smart_sobol_indices_hip(int64_t n_base, int32_t n_params, int64_t n_rows, const double *y, int64_t ld, double *s1,
+                            double *st, double *moments, const uint16_t *counts, int32_t n_resamples, double *s1_std,
+                            double *st_std, void *workspace, int64_t workspace_bytes, void *stream)
+{
+    static const char entry[] = "smart_sobol_indices_hip";
+    int rc;
+    if (!y || !s1 || !st || !moments)
+        return fail(SMART_E_NULL, "%s: y, s1, st and moments are required (%s is NULL)", entry,
+                    !y ? "y" : (!s1 ? "s1" : (!st ? "st" : "moments")));
+    if (n_resamples > 0 && (!counts || !s1_std || !st_std))
+        return fail(SMART_E_NULL, "%s: n_resamples %d needs counts, s1_std and st_std (%s is NULL)", entry,
+                    (int)n_resamples, !counts ? "counts" : (!s1_std ? "s1_std" : "st_std"));
+    char text[160];
+    if (sobol_sizes(n_base, n_params, n_rows, n_resamples, text, sizeof text))
+        return fail(SMART_E_SIZE, "%s: %s", entry, text);
+    if (ld < n_base * (n_params + 2))
+        return fail(SMART_E_SIZE, "%s: ld %lld is less than n_base * (n_params + 2) = %lld", entry, (long long)ld,
+                    (long long)(n_base * (n_params + 2)));
+    if ((rc = workspace_fits(entry, /*for_objfn=*/false, workspace, workspace_bytes, sobol_workspace_bytes())) ||
+        (rc = device_ready()))
+        return rc;
+    launch_sobol((long)n_base, (int)n_params, (long)n_rows, y, (long)ld, s1, st, moments, counts, (int)n_resamples,
+                 s1_std, st_std, (hipStream_t)stream);
+    return launched();
+}
+
+int64_t smart_sobol_workspace_bytes(int64_t n_base, int32_t n_params, int64_t n_rows, int32_t n_resamples)
+{
+    char text[160];
+    if (sobol_sizes(n_base, n_params, n_rows, n_resamples, text, sizeof text))
+        return SMART_E_SIZE;
+    return sobol_workspace_bytes();
+}
+
+int32_t smart_sobol_max_resamples(void) { return sobol_max_resamples(); }
+
+int64_t smart_sobol_lds_capacity(void) { return sobol_lds_capacity(); }
+
+} // extern "C"

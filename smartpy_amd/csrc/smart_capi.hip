@@ -1,6 +1,7 @@
-// smart_capi.hip -- the C ABI of include/smart_amd.h: validation, launch plumbing, and the two small
-// kernels around the ensemble launch (observation statistics, objective functions of a stored matrix).
-#include "../../include/smart_amd.h"
+// smart_capi.hip -- the C ABI of include/smart_amd.h for the ensemble engine: validation, planning, workspace, launch
+// plumbing, the smartcpp.allsteps hook, and the small kernels around the ensemble launch.  The analyses of a stored
+// discharge matrix have their entries in smart_analysis_capi.hip; smart_capi_internal.h is what the two share.
+#include "smart_capi_internal.h"
 #include "smart_fast_entry.h"
 
 #include <cmath>
@@ -12,33 +13,13 @@
 #include <vector>
 
 namespace smart {
-void launch_literal(const KArgs &a, dim3 grid, size_t lds_bytes, hipStream_t s, bool rows);
-void launch_onestep(long n, const double *in, double *out, hipStream_t s);
-void launch_river(long n, const double *in, double *out, hipStream_t s);
-long quantiles_sort_capacity();     // smart_quantiles.hip
-int quantiles_max_probs();
-void launch_quantiles(long N, long R, const double *sim, long ld, const double *weights, const double *probs, int K,
-                      double *out, bool sort, hipStream_t s);
-int objfn_max_windows();            // smart_objfn_windows.hip
-void launch_objfn_windows(long N, long R, const double *sim, long ld, const double *obs, const int *window, int W,
-                          int transform, double eps, double *objfn, hipStream_t s);
-long flow_duration_sort_capacity(); // smart_flow_duration.hip
-long flow_duration_workspace_bytes(long R, int W, bool with_objfn);
-void launch_flow_duration(long N, long R, const double *sim, long ld, const double *obs, const int *window, int W,
-                          const double *probs, int K, double *quant, int transform, double eps, double seg_lo,
-                          double seg_hi, double *objfn, double *ws, bool sort, hipStream_t s);
-long sobol_lds_capacity();          // smart_sobol.hip
-int sobol_max_resamples();
-long sobol_workspace_bytes();
-void launch_sobol(long n, int k, long M, const double *y, long ld, double *s1, double *st, double *moments,
-                  const unsigned short *counts, int B, double *s1_std, double *st_std, hipStream_t s);
 
 static_assert(kStatusSliceTimeout == SMART_STATUS_SLICE_TIMEOUT && kStatusStalePlan == SMART_STATUS_STALE_PLAN,
               "status bits of smart_device.h and include/smart_amd.h");
 
 static thread_local char g_err[512] = "";
 
-int fail(int code, const char *fmt, ...) // also used by smart_hostio.cpp
+int fail(int code, const char *fmt, ...)
 {
     va_list ap;
     va_start(ap, fmt);
@@ -47,157 +28,20 @@ int fail(int code, const char *fmt, ...) // also used by smart_hostio.cpp
     return code;
 }
 
-static int hip_fail(hipError_t e, const char *what)
-{
-    return fail(SMART_E_NO_DEVICE, "%s: %s", what, hipGetErrorString(e));
-}
+void clear_error() { g_err[0] = 0; }
 
-#define HIP_TRY(expr)                                                                                                  \
-    do {                                                                                                               \
-        hipError_t _e = (expr);                                                                                        \
-        if (_e != hipSuccess)                                                                                          \
-            return hip_fail(_e, #expr);                                                                                \
-    } while (0)
+int hip_fail(hipError_t e, const char *what) { return fail(SMART_E_NO_DEVICE, "%s: %s", what, hipGetErrorString(e)); }
 
-// ---- block reduction helper (256 threads), deterministic order -----------------------------------------
-__device__ inline double block_sum(double v, double *sh)
-{
-    const int tid = threadIdx.x;
-    sh[tid] = v;
-    __syncthreads();
-    for (int s = blockDim.x / 2; s > 0; s >>= 1) {
-        if (tid < s)
-            sh[tid] += sh[tid + s];
-        __syncthreads();
-    }
-    const double r = sh[0];
-    __syncthreads();
-    return r;
-}
-
-// statistics of one observation series (NaN = missing, montecarlo.py:195-196): st[0..4] = n, mean, sum,
-// sum((e-mean)^2), sum(e-mean); dev[r] = e[r] - mean when dev != null -- and kMissingObs where e[r] is missing: a NaN of a
-// payload no arithmetic produces, so that a kernel with a report every step can tell a missing observation by ONE 32-bit
-// scalar compare on the deviation it loads anyway (Reporter's other users test e itself and never read dev then)
-__device__ inline void obs_stats(const double *obs, long R, double *st, double *dev, double *sh)
-{
-    double cnt = 0.0, s = 0.0;
-    for (long r = threadIdx.x; r < R; r += blockDim.x) {
-        const double e = obs[r];
-        if (!is_nan_bits(e)) {
-            cnt += 1.0;
-            s += e;
-        }
-    }
-    cnt = block_sum(cnt, sh);
-    s = block_sum(s, sh);
-    const double mean = s / cnt;
-    double s2 = 0.0, s1 = 0.0;
-    for (long r = threadIdx.x; r < R; r += blockDim.x) {
-        const double e = obs[r];
-        const bool missing = is_nan_bits(e);
-        const double d = !missing ? e - mean : 0.0;
-        s2 += d * d;
-        s1 += d;
-        if (dev)
-            dev[r] = missing ? __builtin_bit_cast(double, kMissingObs) : d;
-    }
-    s2 = block_sum(s2, sh);
-    s1 = block_sum(s1, sh);
-    st[0] = cnt;
-    st[1] = mean;
-    st[2] = s;
-    st[3] = s2;
-    st[4] = s1;
-}
-
+// (block_sum and obs_stats: smart_matrix_common.h)
 __global__ __launch_bounds__(256) void smart_obs_prepare(const double *obs, long R, double *ws)
 {
     __shared__ double sh[512];
     __shared__ double st[5];
     const long c = blockIdx.x;
     double *w = ws + c * (kWsHead + R);
-    obs_stats(obs + c * R, R, st, w + kWsHead, sh);
+    obs_stats<true>(obs + c * R, R, st, w + kWsHead, sh);
     if (threadIdx.x < 5)
         w[threadIdx.x] = st[threadIdx.x];
-}
-
-// Objective functions of a stored discharge matrix sim[R][ld] (sample-minor).  HBM-bound: the matrix is read
-// exactly once, 8 * R bytes per sample, every wavefront load one contiguous 512-byte row segment, UNROLL of them in
-// flight per lane.  Moments are taken about the observation mean (the same one-pass form as the fused path of the
-// time-loop kernel).  A workgroup is WX wavefronts wide along the samples and WR deep along the report rows:
-//   WX = 4, WR = 1 : one lane walks all rows of its sample (large N: enough wavefronts, 2 KB contiguous per row);
-//   WX = 1, WR = 8 : 8 wavefronts share 64 samples and take the rows round-robin, partial moments are reduced
-//                    through LDS in a fixed order (N ~ 1e5: 8x more wavefronts in flight).
-template <int WX, int WR, int UNROLL>
-__global__ __launch_bounds__(WX *WR *kWave) void smart_objfn_matrix(long N, long R, const double *__restrict__ sim,
-                                                                    long ld, const double *__restrict__ obs,
-                                                                    const double *__restrict__ gw_sim, double gw_obs,
-                                                                    double *__restrict__ objfn)
-{
-    __shared__ double sh[512];
-    __shared__ double st[5];
-    __shared__ double part[WR > 1 ? WR : 1][5][kWave];
-    obs_stats(obs, R, st, nullptr, sh); // every thread stores the same five values to st
-    __syncthreads();
-    const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
-    const int wx = wave % WX, wr = wave / WX;
-    long n = ((long)blockIdx.x * WX + wx) * kWave + lane;
-    const bool live = n < N;
-    if (!live)
-        n = N - 1;
-    const double ebar = st[1];
-    const double *col = sim + n;
-    const double shift = col[0]; // any constant per sample works (finish_objectives); the first value keeps the digits
-    double A = 0.0, B = 0.0, C1 = 0.0, C2 = 0.0, C3 = 0.0;
-    auto add = [&](double e, double s) {
-        if (!is_nan_bits(e)) { // montecarlo.py:195-196
-            const double d = s - e, u = s - shift;
-            A += d;
-            B += d * d;
-            C1 += u;
-            C2 += u * u;
-            C3 += (e - ebar) * u;
-        }
-    };
-    long r = wr;
-    for (; r + (UNROLL - 1) * WR < R; r += UNROLL * WR) { // UNROLL independent row loads in flight
-        double s[UNROLL];
-#pragma unroll
-        for (int j = 0; j < UNROLL; ++j)
-            s[j] = col[(r + j * WR) * ld];
-#pragma unroll
-        for (int j = 0; j < UNROLL; ++j)
-            add(obs[r + j * WR], s[j]);
-    }
-    for (; r < R; r += WR)
-        add(obs[r], col[r * ld]);
-    double m[5] = {A, B, C1, C2, C3};
-    if (WR > 1) {
-#pragma unroll
-        for (int k = 0; k < 5; ++k)
-            part[wr][k][lane] = m[k];
-        __syncthreads();
-        if (wr != 0)
-            return;
-#pragma unroll
-        for (int k = 0; k < 5; ++k) {
-            double t = part[0][k][lane];
-#pragma unroll
-            for (int w = 1; w < WR; ++w)
-                t += part[w][k][lane];
-            m[k] = t;
-        }
-    }
-    if (live) {
-        double o[8];
-        finish_objectives(st, m[0], m[1], m[2], m[3], m[4], gw_sim ? gw_sim[n] : 0.0,
-                          gw_sim ? gw_obs : __builtin_nan(""), o);
-        double *op = objfn + n * 8;
-#pragma unroll
-        for (int k = 0; k < 8; ++k)
-            op[k] = o[k];
-    }
 }
 
 // ---- small kernels around the launch -------------------------------------------------------------------------
@@ -497,11 +341,11 @@ static int check(const SmartEnsemble *e)
         return fail(SMART_E_SIZE, "plan must be 0 or a value returned by smart_plan_ensemble");
     if (e->literal_form < SMART_LITERAL_FORM_AUTO || e->literal_form > SMART_LITERAL_FORM_LANES)
         return fail(SMART_E_MODE, "literal_form must be SMART_LITERAL_FORM_AUTO, _ROWS or _LANES");
-    g_err[0] = 0;
+    clear_error();
     return SMART_OK;
 }
 
-static int device_ready()
+int device_ready()
 {
     int n = 0;
     hipError_t err = hipGetDeviceCount(&n);
@@ -1255,7 +1099,7 @@ static int allsteps(double area_m2, double delta_sec, int64_t length_simu, const
     std::memcpy(discharge, h.stage.data(), (size_t)(R > 0 ? R : 0) * sizeof(double));
     *groundwater_component = h.stage[n_rep];
     std::memcpy(final_vars, h.stage.data() + n_rep + 1, 19 * sizeof(double));
-    g_err[0] = 0;
+    clear_error();
     return SMART_OK;
 }
 
@@ -1325,7 +1169,7 @@ int smart_onestep_hip(int64_t n, const double *in, double *out)
     (void)hipFree(dev);
     if (err != hipSuccess)
         return hip_fail(err, "smart_onestep_hip");
-    g_err[0] = 0;
+    clear_error();
     return SMART_OK;
 }
 
@@ -1350,244 +1194,9 @@ int smart_river_step_hip(int64_t n, const double *in, double *out)
     (void)hipFree(dev);
     if (err != hipSuccess)
         return hip_fail(err, "smart_river_step_hip");
-    g_err[0] = 0;
+    clear_error();
     return SMART_OK;
 }
-
-int smart_objfn_hip(int64_t n_samples, int64_t n_reports, const double *sim, int64_t ld, const double *obs,
-                    const double *gw_sim, double gw_obs, double *objfn, void *stream)
-{
-    if (!sim || !obs || !objfn)
-        return fail(SMART_E_NULL, "smart_objfn_hip: sim, obs and objfn are required");
-    if (n_samples < 1 || n_reports < 1 || ld < n_samples)
-        return fail(SMART_E_SIZE, "smart_objfn_hip: need n_samples, n_reports >= 1 and ld >= n_samples");
-    int rc = device_ready();
-    if (rc)
-        return rc;
-    if (n_samples >= 4 * 65536) // >= 4 wavefronts per SIMD even with one lane per sample
-        hipLaunchKernelGGL((smart_objfn_matrix<4, 1, 8>), dim3((unsigned)((n_samples + 4 * kWave - 1) / (4 * kWave))),
-                           dim3(4 * kWave), 0, (hipStream_t)stream, (long)n_samples, (long)n_reports, sim, (long)ld, obs,
-                           gw_sim, gw_obs, objfn);
-    else
-        hipLaunchKernelGGL((smart_objfn_matrix<1, 8, 4>), dim3((unsigned)((n_samples + kWave - 1) / kWave)),
-                           dim3(8 * kWave), 0, (hipStream_t)stream, (long)n_samples, (long)n_reports, sim, (long)ld, obs,
-                           gw_sim, gw_obs, objfn);
-    HIP_TRY(hipGetLastError());
-    g_err[0] = 0;
-    return SMART_OK;
-}
-
-int smart_weighted_quantiles_hip(int64_t n_samples, int64_t n_reports, const double *sim, int64_t ld,
-                                 const double *weights, const double *probs, int32_t n_probs, double *out,
-                                 int32_t method, void *stream)
-{
-    static_assert(SMART_QUANTILES_MAX_PROBS == 16, "QuantileProbs of smart_quantiles.hip");
-    if (!sim || !probs || !out)
-        return fail(SMART_E_NULL, "smart_weighted_quantiles_hip: sim, probs and out are required");
-    if (n_samples < 1 || n_reports < 1 || n_probs < 1 || ld < n_samples)
-        return fail(SMART_E_SIZE, "smart_weighted_quantiles_hip: need n_samples, n_reports, n_probs >= 1 and "
-                                  "ld >= n_samples");
-    if (n_reports > 0x7fffffffll)
-        return fail(SMART_E_SIZE, "smart_weighted_quantiles_hip: n_reports %lld is more than one launch takes (2^31 - 1)",
-                    (long long)n_reports);
-    if (n_probs > SMART_QUANTILES_MAX_PROBS || n_probs > quantiles_max_probs())
-        return fail(SMART_E_SIZE, "smart_weighted_quantiles_hip: %d probabilities, at most %d per call", (int)n_probs,
-                    SMART_QUANTILES_MAX_PROBS);
-    for (int32_t k = 0; k < n_probs; ++k)
-        if (!(probs[k] > 0.0 && probs[k] <= 1.0))
-            return fail(SMART_E_SIZE, "smart_weighted_quantiles_hip: probability %d is %g, outside (0, 1]", (int)k,
-                        probs[k]);
-    if (method != SMART_QUANTILES_AUTO && method != SMART_QUANTILES_SORT && method != SMART_QUANTILES_SELECT)
-        return fail(SMART_E_MODE, "smart_weighted_quantiles_hip: method '%d' unknown.", (int)method);
-    if (method == SMART_QUANTILES_SORT && n_samples > quantiles_sort_capacity())
-        return fail(SMART_E_SIZE, "smart_weighted_quantiles_hip: the sort form takes at most %lld samples, not %lld",
-                    (long long)quantiles_sort_capacity(), (long long)n_samples);
-    int rc = device_ready();
-    if (rc)
-        return rc;
-    const bool sort = method == SMART_QUANTILES_SORT ||
-                      (method == SMART_QUANTILES_AUTO && n_samples <= quantiles_sort_capacity());
-    launch_quantiles((long)n_samples, (long)n_reports, sim, (long)ld, weights, probs, (int)n_probs, out, sort,
-                     (hipStream_t)stream);
-    HIP_TRY(hipGetLastError());
-    g_err[0] = 0;
-    return SMART_OK;
-}
-
-int64_t smart_quantiles_sort_capacity(void) { return quantiles_sort_capacity(); }
-
-int smart_objfn_windows_hip(int64_t n_samples, int64_t n_reports, const double *sim, int64_t ld, const double *obs,
-                            const int32_t *window, int32_t n_windows, int32_t transform, double eps, double *objfn,
-                            void *stream)
-{
-    if (!sim || !obs || !window || !objfn)
-        return fail(SMART_E_NULL, "smart_objfn_windows_hip: sim, obs, window and objfn are required (%s is NULL)",
-                    !sim ? "sim" : (!obs ? "obs" : (!window ? "window" : "objfn")));
-    if (n_samples < 1 || n_reports < 1 || n_windows < 1)
-        return fail(SMART_E_SIZE, "smart_objfn_windows_hip: need n_samples, n_reports, n_windows >= 1 (got %lld, %lld, %d)",
-                    (long long)n_samples, (long long)n_reports, (int)n_windows);
-    if (ld < n_samples)
-        return fail(SMART_E_SIZE, "smart_objfn_windows_hip: ld %lld is less than n_samples %lld", (long long)ld,
-                    (long long)n_samples);
-    if (n_reports > 0x7fffffffll)
-        return fail(SMART_E_SIZE, "smart_objfn_windows_hip: n_reports %lld is more than one launch takes (2^31 - 1)",
-                    (long long)n_reports);
-    if (n_windows > objfn_max_windows())
-        return fail(SMART_E_SIZE, "smart_objfn_windows_hip: n_windows %d, at most %d per call", (int)n_windows,
-                    objfn_max_windows());
-    if (!(eps >= 0.0) || std::isinf(eps))
-        return fail(SMART_E_SIZE, "smart_objfn_windows_hip: eps %g must be finite and >= 0", eps);
-    if (transform < SMART_TRANSFORM_NONE || transform > SMART_TRANSFORM_INVERSE)
-        return fail(SMART_E_MODE, "smart_objfn_windows_hip: transform '%d' unknown.", (int)transform);
-    int rc = device_ready();
-    if (rc)
-        return rc;
-    launch_objfn_windows((long)n_samples, (long)n_reports, sim, (long)ld, obs, window, (int)n_windows, (int)transform, eps,
-                         objfn, (hipStream_t)stream);
-    HIP_TRY(hipGetLastError());
-    g_err[0] = 0;
-    return SMART_OK;
-}
-
-int32_t smart_objfn_max_windows(void) { return objfn_max_windows(); }
-
-int smart_flow_duration_hip(int64_t n_samples, int64_t n_reports, const double *sim, int64_t ld, const double *obs,
-                            const int32_t *window, int32_t n_windows, const double *probs, int32_t n_probs,
-                            double *quant, int32_t transform, double eps, double seg_lo, double seg_hi, double *objfn,
-                            void *workspace, int64_t workspace_bytes, int32_t method, void *stream)
-{
-    if (!sim || !probs || !quant)
-        return fail(SMART_E_NULL, "smart_flow_duration_hip: sim, probs and quant are required (%s is NULL)",
-                    !sim ? "sim" : (!probs ? "probs" : "quant"));
-    if (objfn && !obs)
-        return fail(SMART_E_NULL, "smart_flow_duration_hip: objfn needs obs (obs is NULL)");
-    if (n_samples < 1 || n_reports < 1 || n_windows < 1 || n_probs < 1)
-        return fail(SMART_E_SIZE, "smart_flow_duration_hip: need n_samples, n_reports, n_windows, n_probs >= 1 (got %lld, "
-                                  "%lld, %d, %d)",
-                    (long long)n_samples, (long long)n_reports, (int)n_windows, (int)n_probs);
-    if (ld < n_samples)
-        return fail(SMART_E_SIZE, "smart_flow_duration_hip: ld %lld is less than n_samples %lld", (long long)ld,
-                    (long long)n_samples);
-    if (n_reports > 0x7fffffffll)
-        return fail(SMART_E_SIZE, "smart_flow_duration_hip: n_reports %lld is more than one launch takes (2^31 - 1)",
-                    (long long)n_reports);
-    if (n_windows > objfn_max_windows())
-        return fail(SMART_E_SIZE, "smart_flow_duration_hip: n_windows %d, at most %d per call", (int)n_windows,
-                    objfn_max_windows());
-    if (!window && n_windows != 1)
-        return fail(SMART_E_SIZE, "smart_flow_duration_hip: n_windows %d without a window array (NULL is one window)",
-                    (int)n_windows);
-    if (n_probs > SMART_QUANTILES_MAX_PROBS)
-        return fail(SMART_E_SIZE, "smart_flow_duration_hip: n_probs %d, at most %d probabilities per call", (int)n_probs,
-                    SMART_QUANTILES_MAX_PROBS);
-    for (int32_t k = 0; k < n_probs; ++k)
-        if (!(probs[k] >= 0.0 && probs[k] <= 1.0))
-            return fail(SMART_E_SIZE, "smart_flow_duration_hip: probability %d is %g, outside [0, 1]", (int)k, probs[k]);
-    if (!(eps >= 0.0) || std::isinf(eps))
-        return fail(SMART_E_SIZE, "smart_flow_duration_hip: eps %g must be finite and >= 0", eps);
-    if (!(seg_lo >= 0.0 && seg_lo < seg_hi && seg_hi <= 1.0))
-        return fail(SMART_E_SIZE, "smart_flow_duration_hip: the segment (%g, %g) is not 0 <= seg_lo < seg_hi <= 1", seg_lo,
-                    seg_hi);
-    if (transform < SMART_TRANSFORM_NONE || transform > SMART_TRANSFORM_INVERSE)
-        return fail(SMART_E_MODE, "smart_flow_duration_hip: transform '%d' unknown.", (int)transform);
-    if (method != SMART_FDC_AUTO && method != SMART_FDC_SORT && method != SMART_FDC_SELECT)
-        return fail(SMART_E_MODE, "smart_flow_duration_hip: method '%d' unknown.", (int)method);
-    if (objfn && method == SMART_FDC_SELECT)
-        return fail(SMART_E_MODE, "smart_flow_duration_hip: the select form gives order statistics only (objfn given)");
-    const long capacity = flow_duration_sort_capacity();
-    if (n_reports > capacity && (objfn || method == SMART_FDC_SORT))
-        return fail(SMART_E_SIZE, "smart_flow_duration_hip: %s at most %ld report steps (the sort capacity), not %lld",
-                    objfn ? "the objective functions of the curve take" : "the sort form takes", capacity,
-                    (long long)n_reports);
-    if (objfn) {
-        const long need = flow_duration_workspace_bytes((long)n_reports, (int)n_windows, true);
-        if (!workspace)
-            return fail(SMART_E_NULL, "smart_flow_duration_hip: objfn needs a workspace of %ld bytes (workspace is NULL)",
-                        need);
-        if (workspace_bytes < need)
-            return fail(SMART_E_SIZE, "smart_flow_duration_hip: workspace_bytes %lld, need %ld", (long long)workspace_bytes,
-                        need);
-    }
-    int rc = device_ready();
-    if (rc)
-        return rc;
-    const bool sort = method != SMART_FDC_SELECT && n_reports <= capacity;
-    launch_flow_duration((long)n_samples, (long)n_reports, sim, (long)ld, obs, window, (int)n_windows, probs, (int)n_probs,
-                         quant, (int)transform, eps, seg_lo, seg_hi, objfn, (double *)workspace, sort,
-                         (hipStream_t)stream);
-    HIP_TRY(hipGetLastError());
-    g_err[0] = 0;
-    return SMART_OK;
-}
-
-int64_t smart_flow_duration_workspace_bytes(int64_t n_reports, int32_t n_windows, int32_t with_objfn)
-{
-    if (n_reports < 1 || n_reports > 0x7fffffffll || n_windows < 1)
-        return SMART_E_SIZE;
-    return flow_duration_workspace_bytes((long)n_reports, (int)n_windows, with_objfn != 0);
-}
-
-int64_t smart_flow_duration_sort_capacity(void) { return flow_duration_sort_capacity(); }
-
-// the size rules of smart_sobol_indices_hip, shared with smart_sobol_workspace_bytes; 0 or the text of the refusal
-static const char *sobol_sizes(int64_t n_base, int32_t n_params, int64_t n_rows, int32_t n_resamples, char *text, size_t len)
-{
-    if (n_base < 1 || n_base > 0x7fffffffll)
-        snprintf(text, len, "n_base %lld must be in 1 .. 2^31 - 1", (long long)n_base);
-    else if (n_params < 1 || n_params > SMART_SOBOL_MAX_PARAMS)
-        snprintf(text, len, "n_params %d must be in 1 .. %d", (int)n_params, SMART_SOBOL_MAX_PARAMS);
-    else if (n_rows < 1 || n_rows > 0x7fffffffll)
-        snprintf(text, len, "n_rows %lld must be in 1 .. 2^31 - 1", (long long)n_rows);
-    else if (n_resamples < 0 || n_resamples > sobol_max_resamples())
-        snprintf(text, len, "n_resamples %d must be in 0 .. %d", (int)n_resamples, sobol_max_resamples());
-    else
-        return nullptr;
-    return text;
-}
-
-int smart_sobol_indices_hip(int64_t n_base, int32_t n_params, int64_t n_rows, const double *y, int64_t ld, double *s1,
-                            double *st, double *moments, const uint16_t *counts, int32_t n_resamples, double *s1_std,
-                            double *st_std, void *workspace, int64_t workspace_bytes, void *stream)
-{
-    if (!y || !s1 || !st || !moments)
-        return fail(SMART_E_NULL, "smart_sobol_indices_hip: y, s1, st and moments are required (%s is NULL)",
-                    !y ? "y" : (!s1 ? "s1" : (!st ? "st" : "moments")));
-    if (n_resamples > 0 && (!counts || !s1_std || !st_std))
-        return fail(SMART_E_NULL, "smart_sobol_indices_hip: n_resamples %d needs counts, s1_std and st_std (%s is NULL)",
-                    (int)n_resamples, !counts ? "counts" : (!s1_std ? "s1_std" : "st_std"));
-    char text[160];
-    if (sobol_sizes(n_base, n_params, n_rows, n_resamples, text, sizeof text))
-        return fail(SMART_E_SIZE, "smart_sobol_indices_hip: %s", text);
-    if (ld < n_base * (n_params + 2))
-        return fail(SMART_E_SIZE, "smart_sobol_indices_hip: ld %lld is less than n_base * (n_params + 2) = %lld",
-                    (long long)ld, (long long)(n_base * (n_params + 2)));
-    const long need = sobol_workspace_bytes();
-    if (need > 0 && !workspace)
-        return fail(SMART_E_NULL, "smart_sobol_indices_hip: a workspace of %ld bytes is needed (workspace is NULL)", need);
-    if (workspace_bytes < (workspace ? need : 0))
-        return fail(SMART_E_SIZE, "smart_sobol_indices_hip: workspace_bytes %lld, need %ld", (long long)workspace_bytes,
-                    need);
-    int rc = device_ready();
-    if (rc)
-        return rc;
-    launch_sobol((long)n_base, (int)n_params, (long)n_rows, y, (long)ld, s1, st, moments, counts, (int)n_resamples,
-                 s1_std, st_std, (hipStream_t)stream);
-    HIP_TRY(hipGetLastError());
-    g_err[0] = 0;
-    return SMART_OK;
-}
-
-int64_t smart_sobol_workspace_bytes(int64_t n_base, int32_t n_params, int64_t n_rows, int32_t n_resamples)
-{
-    char text[160];
-    if (sobol_sizes(n_base, n_params, n_rows, n_resamples, text, sizeof text))
-        return SMART_E_SIZE;
-    return sobol_workspace_bytes();
-}
-
-int32_t smart_sobol_max_resamples(void) { return sobol_max_resamples(); }
-
-int64_t smart_sobol_lds_capacity(void) { return sobol_lds_capacity(); }
 
 int smart_row_class(const double *params, double delta_sec, const double *initial12, double area_m2)
 {

@@ -1,0 +1,55 @@
+// smart_capi_internal.h -- what the units behind include/smart_amd.h share: the error text of the calling thread
+// (smart_capi.hip), and the host-side launch and capacity functions of the kernel units.  Every unit that defines one
+// of these includes this header, so the compiler holds each definition against its declaration.
+#pragma once
+
+#include "../../include/smart_amd.h"
+
+#include <hip/hip_runtime.h>
+
+namespace smart {
+
+// ---- smart_capi.hip: the text smart_last_error() returns, per thread
+int fail(int code, const char *fmt, ...); // sets the text, returns code (smart_hostio.cpp, host only, declares it itself)
+void clear_error();                       // what an entry does on success
+int hip_fail(hipError_t e, const char *what);
+int device_ready(); // SMART_OK, or SMART_E_NO_DEVICE with its text: every entry asks AFTER it has validated its arguments
+
+#define HIP_TRY(expr)                                                                                                  \
+    do {                                                                                                               \
+        hipError_t _e = (expr);                                                                                        \
+        if (_e != hipSuccess)                                                                                          \
+            return hip_fail(_e, #expr);                                                                                \
+    } while (0)
+
+// ---- smart_literal.hip
+struct KArgs;
+void launch_literal(const KArgs &a, dim3 grid, size_t lds_bytes, hipStream_t s, bool rows);
+void launch_onestep(long n, const double *in, double *out, hipStream_t s);
+void launch_river(long n, const double *in, double *out, hipStream_t s);
+
+// ---- smart_quantiles.hip
+long quantiles_sort_capacity();
+void launch_quantiles(long N, long R, const double *sim, long ld, const double *weights, const double *probs, int K,
+                      double *out, bool sort, hipStream_t s);
+
+// ---- smart_objfn_windows.hip
+int objfn_max_windows();
+void launch_objfn_windows(long N, long R, const double *sim, long ld, const double *obs, const int *window, int W,
+                          int transform, double eps, double *objfn, hipStream_t s);
+
+// ---- smart_flow_duration.hip
+long flow_duration_sort_capacity();
+long flow_duration_workspace_bytes(long R, int W, bool with_objfn);
+void launch_flow_duration(long N, long R, const double *sim, long ld, const double *obs, const int *window, int W,
+                          const double *probs, int K, double *quant, int transform, double eps, double seg_lo,
+                          double seg_hi, double *objfn, double *ws, bool sort, hipStream_t s);
+
+// ---- smart_sobol.hip
+long sobol_lds_capacity();
+int sobol_max_resamples();
+long sobol_workspace_bytes();
+void launch_sobol(long n, int k, long M, const double *y, long ld, double *s1, double *st, double *moments,
+                  const unsigned short *counts, int B, double *s1_std, double *st_std, hipStream_t s);
+
+} // namespace smart

@@ -19,6 +19,8 @@
 //   SMART_STEPS_PHASE, SMART_EVERY_PHASE    loop placement   tools/gpu_round.sh phases-every
 #pragma once
 
+#include "smart_matrix_common.h" // kWave, is_nan_bits, kMissingObs, quiet_nan: one definition for every kernel
+
 #include <hip/hip_runtime.h>
 
 #include <type_traits>
@@ -128,30 +130,8 @@ __device__ __forceinline__ void raise_status(const KArgs &a, int bit)
 #define SMART_STEP_ARMS 1 // the step loop of sub-daily forcing as three asm arms (0: the compiled step_lazy of round 2)
 #endif
 
-constexpr int kWave = 64;
 constexpr int kIllCondWaves = 16; // workgroups per block of 64 samples of the kernels that take one sample per DPP row
-
-// NaN test on the bit pattern (missing observation / absent constraint): survives -fno-honor-nans, and for the
-// wave-uniform values it is applied to it is scalar integer work.
-__device__ __forceinline__ bool is_nan_bits(double x)
-{
-    return (__builtin_bit_cast(unsigned long long, x) & 0x7fffffffffffffffull) > 0x7ff0000000000000ull;
-}
 constexpr int kWsHead = 8;
-
-// What smart_obs_prepare writes for the deviation e - mean of a MISSING observation: a NaN whose payload no arithmetic
-// produces (a computed NaN is the canonical 0x7ff8000000000000, or carries the payload of an input NaN -- and an
-// observation that is a NaN is missing whatever its payload).  A report every step tells a missing observation from the
-// upper half of the deviation it has in a scalar register anyway: one s_cmp_eq_u32 (the exact NaN test of the
-// observation itself in 32-bit pieces was eleven scalar instructions a step in hipcc's hands).
-constexpr unsigned long long kMissingObs = 0x7ff8dead00000000ull;
-__device__ __forceinline__ bool is_missing_mark(double w)
-{
-    return (unsigned)(__builtin_bit_cast(unsigned long long, w) >> 32) == (unsigned)(kMissingObs >> 32);
-}
-
-// a quiet NaN that does not trip -fno-honor-nans diagnostics (the fast kernels never do arithmetic on one)
-__host__ __device__ __forceinline__ double quiet_nan() { return __builtin_bit_cast(double, 0x7ff8000000000000ull); }
 
 // objective functions from the one-pass moments (montecarlo.py:193-209; formulas of spotpy's nashsutcliffe,
 // kge(return_all=True), pbias, rmse).  Moments are taken about the observation mean, known before the run:

@@ -42,7 +42,7 @@
 //
 // Determinism.  No floating-point atomics; integer counts in select; every sum of the sort form has one association for
 // a given (N, R, window array, segment): two launches give the same bits.
-#include "../../include/smart_amd.h"
+#include "smart_capi_internal.h"
 #include "smart_device.h"
 #include "smart_order_keys.h"
 #include <cstdlib>
@@ -54,36 +54,13 @@ constexpr int kFdcWaves = kFdcThreads / kWave;
 constexpr int kFdcElems = 16384;         // keys in LDS: 128 KiB
 constexpr int kFdcChunk = kFdcThreads;   // rows of window[] looked at per compaction, one per thread
 constexpr long kFdcCapacity = 16384;     // rows of the sort form: the COLS = 1 instance
-constexpr int kFdcMaxProbs = 16;
 constexpr int kFdcHead = 8;              // doubles in front of a window's sorted f(obs) in the workspace:
                                          // m, i0, i1, mean, sum, sum (e - mean)^2, sum (e - mean), usable (1 / 0)
-static_assert(kFdcMaxProbs == SMART_QUANTILES_MAX_PROBS, "K <= the quantile entry's 16");
-
-struct FdcProbs {
-    double q[kFdcMaxProbs];
-};
-
-__device__ __forceinline__ double fdc_transform(int t, double x, double eps)
-{
-    switch (t) {
-    case SMART_TRANSFORM_SQRT:
-        return sqrt(x);
-    case SMART_TRANSFORM_LOG:
-        return log(x + eps);
-    case SMART_TRANSFORM_INVERSE:
-        return 1.0 / (x + eps);
-    default:
-        return x;
-    }
-}
-
-__device__ __forceinline__ bool fdc_finite(double x)
-{
-    return (__builtin_bit_cast(unsigned long long, x) & 0x7ff0000000000000ull) != 0x7ff0000000000000ull;
-}
 
 // the rows of window w among [c0, c0 + kFdcChunk), in row order, into rows[]; -> how many (the same in every thread).
 // The caller puts a barrier between its last read of rows[] and the next call.
+// (The compaction inside smart_objfn_windows is the same idea written for its own shape -- two rows per thread, f(obs)
+// carried along into the list -- and stays apart.)
 __device__ inline int fdc_compact(long c0, long R, const double *__restrict__ obs, const int *__restrict__ window, int w,
                                   int *cnt, int *rows)
 {
@@ -206,19 +183,19 @@ __global__ __launch_bounds__(kFdcThreads) void smart_fdc_observed(long R, const 
     const int i1 = min(m, (int)ceil(seg_hi * (double)m));   // i < hi * m   <=>  i < ceil(hi * m)
     double s = 0.0;
     for (int i = tid; i < m; i += kFdcThreads) {
-        const double v = fdc_transform(transform, key_value(keys[i]), eps);
+        const double v = flow_transform(transform, key_value(keys[i]), eps);
         fe[i] = v;
         if (i >= i0 && i < i1)
             s += v;
     }
     s = fdc_column_sum<1>(s, sh);
     const int c = i1 - i0;
-    const bool usable = c >= 2 && fdc_finite(s);    // the two rules, for the whole window
+    const bool usable = c >= 2 && is_finite_bits(s);    // the two rules, for the whole window
     const double mean = usable ? s / (double)c : 0.0;
     double s2 = 0.0, s1 = 0.0;
     if (usable)
         for (int i = i0 + tid; i < i1; i += kFdcThreads) {
-            const double d = fdc_transform(transform, key_value(keys[i]), eps) - mean;
+            const double d = flow_transform(transform, key_value(keys[i]), eps) - mean;
             s2 += d * d;
             s1 += d;
         }
@@ -240,7 +217,7 @@ __global__ __launch_bounds__(kFdcThreads) void smart_fdc_observed(long R, const 
 template <int CAP, int COLS>
 __global__ __launch_bounds__(kFdcThreads) void smart_fdc_sort(long N, long R, const double *__restrict__ sim, long ld,
                                                              const double *__restrict__ obs,
-                                                             const int *__restrict__ window, FdcProbs probs, int K,
+                                                             const int *__restrict__ window, MatrixProbs probs, int K,
                                                              double *__restrict__ quant, int transform, double eps,
                                                              const double *__restrict__ ws, double *__restrict__ objfn,
                                                              int remap)
@@ -299,10 +276,10 @@ __global__ __launch_bounds__(kFdcThreads) void smart_fdc_sort(long N, long R, co
     const double ebar = head[3];
     double mo[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
     if (usable) {
-        const double shift = fdc_transform(transform, key_value(keys[i0 * COLS + c]), eps);
+        const double shift = flow_transform(transform, key_value(keys[i0 * COLS + c]), eps);
         for (int i = i0 + tid / COLS; i < i1; i += kFdcThreads / COLS) {
             const double e = fe[i];
-            const double s = fdc_transform(transform, key_value(keys[i * COLS + c]), eps);
+            const double s = flow_transform(transform, key_value(keys[i * COLS + c]), eps);
             const double d = s - e, u = s - shift;
             mo[0] += d;
             mo[1] += d * d;
@@ -319,7 +296,7 @@ __global__ __launch_bounds__(kFdcThreads) void smart_fdc_sort(long N, long R, co
     const double st[5] = {(double)(i1 - i0), ebar, head[4], head[5], head[6]};
     double o[8];
     finish_objectives(st, mo[0], mo[1], mo[2], mo[3], mo[4], 0.0, quiet_nan(), o);
-    const bool ok = usable && fdc_finite(mo[2]);    // some f(sim) of the segment was not finite (header comment)
+    const bool ok = usable && is_finite_bits(mo[2]);    // some f(sim) of the segment was not finite (header comment)
     double *const out = objfn + ((long)w * N + n0 + c) * SMART_OBJFN_WINDOW_COLS;
 #pragma unroll
     for (int k = 0; k < SMART_OBJFN_WINDOW_COLS; ++k)
@@ -330,7 +307,7 @@ __global__ __launch_bounds__(kFdcThreads) void smart_fdc_sort(long N, long R, co
 template <int KB>
 __global__ __launch_bounds__(kWave) void smart_fdc_select(long N, long R, const double *__restrict__ sim, long ld,
                                                          const double *__restrict__ obs, const int *__restrict__ window,
-                                                         FdcProbs probs, int K, double *__restrict__ quant)
+                                                         MatrixProbs probs, int K, double *__restrict__ quant)
 {
     const int w = blockIdx.y;
     long n = (long)blockIdx.x * kWave + threadIdx.x;
@@ -425,7 +402,7 @@ __global__ __launch_bounds__(kWave) void smart_fdc_select(long N, long R, const 
     }
 }
 
-// ---- launch (validated by smart_capi.hip) ---------------------------------------------------------------------------
+// ---- launch (validated by smart_analysis_capi.hip) ---------------------------------------------------------------------------
 long flow_duration_sort_capacity() { return kFdcCapacity; }
 
 long flow_duration_workspace_bytes(long R, int W, bool with_objfn)
@@ -443,7 +420,7 @@ static bool fdc_remap_wanted()
 
 template <int CAP, int COLS>
 static void launch_fdc_sort(long N, long R, const double *sim, long ld, const double *obs, const int *window, int W,
-                            const FdcProbs &p, int K, double *quant, int transform, double eps, const double *ws,
+                            const MatrixProbs &p, int K, double *quant, int transform, double eps, const double *ws,
                             double *objfn, hipStream_t s)
 {
     const dim3 grid((unsigned)((N + COLS - 1) / COLS), (unsigned)W);
@@ -455,8 +432,8 @@ void launch_flow_duration(long N, long R, const double *sim, long ld, const doub
                           const double *probs, int K, double *quant, int transform, double eps, double seg_lo,
                           double seg_hi, double *objfn, double *ws, bool sort, hipStream_t s)
 {
-    FdcProbs p;
-    for (int k = 0; k < kFdcMaxProbs; ++k)
+    MatrixProbs p;
+    for (int k = 0; k < SMART_QUANTILES_MAX_PROBS; ++k)
         p.q[k] = k < K ? probs[k] : 0.0;
     if (!sort) {
         const dim3 grid((unsigned)((N + kWave - 1) / kWave), (unsigned)W), block(kWave);

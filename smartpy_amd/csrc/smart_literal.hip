@@ -6,6 +6,7 @@
 // (tests/test_gpu_parity.py), which pins every branch and every operation order of the GPU path.
 //
 // This mode is the parity anchor, not the fast path: ~39 (wet) / 26 (dry) fp64 divisions per step.
+#include "smart_capi_internal.h"
 #include "smart_literal_lanes.h"
 
 namespace smart {

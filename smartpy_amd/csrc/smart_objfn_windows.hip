@@ -31,7 +31,7 @@
 //
 // Determinism.  No floating-point atomics; the list order, the round-robin and both reductions are fixed by (N, R, the
 // window array): two launches give the same bits.
-#include "../../include/smart_amd.h"
+#include "smart_capi_internal.h"
 #include "smart_device.h"
 
 namespace smart {
@@ -44,24 +44,6 @@ constexpr int kWinUnroll = 4;                     // row segments in flight per 
 // each workgroup re-reads window[] and obs[] (R * 12 bytes, three times): W times per 64 samples over the launch.  The
 // bound keeps that beside the matrix traffic for windows of a useful length, and the grid's y inside its 65,535.
 constexpr int kWinMaxWindows = 1024;
-
-template <int T>
-__device__ __forceinline__ double flow_transform(double x, double eps)
-{
-    if constexpr (T == SMART_TRANSFORM_SQRT)
-        return sqrt(x);
-    else if constexpr (T == SMART_TRANSFORM_LOG)
-        return log(x + eps);
-    else if constexpr (T == SMART_TRANSFORM_INVERSE)
-        return 1.0 / (x + eps);
-    else
-        return x;
-}
-
-__device__ __forceinline__ bool is_finite_bits(double x)
-{
-    return (__builtin_bit_cast(unsigned long long, x) & 0x7ff0000000000000ull) != 0x7ff0000000000000ull;
-}
 
 // sum over the workgroup's kWinThreads threads, the same tree for every call
 __device__ inline double win_block_sum(double v, double *sh)
@@ -102,7 +84,7 @@ __global__ __launch_bounds__(kWinThreads) void smart_objfn_windows(long N, long 
     double *const out = objfn + ((long)w * N + n) * SMART_OBJFN_WINDOW_COLS;
 
     // ---- 1. the window's observations: n, mean, sum, sum((e - mean)^2), sum(e - mean) of e = f(obs) (obs_stats of
-    // smart_capi.hip, masked by the window)
+    // smart_matrix_common.h, masked by the window)
     double st[5];
     {
         double c = 0.0, s = 0.0;
@@ -111,7 +93,7 @@ __global__ __launch_bounds__(kWinThreads) void smart_objfn_windows(long N, long 
                 const double e = obs[r];
                 if (!is_nan_bits(e)) {
                     c += 1.0;
-                    s += flow_transform<T>(e, eps);
+                    s += flow_transform(T, e, eps);
                 }
             }
         c = win_block_sum(c, sh);
@@ -129,7 +111,7 @@ __global__ __launch_bounds__(kWinThreads) void smart_objfn_windows(long N, long 
             if (window[r] == w) {
                 const double e = obs[r];
                 if (!is_nan_bits(e)) {
-                    const double d = flow_transform<T>(e, eps) - mean;
+                    const double d = flow_transform(T, e, eps) - mean;
                     s2 += d * d;
                     s1 += d;
                 }
@@ -142,7 +124,8 @@ __global__ __launch_bounds__(kWinThreads) void smart_objfn_windows(long N, long 
     }
     const double ebar = st[1];
 
-    // ---- 2. the rows of the window, chunk by chunk
+    // ---- 2. the rows of the window, chunk by chunk (the compaction is the idea of fdc_compact, smart_flow_duration.hip,
+    // which takes one row per thread and lists rows alone; the two stay apart)
     const double *const col = sim + n;
     double shift = 0.0;
     bool have_shift = false; // (the same in every thread of the workgroup)
@@ -168,7 +151,7 @@ __global__ __launch_bounds__(kWinThreads) void smart_objfn_windows(long N, long 
                 const double e = obs[r];
                 if (!is_nan_bits(e)) {
                     in[k] = true;
-                    fe[k] = flow_transform<T>(e, eps);
+                    fe[k] = flow_transform(T, e, eps);
                 }
             }
             votes[k] = __ballot(in[k]);
@@ -201,7 +184,7 @@ __global__ __launch_bounds__(kWinThreads) void smart_objfn_windows(long N, long 
         if (!have_shift) { // entry 0 of the first chunk that has one: the sample's shift, read by wavefront 0 alone
             double s0 = 0.0;
             if (wr == 0) {
-                s0 = flow_transform<T>(col[(long)__builtin_amdgcn_readfirstlane(rows[0]) * ld], eps);
+                s0 = flow_transform(T, col[(long)__builtin_amdgcn_readfirstlane(rows[0]) * ld], eps);
                 first[lane] = s0;
             }
             __syncthreads();
@@ -219,10 +202,10 @@ __global__ __launch_bounds__(kWinThreads) void smart_objfn_windows(long N, long 
                 s[k] = col[(long)__builtin_amdgcn_readfirstlane(rows[j + k * kWinWaves]) * ld];
 #pragma unroll
             for (int k = 0; k < kWinUnroll; ++k)
-                add(fes[j + k * kWinWaves], flow_transform<T>(s[k], eps));
+                add(fes[j + k * kWinWaves], flow_transform(T, s[k], eps));
         }
         for (; j < m; j += kWinWaves)
-            add(fes[j], flow_transform<T>(col[(long)__builtin_amdgcn_readfirstlane(rows[j]) * ld], eps));
+            add(fes[j], flow_transform(T, col[(long)__builtin_amdgcn_readfirstlane(rows[j]) * ld], eps));
     }
 
     // ---- 3. the wavefronts' partial moments, added in wavefront order

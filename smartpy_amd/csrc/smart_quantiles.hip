@@ -30,14 +30,13 @@
 //           W is that same sum with every term in, so S(largest key) == W bit for bit.
 // The threshold t = q * W is ONE multiplication, made once per step and probability; the comparison is cum >= t.
 // Weights must be finite and >= 0 (checked by the caller, not here); weights == nullptr means equal weights.
-#include <hip/hip_runtime.h>
-#include <cstdint>
+#include "smart_capi_internal.h"
+#include "smart_matrix_common.h"
 #include "smart_order_keys.h"
+#include <cstdint>
 
 namespace smart {
 
-constexpr int kQWave = 64;
-constexpr int kQuantilesMaxProbs = 16;
 constexpr long kLdsBytesPerWorkgroup = 160 * 1024;  // gfx950: the whole LDS of a compute unit
 constexpr long kSortBytesPerElement = 8 + 2 + 8;    // key, sample index, running weight
 constexpr long kSortScratchBytes = 16 * 8;          // the wavefronts' totals
@@ -53,21 +52,15 @@ constexpr long kSortCapacity = largest_pow2_capacity(kLdsBytesPerWorkgroup);
 static_assert(kSortCapacity == 8192, "the sort form is instantiated for 1024 .. 8192 elements");
 static_assert(kSortCapacity <= 65536, "sample indices are kept as 16-bit numbers");
 
-struct QuantileProbs {
-    double q[kQuantilesMaxProbs];
-};
-
-__device__ inline double quiet_nan() { return __longlong_as_double(0x7ff8000000000000ll); }
-
 // ---- sort form ------------------------------------------------------------------------------------------------------
 template <int CAP, int THREADS>
 __global__ __launch_bounds__(THREADS) void smart_quantiles_sort(int N, long R, const double *__restrict__ sim, long ld,
-                                                                const double *__restrict__ weights, QuantileProbs probs,
+                                                                const double *__restrict__ weights, MatrixProbs probs,
                                                                 int K, double *__restrict__ out)
 {
     constexpr int E = CAP / THREADS;    // sorted positions per thread in the scan
-    constexpr int WAVES = THREADS / kQWave;
-    static_assert(CAP % THREADS == 0 && THREADS % kQWave == 0 && WAVES <= 16 && CAP / 2 >= THREADS, "shape");
+    constexpr int WAVES = THREADS / kWave;
+    static_assert(CAP % THREADS == 0 && THREADS % kWave == 0 && WAVES <= 16 && CAP / 2 >= THREADS, "shape");
     __shared__ unsigned long long keys[CAP];
     __shared__ double cum[CAP];
     __shared__ double wave_total[16];
@@ -114,15 +107,15 @@ __global__ __launch_bounds__(THREADS) void smart_quantiles_sort(int N, long R, c
         w[e] = total;
     }
     double before = 0.0;    // B_lane: the lanes to the left, chained
-    const int lane = tid & (kQWave - 1), wave = tid / kQWave;
-    for (int j = 0; j < kQWave - 1; ++j) {
-        const double tj = __shfl(total, j, kQWave);
+    const int lane = tid & (kWave - 1), wave = tid / kWave;
+    for (int j = 0; j < kWave - 1; ++j) {
+        const double tj = __shfl(total, j, kWave);
         if (j == 0)
             before = lane > 0 ? tj : 0.0;
         else if (lane > j)
             before += tj;
     }
-    if (lane == kQWave - 1)
+    if (lane == kWave - 1)
         wave_total[wave] = lane > 0 ? before + total : total;
     __syncthreads();
     double ahead = 0.0;     // A_wave: the wavefronts to the left, chained
@@ -162,16 +155,16 @@ constexpr int select_threads(int kb) { return kb <= 4 ? 1024 : kb <= 8 ? 512 : 2
 // sum of v over the workgroup, the same bits in every thread: butterfly over the lanes (a + b == b + a, so both
 // partners hold the same bits after every exchange), then the wavefronts' totals chained left to right
 template <int KB>
-__device__ inline void select_block_sums(double (&acc)[KB], double (*sh)[select_threads(KB) / kQWave])
+__device__ inline void select_block_sums(double (&acc)[KB], double (*sh)[select_threads(KB) / kWave])
 {
     constexpr int kSelectThreads = select_threads(KB);
-    const int lane = threadIdx.x & (kQWave - 1), wave = threadIdx.x / kQWave;
+    const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
 #pragma unroll
     for (int k = 0; k < KB; ++k) {
         double v = acc[k];
 #pragma unroll
-        for (int d = 1; d < kQWave; d <<= 1)
-            v += __shfl_xor(v, d, kQWave);
+        for (int d = 1; d < kWave; d <<= 1)
+            v += __shfl_xor(v, d, kWave);
         if (lane == 0)
             sh[k][wave] = v;
     }
@@ -179,7 +172,7 @@ __device__ inline void select_block_sums(double (&acc)[KB], double (*sh)[select_
 #pragma unroll
     for (int k = 0; k < KB; ++k) {
         double v = sh[k][0];
-        for (int x = 1; x < kSelectThreads / kQWave; ++x)
+        for (int x = 1; x < kSelectThreads / kWave; ++x)
             v += sh[k][x];
         acc[k] = v;
     }
@@ -189,14 +182,14 @@ __device__ inline void select_block_sums(double (&acc)[KB], double (*sh)[select_
 template <int KB>
 __global__ __launch_bounds__(select_threads(KB)) void smart_quantiles_select(long N, long R, const double *__restrict__ sim,
                                                                          long ld, const double *__restrict__ weights,
-                                                                         QuantileProbs probs, int K,
+                                                                         MatrixProbs probs, int K,
                                                                          double *__restrict__ out)
 {
     constexpr int kSelectThreads = select_threads(KB);
-    __shared__ double sh[KB][kSelectThreads / kQWave];
-    __shared__ unsigned long long ends[2][kSelectThreads / kQWave];
+    __shared__ double sh[KB][kSelectThreads / kWave];
+    __shared__ unsigned long long ends[2][kSelectThreads / kWave];
     const int tid = threadIdx.x;
-    const int lane = tid & (kQWave - 1), wave = tid / kQWave;
+    const int lane = tid & (kWave - 1), wave = tid / kWave;
     const long r = blockIdx.x;
     const double *row = sim + r * ld;
 
@@ -212,8 +205,8 @@ __global__ __launch_bounds__(select_threads(KB)) void smart_quantiles_select(lon
         kmax = key > kmax ? key : kmax;
         acc[0] += weights ? weights[n] : 1.0;
     }
-    for (int d = 1; d < kQWave; d <<= 1) {
-        const unsigned long long a = __shfl_xor(kmin, d, kQWave), b = __shfl_xor(kmax, d, kQWave);
+    for (int d = 1; d < kWave; d <<= 1) {
+        const unsigned long long a = __shfl_xor(kmin, d, kWave), b = __shfl_xor(kmax, d, kWave);
         kmin = a < kmin ? a : kmin;
         kmax = b > kmax ? b : kmax;
     }
@@ -222,7 +215,7 @@ __global__ __launch_bounds__(select_threads(KB)) void smart_quantiles_select(lon
         ends[1][wave] = kmax;
     }
     select_block_sums<KB>(acc, sh);     // (its barriers publish ends[] as well)
-    for (int x = 0; x < kSelectThreads / kQWave; ++x) {
+    for (int x = 0; x < kSelectThreads / kWave; ++x) {
         kmin = ends[0][x] < kmin ? ends[0][x] : kmin;
         kmax = ends[1][x] > kmax ? ends[1][x] : kmax;
     }
@@ -276,15 +269,14 @@ __global__ __launch_bounds__(select_threads(KB)) void smart_quantiles_select(lon
     }
 }
 
-// ---- launch (validated by smart_capi.hip: 1 <= n_reports < 2^31, 1 <= n_probs <= 16, sort only within capacity) ------
+// ---- launch (validated by smart_analysis_capi.hip: 1 <= n_reports < 2^31, 1 <= n_probs <= 16, sort only within capacity) ------
 long quantiles_sort_capacity() { return kSortCapacity; }
-int quantiles_max_probs() { return kQuantilesMaxProbs; }
 
 void launch_quantiles(long N, long R, const double *sim, long ld, const double *weights, const double *probs, int K,
                       double *out, bool sort, hipStream_t s)
 {
-    QuantileProbs p;
-    for (int k = 0; k < kQuantilesMaxProbs; ++k)
+    MatrixProbs p;
+    for (int k = 0; k < SMART_QUANTILES_MAX_PROBS; ++k)
         p.q[k] = k < K ? probs[k] : 0.0;
     const dim3 grid((unsigned)R);
     if (sort) {

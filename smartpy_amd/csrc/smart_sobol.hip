@@ -35,37 +35,29 @@
 //
 // Determinism.  No atomics; the shape of every sum is fixed by (n, k, B): two launches give the same bits, and the point
 // kernel is the same launch with or without the bootstrap.
-#include "../../include/smart_amd.h"
-#include <hip/hip_runtime.h>
+#include "smart_capi_internal.h"
+#include "smart_matrix_common.h"
 
 namespace smart {
 
-constexpr int kSobLanes = 64;
 constexpr int kSobThreads = 1024;                    // point kernel
-constexpr int kSobWaves = kSobThreads / kSobLanes;
+constexpr int kSobWaves = kSobThreads / kWave;
 constexpr int kSobSmall = 1024;                      // base rows of the small LDS instance
 constexpr long kSobLdsCapacity = 8192;               // base rows whose yA and uB stay in LDS: 16 n bytes = 128 KiB
 constexpr int kSobMaxParams = SMART_SOBOL_MAX_PARAMS;
 constexpr int kSobSums = 2 + 2 * kSobMaxParams;      // the two moments and two numerators per parameter
 constexpr int kBootThreads = 512;                    // bootstrap kernel
-constexpr int kBootWaves = kBootThreads / kSobLanes;
+constexpr int kBootWaves = kBootThreads / kWave;
 constexpr int kBootTile = 128;                       // base rows whose terms lie in LDS at a time
 constexpr int kSobMaxResamples = kBootThreads;       // one lane per replicate
 static_assert(kSobMaxParams == 16 && kBootTile % kBootWaves == 0, "instances below");
-
-__device__ __forceinline__ bool sobol_finite(double x)
-{
-    return (__builtin_bit_cast(unsigned long long, x) & 0x7ff0000000000000ull) != 0x7ff0000000000000ull;
-}
-
-__device__ __forceinline__ double sobol_nan() { return __builtin_bit_cast(double, 0x7ff8000000000000ull); }
 
 // the sum over the 64 lanes, the same bits in every lane (a + b == b + a)
 __device__ __forceinline__ double sobol_wave_sum(double v)
 {
 #pragma unroll
-    for (int d = kSobLanes / 2; d > 0; d >>= 1)
-        v += __shfl_xor(v, d, kSobLanes);
+    for (int d = kWave / 2; d > 0; d >>= 1)
+        v += __shfl_xor(v, d, kWave);
     return v;
 }
 
@@ -79,7 +71,7 @@ __global__ __launch_bounds__(kSobThreads) void smart_sobol_point(long n, int k, 
     __shared__ double ya[kLds ? CAP : 1], ub[kLds ? CAP : 1];
     __shared__ double part[kSobWaves][kSobSums];
     __shared__ double fin[kSobSums];
-    const int tid = threadIdx.x, lane = tid & (kSobLanes - 1), w = tid / kSobLanes;
+    const int tid = threadIdx.x, lane = tid & (kWave - 1), w = tid / kWave;
     const double *const row = y + (long)blockIdx.x * ld;
     const double dn = (double)n, two_n = 2.0 * dn;
 
@@ -97,9 +89,9 @@ __global__ __launch_bounds__(kSobThreads) void smart_sobol_point(long n, int k, 
     }
     s = sobol_wave_sum(s);
 #pragma unroll
-    for (int d = kSobLanes / 2; d > 0; d >>= 1) {
-        lo = fmin(lo, __shfl_xor(lo, d, kSobLanes));
-        hi = fmax(hi, __shfl_xor(hi, d, kSobLanes));
+    for (int d = kWave / 2; d > 0; d >>= 1) {
+        lo = fmin(lo, __shfl_xor(lo, d, kWave));
+        hi = fmax(hi, __shfl_xor(hi, d, kWave));
     }
     if (lane == 0) {
         part[w][0] = s;
@@ -165,16 +157,16 @@ __global__ __launch_bounds__(kSobThreads) void smart_sobol_point(long n, int k, 
     double all = sab;           // the one sum that has taken every value of the row (header comment)
     for (int j = 0; j < k; ++j)
         all += fin[3 + 2 * j];
-    const bool clean = sobol_finite(all);
+    const bool clean = is_finite_bits(all);
     const double m1 = fin[1] / two_n;
     const double V = lo == hi ? 0.0 : fin[0] / two_n - m1 * m1;
     const bool ok = clean && V > 0.0;
     const long o = (long)blockIdx.x * k + tid;
-    s1[o] = ok ? fin[2 + 2 * tid] / (dn * V) : sobol_nan();
-    st[o] = ok ? fin[3 + 2 * tid] / (two_n * V) : sobol_nan();
+    s1[o] = ok ? fin[2 + 2 * tid] / (dn * V) : quiet_nan();
+    st[o] = ok ? fin[3 + 2 * tid] / (two_n * V) : quiet_nan();
     if (tid == 0) {
-        moments[2 * (long)blockIdx.x] = clean ? mu : sobol_nan();
-        moments[2 * (long)blockIdx.x + 1] = clean ? V : sobol_nan();
+        moments[2 * (long)blockIdx.x] = clean ? mu : quiet_nan();
+        moments[2 * (long)blockIdx.x + 1] = clean ? V : quiet_nan();
     }
 }
 
@@ -186,25 +178,25 @@ __global__ __launch_bounds__(kBootThreads) void smart_sobol_bootstrap(long n, in
                                                                      double *__restrict__ s1_std, double *__restrict__ st_std)
 {
     constexpr int NT = 2 + 2 * KP;
-    constexpr int kTerms = kBootTile * NT, kComb = (kBootWaves / 2) * NT * kSobLanes;
+    constexpr int kTerms = kBootTile * NT, kComb = (kBootWaves / 2) * NT * kWave;
     __shared__ double sh[kComb > kTerms ? kComb : kTerms];     // the tile's terms, then the registers of a chunk
     __shared__ double first[2 * KP];
     __shared__ double partb[kBootWaves][2 * KP];
-    const int tid = threadIdx.x, lane = tid & (kSobLanes - 1), w = tid / kSobLanes;
+    const int tid = threadIdx.x, lane = tid & (kWave - 1), w = tid / kWave;
     const long r = blockIdx.x;
     const double *const row = y + r * ld;
     const double mu = moments[2 * r], V = moments[2 * r + 1];
-    if (!sobol_finite(mu) || !(V > 0.0)) {      // the row's indices are NaN (the same answer in every thread)
+    if (!is_finite_bits(mu) || !(V > 0.0)) {      // the row's indices are NaN (the same answer in every thread)
         if (tid < k)
-            s1_std[r * k + tid] = st_std[r * k + tid] = sobol_nan();
+            s1_std[r * k + tid] = st_std[r * k + tid] = quiet_nan();
         return;
     }
-    const int nbg = (B + kSobLanes - 1) / kSobLanes;        // wavefronts side by side over the replicates, <= 8
+    const int nbg = (B + kWave - 1) / kWave;        // wavefronts side by side over the replicates, <= 8
     int nchunk = kBootWaves / nbg;                          // ... and over the rows of a tile: 8, 4, 2, 1, 1 ...
     nchunk = 1 << (31 - __clz(nchunk));
     const int bg = w % nbg, chunk = w / nbg, per = kBootTile / nchunk;
     const bool active = chunk < nchunk;
-    const int b = bg * kSobLanes + lane;
+    const int b = bg * kWave + lane;
     const bool live = active && b < B;
     const double dn = (double)n, two_n = 2.0 * dn;
 
@@ -265,13 +257,13 @@ __global__ __launch_bounds__(kBootThreads) void smart_sobol_bootstrap(long n, in
         if (active && chunk == c) {
 #pragma unroll
             for (int x = 0; x < NT; ++x)
-                sh[(bg * NT + x) * kSobLanes + lane] = acc[x];
+                sh[(bg * NT + x) * kWave + lane] = acc[x];
         }
         __syncthreads();
         if (chunk == 0) {
 #pragma unroll
             for (int x = 0; x < NT; ++x)
-                acc[x] += sh[(bg * NT + x) * kSobLanes + lane];
+                acc[x] += sh[(bg * NT + x) * kWave + lane];
         }
     }
 
@@ -322,7 +314,7 @@ __global__ __launch_bounds__(kBootThreads) void smart_sobol_bootstrap(long n, in
     }
 }
 
-// ---- launch (validated by smart_capi.hip) ---------------------------------------------------------------------------
+// ---- launch (validated by smart_analysis_capi.hip) ---------------------------------------------------------------------------
 long sobol_lds_capacity() { return kSobLdsCapacity; }
 int sobol_max_resamples() { return kSobMaxResamples; }
 long sobol_workspace_bytes() { return 0; }      // both kernels keep what they share in the caller's moments[]

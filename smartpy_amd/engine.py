@@ -560,300 +560,10 @@ class SingleRun(object):
         return np.ascontiguousarray(out.discharge.cpu().numpy()[0]), float(out.gw.cpu().numpy()[0])
 
 
-def objective_functions(discharge_report_major, obs, gw_sim=None, gw_obs=None):
-    """montecarlo.py:193-209 for every column of a stored [R, N] discharge matrix (one pass over it, HBM-bound)."""
-    L = _lib.lib()
-    sim = discharge_report_major
-    if not (isinstance(sim, torch.Tensor) and sim.is_cuda):
-        sim = as_device(sim, default_device())
-    if sim.stride(-1) != 1:
-        sim = sim.contiguous()
-    R, N = sim.shape
-    ld = sim.stride(0)
-    obs = as_device(obs, sim.device, (R,))
-    gw_sim = as_device(gw_sim, sim.device, (N,)) if gw_sim is not None else None
-    out = torch.empty((N, 8), dtype=torch.float64, device=sim.device)
-    with torch.cuda.device(sim.device):
-        _lib.check(L.smart_objfn_hip(N, R, sim.data_ptr(), ld, obs.data_ptr(),
-                                     None if gw_sim is None else gw_sim.data_ptr(),
-                                     float('nan') if gw_obs is None else float(gw_obs), out.data_ptr(),
-                                     torch.cuda.current_stream(sim.device).cuda_stream))
-    return out
-
-
-_QUANTILE_METHODS = {'auto': _lib.QUANTILES_AUTO, 'sort': _lib.QUANTILES_SORT, 'select': _lib.QUANTILES_SELECT}
-
-
-def quantiles_sort_capacity():
-    """The largest number of samples the sort form of weighted_quantiles takes (no device needed)."""
-    return int(_lib.lib().smart_quantiles_sort_capacity())
-
-
-def weighted_quantiles(discharge_report_major, probs, weights=None, method='auto'):
-    """Weighted quantiles over the samples of a stored [R, N] discharge matrix, per report step -> device tensor
-    [K, R] float64 (the GLUE prediction bounds).  Q(q) is the smallest value v of the step with
-    sum(w[x <= v]) >= q * sum(w): numpy's method='inverted_cdf' with weights=, no interpolation; NaN sorts last; a step
-    whose weights sum to zero gives NaN.  probs: K <= 16 probabilities in (0, 1]; weights: [N], finite and >= 0, or
-    None for equal weights; method: 'auto' (by size), 'sort' (N <= quantiles_sort_capacity()) or 'select'."""
-    L = _lib.lib()
-    try:
-        code = _QUANTILE_METHODS[method]
-    except KeyError:
-        raise SmartEngineError(-7, "weighted_quantiles: method '{}' unknown.".format(method))
-    sim = discharge_report_major
-    if not (isinstance(sim, torch.Tensor) and sim.is_cuda):
-        sim = as_device(sim, default_device())
-    if sim.stride(-1) != 1:
-        sim = sim.contiguous()
-    R, N = sim.shape
-    ld = sim.stride(0) if R > 1 else N
-    q = np.ascontiguousarray(np.atleast_1d(np.asarray(probs, dtype=np.float64)))
-    if weights is not None:
-        weights = as_device(weights, sim.device, (N,))
-        bad = int((~(torch.isfinite(weights) & (weights >= 0))).sum())
-        if bad:
-            raise SmartEngineError(-2, "weighted_quantiles: {} of the {} weights are negative or not finite."
-                                   .format(bad, N))
-    out = torch.empty((q.size, R), dtype=torch.float64, device=sim.device)
-    with torch.cuda.device(sim.device):
-        _lib.check(L.smart_weighted_quantiles_hip(N, R, sim.data_ptr(), ld,
-                                                  None if weights is None else weights.data_ptr(),
-                                                  q.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), q.size,
-                                                  out.data_ptr(), code,
-                                                  torch.cuda.current_stream(sim.device).cuda_stream))
-    return out
-
-
-def _checked_windows(who, windows, n_windows):
-    """The window ids of a call, checked where they lie (host array or device tensor), before anything is moved or
-    launched -> (flat ids, W)."""
-    if isinstance(windows, torch.Tensor):
-        win = windows.reshape(-1)
-        if win.dtype.is_floating_point or win.dtype == torch.bool:
-            raise SmartEngineError(-2, "{}: windows must be integers.".format(who))
-        top = int(win.max()) if win.numel() else -1
-    else:
-        win = np.asarray(windows).reshape(-1)
-        if win.dtype.kind not in 'iu':
-            raise SmartEngineError(-2, "{}: windows must be integers.".format(who))
-        top = int(win.max()) if win.size else -1
-    W = top + 1 if n_windows is None else int(n_windows)
-    if W < 1:
-        raise SmartEngineError(-2, "{}: no window (n_windows = {}).".format(who, W))
-    bad = int(((win < -1) | (win >= W)).sum())
-    if bad:
-        raise SmartEngineError(-2, "{}: {} of the {} window ids are outside -1 .. {}."
-                               .format(who, bad, len(win), W - 1))
-    return win, W
-
-
-def objfn_max_windows():
-    """The largest number of windows objective_functions_windows takes in one call (no device needed)."""
-    return int(_lib.lib().smart_objfn_max_windows())
-
-
-def objective_functions_windows(discharge_report_major, obs, windows, n_windows=None, transform='none', eps=0.0):
-    """The seven objective functions NSE, KGE, KGEc, KGEa, KGEb, PBias, RMSE of every column of a stored [R, N]
-    discharge matrix, PER WINDOW of report steps and on transformed flows -> device tensor [W, N, 7] float64.
-    windows: [R] integers, -1 = the report step belongs to no window, else 0 .. n_windows-1 (n_windows defaults to
-    max + 1); transform: 'none', 'sqrt', 'log' (ln(x + eps)) or 'inverse' (1 / (x + eps)), applied to the observed and
-    to the simulated flows.  A window with fewer than two observed steps is NaN for every sample; a (window, sample)
-    that meets a transformed value that is not finite is NaN (include/smart_amd.h: smart_objfn_windows_hip)."""
-    L = _lib.lib()
-    try:
-        code = _lib.TRANSFORMS[transform]
-    except (KeyError, TypeError):
-        raise SmartEngineError(-7, "objective_functions_windows: transform '{}' unknown.".format(transform))
-    win, W = _checked_windows('objective_functions_windows', windows, n_windows)
-    sim = discharge_report_major
-    if len(sim.shape) != 2 or sim.shape[0] != len(win):
-        raise SmartEngineError(-2, "objective_functions_windows: {} window ids for a matrix of shape {}."
-                               .format(len(win), tuple(sim.shape)))
-    if not (isinstance(sim, torch.Tensor) and sim.is_cuda):
-        sim = as_device(sim, default_device())
-    if sim.stride(-1) != 1:
-        sim = sim.contiguous()
-    R, N = sim.shape
-    ld = sim.stride(0) if R > 1 else N
-    obs = as_device(obs, sim.device, (R,))
-    if not isinstance(win, torch.Tensor):
-        win = torch.from_numpy(np.ascontiguousarray(win.astype(np.int32)))
-    win = win.to(device=sim.device, dtype=torch.int32).contiguous()
-    out = torch.empty((W, N, _lib.OBJFN_WINDOW_COLS), dtype=torch.float64, device=sim.device)
-    if N == 0:
-        return out
-    with torch.cuda.device(sim.device):
-        _lib.check(L.smart_objfn_windows_hip(N, R, sim.data_ptr(), ld, obs.data_ptr(), win.data_ptr(), W, code,
-                                             float(eps), out.data_ptr(),
-                                             torch.cuda.current_stream(sim.device).cuda_stream))
-    return out
-
-
-def flow_duration_sort_capacity():
-    """The largest number of report steps the sort form of flow_duration takes (no device needed)."""
-    return int(_lib.lib().smart_flow_duration_sort_capacity())
-
-
-def flow_duration(discharge_report_major, probs, obs=None, windows=None, n_windows=None, transform='none', eps=0.0,
-                  segment=(0.0, 1.0), objfn=False, method='auto'):
-    """Flow duration curves of every column of a stored [R, N] discharge matrix: order statistics ALONG TIME, per sample
-    and per window of report steps -> (quant [W, K, N], objfn [W, N, 7] or None), device tensors, float64.
-    probs: K <= 16 NON-exceedance probabilities q in [0, 1]; Q(q) is the max(1, ceil(q * m))-th smallest of the window's
-    m values of the column (numpy's method='inverted_cdf': an element of the column, NaN sorts last, m == 0 gives NaN).
-    obs: [R] or None -- report steps without an observation (NaN) are left out; windows: [R] integers as for
-    objective_functions_windows, or None for one window holding every step.  objfn=True (needs obs) adds NSE, KGE, KGEc,
-    KGEa, KGEb, PBias, RMSE of f(sorted simulation) against f(sorted observations), paired by rank, over the ranks i with
-    segment[0] * m <= i < segment[1] * m; transform / eps as for objective_functions_windows, and its two rules.
-    method: 'auto', 'sort' (R <= flow_duration_sort_capacity(); the only one that gives objfn) or 'select'.  The
-    workspace of the call is sized and owned here (include/smart_amd.h: smart_flow_duration_hip)."""
-    L = _lib.lib()
-    try:
-        code = _lib.TRANSFORMS[transform]
-    except (KeyError, TypeError):
-        raise SmartEngineError(-7, "flow_duration: transform '{}' unknown.".format(transform))
-    try:
-        how = _lib.FDC_METHODS[method]
-    except (KeyError, TypeError):
-        raise SmartEngineError(-7, "flow_duration: method '{}' unknown.".format(method))
-    if objfn and obs is None:
-        raise SmartEngineError(-1, "flow_duration: the objective functions of the curve need obs.")
-    sim = discharge_report_major
-    if windows is None:
-        win, W = None, 1
-        if n_windows is not None and int(n_windows) != 1:
-            raise SmartEngineError(-2, "flow_duration: n_windows = {} without windows.".format(n_windows))
-    else:
-        win, W = _checked_windows('flow_duration', windows, n_windows)
-        if len(sim.shape) != 2 or sim.shape[0] != len(win):
-            raise SmartEngineError(-2, "flow_duration: {} window ids for a matrix of shape {}."
-                                   .format(len(win), tuple(sim.shape)))
-    if len(sim.shape) != 2:
-        raise SmartEngineError(-2, "flow_duration: a matrix [R, N] is needed, not shape {}.".format(tuple(sim.shape)))
-    if not (isinstance(sim, torch.Tensor) and sim.is_cuda):
-        sim = as_device(sim, default_device())
-    if sim.stride(-1) != 1:
-        sim = sim.contiguous()
-    R, N = sim.shape
-    ld = sim.stride(0) if R > 1 else N
-    q = np.ascontiguousarray(np.atleast_1d(np.asarray(probs, dtype=np.float64)))
-    lo, hi = (float(x) for x in segment)
-    if obs is not None:
-        obs = as_device(obs, sim.device, (R,))
-    if win is not None:
-        if not isinstance(win, torch.Tensor):
-            win = torch.from_numpy(np.ascontiguousarray(win.astype(np.int32)))
-        win = win.to(device=sim.device, dtype=torch.int32).contiguous()
-    quant = torch.empty((W, q.size, N), dtype=torch.float64, device=sim.device)
-    scores = torch.empty((W, N, _lib.OBJFN_WINDOW_COLS), dtype=torch.float64, device=sim.device) if objfn else None
-    if N == 0:
-        return quant, scores
-    need = int(L.smart_flow_duration_workspace_bytes(R, W, 1 if objfn else 0))
-    if need < 0:
-        _lib.check(need)
-    work = torch.empty(need, dtype=torch.uint8, device=sim.device) if need else None
-    with torch.cuda.device(sim.device):
-        _lib.check(L.smart_flow_duration_hip(N, R, sim.data_ptr(), ld, None if obs is None else obs.data_ptr(),
-                                             None if win is None else win.data_ptr(), W,
-                                             q.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), q.size, quant.data_ptr(),
-                                             code, float(eps), lo, hi, None if scores is None else scores.data_ptr(),
-                                             None if work is None else work.data_ptr(), need, how,
-                                             torch.cuda.current_stream(sim.device).cuda_stream))
-    return quant, scores
-
-
-def sobol_max_resamples():
-    """The largest number of bootstrap replicates of one sobol_indices call (no device needed)."""
-    return int(_lib.lib().smart_sobol_max_resamples())
-
-
-def sobol_lds_capacity():
-    """The largest base size whose A and B blocks sobol_indices keeps in LDS (no device needed)."""
-    return int(_lib.lib().smart_sobol_lds_capacity())
-
-
-def sobol_counts(n_base, resamples, seed=None):
-    """The bootstrap counts of sobol_indices -> [n_base, resamples] uint16 on the host: replicate b draws n_base base rows
-    with replacement, numpy.random.Generator(PCG64(seed)).integers(n_base, size=(resamples, n_base)), and counts[i, b] is
-    how often it drew row i (every column sums to n_base)."""
-    n, B = int(n_base), int(resamples)
-    if n < 1:
-        raise SmartEngineError(-2, "sobol_counts: n_base must be at least 1 (got {}).".format(n_base))
-    if B < 0 or B > sobol_max_resamples():
-        raise SmartEngineError(-2, "sobol_counts: {} resamples, between 0 and {} per call.".format(resamples, sobol_max_resamples()))
-    draws = np.random.Generator(np.random.PCG64(seed)).integers(n, size=(B, n))
-    counts = np.zeros((n, B), dtype=np.int64)
-    for b in range(B):
-        counts[:, b] = np.bincount(draws[b], minlength=n)
-    if counts.size and counts.max() > 65535:
-        raise SmartEngineError(-2, "sobol_counts: a count of {} does not fit the uint16 of the kernel.".format(counts.max()))
-    return np.ascontiguousarray(counts.astype(np.uint16))
-
-
-class SobolResult(object):
-    """Device tensors of one sobol_indices call: S1, ST [M, k], moments [M, 2] (mean and variance of A u B), S1_std and
-    ST_std [M, k] or None without counts."""
-
-    def __init__(self, S1, ST, moments, S1_std, ST_std):
-        self.S1, self.ST, self.moments, self.S1_std, self.ST_std = S1, ST, moments, S1_std, ST_std
-
-
-def sobol_indices(values, n_base, n_params, counts=None):
-    """First-order (Saltelli 2010) and total (Jansen) Sobol indices of every row of `values` -> SobolResult.
-    values: [M, N] or [N], host or device, N >= n_base * (n_params + 2) columns in the block-major order of
-    sampling.saltelli_design ([A ; B ; AB_0 ; ...]; a row is a report step of a stored discharge matrix, or one scalar
-    target); the leading dimension of a device matrix is honoured.  counts: [n_base, B] uint16 from sobol_counts (or a
-    device tensor of those 16-bit patterns, uint16 or int16) adds the standard deviation of both indices over the B bootstrap replicates; None leaves it out.  A row with a
-    value that is not finite, or without variance, is NaN (include/smart_amd.h: smart_sobol_indices_hip)."""
-    L = _lib.lib()
-    n, k = int(n_base), int(n_params)
-    y = values
-    if len(y.shape) == 1:
-        y = y.reshape(1, -1)
-    if len(y.shape) != 2:
-        raise SmartEngineError(-2, "sobol_indices: values [M, N] or [N] are needed, not shape {}.".format(tuple(values.shape)))
-    if n < 1 or k < 1 or k > _lib.SOBOL_MAX_PARAMS or y.shape[1] != n * (k + 2):
-        raise SmartEngineError(-2, "sobol_indices: {} columns are not n_base * (n_params + 2) with n_base = {} >= 1 and "
-                                   "n_params = {} in 1 .. {}.".format(y.shape[1], n_base, n_params, _lib.SOBOL_MAX_PARAMS))
-    B = 0
-    if counts is not None:
-        if len(counts.shape) != 2 or counts.shape[0] != n or \
-                str(counts.dtype).split('.')[-1] not in (('uint16', 'int16') if isinstance(counts, torch.Tensor) else ('uint16',)):
-            raise SmartEngineError(-2, "sobol_indices: counts must be uint16 [n_base, resamples] (engine.sobol_counts), "
-                                       "not {} {}.".format(counts.dtype, tuple(counts.shape)))
-        B = int(counts.shape[1])
-        if B > sobol_max_resamples():
-            raise SmartEngineError(-2, "sobol_indices: {} resamples, at most {} per call.".format(B, sobol_max_resamples()))
-    if not (isinstance(y, torch.Tensor) and y.is_cuda):
-        y = as_device(y, default_device())
-    if y.dtype != torch.float64:
-        y = y.to(torch.float64)
-    if y.stride(-1) != 1:
-        y = y.contiguous()
-    M, N = y.shape
-    ld = y.stride(0) if M > 1 else N
-    dev = y.device
-    S1 = torch.empty((M, k), dtype=torch.float64, device=dev)
-    ST = torch.empty((M, k), dtype=torch.float64, device=dev)
-    moments = torch.empty((M, 2), dtype=torch.float64, device=dev)
-    S1_std = ST_std = None
-    if M == 0:
-        return SobolResult(S1, ST, moments, None, None)
-    if B > 0:
-        if not isinstance(counts, torch.Tensor):
-            counts = torch.from_numpy(np.ascontiguousarray(counts).view(np.int16))     # (the same 16 bits)
-        counts = counts.to(dev).contiguous()
-        S1_std, ST_std = torch.empty_like(S1), torch.empty_like(ST)
-    need = int(L.smart_sobol_workspace_bytes(n, k, M, B))
-    if need < 0:
-        _lib.check(need)
-    work = torch.empty(need, dtype=torch.uint8, device=dev) if need else None
-    with torch.cuda.device(dev):
-        _lib.check(L.smart_sobol_indices_hip(n, k, M, y.data_ptr(), ld, S1.data_ptr(), ST.data_ptr(), moments.data_ptr(),
-                                             counts.data_ptr() if B else None, B,
-                                             S1_std.data_ptr() if B else None, ST_std.data_ptr() if B else None,
-                                             None if work is None else work.data_ptr(), need,
-                                             torch.cuda.current_stream(dev).cuda_stream))
-    return SobolResult(S1, ST, moments, S1_std, ST_std)
+# the analyses of a stored discharge matrix live in analysis.py; every name of them is a name of this module as well
+from .analysis import (objective_functions, quantiles_sort_capacity, weighted_quantiles, _checked_windows,  # noqa: E402,F401
+                       objfn_max_windows, objective_functions_windows, flow_duration_sort_capacity, flow_duration,
+                       sobol_max_resamples, sobol_lds_capacity, sobol_counts, SobolResult, sobol_indices)
 
 
 def allsteps(area_m2, delta_sec, length_simu, nd_rain, nd_peva, nd_parameters, nd_initial, report_type, report_gap):

@@ -101,11 +101,9 @@ class GLUE(SecondStage, MonteCarlo):
         if n == 0:      # no behavioural set: nothing to launch
             bounds, containment = np.full((q.size, len(stamps)), np.nan), float('nan')
         else:
-            rows = self._device_sample if self._device_sample is not None else self._sample
-            out = self.model.simulate_ensemble(rows, save_discharge=True, math_mode=self.math_mode)
+            out, obs = self._launch_stored()
             on_device = engine.weighted_quantiles(out.discharge_report_major, q, weights)
             containment = float('nan')
-            obs = self.model._device_cache[2]       # the observations the launch has left on the device, or None
             if obs is not None:
                 there = ~torch.isnan(obs)
                 inside = there & (on_device[0] <= obs) & (obs <= on_device[-1])
@@ -114,7 +112,7 @@ class GLUE(SecondStage, MonteCarlo):
             bounds = on_device.cpu().numpy()
         path = None
         if write and sdist.rank_world()[0] == 0:
-            path = '{}{}.SMART.glue.bounds'.format(self.model.out_f, self.model.catchment)
+            path = self._side_file('.bounds')
             with open(path, 'w', newline='', encoding='utf8') as f:
                 w = writer(f, delimiter=',')
                 w.writerow(['DateTime'] + ['q%g' % p for p in q])

@@ -22,6 +22,7 @@ from ..objfunctions import groundwater_constraint
 from .. import distributed as sdist
 from ..engine import SmartEngineError
 from .database import database_for
+from .selection import append_float32_rows
 
 OBJ_FN_NAMES = ['NSE', 'KGE', 'KGEc', 'KGEa', 'KGEb', 'PBias', 'RMSE']      # montecarlo.py:71-74; 'GW' is appended
                                                                              # when the settings hold a gw_constraint
@@ -179,6 +180,39 @@ class MonteCarlo(object):
         elif failure is not None:
             raise failure
 
+    # ---- what the analyses of the stored discharge matrix share (this class, GLUE, Sobol) --------------------
+    @staticmethod
+    def _check_transform(transform):
+        from .._lib import TRANSFORMS
+        if transform not in list(TRANSFORMS):
+            raise Exception("The flow transform '{}' is not recognised. Please choose one of: {}."
+                            .format(transform, ', '.join(TRANSFORMS)))
+
+    def _resolve_windows(self, windows, start_month, split):
+        """a `by` word of windows.evaluation_windows over the report stamps, or a ready (ids, labels) pair -> (ids, labels)"""
+        from .. import windows as swin
+        if isinstance(windows, str):
+            return swin.evaluation_windows(self.model.timeseries_report[1:], by=windows, start_month=start_month,
+                                           split=split)
+        ids, labels = windows
+        return np.asarray(ids), list(labels)
+
+    def _check_observations(self):
+        if self.model.nd_flow is None:
+            raise Exception("The observation array does not exist. Please make sure that a value is assigned "
+                            "to the gauged_area_m2 attribute of your SMART class instance.")
+
+    def _launch_stored(self):
+        """One launch over the sample with the [R, N] discharge matrix kept on the device -> (the launch's result, the
+        observations it has left on the device, or None)"""
+        rows = self._device_sample if self._device_sample is not None else self._sample
+        out = self.model.simulate_ensemble(rows, save_discharge=True, math_mode=self.math_mode)
+        return out, self.model._device_cache[2]
+
+    def _side_file(self, suffix):
+        """`<out>/<catchment>.SMART.<func><suffix>`: beside the sampling database, whatever its format."""
+        return (self.db_file[:-3] if self.db_file.endswith('.nc') else self.db_file) + suffix
+
     # ---- split-sample and low-flow scores -----------------------------------------------------------------
     def window_objective_functions(self, windows='hydro_year', transform='none', eps=None, start_month=10, split=None,
                                    write=False):
@@ -192,27 +226,16 @@ class MonteCarlo(object):
         of the sampling database; header NSE@<label>,KGE@<label>,... window by window).  Under torch.distributed every
         rank that calls this computes all rows itself (no collective); rank 0 alone writes.  -> WindowObjectives"""
         from .. import engine, windows as swin
-        if transform not in _lib_transforms():
-            raise Exception("The flow transform '{}' is not recognised. Please choose one of: {}."
-                            .format(transform, ', '.join(_lib_transforms())))
-        if isinstance(windows, str):
-            ids, labels = swin.evaluation_windows(self.model.timeseries_report[1:], by=windows, start_month=start_month,
-                                                  split=split)
-        else:
-            ids, labels = windows
-            ids, labels = np.asarray(ids), list(labels)
+        self._check_transform(transform)
+        ids, labels = self._resolve_windows(windows, start_month, split)
         n = self._sample.shape[0]
-        if self.model.nd_flow is None:
-            raise Exception("The observation array does not exist. Please make sure that a value is assigned "
-                            "to the gauged_area_m2 attribute of your SMART class instance.")
+        self._check_observations()
         if eps is None:
             eps = swin.default_eps(transform, self.model.nd_flow)
         if n == 0:      # e.g. GLUE with no behavioural set: nothing to launch
             on_device, values = None, np.empty((len(labels), 0, len(swin.OBJ_FN_NAMES)))
         else:
-            rows = self._device_sample if self._device_sample is not None else self._sample
-            out = self.model.simulate_ensemble(rows, save_discharge=True, math_mode=self.math_mode)
-            obs = self.model._device_cache[2]       # the observations the launch has left on the device
+            out, obs = self._launch_stored()
             on_device = engine.objective_functions_windows(out.discharge_report_major, obs, ids, n_windows=len(labels),
                                                            transform=transform, eps=eps)
             values = on_device.cpu().numpy()
@@ -225,8 +248,7 @@ class MonteCarlo(object):
     @property
     def windows_file(self):
         """`<out>/<catchment>.SMART.<func>.windows`: beside the sampling database, whatever its format."""
-        base = self.db_file[:-3] if self.db_file.endswith('.nc') else self.db_file
-        return base + '.windows'
+        return self._side_file('.windows')
 
     # ---- flow duration curves -----------------------------------------------------------------------------
     def flow_duration_curves(self, exceedance=(0.01, 0.05, 0.1, 0.2, 0.5, 0.8, 0.9, 0.95, 0.99), windows='all',
@@ -245,21 +267,12 @@ class MonteCarlo(object):
         window, then NSE@<label>,KGE@<label>,...).  Under torch.distributed every rank that calls this computes all rows
         itself (no collective); rank 0 alone writes.  -> FlowDuration"""
         from .. import engine, windows as swin
-        if transform not in _lib_transforms():
-            raise Exception("The flow transform '{}' is not recognised. Please choose one of: {}."
-                            .format(transform, ', '.join(_lib_transforms())))
+        self._check_transform(transform)
         exceedance = [float(p) for p in np.atleast_1d(np.asarray(exceedance, dtype=np.float64))]
         q = swin.non_exceedance(exceedance)
-        if isinstance(windows, str):
-            ids, labels = swin.evaluation_windows(self.model.timeseries_report[1:], by=windows, start_month=start_month,
-                                                  split=split)
-        else:
-            ids, labels = windows
-            ids, labels = np.asarray(ids), list(labels)
+        ids, labels = self._resolve_windows(windows, start_month, split)
         n = self._sample.shape[0]
-        if self.model.nd_flow is None:
-            raise Exception("The observation array does not exist. Please make sure that a value is assigned "
-                            "to the gauged_area_m2 attribute of your SMART class instance.")
+        self._check_observations()
         if eps is None:
             eps = swin.default_eps(transform, self.model.nd_flow)
         W = len(labels)
@@ -267,9 +280,7 @@ class MonteCarlo(object):
             on_device, curves = None, np.empty((W, len(q), 0))
             values = np.empty((W, 0, len(swin.OBJ_FN_NAMES)))
         else:
-            rows = self._device_sample if self._device_sample is not None else self._sample
-            out = self.model.simulate_ensemble(rows, save_discharge=True, math_mode=self.math_mode)
-            obs = self.model._device_cache[2]       # the observations the launch has left on the device
+            out, obs = self._launch_stored()
             quant, on_device = engine.flow_duration(out.discharge_report_major, q, obs=obs, windows=ids, n_windows=W,
                                                     transform=transform, eps=eps, segment=segment, objfn=True)
             curves, values = quant.cpu().numpy(), on_device.cpu().numpy()
@@ -284,8 +295,7 @@ class MonteCarlo(object):
     @property
     def fdc_file(self):
         """`<out>/<catchment>.SMART.<func>.fdc`: beside the sampling database, whatever its format."""
-        base = self.db_file[:-3] if self.db_file.endswith('.nc') else self.db_file
-        return base + '.fdc'
+        return self._side_file('.fdc')
 
     # ---- the per-sample protocol of the reference (spotpy setup class) ------------------------------------
     def parameters(self):
@@ -328,31 +338,22 @@ def _f64():
     return torch.float64
 
 
-def _lib_transforms():
-    from .._lib import TRANSFORMS
-    return list(TRANSFORMS)
-
-
 def _write_windows_file(path, labels, transform, values):
     """values [W, N, 7] -> header line + one line per sample, window by window (the sampling database's float32
     '%.6e', formatted by the library)."""
-    import ctypes
-    from .. import _lib, windows as swin
+    from .. import windows as swin
     with open(path, 'w', newline='', encoding='utf8') as f:
         f.write(swin.header_line(labels, transform))
     W, n, k = values.shape
     if n == 0:
         return
-    table = np.ascontiguousarray(np.transpose(values, (1, 0, 2)).reshape(n, W * k).astype(np.float32))
-    _lib.check(_lib.lib().smart_db_append_rows(path.encode('utf8'), table.ctypes.data_as(ctypes.POINTER(ctypes.c_float)),
-                                               table.shape[0], table.shape[1], 0))
+    append_float32_rows(path, np.ascontiguousarray(np.transpose(values, (1, 0, 2)).reshape(n, W * k).astype(np.float32)))
 
 
 def _write_fdc_file(path, exceedance, labels, transform, curves, values):
     """curves [W, K, N] and values [W, N, 7] -> header line + one line per sample: the K flows of every window, then
     the seven objective functions of every window (the sampling database's float32 '%.6e', formatted by the library)."""
-    import ctypes
-    from .. import _lib, windows as swin
+    from .. import windows as swin
     with open(path, 'w', newline='', encoding='utf8') as f:
         f.write(swin.fdc_header_line(exceedance, labels, transform))
     W, K, n = curves.shape
@@ -360,6 +361,4 @@ def _write_fdc_file(path, exceedance, labels, transform, curves, values):
         return
     table = np.concatenate([np.transpose(curves, (2, 0, 1)).reshape(n, W * K),
                             np.transpose(values, (1, 0, 2)).reshape(n, W * values.shape[2])], axis=1)
-    table = np.ascontiguousarray(table.astype(np.float32))
-    _lib.check(_lib.lib().smart_db_append_rows(path.encode('utf8'), table.ctypes.data_as(ctypes.POINTER(ctypes.c_float)),
-                                               table.shape[0], table.shape[1], 0))
+    append_float32_rows(path, np.ascontiguousarray(table.astype(np.float32)))

@@ -93,6 +93,14 @@ def best_rows(sort_fn, constrained, nb_best):
     return idx[np.argsort(sort_fn[idx])][-nb_best:]
 
 
+def append_float32_rows(path, table):
+    """The rows of a contiguous float32 [n, k] table onto the end of the file `path`, as a sampling database prints them
+    ('%.6e', comma-separated, formatted by the library)."""
+    from .. import _lib
+    _lib.check(_lib.lib().smart_db_append_rows(path.encode('utf8'), table.ctypes.data_as(ctypes.POINTER(ctypes.c_float)),
+                                               table.shape[0], table.shape[1], 0))
+
+
 def as_stored(matrix):
     """What a float64 matrix becomes on its way through a sampling database: cast to float32, printed '%.6e', parsed
     back to float32 (montecarlo.py:225-231, :262) -- 7 significant digits, not a float32 round trip.  Done with the
@@ -105,17 +113,15 @@ def as_stored(matrix):
     fd, path = tempfile.mkstemp(prefix='smart_rows_')
     os.close(fd)
     try:
-        L = _lib.lib()
-        _lib.check(L.smart_db_append_rows(path.encode('utf8'), table.ctypes.data_as(ctypes.POINTER(ctypes.c_float)),
-                                          table.shape[0], table.shape[1], 0))
+        append_float32_rows(path, table)
         with open(path, 'rb') as f:
             text = f.read()
     finally:
         os.remove(path)
     out = np.empty_like(table)
     cols = np.arange(table.shape[1], dtype=np.int32)
-    n = L.smart_db_parse_rows(text, len(text), table.shape[1], cols.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
-                              table.shape[1], out.ctypes.data_as(ctypes.POINTER(ctypes.c_float)), table.shape[0], 0)
+    n = _lib.lib().smart_db_parse_rows(text, len(text), table.shape[1], cols.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
+                                       table.shape[1], out.ctypes.data_as(ctypes.POINTER(ctypes.c_float)), table.shape[0], 0)
     if n != table.shape[0]:
         raise Exception("as_stored: %d of %d rows came back" % (n, table.shape[0]))
     return out

@@ -13,6 +13,7 @@ from statistics import NormalDist
 import numpy as np
 
 from .montecarlo import MonteCarlo
+from .selection import append_float32_rows
 from .. import distributed as sdist
 from ..sampling import saltelli_design
 
@@ -139,8 +140,7 @@ class Sobol(MonteCarlo):
         design).  resamples > 0 adds the confidence half-widths per step.  write=True also writes
         `<catchment>.SMART.sobol.series` (DateTime,S1_<p>...,ST_<p>..., the float32 '%.6e' of the sampling database;
         rank 0 alone writes).  Under torch.distributed every rank computes everything itself.  -> SobolSeries"""
-        rows = self._device_sample if self._device_sample is not None else self._sample
-        out = self.model.simulate_ensemble(rows, save_discharge=True, math_mode=self.math_mode)
+        out, _ = self._launch_stored()
         res, S1, ST, S1_conf, ST_conf, mean, variance = self._analyse(out.discharge_report_major, resamples, conf_level,
                                                                       seed)
         stamps = self.model.timeseries_report[1:]
@@ -152,18 +152,14 @@ class Sobol(MonteCarlo):
                            res, path)
 
     @property
-    def _file_base(self):
-        return self.db_file[:-3] if self.db_file.endswith('.nc') else self.db_file
-
-    @property
     def indices_file(self):
         """`<out>/<catchment>.SMART.sobol.indices`: beside the sampling database, whatever its format."""
-        return self._file_base + '.indices'
+        return self._side_file('.indices')
 
     @property
     def series_file(self):
         """`<out>/<catchment>.SMART.sobol.series`"""
-        return self._file_base + '.series'
+        return self._side_file('.series')
 
 
 def series_header_line(parameters):
@@ -173,8 +169,6 @@ def series_header_line(parameters):
 def _write_labelled_rows(path, header, labels, table):
     """header line, then `label,` + the row of the table as the sampling database prints it (float32 '%.6e', formatted by
     the library into a file of its own beside `path`, which is then removed)."""
-    import ctypes
-    from .. import _lib
     table = np.ascontiguousarray(np.asarray(table, dtype=np.float64).astype(np.float32))
     lines = []
     if table.shape[0]:
@@ -182,8 +176,7 @@ def _write_labelled_rows(path, header, labels, table):
         if os.path.exists(raw):
             os.remove(raw)
         try:
-            _lib.check(_lib.lib().smart_db_append_rows(raw.encode('utf8'), table.ctypes.data_as(ctypes.POINTER(ctypes.c_float)),
-                                                       table.shape[0], table.shape[1], 0))
+            append_float32_rows(raw, table)
             with open(raw, encoding='utf8') as f:
                 lines = f.read().split('\n')[:-1]
         finally:
