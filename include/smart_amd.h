@@ -427,6 +427,42 @@ int32_t smart_sobol_max_resamples(void);
 int64_t smart_sobol_lds_capacity(void);
 
 /*
+ * Pareto selection: for every row of a score matrix, the number of rows that dominate it over n_objectives selected
+ * columns, each with a direction.  0 = the row is on the Pareto front (no row beats it on every selected score at once).
+ *   scores[n_rows][ld] (row-major: a row's scores together, ld > the largest selected column), eligible [n_rows] bytes
+ *   or NULL, dominated_by [n_rows] int32, workspace: device pointers.  columns, direction, target [n_objectives]: HOST
+ *   arrays, read before the call returns.  Asynchronous on stream; allocates nothing.
+ * key[i][m], in fp64 exactly as written, from x = scores[i][columns[m]]: x for SMART_PARETO_MAX, -x for SMART_PARETO_MIN,
+ * -|x - target[m]| for SMART_PARETO_TARGET (target may be NULL when no column is a TARGET).  Row i TAKES PART iff eligible
+ * is NULL or eligible[i] != 0, and none of its selected scores is a NaN; columns that are not selected, and the padding of
+ * ld, are never read.  Row j dominates row i iff both take part, key[j][m] >= key[i][m] for every m and key[j][m] >
+ * key[i][m] for at least one m (IEEE compares: -0.0 equals +0.0, infinities take part).  Rows whose keys are all equal do
+ * not dominate each other: a front keeps its duplicates.
+ *   dominated_by[i] = the number of rows that dominate row i; -1 where row i does not take part.
+ * The rows that take part are compacted first, so the work is E^2 pairs for E such rows, not n_rows^2.  Deterministic: the
+ * results are sums of integers that no atomic touches.
+ * Errors (all found before the device is touched): SMART_E_NULL scores, columns, direction or dominated_by missing, target
+ * missing where a direction is TARGET, workspace missing; SMART_E_SIZE n_rows outside 1 .. 2^31 - 1, n_objectives outside
+ * 1 .. SMART_PARETO_MAX_OBJECTIVES, a column negative or >= ld, a column named twice, a TARGET's target NaN or infinite,
+ * workspace_bytes below smart_pareto_workspace_bytes; SMART_E_MODE an unknown direction; then SMART_E_NO_DEVICE.
+ */
+#define SMART_PARETO_MAX_OBJECTIVES 16
+#define SMART_PARETO_MAX 0
+#define SMART_PARETO_MIN 1
+#define SMART_PARETO_TARGET 2
+int smart_pareto_counts_hip(int64_t n_rows, const double *scores, int64_t ld, const int32_t *columns,
+                            const int32_t *direction, const double *target, int32_t n_objectives, const uint8_t *eligible,
+                            int32_t *dominated_by, void *workspace, int64_t workspace_bytes, void *stream);
+
+/* The workspace smart_pareto_counts_hip needs, in bytes: a counter, the compacted keys (n_rows x 2, 4, 8 or 16 doubles),
+ * the list of the rows that take part and 16 partial counts per row.  Monotone in both arguments; 0 for sizes the entry
+ * refuses.  Needs no device. */
+int64_t smart_pareto_workspace_bytes(int64_t n_rows, int32_t n_objectives);
+
+/* SMART_PARETO_MAX_OBJECTIVES as the library was built.  Needs no device. */
+int smart_pareto_max_objectives(void);
+
+/*
  * Sampling database, CSV flavour -- the rows MonteCarlo.save writes one by one (montecarlo.py:211-231): every value
  * cast to float32 and printed '%.6e', comma separated, one '\n'-terminated line per sample.  HOST pointers, no
  * device involved.  Appends n_rows lines of n_cols values (row-major float32 table: objective functions, parameters,

@@ -28,6 +28,8 @@ TRANSFORMS = {'none': 0, 'sqrt': 1, 'log': 2, 'inverse': 3}     # SMART_TRANSFOR
 OBJFN_WINDOW_COLS = 7
 FDC_METHODS = {'auto': 0, 'sort': 1, 'select': 2}              # SMART_FDC_*
 SOBOL_MAX_PARAMS = 16
+PARETO_MAX_OBJECTIVES = 16
+PARETO_DIRECTIONS = {'max': 0, 'min': 1, 'target': 2}           # SMART_PARETO_*
 
 _dp = ctypes.c_void_p   # device or host address, passed as an integer
 
@@ -81,6 +83,11 @@ SYMBOLS = {
     'smart_sobol_workspace_bytes': (ctypes.c_int64, [ctypes.c_int64, ctypes.c_int32, ctypes.c_int64, ctypes.c_int32]),
     'smart_sobol_max_resamples': (ctypes.c_int32, []),
     'smart_sobol_lds_capacity': (ctypes.c_int64, []),
+    'smart_pareto_counts_hip': (ctypes.c_int, [ctypes.c_int64, _dp, ctypes.c_int64, ctypes.POINTER(ctypes.c_int32),
+                                               ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_double),
+                                               ctypes.c_int32, _dp, _dp, _dp, ctypes.c_int64, _dp]),
+    'smart_pareto_workspace_bytes': (ctypes.c_int64, [ctypes.c_int64, ctypes.c_int32]),
+    'smart_pareto_max_objectives': (ctypes.c_int, []),
     'smart_db_append_rows': (ctypes.c_int, [ctypes.c_char_p, ctypes.POINTER(ctypes.c_float), ctypes.c_int64,
                                             ctypes.c_int64, ctypes.c_int32]),
     'smart_db_parse_rows': (ctypes.c_int64, [ctypes.c_char_p, ctypes.c_int64, ctypes.c_int64,

@@ -1,8 +1,9 @@
 """The analyses of a stored [R, N] discharge matrix (row r = every sample's discharge of report step r), each one launch
 through the C ABI (csrc/smart_analysis_capi.hip): objective functions, weighted quantiles over the samples, objective
-functions per window of report steps, flow duration curves, Sobol indices.  torch tensors in, torch tensors out, as in
+functions per window of report steps, flow duration curves, Sobol indices -- and the Pareto selection over the scores
+they leave, [N, C] with a row per sample.  torch tensors in, torch tensors out, as in
 engine.py -- which imports this module and re-exports every public name of it (engine.flow_duration and the others are
-these functions); what the five share on the way to the launch are the private helpers at the top.
+these functions); what they share on the way to the launch are the private helpers at the top.
 """
 import ctypes
 
@@ -302,3 +303,127 @@ def sobol_indices(values, n_base, n_params, counts=None):
                                              counts.data_ptr() if B else None, B, _ptr(S1_std), _ptr(ST_std), _ptr(work),
                                              need, _stream(dev)))
     return SobolResult(S1, ST, moments, S1_std, ST_std)
+
+
+def pareto_max_objectives():
+    """The largest number of objectives of one pareto_counts call (no device needed)."""
+    return int(_lib.lib().smart_pareto_max_objectives())
+
+
+class _ParetoCall(object):
+    """The checked arguments of pareto_counts / pareto_ranks.  Everything that can be refused from the words and the
+    shapes alone is refused in the constructor, before anything is moved to a device; `counts` then launches the C
+    entry, as often as a ranking has fronts."""
+
+    def __init__(self, who, scores, directions, targets, columns, eligible):
+        self.who = who
+        if isinstance(directions, (str, bytes)) or (isinstance(directions, tuple) and len(directions) == 2
+                                                    and directions[0] == 'target'):
+            directions = [directions]
+        directions = list(directions)
+        M = len(directions)
+        if M < 1 or M > _lib.PARETO_MAX_OBJECTIVES:
+            raise SmartEngineError(-2, "{}: {} objectives, between 1 and {} per call."
+                                   .format(who, M, _lib.PARETO_MAX_OBJECTIVES))
+        if targets is not None and len(targets) != M:
+            raise SmartEngineError(-2, "{}: {} targets for {} objectives.".format(who, len(targets), M))
+        code, target = np.zeros(M, dtype=np.int32), np.zeros(M, dtype=np.float64)
+        for m, word in enumerate(directions):
+            value = None
+            if isinstance(word, (tuple, list)):
+                if len(word) != 2:
+                    raise SmartEngineError(-7, "{}: direction '{}' unknown.".format(who, word))
+                word, value = word
+            code[m] = _code(who, 'direction', _lib.PARETO_DIRECTIONS, word)
+            if word == 'target':
+                if value is None and targets is not None:
+                    value = targets[m]
+                if value is None:
+                    raise SmartEngineError(-1, "{}: objective {} is a 'target' without a value.".format(who, m))
+                target[m] = float(value)
+                if not np.isfinite(target[m]):
+                    raise SmartEngineError(-2, "{}: target {} of objective {} must be finite.".format(who, value, m))
+            elif value is not None:
+                raise SmartEngineError(-7, "{}: direction '{}' takes no value.".format(who, word))
+        shape = tuple(scores.shape)
+        if len(shape) == 1:
+            shape = (shape[0], 1)
+        if len(shape) != 2:
+            raise SmartEngineError(-2, "{}: scores [N, C] or [N] are needed, not shape {}.".format(who, tuple(scores.shape)))
+        N, C = shape
+        cols = np.arange(M, dtype=np.int32) if columns is None else np.asarray(columns).reshape(-1)
+        if cols.dtype.kind not in 'iu' or len(cols) != M:
+            raise SmartEngineError(-2, "{}: columns must be {} integers, one per objective.".format(who, M))
+        if len(set(cols.tolist())) != M or cols.min() < 0 or cols.max() >= C:
+            raise SmartEngineError(-2, "{}: the columns {} are not {} different ones of the {} of the scores."
+                                   .format(who, cols.tolist(), M, C))
+        if eligible is not None and tuple(eligible.shape) != (N,):
+            raise SmartEngineError(-2, "{}: eligible has shape {} where one entry per row ({},) is expected."
+                                   .format(who, tuple(eligible.shape), N))
+        self.N, self.M = N, M
+        self.code, self.target = code, target
+        self.cols = np.ascontiguousarray(cols.astype(np.int32))
+        # ---- from here on the device
+        self.L = _lib.lib()
+        if len(scores.shape) == 1:
+            scores = scores.reshape(-1, 1)
+        self.scores, _, _, self.ld = _matrix(scores)
+        self.device = self.scores.device
+        self.eligible = None if eligible is None else self.mask(eligible)
+        self.work, self.need = (None, 0) if N == 0 else \
+            _workspace(int(self.L.smart_pareto_workspace_bytes(N, M)), self.device)
+
+    def mask(self, flags):
+        """flags [N] (bool or numbers, host or device) -> contiguous uint8 device tensor, 1 where not zero"""
+        if not isinstance(flags, torch.Tensor):
+            flags = torch.from_numpy(np.ascontiguousarray(np.asarray(flags) != 0))
+        return (flags.to(self.device) != 0).to(torch.uint8).contiguous()
+
+    def counts(self, eligible):
+        """eligible: uint8 device tensor [N] or None -> int32 device tensor [N]"""
+        out = torch.empty((self.N,), dtype=torch.int32, device=self.device)
+        if self.N == 0:
+            return out
+        i32, f64 = ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_double)
+        with torch.cuda.device(self.device):
+            _lib.check(self.L.smart_pareto_counts_hip(self.N, self.scores.data_ptr(), self.ld, self.cols.ctypes.data_as(i32),
+                                                      self.code.ctypes.data_as(i32), self.target.ctypes.data_as(f64),
+                                                      self.M, _ptr(eligible), out.data_ptr(), _ptr(self.work), self.need,
+                                                      _stream(self.device)))
+        return out
+
+
+def pareto_counts(scores, directions, targets=None, columns=None, eligible=None):
+    """For every row of a score matrix, the number of rows that dominate it over the selected columns -> int32 device
+    tensor [N]: 0 = the row is on the Pareto front, -1 = the row does not take part.
+    scores: [N, C] or [N], host array or device tensor, float64 or float32 (widened exactly); the leading dimension of a
+    device matrix is honoured.  directions: one word per objective, at most pareto_max_objectives(): 'max', 'min' or
+    ('target', value) -- or 'target' with its value in targets[m].  columns: the column of every objective (default
+    0 .. M-1), no column twice; columns that are not selected are never read.  eligible: [N] flags, or None for every row.
+    The key of a score x is x, -x or -|x - value|; a row takes part iff it is eligible and none of its selected scores is
+    a NaN; row j dominates row i iff both take part, every key of j is >= that of i and one is > (rows with equal keys do
+    not dominate each other: a front keeps its duplicates).  include/smart_amd.h: smart_pareto_counts_hip."""
+    call = _ParetoCall('pareto_counts', scores, directions, targets, columns, eligible)
+    return call.counts(call.eligible)
+
+
+def pareto_ranks(scores, directions, targets=None, columns=None, eligible=None, max_rank=1):
+    """The non-dominated ranks of the rows of a score matrix, by peeling -> int32 device tensor [N]: rank 1 is the rows
+    that pareto_counts gives 0, rank r the rows it gives 0 once the ranks below r are left out; 0 = not ranked within
+    max_rank, -1 = the row does not take part.  max_rank=None ranks every row.  One launch and one read of the number of
+    rows that are left per front; arguments as for pareto_counts."""
+    if max_rank is not None and int(max_rank) < 1:
+        raise SmartEngineError(-2, "pareto_ranks: max_rank must be at least 1 or None (got {}).".format(max_rank))
+    call = _ParetoCall('pareto_ranks', scores, directions, targets, columns, eligible)
+    ranks = torch.zeros((call.N,), dtype=torch.int32, device=call.device)
+    left, rank = call.eligible, 0
+    while call.N and (max_rank is None or rank < int(max_rank)):
+        counts = call.counts(left)
+        rank += 1
+        if rank == 1:
+            ranks[counts < 0] = -1
+        ranks[counts == 0] = rank
+        left = (counts > 0).to(torch.uint8)
+        if int(left.sum()) == 0:        # the one read of this front
+            break
+    return ranks

@@ -39,6 +39,9 @@ UNITS = {
     # Sobol sensitivity indices of a Saltelli design (point estimates and bootstrap): default flags, NaNs honoured -- a
     # value that is not finite has to reach the one sum that finds it
     'smart_sobol.hip': [],
+    # Pareto selection over the scores of the analyses (dominance counts): default flags, NaNs honoured -- the keys are
+    # compared as IEEE says
+    'smart_pareto.hip': [],
     'smart_capi.hip': [],
     # the C entries of the matrix analyses, and smart_objfn_matrix: the flags smart_capi.hip had it compiled with
     'smart_analysis_capi.hip': [],

@@ -1,7 +1,7 @@
 // smart_analysis_capi.hip -- the C ABI of the analyses of a stored discharge matrix sim[R][ld] (include/smart_amd.h):
-// objective functions, weighted quantiles, objective functions per window, flow duration curves, Sobol indices, with
-// their capacity and workspace entries -- validation and launch -- and the one kernel among them that has no unit of its
-// own, smart_objfn_matrix.  Every refusal comes before the device is asked for; the rules the entries share are the
+// objective functions, weighted quantiles, objective functions per window, flow duration curves, Sobol indices, and of
+// the Pareto selection over the scores they leave, with their capacity and workspace entries -- validation and launch --
+// and the one kernel among them that has no unit of its own, smart_objfn_matrix.  Every refusal comes before the device is asked for; the rules the entries share are the
 // static helpers below, which take the entry's name for the text.
 #include "smart_capi_internal.h"
 #include "smart_device.h"
@@ -178,6 +178,18 @@ static const char *sobol_sizes(int64_t n_base, int32_t n_params, int64_t n_rows,
     return text;
 }
 
+// the size rules of smart_pareto_counts_hip, shared with smart_pareto_workspace_bytes; 0 or the text of the refusal
+static const char *pareto_sizes(int64_t n_rows, int32_t n_objectives, char *text, size_t len)
+{
+    if (n_rows < 1 || n_rows > 0x7fffffffll)
+        snprintf(text, len, "n_rows %lld must be in 1 .. 2^31 - 1", (long long)n_rows);
+    else if (n_objectives < 1 || n_objectives > SMART_PARETO_MAX_OBJECTIVES)
+        snprintf(text, len, "n_objectives %d must be in 1 .. %d", (int)n_objectives, SMART_PARETO_MAX_OBJECTIVES);
+    else
+        return nullptr;
+    return text;
+}
+
 } // namespace smart
 
 using namespace smart;
@@ -348,5 +360,56 @@ int64_t smart_sobol_workspace_bytes(int64_t n_base, int32_t n_params, int64_t n_
 int32_t smart_sobol_max_resamples(void) { return sobol_max_resamples(); }
 
 int64_t smart_sobol_lds_capacity(void) { return sobol_lds_capacity(); }
+
+int smart_pareto_counts_hip(int64_t n_rows, const double *scores, int64_t ld, const int32_t *columns,
+                            const int32_t *direction, const double *target, int32_t n_objectives, const uint8_t *eligible,
+                            int32_t *dominated_by, void *workspace, int64_t workspace_bytes, void *stream)
+{
+    static const char entry[] = "smart_pareto_counts_hip";
+    int rc;
+    if (!scores || !columns || !direction || !dominated_by)
+        return fail(SMART_E_NULL, "%s: scores, columns, direction and dominated_by are required (%s is NULL)", entry,
+                    !scores ? "scores" : (!columns ? "columns" : (!direction ? "direction" : "dominated_by")));
+    char text[160];
+    if (pareto_sizes(n_rows, n_objectives, text, sizeof text))
+        return fail(SMART_E_SIZE, "%s: %s", entry, text);
+    for (int32_t m = 0; m < n_objectives; ++m) {
+        if (columns[m] < 0 || columns[m] >= ld)
+            return fail(SMART_E_SIZE, "%s: column %d of objective %d is outside 0 .. ld - 1 = %lld", entry, (int)columns[m],
+                        (int)m, (long long)ld - 1);
+        for (int32_t k = 0; k < m; ++k)
+            if (columns[k] == columns[m])
+                return fail(SMART_E_SIZE, "%s: column %d is named twice (objectives %d and %d)", entry, (int)columns[m],
+                            (int)k, (int)m);
+    }
+    for (int32_t m = 0; m < n_objectives; ++m)
+        if (direction[m] != SMART_PARETO_MAX && direction[m] != SMART_PARETO_MIN && direction[m] != SMART_PARETO_TARGET)
+            return fail(SMART_E_MODE, "%s: direction '%d' of objective %d unknown.", entry, (int)direction[m], (int)m);
+    for (int32_t m = 0; m < n_objectives; ++m) {
+        if (direction[m] != SMART_PARETO_TARGET)
+            continue;
+        if (!target)
+            return fail(SMART_E_NULL, "%s: objective %d is a TARGET (target is NULL)", entry, (int)m);
+        if (!std::isfinite(target[m]))
+            return fail(SMART_E_SIZE, "%s: target %g of objective %d must be finite", entry, target[m], (int)m);
+    }
+    if ((rc = workspace_fits(entry, /*for_objfn=*/false, workspace, workspace_bytes,
+                             pareto_workspace_bytes((long)n_rows, (int)n_objectives))) ||
+        (rc = device_ready()))
+        return rc;
+    launch_pareto((long)n_rows, scores, (long)ld, columns, direction, target, (int)n_objectives, eligible, dominated_by,
+                  workspace, (hipStream_t)stream);
+    return launched();
+}
+
+int64_t smart_pareto_workspace_bytes(int64_t n_rows, int32_t n_objectives)
+{
+    char text[160];
+    if (pareto_sizes(n_rows, n_objectives, text, sizeof text))
+        return 0;
+    return pareto_workspace_bytes((long)n_rows, (int)n_objectives);
+}
+
+int smart_pareto_max_objectives(void) { return SMART_PARETO_MAX_OBJECTIVES; }
 
 } // extern "C"

@@ -52,4 +52,9 @@ long sobol_workspace_bytes();
 void launch_sobol(long n, int k, long M, const double *y, long ld, double *s1, double *st, double *moments,
                   const unsigned short *counts, int B, double *s1_std, double *st_std, hipStream_t s);
 
+// ---- smart_pareto.hip
+long pareto_workspace_bytes(long N, int M);
+void launch_pareto(long N, const double *scores, long ld, const int *columns, const int *direction, const double *target,
+                   int M, const unsigned char *eligible, int *dominated_by, void *workspace, hipStream_t s);
+
 } // namespace smart

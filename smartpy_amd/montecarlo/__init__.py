@@ -1,9 +1,10 @@
-"""Monte-Carlo workflows on the GPU engine (counterpart of smartpy/montecarlo): LHS, GLUE, Best, Total, and the Sobol
-sensitivity analysis on a Saltelli design."""
+"""Monte-Carlo workflows on the GPU engine (counterpart of smartpy/montecarlo): LHS, GLUE, Best, Total, the Sobol
+sensitivity analysis on a Saltelli design, and the Pareto selection over several objective functions."""
 from .lhs import LHS
 from .glue import GLUE
 from .best import Best
 from .total import Total
 from .sobol import Sobol
+from .pareto import Pareto
 
-__all__ = ['LHS', 'GLUE', 'Best', 'Total', 'Sobol']
+__all__ = ['LHS', 'GLUE', 'Best', 'Total', 'Sobol', 'Pareto']

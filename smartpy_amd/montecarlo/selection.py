@@ -1,6 +1,7 @@
-"""Conditions on objective functions shared by GLUE and Best (glue.py:222-289, best.py:221-287).
+"""Conditions on objective functions shared by GLUE and Best (glue.py:222-289, best.py:221-287), and the Pareto
+selection over several of them (pareto_rows: no counterpart in the reference).
 
-`condition_mask` and `best_rows` accept numpy arrays (what the file-based second stages of the reference hand them)
+`condition_mask`, `best_rows` and `pareto_rows` accept numpy arrays (what the file-based second stages of the reference hand them)
 as well as torch tensors on any device: on an `[N, 8]` objective matrix that is still on the GPU the behavioural
 mask, its count and the top-k rows are computed there and only the selected rows travel.
 """
@@ -91,6 +92,24 @@ def best_rows(sort_fn, constrained, nb_best):
         return idx[picked]
     idx = np.nonzero(constrained)[0]
     return idx[np.argsort(sort_fn[idx])][-nb_best:]
+
+
+def pareto_rows(obj_fns, directions, allowed=None, max_rank=1):
+    """The rows of the first max_rank non-dominated fronts of obj_fns [N, k] (every column an objective, directions[c]
+    its word: 'max', 'min' or ('target', value)) among the rows where `allowed` is true (None: every row) -> (row
+    indices sorted by rank, then by row index; their ranks, 1 .. max_rank).  max_rank=None ranks every row that takes
+    part; a row with a NaN among its objectives does not.  The fronts are peeled on the GPU (engine.pareto_ranks) -- a
+    numpy matrix is uploaded and numpy arrays come back, a torch tensor gives tensors on its device; there is no CPU
+    form."""
+    from .. import engine
+    ranks = engine.pareto_ranks(obj_fns, directions, eligible=allowed, max_rank=max_rank)
+    import torch
+    rows = torch.nonzero(ranks > 0, as_tuple=False)[:, 0]
+    rows = rows[torch.argsort(ranks[rows], stable=True)]        # (rows ascend within a rank: the sort is stable)
+    picked = ranks[rows]
+    if _is_torch(obj_fns):
+        return rows.to(obj_fns.device), picked.to(obj_fns.device)
+    return rows.cpu().numpy(), picked.cpu().numpy()
 
 
 def append_float32_rows(path, table):
