@@ -674,23 +674,40 @@ struct Reporter {
             row += a.ld;
     }
 
-    // The same with the observation e = obs[r] and w = e - mean(e) requested ahead of time by the caller
-    // (interval_loop_obs): no scalar-load latency between the last step of the interval and the moments.
-    __device__ __forceinline__ void emit_prefetched(const KArgs &a, const LaneCtx &x, long r, double val, double e,
-                                                    double w)
+    // The report of the interval engine (run_ensemble_merged over piecewise-constant forcing): what emit() does, operation
+    // for operation, in the form of the streamed step loop above -- the row pointer (begin_rows), no test for the lanes
+    // beyond the batch, a missing observation told by the mark in its deviation (one 32-bit scalar compare: e and w are in
+    // scalar registers, requested an interval ahead by interval_loop_obs) -- and with report 0, the one that sets `shift`,
+    // looked for only where the caller says it may be (MAY_BE_FIRST: the intervals interval_loop takes on their own;
+    // `first`: this is report 0).  OBJ: the caller has observations (Reporter::want_obj, decided outside its loop).
+    template <bool OBJ, bool MAY_BE_FIRST, bool NONTEMPORAL>
+    __device__ __forceinline__ void emit_interval(bool store, long ld, bool first, double val, double e, double w)
     {
-        if (a.discharge && x.live)
-            a.discharge[(x.c * a.R + r) * a.ld + x.n] = val;
-        if (want_obj && r == 0)
-            shift = val;
-        if (want_obj && !is_nan_bits(e)) { // montecarlo.py:195-196
-            const double d = val - e;
-            const double u = val - shift;
-            A += d;
-            B += d * d;
-            C1 += u;
-            C2 += u * u;
-            C3 += w * u;
+        if (store) {
+            if constexpr (NONTEMPORAL)
+                __builtin_nontemporal_store(val, row);
+            else
+                *row = val;
+            row += ld;
+        }
+        if constexpr (OBJ) {
+            if constexpr (MAY_BE_FIRST) {
+                if (first)
+                    shift = val;
+            }
+            // is_missing_mark(w), with the upper half of w as an integer of its own in a scalar register (no instruction):
+            // left to itself hipcc widens both sides and compares 64 bits, four scalar instructions for one
+            unsigned hi = (unsigned)(__builtin_bit_cast(unsigned long long, w) >> 32);
+            asm("" : "+s"(hi));
+            if (hi != (unsigned)(kMissingObs >> 32)) { // montecarlo.py:195-196
+                const double d = val - e;
+                const double u = val - shift;
+                A += d;
+                B += d * d;
+                C1 += u;
+                C2 += u * u;
+                C3 += w * u;
+            }
         }
     }
 };
@@ -1003,49 +1020,111 @@ __device__ __forceinline__ int forcing_kind(const KArgs &a, int flags)
 // loads kGroup intervals ahead (a dry interval takes ~100 cycles, far less than a load's latency).
 constexpr int kGroup = 4;
 
+//
+// The bookkeeping of the walk is the scalar unit's, and a lone wavefront pays for every instruction of it: the intervals
+// of a stretch are COUNTED from 0 in 32 bits (a stretch is a slice's share of the T / gap intervals of the run; the
+// scalar unit compares 32-bit counters, a 64-bit signed compare goes through the vector unit and VCC), and the forcing
+// of the next group is at a pointer that moves on by kGroup * gap, not at a product rebuilt for each of its intervals.
+//
+// OBS (the run proper of a caller with observations): the observation e of each interval's report and its deviation w
+// from the mean travel with the forcing -- scalar loads, a group ahead, four values of each to a request.  The two
+// arrays were written by smart_obs_prepare, a kernel that has ended, and nothing of this launch writes them; with the
+// discharge stores in the same loop hipcc does not take that from __restrict__ pointers that have been through a
+// struct and a lambda, and fetched each value into all 64 lanes with a vector load per interval: the constant address
+// space says it (as_constant).  With the forcing, not one report ahead of their use: scalar loads return out of order,
+// the only wait there is waits for all of them, and a request from the middle of a turn would put that wait in front
+// of whatever next touches a scalar register hipcc has given a second use.  obs / dev point at interval i0's entries.
+//
+// body(k, v, e, w, lead_tag): k the interval's number within the stretch; lead_tag says at compile time whether the
+// call is one of the `lead` intervals taken on their own ahead of the groups (or of the n % kGroup behind them: the
+// same code) -- the run proper takes report 0 there, the one report that sets Reporter::shift, so that the groups
+// carry no test for it.
+template <bool OBS, class Body>
+__device__ __forceinline__ void interval_walk(const double2 *__restrict__ f, const double *obs_, const double *dev_,
+                                              long i0, long i1, long gap, int lead, Body &&body)
+{
+    const int n = i1 > i0 ? (int)(i1 - i0) : 0;
+    const int n_lead = lead < n ? lead : n;
+    const int n_groups = (n - n_lead) / kGroup;
+    const int behind = n_lead + n_groups * kGroup; // the first interval behind the groups
+    const double2 *__restrict__ const f0 = f + i0 * gap;
+    const const_f64 obs = as_constant(obs_), dev = as_constant(dev_);
+#pragma nounroll
+    for (int pass = 0; pass < 2; ++pass) { // ONE instance of the single intervals for those ahead and those behind
+        const int s0 = pass ? behind : 0, s1 = pass ? n : n_lead;
+        const double2 *__restrict__ p1 = f0 + (long)s0 * gap;
+        for (int k = s0; k < s1; ++k, p1 += gap) {
+            if constexpr (OBS)
+                body(k, *p1, obs[k], dev[k], std::true_type{});
+            else
+                body(k, *p1, 0.0, 0.0, std::true_type{});
+        }
+        if (pass == 0 && n_groups > 0) {
+            const long group = (long)kGroup * gap;
+            const double2 *__restrict__ p = f0 + (long)n_lead * gap; // the group whose forcing is requested
+            const_f64 pe = obs + n_lead, pw = dev + n_lead;
+            double2 cur[kGroup], nxt[kGroup];
+            double e_cur[kGroup] = {}, e_nxt[kGroup] = {}, w_cur[kGroup] = {}, w_nxt[kGroup] = {};
+#pragma unroll
+            for (int j = 0; j < kGroup; ++j) {
+                cur[j] = p[j * gap];
+                if constexpr (OBS) {
+                    e_cur[j] = pe[j];
+                    w_cur[j] = pw[j];
+                }
+            }
+            // wait for the first group HERE: left pending into the loop, its s_waitcnt lands in the body, behind the
+            // requests for the next group -- and then waits for those too, every turn (time_loop_arms)
+#pragma unroll
+            for (int j = 0; j < kGroup; ++j) {
+                asm volatile("" ::"s"(cur[j].x), "s"(cur[j].y));
+                if constexpr (OBS)
+                    asm volatile("" ::"s"(e_cur[j]), "s"(w_cur[j]));
+            }
+            for (int g = 0; g < n_groups; ++g) {
+                if (g + 1 < n_groups) { // (last group: harmless re-load of itself)
+                    p += group;
+                    if constexpr (OBS) {
+                        pe += kGroup;
+                        pw += kGroup;
+                    }
+                }
+#pragma unroll
+                for (int j = 0; j < kGroup; ++j) {
+                    nxt[j] = p[j * gap];
+                    if constexpr (OBS) {
+                        e_nxt[j] = pe[j];
+                        w_nxt[j] = pw[j];
+                    }
+                }
+#pragma unroll
+                for (int j = 0; j < kGroup; ++j)
+                    body(n_lead + g * kGroup + j, cur[j], e_cur[j], w_cur[j], std::false_type{});
+#pragma unroll
+                for (int j = 0; j < kGroup; ++j) {
+                    cur[j] = nxt[j];
+                    e_cur[j] = e_nxt[j];
+                    w_cur[j] = w_nxt[j];
+                }
+            }
+        }
+    }
+}
+
 template <class Body>
 __device__ __forceinline__ void interval_loop(const double2 *__restrict__ f, long i0, long i1, long gap, Body &&body)
 {
-    const long n_groups = (i1 - i0) / kGroup;
-    double2 cur[kGroup], nxt[kGroup];
-    if (n_groups > 0) {
-#pragma unroll
-        for (int j = 0; j < kGroup; ++j)
-            cur[j] = f[(i0 + j) * gap];
-    }
-    for (long g = 0; g < n_groups; ++g) {
-        const long pre = i0 + (g + 1 < n_groups ? g + 1 : g) * kGroup; // last group: harmless re-load of itself
-#pragma unroll
-        for (int j = 0; j < kGroup; ++j)
-            nxt[j] = f[(pre + j) * gap];
-#pragma unroll
-        for (int j = 0; j < kGroup; ++j)
-            body(i0 + g * kGroup + j, cur[j]);
-#pragma unroll
-        for (int j = 0; j < kGroup; ++j)
-            cur[j] = nxt[j];
-    }
-    for (long i = i0 + n_groups * kGroup; i < i1; ++i)
-        body(i, f[i * gap]);
+    interval_walk<false>(f, nullptr, nullptr, i0, i1, gap, 0,
+                         [&](int k, const double2 v, double, double, auto) { body(k, v); });
 }
 
-// The same walk for the run proper: the observation of each interval and its deviation from the mean
-// (Reporter::emit_prefetched) are requested one interval ahead of their use (an interval takes 700-7,000 cycles).
+// The same walk for the run proper, with the observation of each interval and its deviation from the mean
+// (Reporter::emit_interval); `lead`: 1 where the stretch starts with report 0.
 template <class Body>
-__device__ __forceinline__ void interval_loop_obs(const double2 *__restrict__ f, const double *__restrict__ obs,
-                                                  const double *__restrict__ dev, long i0, long i1, long gap,
-                                                  Body &&body)
+__device__ __forceinline__ void interval_loop_obs(const double2 *__restrict__ f, const double *obs, const double *dev,
+                                                  long i0, long i1, long gap, int lead, Body &&body)
 {
-    if (i1 <= i0)
-        return;
-    double e = obs[i0], w = dev[i0];
-    interval_loop(f, i0, i1, gap, [&](long i, const double2 v) {
-        const long nx = i + 1 < i1 ? i + 1 : i;
-        const double e_nx = obs[nx], w_nx = dev[nx];
-        body(i, v, e, w);
-        e = e_nx;
-        w = w_nx;
-    });
+    interval_walk<true>(f, obs + i0, dev + i0, i0, i1, gap, lead, body);
 }
 
 // ---- time-sliced launch ----------------------------------------------------------------------------------------
@@ -1174,16 +1253,30 @@ __device__ __forceinline__ void run_ensemble_merged(const KArgs &a, const double
     // evaporation, the night block of sub-daily data -- the filling.  For forcing without negative or non-finite values
     // and waves with no layer above capacity (`quick`, as in the step loop); the kernels whose wet interval is the
     // asm loop.
-    bool quick = false, fits = false;
+    // (the two as integers in scalar registers, made once: a bool that lives through the loop lives as a lane mask, and
+    // hipcc makes the integer an asm operand or a scalar compare wants from it with v_cndmask / v_readfirstlane, per
+    // interval.  not_quick: all ones unless the shortcuts apply, to be or-ed onto the bits that must be zero.)
+    int fits = 0;
+    unsigned not_quick = ~0u;
     if constexpr (piecewise && Model::kWetAsm) {
         m.note_capacity();
-        fits = m.over_mask == 0; // for good: only a caller's initial state puts a layer above its capacity (no GUARD here)
-        quick = fits && !(fflags & kForcingInsane);
+        const bool fits_b = m.over_mask == 0; // for good: only a caller's initial state puts a layer above its capacity (no GUARD here)
+        fits = __builtin_amdgcn_readfirstlane((int)fits_b);
+        not_quick = 0u - (unsigned)__builtin_amdgcn_readfirstlane((int)!(fits_b && !(fflags & kForcingInsane)));
+        asm("" : "+s"(fits), "+s"(not_quick));
     }
+    // (the two tests on the BITS of the forcing, as integers the scalar unit compares: written as a compare of the bit
+    // pattern with 0 alone, hipcc turns them back into floating-point class tests, which only the vector unit has -- a
+    // v_cmp_class_f64 on a scalar pair, mask arithmetic and a branch on VCC per interval)
+    auto no_bits = [](double x, unsigned unless = 0) {
+        unsigned long long b = __builtin_bit_cast(unsigned long long, x) | unless;
+        asm("" : "+s"(b)); // (no instruction: the value as an integer in scalar registers, opaque to the optimiser)
+        return b == 0;
+    };
     auto interval = [&](const double2 v, double &acc, double &num, double &den) {
         if constexpr (piecewise && Model::kWetAsm) {
-            if (quick && __builtin_bit_cast(unsigned long long, v.x) == 0) {
-                if (__builtin_bit_cast(unsigned long long, v.y) == 0) {
+            if (no_bits(v.x, not_quick)) {
+                if (no_bits(v.y)) {
                     m.calm_interval(run_len, acc);
                 } else {
                     m.dry_interval(-v.y, run_len, acc);
@@ -1206,8 +1299,8 @@ __device__ __forceinline__ void run_ensemble_merged(const KArgs &a, const double
     [[maybe_unused]] auto interval_last = [&](const double2 v, double &qo, double &qg, double &qi) {
         if constexpr (piecewise && REPORT == kReportLast && Model::kWetAsm) {
             double sink = 0.0, n0 = 0.0, n1 = 0.0;
-            if (quick && __builtin_bit_cast(unsigned long long, v.x) == 0) {
-                if (__builtin_bit_cast(unsigned long long, v.y) == 0) {
+            if (no_bits(v.x, not_quick)) {
+                if (no_bits(v.y)) {
                     m.calm_interval(gap - 1, sink);
                     m.last_step_flows(qo, qg, qi);
                     m.calm_interval(1, sink);
@@ -1309,16 +1402,26 @@ __device__ __forceinline__ void run_ensemble_merged(const KArgs &a, const double
     const double inv_gap = 1.0 / (double)gap;
     const bool starts_run = ra == 0 && (rb > 0 || last);
     constexpr bool deferring = !piecewise; // is an evaporation demand carried in `pend`?  (the step loop's lazy dry steps)
+    // The report of the interval engine: the row of the discharge matrix at a per-lane pointer that moves on by ld (the
+    // lanes beyond the batch carry its last sample and store that sample's value where its own lane does: no EXEC mask
+    // around the store), report 0 -- only the slice with ra == 0 has it -- among the intervals interval_loop takes on
+    // their own, the last report interval (where the SPLIT models park their state) as a count within the slice.
+    [[maybe_unused]] const bool first_slice = ra == 0;
+    [[maybe_unused]] int store = __builtin_amdgcn_readfirstlane((int)(a.discharge != nullptr));
+    asm("" : "+s"(store)); // (an integer in a scalar register, as above)
+    [[maybe_unused]] const int k_park = Model::kSplit && ra <= a.R - 1 && a.R - 1 < rb ? (int)(a.R - 1 - ra) : -1;
+    if constexpr (piecewise)
+        rep.begin_rows(a, x, ra);
     if constexpr (runs) {
         // `per` runs make a report interval; the walk is over runs, the report falls on every per-th of them
         const long per = gap / run_len;
-        interval_loop(f, wa * per, wb * per, run_len, [&](long, const double2 v) { interval(v, s0, s1, s2); });
+        interval_loop(f, wa * per, wb * per, run_len, [&](int, const double2 v) { interval(v, s0, s1, s2); });
         if (starts_run)
             m.begin_run();
         long j = 0, r = ra;
         double acc = 0.0;
         rep.prime(a, ra);
-        interval_loop(f, ra * per, rb * per, run_len, [&](long, const double2 v) {
+        interval_loop(f, ra * per, rb * per, run_len, [&](int, const double2 v) {
             if (Model::kSplit && j == 0 && r == a.R - 1)
                 park_state();
             interval(v, acc, num, den);
@@ -1331,48 +1434,50 @@ __device__ __forceinline__ void run_ensemble_merged(const KArgs &a, const double
             }
         });
     } else if constexpr (piecewise && REPORT == kReportLast) {
-        interval_loop(f, wa, wb, gap, [&](long, const double2 v) { interval_last(v, s0, s1, s2); });
+        interval_loop(f, wa, wb, gap, [&](int, const double2 v) { interval_last(v, s0, s1, s2); });
         if (starts_run)
             m.begin_run();
         if (rep.want_obj) {
-            interval_loop_obs(f, rep.obs, rep.ws + kWsHead, ra, rb, gap,
-                              [&](long r, const double2 v, const double e, const double w) {
+            interval_loop_obs(f, rep.obs, rep.ws + kWsHead, ra, rb, gap, first_slice ? 1 : 0,
+                              [&](int k, const double2 v, const double e, const double w, auto lead_tag) {
                                   double qo, qg, qi;
                                   interval_last(v, qo, qg, qi);
-                                  rep.emit_prefetched(a, x, r, qo, e, w);
+                                  rep.template emit_interval<true, decltype(lead_tag)::value, false>(
+                                      store, a.ld, first_slice && k == 0, qo, e, w);
                                   num_raw += qg;
                                   den_raw += qi;
                               });
         } else {
-            interval_loop(f, ra, rb, gap, [&](long r, const double2 v) {
+            interval_loop(f, ra, rb, gap, [&](int, const double2 v) {
                 double qo, qg, qi;
                 interval_last(v, qo, qg, qi);
-                rep.emit(a, x, r, qo);
+                rep.template emit_interval<false, false, true>(store, a.ld, false, qo, 0.0, 0.0);
                 num_raw += qg;
                 den_raw += qi;
             });
         }
     } else if constexpr (piecewise) {
-        interval_loop(f, wa, wb, gap, [&](long, const double2 v) { interval(v, s0, s1, s2); });
+        interval_loop(f, wa, wb, gap, [&](int, const double2 v) { interval(v, s0, s1, s2); });
         if (starts_run)
             m.begin_run();
         if (rep.want_obj) {
-            interval_loop_obs(f, rep.obs, rep.ws + kWsHead, ra, rb, gap,
-                              [&](long r, const double2 v, const double e, const double w) {
-                                  if (Model::kSplit && r == a.R - 1)
+            interval_loop_obs(f, rep.obs, rep.ws + kWsHead, ra, rb, gap, first_slice ? 1 : 0,
+                              [&](int k, const double2 v, const double e, const double w, auto lead_tag) {
+                                  if (Model::kSplit && k == k_park)
                                       park_state();
                                   double acc = 0.0;
                                   interval(v, acc, num, den);
-                                  rep.emit_prefetched(a, x, r, acc * inv_gap, e, w);
+                                  rep.template emit_interval<true, decltype(lead_tag)::value, false>(
+                                      store, a.ld, first_slice && k == 0, acc * inv_gap, e, w);
                                   q_out_total += acc;
                               });
         } else {
-            interval_loop(f, ra, rb, gap, [&](long r, const double2 v) {
-                if (Model::kSplit && r == a.R - 1)
+            interval_loop(f, ra, rb, gap, [&](int k, const double2 v) {
+                if (Model::kSplit && k == k_park)
                     park_state();
                 double acc = 0.0;
                 interval(v, acc, num, den);
-                rep.emit(a, x, r, acc * inv_gap);
+                rep.template emit_interval<false, false, true>(store, a.ld, false, acc * inv_gap, 0.0, 0.0);
                 q_out_total += acc;
             });
         }

@@ -5,12 +5,14 @@
 REV=${1:-HEAD}; NAME=${2:-prev}
 ROOT=$(cd "$(dirname "$0")/.." && pwd)
 TMP=$(mktemp -d)
-git -C $ROOT archive $REV smartpy_amd/csrc smartpy_amd/build.py include | tar -x -C $TMP
+git -C $ROOT archive $REV smartpy_amd/csrc smartpy_amd/build.py smartpy_amd/isa_lint.py include | tar -x -C $TMP
 mkdir -p $ROOT/tools/variants
+# (build.py imports its sibling isa_lint: the revision's two files as a package of their own, under another name)
+mv $TMP/smartpy_amd $TMP/rev_pkg && touch $TMP/rev_pkg/__init__.py
 python3 - <<PY
-import importlib.util, shutil
-spec = importlib.util.spec_from_file_location('rev_build', '$TMP/smartpy_amd/build.py')
-b = importlib.util.module_from_spec(spec); spec.loader.exec_module(b)
+import shutil, sys
+sys.path.insert(0, '$TMP')
+from rev_pkg import build as b
 out = b.build(force=True, lib_path=b.LIB)
 shutil.copy(out, '$ROOT/tools/variants/libsmart_amd_$NAME.so')
 print('$ROOT/tools/variants/libsmart_amd_$NAME.so')
