@@ -120,8 +120,6 @@ __global__ void smart_workspace_reset(int *hdr, long n_hdr, int *flags, long n_f
 }
 
 // smart_plan_ensemble: the arithmetic classes present among the blocks of 64 rows, and the kinds of forcing
-constexpr int kHdrPlan = 8, kHdrPlanIllCond = 9;
-
 __global__ __launch_bounds__(kWave) void smart_classify_rows(KArgs a)
 {
     const int cls = wave_class(a, (long)blockIdx.x, (long)blockIdx.y);
@@ -178,24 +176,58 @@ static DeviceCtx *device_ctx()
     return d->n_simd > 0 ? d : nullptr;
 }
 
-static const void *fast_kernel(FastKernel k)
+// ---- what the environment may override.  Read once at the top of each entry that needs it -- per call, not per
+// process: the tests and the tools under tools/ flip these between two calls, and smartpy_amd._lib sets the first.
+struct Overrides {
+    int pair_blocks = -1;   // SMART_PAIR_BLOCKS=0|1: the threaded chunks / the pair blocks of the streaming step loops,
+                            // whatever the lint stamp says (pair_blocks_wanted); -1: unset, the stamp decides
+    int time_slices = 0;    // SMART_TIME_SLICES=n: the time slices of a sliceable launch when SmartEnsemble.time_slices
+                            // is 0 (n <= 0 counts as 1); 0: unset, plan_time_slices decides
+    int illcond_form = SMART_LITERAL_FORM_AUTO; // SMART_ILLCOND_FORM=rows|lanes: the class-3 kernel when
+                                                // SmartEnsemble.literal_form is _AUTO; anything else: illcond_form decides
+    int exits = -1;         // SMART_EXITS=0|1: the interval engine without / with early exits; -1: unset, from the load
+    long max_polls = kDefaultMaxPolls; // SMART_DEBUG_MAX_POLLS=n > 0: bound of a slice's wait for its predecessor (tests)
+    int drop_slice = 0;     // SMART_DEBUG_DROP_SLICE=1: slice 0 of block 0 never publishes (tests)
+    bool allsteps_fast = false; // SMART_ALLSTEPS_MATH=fast: smart_allsteps_hip through the fast kernels
+    // (SMART_FDC_XCD_REMAP belongs to the flow duration curves: smart_analysis_capi.hip)
+};
+
+static Overrides read_overrides()
 {
-    if (const void *f = fast_kernel_intervals(k))
-        return f;
-    if (const void *f = fast_kernel_steps(k))
-        return f;
-    if (const void *f = fast_kernel_runs(k))
-        return f;
-    if (const void *f = fast_kernel_reports(k))
-        return f;
-    return fast_kernel_guarded(k);
+    Overrides o;
+    if (const char *v = getenv("SMART_PAIR_BLOCKS"))
+        o.pair_blocks = atoi(v) != 0;
+    if (const char *v = getenv("SMART_TIME_SLICES"))
+        o.time_slices = atoi(v) <= 0 ? 1 : atoi(v);
+    if (const char *v = getenv("SMART_ILLCOND_FORM"))
+        o.illcond_form = !strcmp(v, "rows")    ? SMART_LITERAL_FORM_ROWS
+                         : !strcmp(v, "lanes") ? SMART_LITERAL_FORM_LANES
+                                               : SMART_LITERAL_FORM_AUTO;
+    if (const char *v = getenv("SMART_EXITS"))
+        o.exits = atoi(v) != 0;
+    if (const char *v = getenv("SMART_DEBUG_MAX_POLLS"))
+        o.max_polls = atol(v) > 0 ? atol(v) : kDefaultMaxPolls;
+    if (const char *v = getenv("SMART_DEBUG_DROP_SLICE"))
+        o.drop_slice = atoi(v);
+    if (const char *v = getenv("SMART_ALLSTEPS_MATH"))
+        o.allsteps_fast = !strcmp(v, "fast");
+    return o;
 }
 
-static const char *const kFastKernelNames[kNumFastKernels] = {
-    "smart_fast_intervals_exits", "smart_fast_intervals", "smart_fast_intervals_states", "smart_fast_steps",
-    "smart_fast_steps_states", "smart_fast_plain", "smart_fast_stiff", "smart_fast_guard", "smart_fast_illcond",
-    "smart_fast_runs_exits", "smart_fast_runs", "smart_fast_runs_states", "smart_fast_steps_raw",
-    "smart_fast_intervals_raw", "smart_fast_steps_every", "smart_fast_illcond_lanes"};
+// ---- the fast kernels, by FastKernel: everything here follows from the list in smart_fast_entry.h
+struct FastKernelInfo {
+    const void *handle; // host stub (hipLaunchKernel, the occupancy query)
+    const char *name;   // the symbol, as smart_describe_launch prints it
+    int cls;            // arithmetic class of the rows it takes
+    bool sliced;        // one of a family of time-sliced kernels
+    int waves;          // workgroups per block of 64 samples
+};
+
+static const FastKernelInfo kFastKernels[kNumFastKernels] = {
+#define X(id, symbol, cls, sliced, waves) {reinterpret_cast<const void *>(&symbol), #symbol, cls, sliced, waves},
+    SMART_FAST_KERNELS(X)
+#undef X
+};
 
 // dynamic LDS that lets exactly `per_cu` workgroups of kernel k be resident on a CU (0: no such size); d->mu held
 static size_t lds_for_residency(DeviceCtx *d, FastKernel k, int per_cu)
@@ -207,7 +239,7 @@ static size_t lds_for_residency(DeviceCtx *d, FastKernel k, int per_cu)
         for (size_t x = (size_t)(160 * 1024 / per_cu) / 256 * 256;
              x >= 1024 && x > (size_t)(160 * 1024 / (per_cu + 1)) - 2048; x -= 256) {
             int nb = 0;
-            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, fast_kernel(k), kWave, x) != hipSuccess)
+            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kFastKernels[k].handle, kWave, x) != hipSuccess)
                 break;
             if (nb == per_cu) {
                 found = x;
@@ -222,29 +254,7 @@ static size_t lds_for_residency(DeviceCtx *d, FastKernel k, int per_cu)
     return d->lds_size[k][per_cu];
 }
 
-// ---- workspace layout: header | [C][8 + R] observation statistics (if objfn) | time-slice hand-over | slice flags |
-// code words of the pair blocks (fast summary / raw runs over whole intervals of a multiple of eight steps)
-static size_t header_bytes(int64_t n_catchments)
-{
-    return ((size_t)(kHdrInts + n_catchments) * sizeof(int) + 255) / 256 * 256;
-}
-
-static size_t obs_stats_bytes(const SmartEnsemble *e)
-{
-    if (!e->objfn)
-        return 0;
-    const int64_t R = smart_n_reports(e->n_steps, e->report_gap, e->report_type);
-    return (size_t)e->n_catchments * (size_t)(kWsHead + R) * sizeof(double);
-}
-
-static size_t slice_bytes(int64_t n_samples, int64_t n_catchments)
-{
-    const size_t blocks = (size_t)((n_samples + kWave - 1) / kWave) * (size_t)n_catchments;
-    return blocks * kSegFields * kWave * sizeof(double) + (blocks + 1) / 2 * 2 * sizeof(int);
-}
-
 static int merged_report(const SmartEnsemble *e);
-static int plan_time_slices(const SmartEnsemble *e, int n_simd, int *per_simd, double *load);
 
 // The streaming step loops jump through byte offsets that another kernel wrote (smart_fast_arms.h: pair blocks): right for
 // a library whose code smartpy_amd.isa_lint has looked at.  smartpy_amd.build lints every library it links and, when the
@@ -255,26 +265,15 @@ static int plan_time_slices(const SmartEnsemble *e, int n_simd, int *per_simd, d
 // for the threaded chunks whatever the stamp (A/B runs of the tools).
 extern "C" __attribute__((used, visibility("default"))) volatile char smart_lint_stamp[40] = "SMART_LINT_STAMP=unchecked";
 
-static bool pair_blocks_wanted()
+static bool pair_blocks_wanted(const Overrides &ov)
 {
-    if (const char *env = getenv("SMART_PAIR_BLOCKS"))
-        return atoi(env) != 0;
+    if (ov.pair_blocks >= 0)
+        return ov.pair_blocks != 0;
     static const char ok[] = "SMART_LINT_STAMP=pairs-ok";
     for (size_t i = 0; i + 1 < sizeof(ok); ++i)
         if (smart_lint_stamp[i] != ok[i])
             return false;
     return true;
-}
-
-// what a sliced launch of this call needs for its hand-over (0: the call is not sliced, or no device to ask)
-static size_t slices_need(const SmartEnsemble *e)
-{
-    if (e->math_mode != SMART_MATH_FAST)
-        return 0;
-    int per_simd = 0, n_dev = 0;
-    double load = 0.0;
-    DeviceCtx *d = hipGetDeviceCount(&n_dev) == hipSuccess && n_dev > 0 ? device_ctx() : nullptr;
-    return d && plan_time_slices(e, d->n_simd, &per_simd, &load) > 1 ? slice_bytes(e->n_samples, e->n_catchments) : 0;
 }
 
 // the stream of records (rain, PE, observation, deviation per step) instead of the pair blocks' code words: a report every
@@ -285,19 +284,58 @@ static bool uses_records(const SmartEnsemble *e)
     return merged == kReportEvery || ((merged == kReportMean || merged == kReportLast) && e->report_gap % kChunk != 0);
 }
 
-// the code words of the pair blocks: for the calls whose regular rows may take the streaming step loop; for a report every
-// step (gap 1, where there are no pair blocks of that kind) the stream of records and its code words instead
-static size_t codes_bytes(const SmartEnsemble *e)
+// ---- where things lie in the caller's workspace: offset and size in bytes of every part, in their order
+struct Layout {
+    size_t header = 0; // at 0: kHdrInts ints (HdrInt, smart_device.h) and the forcing flags [C], rounded up to 256 bytes
+    size_t stats_off = 0, stats = 0;   // observation statistics [C][kWsHead + R]; nothing without objfn
+    size_t state_off = 0, state = 0;   // hand-over of a sliced launch [blocks][kSegFields][64] doubles; nothing unsliced
+    size_t flags_off = 0, flags = 0;   // its slice flags [blocks] ints, padded to 8 bytes
+    size_t codes_off = 0, codes = 0;   // code words of the pair blocks [C][code_chunks(T)] uint2 (fast summary / raw runs
+                                       // over whole intervals of whole chunks) -- or, for a report every step and gaps that
+                                       // are not whole chunks, the records [C][every_pairs(T)][8] doubles and at
+    size_t ecodes_off = 0;             // ... ecodes_off their code words [C][every_pairs(T)]; rounded up to 256 bytes
+    size_t total = 0;                  // what smart_workspace_bytes asks for (0: the sizes of the call make no sense)
+    size_t handover() const { return state + flags; }
+};
+
+static bool sizes_make_sense(const SmartEnsemble *e)
 {
-    if (e->math_mode == SMART_MATH_FAST && uses_records(e))
-        return ((size_t)e->n_catchments * (size_t)every_pairs(e->n_steps) * (8 * sizeof(double) + sizeof(unsigned)) + 255) /
-               256 * 256;
-    if (e->math_mode != SMART_MATH_FAST || e->report_gap % kChunk != 0)
-        return 0;
+    return e->n_catchments >= 1 && e->n_samples >= 1 && e->n_steps >= 0 && e->report_gap >= 1;
+}
+
+// `sliced`: a device says the call is time-sliced (device_says_sliced; without a device to ask: no)
+static Layout layout(const SmartEnsemble *e, bool sliced)
+{
+    Layout l;
+    const size_t C = (size_t)(e->n_catchments < 1 ? 1 : e->n_catchments);
+    l.header = ((size_t)kHdrInts + C) * sizeof(int);
+    l.header = (l.header + 255) / 256 * 256;
+    if (!sizes_make_sense(e))
+        return l;
+    l.stats_off = l.header;
+    if (e->objfn)
+        l.stats = C * (size_t)(kWsHead + smart_n_reports(e->n_steps, e->report_gap, e->report_type)) * sizeof(double);
+    l.state_off = l.stats_off + l.stats;
+    const size_t blocks = (size_t)((e->n_samples + kWave - 1) / kWave) * C;
+    if (sliced) {
+        l.state = blocks * kSegFields * kWave * sizeof(double);
+        l.flags = (blocks + 1) / 2 * 2 * sizeof(int);
+    }
+    l.flags_off = l.state_off + l.state;
+    l.codes_off = l.ecodes_off = l.flags_off + l.flags; // (behind the hand-over; 8-byte aligned like it)
     const int merged = merged_report(e);
-    if (merged != kReportMean && merged != kReportLast)
-        return 0;
-    return ((size_t)e->n_catchments * (size_t)code_chunks(e->n_steps) * sizeof(uint2) + 255) / 256 * 256;
+    if (e->math_mode != SMART_MATH_FAST) {
+        // (the literal kernels read neither)
+    } else if (uses_records(e)) {
+        const size_t records = C * (size_t)every_pairs(e->n_steps) * 8 * sizeof(double);
+        l.ecodes_off = l.codes_off + records;
+        l.codes = records + C * (size_t)every_pairs(e->n_steps) * sizeof(unsigned);
+    } else if (merged == kReportMean || merged == kReportLast) { // (gaps of whole chunks: the others use records)
+        l.codes = C * (size_t)code_chunks(e->n_steps) * sizeof(uint2);
+    }
+    l.codes = (l.codes + 255) / 256 * 256;
+    l.total = l.codes_off + l.codes;
+    return l;
 }
 
 static int check(const SmartEnsemble *e)
@@ -332,9 +370,9 @@ static int check(const SmartEnsemble *e)
         return fail(SMART_E_SIZE, "discharge_ld must be >= n_samples");
     if (e->objfn && (!e->obs || !e->workspace))
         return fail(SMART_E_NULL, "objfn needs obs and workspace");
-    if (e->objfn && e->workspace_bytes < (int64_t)(header_bytes(e->n_catchments) + obs_stats_bytes(e)))
+    if (e->objfn && e->workspace_bytes < (int64_t)layout(e, false).state_off)
         return fail(SMART_E_SIZE, "workspace_bytes %lld is less than the %lld the header and the observation statistics need",
-                    (long long)e->workspace_bytes, (long long)(header_bytes(e->n_catchments) + obs_stats_bytes(e)));
+                    (long long)e->workspace_bytes, (long long)layout(e, false).state_off);
     if (e->time_slices < 0)
         return fail(SMART_E_SIZE, "time_slices must be >= 0");
     if (e->plan != 0 && !(e->plan & SMART_PLAN_VALID))
@@ -381,7 +419,7 @@ static int merged_report(const SmartEnsemble *e)
 // (measured -14 % at 1e5 samples, -33 % at 1.4e5, -17 % at 4e5; tools/debug/time_slices_sweep.py).  At or below one
 // block per SIMD there is nothing to even out and the hand-over costs 10 %.  e->time_slices (or, for the tuning
 // scripts under tools/, SMART_TIME_SLICES when that field is 0) overrides.
-static int plan_time_slices(const SmartEnsemble *e, int n_simd, int *per_simd, double *load)
+static int plan_time_slices(const SmartEnsemble *e, int n_simd, const Overrides &ov, int *per_simd, double *load)
 {
     const long blocks = (e->n_samples + kWave - 1) / kWave * e->n_catchments;
     const long cap = (blocks + n_simd - 1) / n_simd;
@@ -390,12 +428,7 @@ static int plan_time_slices(const SmartEnsemble *e, int n_simd, int *per_simd, d
     if (merged_report(e) < 0)
         return 1;
     const long n_all = e->n_warm / e->report_gap + e->n_steps / e->report_gap;
-    int forced = e->time_slices;
-    if (forced == 0) {
-        const char *env = getenv("SMART_TIME_SLICES");
-        if (env)
-            forced = atoi(env) <= 0 ? 1 : atoi(env);
-    }
+    const int forced = e->time_slices ? e->time_slices : ov.time_slices;
     if (forced == 1 || n_all < 64)
         return 1;
     if (forced > 1)
@@ -413,34 +446,44 @@ static int plan_time_slices(const SmartEnsemble *e, int n_simd, int *per_simd, d
     return (int)(n_all / 64 < want ? n_all / 64 : want);
 }
 
-// the pieces of e->workspace
+// does a device say that this call is time-sliced?  (no for the literal mode, and without a device to ask)
+static bool device_says_sliced(const SmartEnsemble *e, const Overrides &ov)
+{
+    if (e->math_mode != SMART_MATH_FAST || !sizes_make_sense(e))
+        return false;
+    int per_simd = 0, n_dev = 0;
+    double load = 0.0;
+    DeviceCtx *d = hipGetDeviceCount(&n_dev) == hipSuccess && n_dev > 0 ? device_ctx() : nullptr;
+    return d && plan_time_slices(e, d->n_simd, ov, &per_simd, &load) > 1;
+}
+
+// the pieces of e->workspace that the caller's bytes have room for, by the layout of this call (null: no room, no such part)
 struct Workspace {
+    Layout lay;
     int *hdr = nullptr, *fflags = nullptr;
     double *stats = nullptr;
-    char *slices = nullptr;
-    size_t slice_room = 0;
-    uint2 *codes = nullptr; // behind the hand-over, when the workspace has the room smart_workspace_bytes() asks for
+    char *state = nullptr; // hand-over of a sliced launch, its slice flags behind it; null means a plain launch
+    char *codes = nullptr; // code words or records
 };
 
-static Workspace carve(const SmartEnsemble *e)
+static Workspace carve(const SmartEnsemble *e, const Overrides &ov)
 {
     Workspace w;
-    const size_t hb = header_bytes(e->n_catchments), sb = obs_stats_bytes(e);
-    if (!e->workspace || e->workspace_bytes < (int64_t)hb)
+    const Layout &l = w.lay = layout(e, device_says_sliced(e, ov));
+    const size_t bytes = e->workspace && e->workspace_bytes > 0 ? (size_t)e->workspace_bytes : 0;
+    if (bytes < l.header)
         return w;
     char *base = (char *)e->workspace;
     w.hdr = (int *)base;
     w.fflags = w.hdr + kHdrInts;
-    if ((size_t)e->workspace_bytes >= hb + sb) {
-        w.stats = sb ? (double *)(base + hb) : nullptr;
-        w.slices = base + hb + sb;
-        w.slice_room = (size_t)e->workspace_bytes - hb - sb;
-        const size_t cb = codes_bytes(e), sl = slices_need(e);
-        if (cb && w.slice_room >= sl + cb) { // (behind the hand-over of a sliced launch; 8-byte aligned like it)
-            w.codes = (uint2 *)(w.slices + sl);
-            w.slice_room = sl;
-        }
-    }
+    if (l.stats && bytes >= l.state_off)
+        w.stats = (double *)(base + l.stats_off);
+    if (l.handover() && bytes >= l.codes_off)
+        w.state = base + l.state_off;
+    // the code words go behind the hand-over only when there is room for both; a workspace that ends before them still
+    // serves a sliced launch, which then runs its threaded chunks
+    if (l.codes && bytes >= l.total)
+        w.codes = base + l.codes_off;
     return w;
 }
 
@@ -499,51 +542,46 @@ static void reset_workspace(const Workspace &w, long n_catch, int *flags, long n
                        n_flags);
 }
 
-// which of the two uses of Workspace::codes this call makes (codes_bytes)
-static void set_codes(const SmartEnsemble *e, KArgs *a, const Workspace &w)
+// which of the two uses of Workspace::codes this call makes (Layout)
+static void set_codes(KArgs *a, const Workspace &w, const Overrides &ov)
 {
     a->codes = nullptr, a->estream = nullptr, a->ecodes = nullptr;
-    if (!w.codes || !pair_blocks_wanted())
+    if (!w.codes || !pair_blocks_wanted(ov))
         return;
-    if (uses_records(e)) {
+    if (w.lay.ecodes_off != w.lay.codes_off) { // (uses_records)
         a->estream = (const double *)w.codes;
-        a->ecodes = (const unsigned *)(a->estream + (size_t)e->n_catchments * (size_t)every_pairs(e->n_steps) * 8);
+        a->ecodes = (const unsigned *)(w.codes + (w.lay.ecodes_off - w.lay.codes_off));
     } else {
-        a->codes = w.codes;
+        a->codes = (const uint2 *)w.codes;
     }
 }
 
-static void scan_forcing(const SmartEnsemble *e, KArgs a, const Workspace &w, hipStream_t s)
+static void scan_forcing(const SmartEnsemble *e, KArgs a, const Workspace &w, const Overrides &ov, hipStream_t s)
 {
     a.fflags = w.fflags;
-    set_codes(e, &a, w);
+    set_codes(&a, w, ov);
     hipLaunchKernelGGL(smart_forcing_scan, dim3(64, (unsigned)e->n_catchments), dim3(256), 0, s, a,
                        reinterpret_cast<const double2 *>(e->forcing));
 }
-
-struct Launch {
-    FastKernel k;
-    bool sliced;
-};
 
 static hipError_t launch_kernel(FastKernel k, KArgs a, dim3 grid, size_t lds, hipStream_t s)
 {
     const double2 *forcing = reinterpret_cast<const double2 *>(a.forcing);
     const double *obs = a.obs, *ws = a.ws;
     void *args[] = {&a, &forcing, &obs, &ws};
-    return hipLaunchKernel(fast_kernel(k), grid, dim3(kWave), args, lds, s);
+    return hipLaunchKernel(kFastKernels[k].handle, grid, dim3(kWave), args, lds, s);
 }
 
 // What a SMART_MATH_FAST call launches: the kernels (smart_fast_entry.h), sliced or not, and the load figures behind
 // the choices.  Shared by the launch itself and by smart_describe_launch.
 struct Decision {
-    Launch todo[kMaxTodo];
+    FastKernel todo[kMaxTodo];
     int n_todo = 0;
     bool overflow = false;
-    void push(FastKernel k, bool sliced)
+    void push(FastKernel k)
     {
         if (n_todo < kMaxTodo)
-            todo[n_todo++] = {k, sliced};
+            todo[n_todo++] = k;
         else
             overflow = true;
     }
@@ -578,32 +616,25 @@ static long count_illcond_blocks(const SmartEnsemble *e, int plan)
     return counted > 0 && counted < SMART_PLAN_ILLCOND_BLOCKS_MAX ? counted : all;
 }
 
-static bool illcond_form(const SmartEnsemble *e, int n_simd, long blocks)
+static bool illcond_form(const SmartEnsemble *e, int n_simd, long blocks, const Overrides &ov)
 {
-    if (e->literal_form == SMART_LITERAL_FORM_ROWS)
-        return true;
-    if (e->literal_form == SMART_LITERAL_FORM_LANES)
-        return false;
-    if (const char *env = getenv("SMART_ILLCOND_FORM")) {
-        if (!strcmp(env, "rows"))
-            return true;
-        if (!strcmp(env, "lanes"))
-            return false;
-    }
+    const int form = e->literal_form != SMART_LITERAL_FORM_AUTO ? e->literal_form : ov.illcond_form;
+    if (form != SMART_LITERAL_FORM_AUTO)
+        return form == SMART_LITERAL_FORM_ROWS;
     const long all = (long)((e->n_samples + kWave - 1) / kWave * e->n_catchments);
     return blocks * kIllCondWaves + (all - blocks) <= (long)kIllCondRowRounds * n_simd;
 }
 
-static int decide(const SmartEnsemble *e, const DeviceCtx *d, const Workspace &w, Decision *out)
+static int decide(const SmartEnsemble *e, const DeviceCtx *d, const Workspace &w, const Overrides &ov, Decision *out)
 {
     Decision &x = *out;
     x.report = merged_report(e);
     x.intervals = x.report == kReportMean; // the merged summary kernels apply
     const int plan = (e->plan & SMART_PLAN_VALID) ? e->plan : (0x3f | SMART_PLAN_FORCING_RUNS);
-    x.n_seg = plan_time_slices(e, d->n_simd, &x.per_simd, &x.load);
+    x.n_seg = plan_time_slices(e, d->n_simd, ov, &x.per_simd, &x.load);
     // the hand-over buffer of a time-sliced launch sits behind the observation statistics in the caller's workspace;
     // a workspace without room for it means a plain launch
-    if (x.n_seg > 1 && (!w.slices || w.slice_room < slice_bytes(e->n_samples, e->n_catchments)))
+    if (x.n_seg > 1 && !w.state)
         x.n_seg = 1;
     // Early exits inside every step of the interval engine (FastModel::kExits) cost a wavefront a taken branch where
     // they trigger; the straight-line kernels run their wet intervals as two kinds of step instead (SMART_A_WET_INTERVAL:
@@ -611,47 +642,46 @@ static int decide(const SmartEnsemble *e, const DeviceCtx *d, const Workspace &w
     // work and branches hide behind each other's vector work -- by 1.5 to 2.5 % from 3 blocks per SIMD on (3.05,
     // 4.6, 15: config 4 on one GPU, config 5), level at 2.44, and lose 6 % at 1.9 and 1.53; rows ordered or not
     // (tools/gpu_r03_l.sh, gpu_r03_n.sh: profiles/r03_ab_exits_modes.txt).
-    const char *env = getenv("SMART_EXITS");
-    x.exits = env ? atoi(env) != 0 : x.load > 2.5;
+    x.exits = ov.exits >= 0 ? ov.exits : x.load > 2.5;
     x.class_mask = plan & 0xf;
     if (plan & SMART_PLAN_CLASS_REGULAR) {
         if (x.intervals) {
             if (plan & SMART_PLAN_FORCING_PIECEWISE) {
-                x.push(e->final_vars ? kIntervalsStates : (x.exits ? kIntervalsExits : kIntervals), true);
-                x.pc_mask |= 1;
+                x.push(e->final_vars ? kIntervalsStates : (x.exits ? kIntervalsExits : kIntervals));
+                x.pc_mask |= kPcIntervals;
             }
             if (plan & SMART_PLAN_FORCING_RUNS) {
-                x.push(e->final_vars ? kRunsStates : (x.exits ? kRunsExits : kRuns), true);
-                x.pc_mask |= 4;
+                x.push(e->final_vars ? kRunsStates : (x.exits ? kRunsExits : kRuns));
+                x.pc_mask |= kPcRuns;
             }
             if (plan & SMART_PLAN_FORCING_VARYING) {
-                x.push(e->final_vars ? kStepsStates : kSteps, true);
-                x.pc_mask |= 2;
+                x.push(e->final_vars ? kStepsStates : kSteps);
+                x.pc_mask |= kPcSteps;
             }
         } else if (x.report == kReportLast) {
             if (plan & SMART_PLAN_FORCING_PIECEWISE) {
-                x.push(kIntervalsRaw, true);
-                x.pc_mask |= 1;
+                x.push(kIntervalsRaw);
+                x.pc_mask |= kPcIntervals;
             }
-            if (plan & (SMART_PLAN_FORCING_RUNS | SMART_PLAN_FORCING_VARYING)) {
-                x.push(kStepsRaw, true);
-                x.pc_mask |= 6;
+            if (plan & (SMART_PLAN_FORCING_RUNS | SMART_PLAN_FORCING_VARYING)) { // (no run engine for raw reports)
+                x.push(kStepsRaw);
+                x.pc_mask |= kPcSteps | kPcRuns;
             }
-        } else if (x.report == kReportEvery) {
-            x.push(kStepsEvery, true);
-            x.pc_mask = 7;
+        } else if (x.report == kReportEvery) { // (one kernel whatever the forcing)
+            x.push(kStepsEvery);
+            x.pc_mask = kPcIntervals | kPcSteps | kPcRuns;
         } else {
-            x.push(kPlain, false);
+            x.push(kPlain);
         }
     }
     if (plan & SMART_PLAN_CLASS_STIFF)
-        x.push(kStiff, false);
+        x.push(kStiff);
     if (plan & SMART_PLAN_CLASS_GUARD)
-        x.push(kGuard, false);
+        x.push(kGuard);
     if (plan & SMART_PLAN_CLASS_ILLCOND) {
         x.illcond_blocks = count_illcond_blocks(e, plan);
-        x.illcond_rows = illcond_form(e, d->n_simd, x.illcond_blocks);
-        x.push(x.illcond_rows ? kIllCond : kIllCondLanes, false);
+        x.illcond_rows = illcond_form(e, d->n_simd, x.illcond_blocks, ov);
+        x.push(x.illcond_rows ? kIllCond : kIllCondLanes);
     }
     if (x.overflow)
         return fail(SMART_E_SIZE, "internal: a call wants more than %d kernels", kMaxTodo);
@@ -660,7 +690,7 @@ static int decide(const SmartEnsemble *e, const DeviceCtx *d, const Workspace &w
     return SMART_OK;
 }
 
-static int run(const SmartEnsemble *e, bool literal_rows = false)
+static int run(const SmartEnsemble *e, const Overrides &ov, bool literal_rows = false)
 {
     int rc = check(e);
     if (rc)
@@ -668,7 +698,7 @@ static int run(const SmartEnsemble *e, bool literal_rows = false)
     if ((rc = device_ready()))
         return rc;
     hipStream_t s = (hipStream_t)e->stream;
-    const Workspace w = carve(e);
+    const Workspace w = carve(e, ov);
     KArgs a = kernel_args(e, w);
 
     if (e->objfn)
@@ -688,7 +718,7 @@ static int run(const SmartEnsemble *e, bool literal_rows = false)
     if (!d)
         return fail(SMART_E_NO_DEVICE, "cannot query the current HIP device");
     Decision x;
-    if ((rc = decide(e, d, w, &x)))
+    if ((rc = decide(e, d, w, ov, &x)))
         return rc;
     const int n_seg = x.n_seg, n_todo = x.n_todo;
     a.exits = x.exits;
@@ -699,35 +729,34 @@ static int run(const SmartEnsemble *e, bool literal_rows = false)
     KArgs a_sliced = a;
     if (n_seg > 1) {
         a_sliced.n_seg = n_seg;
-        a_sliced.seg_state = (double *)w.slices;
-        a_sliced.seg_flag = (int *)(w.slices + (size_t)a.seg_blocks * kSegFields * kWave * sizeof(double));
-        const char *mp = getenv("SMART_DEBUG_MAX_POLLS"), *dd = getenv("SMART_DEBUG_DROP_SLICE"); // tests only
-        a_sliced.max_polls = mp && atol(mp) > 0 ? atol(mp) : kDefaultMaxPolls;
-        a_sliced.debug_drop = dd ? atoi(dd) : 0;
+        a_sliced.seg_state = (double *)w.state;
+        a_sliced.seg_flag = (int *)(w.state + (w.lay.flags_off - w.lay.state_off));
+        a_sliced.max_polls = ov.max_polls;
+        a_sliced.debug_drop = ov.drop_slice;
     }
     if (w.hdr) {
         reset_workspace(w, e->n_catchments, a_sliced.seg_flag, n_seg > 1 ? a.seg_blocks : 0, s);
         // every fast launch looks at its forcing (the merged kernels for what the flags say about runs of equal
         // values; all of them for the NaN that belongs to the literal kernel: status word)
-        scan_forcing(e, a, w, s);
+        scan_forcing(e, a, w, ov, s);
         if (x.report >= 0 && (x.class_mask & SMART_PLAN_CLASS_REGULAR)) {
             a.fflags = a_sliced.fflags = w.fflags;
-            set_codes(e, &a, w);
+            set_codes(&a, w, ov);
             a_sliced.codes = a.codes, a_sliced.estream = a.estream, a_sliced.ecodes = a.ecodes;
         }
     }
 
     // ---- launch: one kernel on the caller's stream; several fork onto the device's auxiliary streams and join
     std::lock_guard<std::mutex> lock(d->mu);
-    auto launch = [&](const Launch &l, hipStream_t st) -> hipError_t {
-        if (l.sliced && n_seg > 1) {
+    auto launch = [&](FastKernel k, hipStream_t st) -> hipError_t {
+        if (kFastKernels[k].sliced && n_seg > 1) {
             // dynamic LDS is requested only to cap the resident workgroups at `per_simd` per SIMD (working + waiting;
             // beyond 3 the register file is the limit anyway)
-            const size_t lds = x.per_simd <= 3 ? lds_for_residency(d, l.k, 4 * x.per_simd) : 0;
-            return launch_kernel(l.k, a_sliced, dim3((unsigned)(a.seg_blocks * n_seg), 1), lds, st);
+            const size_t lds = x.per_simd <= 3 ? lds_for_residency(d, k, 4 * x.per_simd) : 0;
+            return launch_kernel(k, a_sliced, dim3((unsigned)(a.seg_blocks * n_seg), 1), lds, st);
         }
-        // (the ill-conditioned rows: one sample per DPP row, sixteen workgroups per block of 64 samples)
-        return launch_kernel(l.k, a, l.k == kIllCond ? dim3(grid.x * kIllCondWaves, grid.y) : grid, 0, st);
+        // (one sample per DPP row: sixteen workgroups per block of 64 samples)
+        return launch_kernel(k, a, dim3(grid.x * kFastKernels[k].waves, grid.y), 0, st);
     };
     if (n_todo == 1) {
         HIP_TRY(launch(x.todo[0], s));
@@ -752,7 +781,7 @@ static int run(const SmartEnsemble *e, bool literal_rows = false)
     return SMART_OK;
 }
 
-static int describe(const SmartEnsemble *e, char *text, int64_t len)
+static int describe(const SmartEnsemble *e, const Overrides &ov, char *text, int64_t len)
 {
     if (!text || len < 1)
         return fail(SMART_E_NULL, "smart_describe_launch: no room for the text");
@@ -770,23 +799,24 @@ static int describe(const SmartEnsemble *e, char *text, int64_t len)
     if (!d)
         return fail(SMART_E_NO_DEVICE, "cannot query the current HIP device");
     Decision x;
-    if ((rc = decide(e, d, carve(e), &x)))
+    if ((rc = decide(e, d, carve(e, ov), ov, &x)))
         return rc;
     const long blocks = (e->n_samples + kWave - 1) / kWave * e->n_catchments;
     size_t used = 0;
     for (int i = 0; i < x.n_todo && used + 1 < (size_t)len; ++i) {
+        const FastKernelInfo &k = kFastKernels[x.todo[i]];
+        char *at = text + used;
+        const size_t room = (size_t)len - used;
         int n;
-        if (x.todo[i].sliced && x.n_seg > 1)
-            n = snprintf(text + used, (size_t)len - used, "%s%s[%d slices x %ld blocks, %d resident per SIMD]",
-                         i ? " + " : "", kFastKernelNames[x.todo[i].k], x.n_seg, blocks, x.per_simd);
-        else if (x.todo[i].k == kIllCond || x.todo[i].k == kIllCondLanes)
+        if (k.sliced && x.n_seg > 1)
+            n = snprintf(at, room, "%s%s[%d slices x %ld blocks, %d resident per SIMD]", i ? " + " : "", k.name, x.n_seg,
+                         blocks, x.per_simd);
+        else if (k.cls == 3)
             // (the class-3 blocks the form was chosen for: the plan's count, or every block where there is none)
-            n = snprintf(text + used, (size_t)len - used, "%s%s[%ld of %ld blocks, one sample per %s]", i ? " + " : "",
-                         kFastKernelNames[x.todo[i].k], x.illcond_blocks, blocks,
-                         x.illcond_rows ? "DPP row x 16 wavefronts" : "lane");
+            n = snprintf(at, room, "%s%s[%ld of %ld blocks, one sample per %s]", i ? " + " : "", k.name, x.illcond_blocks,
+                         blocks, k.waves > 1 ? "DPP row x 16 wavefronts" : "lane");
         else
-            n = snprintf(text + used, (size_t)len - used, "%s%s[%ld blocks]", i ? " + " : "",
-                         kFastKernelNames[x.todo[i].k], blocks);
+            n = snprintf(at, room, "%s%s[%ld blocks]", i ? " + " : "", k.name, blocks);
         if (n < 0)
             break;
         used += (size_t)n;
@@ -794,14 +824,12 @@ static int describe(const SmartEnsemble *e, char *text, int64_t len)
     return SMART_OK;
 }
 
-static int64_t workspace_bytes(const SmartEnsemble *e)
+static int64_t workspace_bytes(const SmartEnsemble *e, const Overrides &ov)
 {
-    if (!e || e->n_catchments < 1 || e->n_samples < 1 || e->n_steps < 0 || e->report_gap < 1)
-        return 0;
-    return (int64_t)(header_bytes(e->n_catchments) + obs_stats_bytes(e) + slices_need(e) + codes_bytes(e));
+    return e ? (int64_t)layout(e, device_says_sliced(e, ov)).total : 0;
 }
 
-static int make_plan(const SmartEnsemble *e, int32_t *plan)
+static int make_plan(const SmartEnsemble *e, const Overrides &ov, int32_t *plan)
 {
     if (!plan)
         return fail(SMART_E_NULL, "smart_plan_ensemble: plan is NULL");
@@ -811,7 +839,7 @@ static int make_plan(const SmartEnsemble *e, int32_t *plan)
         return rc;
     if ((rc = device_ready()))
         return rc;
-    const Workspace w = carve(e);
+    const Workspace w = carve(e, ov);
     if (!w.hdr)
         return fail(SMART_E_NULL, "smart_plan_ensemble needs a workspace of smart_workspace_bytes() bytes");
     hipStream_t s = (hipStream_t)e->stream;
@@ -819,7 +847,7 @@ static int make_plan(const SmartEnsemble *e, int32_t *plan)
     reset_workspace(w, e->n_catchments, nullptr, 0, s);
     hipLaunchKernelGGL(smart_classify_rows, dim3((unsigned)a.n_blocks, (unsigned)e->n_catchments), dim3(kWave), 0, s, a);
     if (merged_report(e) == kReportMean || merged_report(e) == kReportLast) {
-        scan_forcing(e, a, w, s);
+        scan_forcing(e, a, w, ov, s);
         a.fflags = w.fflags;
         hipLaunchKernelGGL(smart_classify_forcing, dim3((unsigned)((e->n_catchments + 255) / 256)), dim3(256), 0, s,
                            a, w.hdr);
@@ -840,7 +868,7 @@ static int launch_status(const SmartEnsemble *e, int32_t *status)
     if (!e || !status)
         return fail(SMART_E_NULL, "smart_launch_status: NULL argument");
     *status = 0;
-    if (!e->workspace || e->workspace_bytes < (int64_t)header_bytes(e->n_catchments < 1 ? 1 : e->n_catchments))
+    if (!e->workspace || e->workspace_bytes < (int64_t)layout(e, false).header)
         return SMART_OK;
     int rc = device_ready();
     if (rc)
@@ -884,7 +912,6 @@ struct HookCache {
 };
 static HookCache g_hook;
 static std::mutex g_hook_mu;
-constexpr size_t kHookHeaderDoubles = 64; // 512 bytes: the workspace header of a one-catchment call (status word)
 
 static int hook_reserve(double **buf, size_t *cap, size_t want)
 {
@@ -938,7 +965,7 @@ static int host_row_class(const double *p, double dt, const double *st12, double
     return wild ? 3 : (guard ? 2 : (stiff ? 1 : 0));
 }
 
-static int allsteps(double area_m2, double delta_sec, int64_t length_simu, const double *nd_rain,
+static int allsteps(const Overrides &ov, double area_m2, double delta_sec, int64_t length_simu, const double *nd_rain,
                     const double *nd_peva, const double *nd_parameters, const double *nd_initial, int32_t report_type,
                     int64_t report_gap, double *discharge, double *groundwater_component, double *final_vars)
 {
@@ -1000,33 +1027,12 @@ static int allsteps(double area_m2, double delta_sec, int64_t length_simu, const
         h.peva.insert(h.peva.end(), nd_peva + from, nd_peva + L);
     }
 
-    // ---- the small block: parameters, states, area in; discharge, ratio, final row out; a workspace header
-    // (SMART_ALLSTEPS_MATH=fast: room for what the fast launch wants beside the header -- the code words of the step loop)
-    const char *math = getenv("SMART_ALLSTEPS_MATH");
-    const bool fast = math && std::strcmp(math, "fast") == 0;
-    size_t ws_doubles = kHookHeaderDoubles;
-    if (fast) {
-        SmartEnsemble sized;
-        std::memset(&sized, 0, sizeof(sized));
-        sized.n_catchments = sized.n_samples = 1;
-        sized.n_steps = length_simu;
-        sized.report_gap = report_gap;
-        sized.report_type = report_type;
-        sized.math_mode = SMART_MATH_FAST;
-        sized.time_slices = 1;
-        sized.final_vars = (double *)1; // (asked for: decides which kernels, and with them what the workspace holds)
-        const size_t want = ((size_t)workspace_bytes(&sized) + 7) / 8;
-        ws_doubles = want > ws_doubles ? want : ws_doubles;
-    }
-    const size_t n_in = 10 + 12 + 1, n_out = n_rep + 1 + 19;
-    if ((rc = hook_reserve(&h.io, &h.io_cap, n_in + n_out + ws_doubles)))
-        return rc;
-    double in[n_in];
-    std::memcpy(in, nd_parameters, 10 * sizeof(double));
-    std::memcpy(in + 10, nd_initial + 7, 12 * sizeof(double)); // only the states are read (structure.py:182-187)
-    in[22] = area_m2;
-    HIP_TRY(hipMemcpy(h.io, in, n_in * sizeof(double), hipMemcpyHostToDevice));
-
+    // ---- the small block: parameters, states, area in; discharge, ratio, final row out; the workspace of the call (the
+    // header for its status word; SMART_ALLSTEPS_MATH=fast: also what the fast launch wants -- the code words of the step
+    // loop)
+    // SMART_ALLSTEPS_MATH=fast: the fast kernels for this one sample (interval engine / step loop, SPLIT: the final row is
+    // asked for) -- <= 1e-9 of the reference instead of its bits, at a tenth of the time.  Default: literal arithmetic.
+    const bool fast = ov.allsteps_fast;
     SmartEnsemble e;
     std::memset(&e, 0, sizeof(e));
     e.n_catchments = 1;
@@ -1036,6 +1042,19 @@ static int allsteps(double area_m2, double delta_sec, int64_t length_simu, const
     e.report_gap = report_gap;
     e.report_type = report_type;
     e.delta_sec = delta_sec;
+    e.time_slices = 1;
+    e.math_mode = fast ? SMART_MATH_FAST : SMART_MATH_LITERAL;
+    e.final_vars = (double *)1; // (asked for: decides which kernels, and with them what the workspace holds)
+    const size_t ws_doubles = (layout(&e, false).total + 7) / 8; // (time_slices = 1: never sliced)
+    const size_t n_in = 10 + 12 + 1, n_out = n_rep + 1 + 19;
+    if ((rc = hook_reserve(&h.io, &h.io_cap, n_in + n_out + ws_doubles)))
+        return rc;
+    double in[n_in];
+    std::memcpy(in, nd_parameters, 10 * sizeof(double));
+    std::memcpy(in + 10, nd_initial + 7, 12 * sizeof(double)); // only the states are read (structure.py:182-187)
+    in[22] = area_m2;
+    HIP_TRY(hipMemcpy(h.io, in, n_in * sizeof(double), hipMemcpyHostToDevice));
+
     e.forcing = h.forcing;
     e.params = h.io;
     e.initial = h.io + 10;
@@ -1047,10 +1066,6 @@ static int allsteps(double area_m2, double delta_sec, int64_t length_simu, const
     e.final_vars = e.gw + 1;
     e.workspace = o + n_out;
     e.workspace_bytes = (int64_t)(ws_doubles * sizeof(double));
-    e.time_slices = 1;
-    // SMART_ALLSTEPS_MATH=fast: the fast kernels for this one sample (interval engine / step loop, SPLIT: the final row is
-    // asked for) -- <= 1e-9 of the reference instead of its bits, at a tenth of the time.  Default: literal arithmetic.
-    e.math_mode = fast ? SMART_MATH_FAST : SMART_MATH_LITERAL;
     if (fast) {
         // ONE kernel for ONE row: the row's class worked out here (ten numbers), the kinds of forcing of this series
         // remembered from the first call with this (length, gap, report type).  Round 4 left e.plan at 0: six kernels,
@@ -1061,7 +1076,7 @@ static int allsteps(double area_m2, double delta_sec, int64_t length_simu, const
                 k = &x;
         if (!k) {
             int32_t plan = 0;
-            if ((rc = make_plan(&e, &plan)))
+            if ((rc = make_plan(&e, ov, &plan)))
                 return rc;
             ++h.n_plans;
             if (h.known.size() >= 8)
@@ -1078,7 +1093,7 @@ static int allsteps(double area_m2, double delta_sec, int64_t length_simu, const
             e.plan = SMART_PLAN_VALID | k->forcing_bits | (1 << cls);
         }
     }
-    rc = run(&e, /*rows=*/true);
+    rc = run(&e, ov, /*rows=*/true);
     if (rc == SMART_OK && e.math_mode == SMART_MATH_FAST) {
         ++h.n_fast;
         int32_t word = 0;
@@ -1089,7 +1104,7 @@ static int allsteps(double area_m2, double delta_sec, int64_t length_simu, const
                     if (x.len == length_simu && x.gap == report_gap && x.type == report_type)
                         x.literal_only = true;
             e.math_mode = SMART_MATH_LITERAL;
-            rc = run(&e, true);
+            rc = run(&e, ov, true);
         }
     }
     if (rc != SMART_OK)
@@ -1118,22 +1133,25 @@ int64_t smart_n_reports(int64_t n_steps, int64_t report_gap, int32_t report_type
 
 int smart_check_ensemble(const SmartEnsemble *e) { return check(e); }
 
-int64_t smart_workspace_bytes(const SmartEnsemble *e) { return workspace_bytes(e); }
+int64_t smart_workspace_bytes(const SmartEnsemble *e) { return workspace_bytes(e, read_overrides()); }
 
-int smart_run_ensemble_hip(const SmartEnsemble *e) { return run(e); }
+int smart_run_ensemble_hip(const SmartEnsemble *e) { return run(e, read_overrides()); }
 
-int smart_plan_ensemble(const SmartEnsemble *e, int32_t *plan) { return make_plan(e, plan); }
+int smart_plan_ensemble(const SmartEnsemble *e, int32_t *plan) { return make_plan(e, read_overrides(), plan); }
 
 int smart_launch_status(const SmartEnsemble *e, int32_t *status) { return launch_status(e, status); }
 
-int smart_describe_launch(const SmartEnsemble *e, char *text, int64_t len) { return describe(e, text, len); }
+int smart_describe_launch(const SmartEnsemble *e, char *text, int64_t len)
+{
+    return describe(e, read_overrides(), text, len);
+}
 
 int smart_allsteps_hip(double area_m2, double delta_sec, int64_t length_simu, const double *nd_rain,
                        const double *nd_peva, const double *nd_parameters, const double *nd_initial,
                        int32_t report_type, int64_t report_gap, double *discharge, double *groundwater_component,
                        double *final_vars)
 {
-    return allsteps(area_m2, delta_sec, length_simu, nd_rain, nd_peva, nd_parameters, nd_initial, report_type,
+    return allsteps(read_overrides(), area_m2, delta_sec, length_simu, nd_rain, nd_peva, nd_parameters, nd_initial, report_type,
                     report_gap, discharge, groundwater_component, final_vars);
 }
 

@@ -53,8 +53,8 @@ struct KArgs {
     // which kernels this call launches (include/smart_amd.h, SMART_PLAN_*): a workgroup that meets a block nobody will
     // run (a stale plan) leaves SMART_STATUS_STALE_PLAN in the status word instead of a silent hole in the outputs
     int class_mask = 0xf;     // bit c: the kernel of arithmetic class c (wave_class) has been launched
-    int pc_mask = 0x7;        // bit 0: the interval engine (forcing constant over each report interval), bit 1: the
-                              // step loop, bit 2: the run engine (constant over runs of k steps, k a divisor of the gap)
+    int pc_mask = 0x7;        // kPcIntervals: the interval engine (forcing constant over each report interval), kPcSteps:
+                              // the step loop, kPcRuns: the run engine (constant over runs of k steps, k a divisor of the gap)
     // workspace header (null without a workspace: no status word, no time slices, every wavefront scans the forcing)
     int *hdr = nullptr;       // [kHdrInts]: status word, ticket counters of the sliced kernels
     int *fflags = nullptr;    // [C]: forcing flags of catchment c (forcing_flags_of_step below), from smart_forcing_scan
@@ -80,9 +80,28 @@ struct KArgs {
     int debug_drop = 0;          // test knob: slice 0 of block 0 never publishes (its successors must time out)
 };
 
-constexpr int kSegFields = 23; // 0-14 model states (13, 14: SPLIT only), 15 pending demand, 16 sum of outflows, 17-22 moments
-constexpr int kHdrInts = 64;      // workspace header: [0] status word, [1 + k] ticket counter of sliced kernel k
-constexpr int kHdrStatus = 0, kHdrTicket = 1;
+// the fields of a block's hand-over between two time slices (KArgs::seg_state), 64 doubles each
+enum SegField : int {
+    kSegState = 0,    // 0-14: the model's states (save_state / load_state; 13 and 14 the SPLIT models' only)
+    kSegDenRaw = 13,  // raw reports (never a SPLIT model): the sum of inflows over the reported steps
+    kSegPend = 15,    // the step loops: evaporation demand not yet taken from the layers
+    kSegOutflows = 16, // sum of outflows (raw reports: of groundwater flows over the reported steps)
+    kSegA = 17,       // Reporter: A, B, C1, C2, C3, shift
+    kSegB,
+    kSegC1,
+    kSegC2,
+    kSegC3,
+    kSegShift,
+    kSegFields
+};
+// the ints of the workspace header, in front of the forcing flags [C]
+enum HdrInt : int {
+    kHdrStatus = 0,       // status word (SMART_STATUS_*)
+    kHdrTicket = 1,       // 1-7: ticket counter of sliced kernel family k at [kHdrTicket + k] (smart_fast_entry.h)
+    kHdrPlan = 8,         // smart_plan_ensemble: classes and kinds of forcing present ...
+    kHdrPlanIllCond = 9,  // ... and the number of class-3 blocks
+    kHdrInts = 64
+};
 constexpr int kStatusSliceTimeout = 1, kStatusStalePlan = 2, kStatusNonFiniteForcing = 4; // = SMART_STATUS_* of include/smart_amd.h
 
 __device__ __forceinline__ void raise_status(const KArgs &a, int bit)
@@ -602,6 +621,18 @@ struct Reporter {
         shift = 0.0;
     }
 
+    // one report with an observation: `e` the observation, `w` its deviation from the observation mean
+    __device__ __forceinline__ void add_moments(double val, double e, double w)
+    {
+        const double d = val - e;
+        const double u = val - shift;
+        A += d;
+        B += d * d;
+        C1 += u;
+        C2 += u * u;
+        C3 += w * u;
+    }
+
     __device__ __forceinline__ void emit(const KArgs &a, const LaneCtx &x, long r, double val)
     {
         if (a.discharge && x.live)
@@ -610,7 +641,8 @@ struct Reporter {
             const double e = obs[r];
             if (r == 0)
                 shift = val;
-            if (!is_nan_bits(e)) { // montecarlo.py:195-196
+            if (!is_nan_bits(e)) { // montecarlo.py:195-196 (add_moments() written out: through the method the code of
+                                   // smart_fast_stiff, _guard, _plain and smart_ensemble_literal comes out different)
                 const double d = val - e;
                 const double u = val - shift;
                 A += d;
@@ -647,15 +679,8 @@ struct Reporter {
             __builtin_nontemporal_store(val, &a.discharge[(x.c * a.R + r) * a.ld + x.n]);
         if (want_obj && r == 0)
             shift = val;
-        if (want_obj && !is_nan_bits(e)) { // montecarlo.py:195-196
-            const double d = val - e;
-            const double u = val - shift;
-            A += d;
-            B += d * d;
-            C1 += u;
-            C2 += u * u;
-            C3 += w * u;
-        }
+        if (want_obj && !is_nan_bits(e)) // montecarlo.py:195-196
+            add_moments(val, e, w);
     }
 
     // The streamed step loop (FastModel::stream_stretch) reports inside its asm (smart_fast_arms.h: SMART_P_REPORT) -- what
@@ -699,15 +724,8 @@ struct Reporter {
             // left to itself hipcc widens both sides and compares 64 bits, four scalar instructions for one
             unsigned hi = (unsigned)(__builtin_bit_cast(unsigned long long, w) >> 32);
             asm("" : "+s"(hi));
-            if (hi != (unsigned)(kMissingObs >> 32)) { // montecarlo.py:195-196
-                const double d = val - e;
-                const double u = val - shift;
-                A += d;
-                B += d * d;
-                C1 += u;
-                C2 += u * u;
-                C3 += w * u;
-            }
+            if (hi != (unsigned)(kMissingObs >> 32)) // montecarlo.py:195-196
+                add_moments(val, e, w);
         }
     }
 };
@@ -828,15 +846,8 @@ __device__ __forceinline__ void run_ensemble(const KArgs &a, const double2 *__re
                 if (obj) {
                     if constexpr (decltype(first)::value)
                         rep.shift = val;
-                    if (!is_missing_mark(w)) { // montecarlo.py:195-196
-                        const double d = val - e;
-                        const double u = val - rep.shift;
-                        rep.A += d;
-                        rep.B += d * d;
-                        rep.C1 += u;
-                        rep.C2 += u * u;
-                        rep.C3 += w * u;
-                    }
+                    if (!is_missing_mark(w)) // montecarlo.py:195-196
+                        rep.add_moments(val, e, w);
                 }
             };
             if (a.T > 0) {
@@ -1009,6 +1020,12 @@ __device__ __forceinline__ long run_length(const KArgs &a, int flags)
 
 // forcing kinds of the merged summary kernels
 constexpr int kForcingVarying = 0, kForcingIntervals = 1, kForcingRuns = 2;
+// ... and the bit of KArgs::pc_mask that says the kernel for a kind has been launched
+constexpr int kPcIntervals = 1, kPcSteps = 2, kPcRuns = 4;
+__host__ __device__ constexpr int pc_bit(int kind)
+{
+    return kind == kForcingIntervals ? kPcIntervals : (kind == kForcingVarying ? kPcSteps : kPcRuns);
+}
 
 __device__ __forceinline__ int forcing_kind(const KArgs &a, int flags)
 {
@@ -1236,6 +1253,7 @@ __device__ __forceinline__ void run_ensemble_merged(const KArgs &a, const double
     constexpr bool runs = FORCING == kForcingRuns;
     static_assert(REPORT == kReportMean || (!Model::kSplit && !runs), "raw / every-step reports: merged model, no runs");
     static_assert(REPORT != kReportEvery || !piecewise, "a report every step is a step loop");
+    static_assert(Model::kStateFields <= kSegPend, "the model's states end in front of the other hand-over fields");
     const LaneCtx x = lane_ctx(a, block, catchment);
     const long slot = catchment * a.n_blocks + block; // this block's place in seg_state / seg_flag
     Model m;
@@ -1367,17 +1385,17 @@ __device__ __forceinline__ void run_ensemble_merged(const KArgs &a, const double
         }
         m.load_state(hand, kWave);
         if constexpr (REPORT == kReportLast) {
-            num_raw = hand[16 * kWave];
-            den_raw = hand[13 * kWave]; // (fields 13, 14 carry the SPLIT models' extra states: free here)
+            num_raw = hand[kSegOutflows * kWave];
+            den_raw = hand[kSegDenRaw * kWave]; // (fields 13, 14 carry the SPLIT models' extra states: free here)
         } else {
-            q_out_total = hand[16 * kWave];
+            q_out_total = hand[kSegOutflows * kWave];
         }
-        rep.A = hand[17 * kWave];
-        rep.B = hand[18 * kWave];
-        rep.C1 = hand[19 * kWave];
-        rep.C2 = hand[20 * kWave];
-        rep.C3 = hand[21 * kWave];
-        rep.shift = hand[22 * kWave];
+        rep.A = hand[kSegA * kWave];
+        rep.B = hand[kSegB * kWave];
+        rep.C1 = hand[kSegC1 * kWave];
+        rep.C2 = hand[kSegC2 * kWave];
+        rep.C3 = hand[kSegC3 * kWave];
+        rep.shift = hand[kSegShift * kWave];
     }
 
     // Callers that ask for the final state vector (the SPLIT models) also get the seven outputs of the last step
@@ -1484,7 +1502,7 @@ __device__ __forceinline__ void run_ensemble_merged(const KArgs &a, const double
     } else {
         // the step loop with deferred evaporation; the demand a slice has not yet taken from the layers travels in the
         // hand-over, so that a sliced run composes exactly like a whole one
-        m.begin_lazy(seg > 0 ? hand[15 * kWave] : 0.0);
+        m.begin_lazy(seg > 0 ? hand[kSegPend * kWave] : 0.0);
         long k = 0, r = ra;
         (void)k;
         double acc = 0.0;
@@ -1520,15 +1538,8 @@ __device__ __forceinline__ void run_ensemble_merged(const KArgs &a, const double
                     row[x.n] = val;
                 row += a.ld;
             }
-            if (decltype(obs_tag)::value && !is_missing_mark(w)) { // montecarlo.py:195-196 (e is a number: smart_obs_prepare)
-                const double d = val - e;
-                const double u = val - rep.shift;
-                rep.A += d;
-                rep.B += d * d;
-                rep.C1 += u;
-                rep.C2 += u * u;
-                rep.C3 += w * u;
-            }
+            if (decltype(obs_tag)::value && !is_missing_mark(w)) // montecarlo.py:195-196 (e is a number: smart_obs_prepare)
+                rep.add_moments(val, e, w);
             q_out_total += val;
         };
 #if SMART_STEP_ARMS
@@ -1748,19 +1759,19 @@ __device__ __forceinline__ void run_ensemble_merged(const KArgs &a, const double
     } else {
         m.save_state(hand, kWave);
         if constexpr (REPORT == kReportLast) {
-            hand[16 * kWave] = num_raw;
-            hand[13 * kWave] = den_raw;
+            hand[kSegOutflows * kWave] = num_raw;
+            hand[kSegDenRaw * kWave] = den_raw;
         } else {
-            hand[16 * kWave] = q_out_total;
+            hand[kSegOutflows * kWave] = q_out_total;
         }
-        hand[17 * kWave] = rep.A;
-        hand[18 * kWave] = rep.B;
-        hand[19 * kWave] = rep.C1;
-        hand[20 * kWave] = rep.C2;
-        hand[21 * kWave] = rep.C3;
-        hand[22 * kWave] = rep.shift;
+        hand[kSegA * kWave] = rep.A;
+        hand[kSegB * kWave] = rep.B;
+        hand[kSegC1 * kWave] = rep.C1;
+        hand[kSegC2 * kWave] = rep.C2;
+        hand[kSegC3 * kWave] = rep.C3;
+        hand[kSegShift * kWave] = rep.shift;
         if constexpr (deferring)
-            hand[15 * kWave] = m.pend;
+            hand[kSegPend * kWave] = m.pend;
         if (!(a.debug_drop && slot == 0 && seg == 0)) // test knob: a hand-over that never arrives
             publish_slice(a, slot, seg, true);
     }

@@ -32,31 +32,48 @@
 
 namespace smart {
 
+// THE list of the fast kernels: enum id, __global__ symbol, arithmetic class (wave_class), whether the kernel belongs to a
+// family of time-sliced kernels, and the workgroups it runs per block of 64 samples.  The enum, the declarations and
+// (smart_capi.hip) the handles, the names smart_describe_launch prints and what a launch does with each follow from it.
+#define SMART_FAST_KERNELS(X)                                                                                          \
+    X(kIntervalsExits, smart_fast_intervals_exits, 0, true, 1)                                                         \
+    X(kIntervals, smart_fast_intervals, 0, true, 1)                                                                    \
+    X(kIntervalsStates, smart_fast_intervals_states, 0, true, 1)                                                       \
+    X(kSteps, smart_fast_steps, 0, true, 1)                                                                            \
+    X(kStepsStates, smart_fast_steps_states, 0, true, 1)                                                               \
+    X(kPlain, smart_fast_plain, 0, false, 1)                                                                           \
+    X(kStiff, smart_fast_stiff, 1, false, 1)                                                                           \
+    X(kGuard, smart_fast_guard, 2, false, 1)                                                                           \
+    X(kIllCond, smart_fast_illcond, 3, false, kIllCondWaves)                                                           \
+    X(kRunsExits, smart_fast_runs_exits, 0, true, 1)                                                                   \
+    X(kRuns, smart_fast_runs, 0, true, 1)                                                                              \
+    X(kRunsStates, smart_fast_runs_states, 0, true, 1)                                                                 \
+    X(kStepsRaw, smart_fast_steps_raw, 0, true, 1)                                                                     \
+    X(kIntervalsRaw, smart_fast_intervals_raw, 0, true, 1)                                                             \
+    X(kStepsEvery, smart_fast_steps_every, 0, true, 1)                                                                 \
+    X(kIllCondLanes, smart_fast_illcond_lanes, 3, false, 1)
+
+#define SMART_FAST_KERNEL(name)                                                                                        \
+    __global__ __launch_bounds__(kWave) void name(KArgs a, const double2 *__restrict__ forcing,                        \
+                                                  const double *__restrict__ obs, const double *__restrict__ ws)
+
 enum FastKernel : int {
-    kIntervalsExits = 0,
-    kIntervals,
-    kIntervalsStates,
-    kSteps,
-    kStepsStates,
-    kPlain,
-    kStiff,
-    kGuard,
-    kIllCond,
-    kRunsExits,
-    kRuns,
-    kRunsStates,
-    kStepsRaw,
-    kIntervalsRaw,
-    kStepsEvery,
-    kIllCondLanes,
+#define X(id, symbol, cls, sliced, waves) id,
+    SMART_FAST_KERNELS(X)
+#undef X
     kNumFastKernels
 };
+
+// (each kernel is defined in one of the smart_fast_*.hip units; smart_capi.hip launches them from these declarations)
+#define X(id, symbol, cls, sliced, waves) SMART_FAST_KERNEL(symbol);
+SMART_FAST_KERNELS(X)
+#undef X
 
 // ticket counters of the families of time-sliced kernels (workspace header, claim_work): at most one kernel of a
 // family runs in a call
 constexpr int kTicketIntervals = 0, kTicketSteps = 1, kTicketRuns = 2, kTicketStepsRaw = 3, kTicketIntervalsRaw = 4,
               kTicketEvery = 5;
-static_assert(kHdrTicket + kTicketEvery < 8, "the plan word of smart_plan_ensemble sits at header int 8");
+static_assert(kHdrTicket + kTicketEvery < kHdrPlan, "the tickets end in front of the plan word of smart_plan_ensemble");
 
 // Do this block's 64 rows belong to the kernel of class CLS?  A block whose class has no kernel in this call (the
 // caller's plan is stale) is reported through the status word by whichever kernel meets it first.
@@ -79,9 +96,7 @@ __device__ __forceinline__ bool forcing_is_mine(const KArgs &a, int fflags, cons
     const int kind = forcing_kind(a, fflags);
     if (kind == FORCING)
         return true;
-    // pc_mask: bit 0 the interval engine, bit 1 the step loop, bit 2 the run engine
-    const int bit = kind == kForcingIntervals ? 0 : (kind == kForcingVarying ? 1 : 2);
-    if (w.seg == 0 && !((a.pc_mask >> bit) & 1))
+    if (w.seg == 0 && !(a.pc_mask & pc_bit(kind)))
         raise_status(a, kStatusStalePlan);
     return false;
 }
@@ -102,7 +117,7 @@ __device__ __forceinline__ void merged_kernel(const KArgs &a, const double2 *__r
         // the step loop of raw reports takes every forcing the interval engine does not (varying, and constant over runs
         // shorter than the report interval: there is no run engine for raw reports)
         if (forcing_kind(a, fflags) == kForcingIntervals) {
-            if (w.seg == 0 && !(a.pc_mask & 1))
+            if (w.seg == 0 && !(a.pc_mask & kPcIntervals))
                 raise_status(a, kStatusStalePlan);
             return;
         }
@@ -112,16 +127,5 @@ __device__ __forceinline__ void merged_kernel(const KArgs &a, const double2 *__r
     }
     run_ensemble_merged<Model, FORCING, REPORT>(a, forcing, obs, ws, w.block, w.c, w.seg, fflags);
 }
-
-#define SMART_FAST_KERNEL(name)                                                                                        \
-    __global__ __launch_bounds__(kWave) void name(KArgs a, const double2 *__restrict__ forcing,                        \
-                                                  const double *__restrict__ obs, const double *__restrict__ ws)
-
-// host stub of a kernel (for hipLaunchKernel / the occupancy query); each translation unit answers for its own
-const void *fast_kernel_intervals(FastKernel k);
-const void *fast_kernel_steps(FastKernel k);
-const void *fast_kernel_guarded(FastKernel k);
-const void *fast_kernel_runs(FastKernel k);
-const void *fast_kernel_reports(FastKernel k);
 
 } // namespace smart

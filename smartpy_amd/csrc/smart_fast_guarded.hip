@@ -53,20 +53,4 @@ SMART_FAST_KERNEL(smart_fast_illcond)
 
 SMART_FAST_KERNEL(smart_fast_illcond_lanes) { guarded_kernel<3, LiteralModelT<true>>(a, forcing, obs, ws); }
 
-const void *fast_kernel_guarded(FastKernel k)
-{
-    switch (k) {
-    case kStiff:
-        return reinterpret_cast<const void *>(&smart_fast_stiff);
-    case kGuard:
-        return reinterpret_cast<const void *>(&smart_fast_guard);
-    case kIllCond:
-        return reinterpret_cast<const void *>(&smart_fast_illcond);
-    case kIllCondLanes:
-        return reinterpret_cast<const void *>(&smart_fast_illcond_lanes);
-    default:
-        return nullptr;
-    }
-}
-
 } // namespace smart

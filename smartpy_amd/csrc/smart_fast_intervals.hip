@@ -14,18 +14,4 @@ SMART_FAST_KERNEL(smart_fast_intervals_states)
     merged_kernel<FastModel<false, false, true, true, true>, kForcingIntervals>(a, forcing, obs, ws);
 }
 
-const void *fast_kernel_intervals(FastKernel k)
-{
-    switch (k) {
-    case kIntervalsExits:
-        return reinterpret_cast<const void *>(&smart_fast_intervals_exits);
-    case kIntervals:
-        return reinterpret_cast<const void *>(&smart_fast_intervals);
-    case kIntervalsStates:
-        return reinterpret_cast<const void *>(&smart_fast_intervals_states);
-    default:
-        return nullptr;
-    }
-}
-
 } // namespace smart

@@ -18,18 +18,4 @@ SMART_FAST_KERNEL(smart_fast_intervals_raw)
 
 SMART_FAST_KERNEL(smart_fast_steps_every) { merged_kernel<FastModel<false, false, true>, kForcingVarying, kReportEvery>(a, forcing, obs, ws); }
 
-const void *fast_kernel_reports(FastKernel k)
-{
-    switch (k) {
-    case kStepsRaw:
-        return reinterpret_cast<const void *>(&smart_fast_steps_raw);
-    case kIntervalsRaw:
-        return reinterpret_cast<const void *>(&smart_fast_intervals_raw);
-    case kStepsEvery:
-        return reinterpret_cast<const void *>(&smart_fast_steps_every);
-    default:
-        return nullptr;
-    }
-}
-
 } // namespace smart

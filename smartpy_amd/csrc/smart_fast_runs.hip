@@ -18,18 +18,4 @@ SMART_FAST_KERNEL(smart_fast_runs_states)
     merged_kernel<FastModel<false, false, true, true, true>, kForcingRuns>(a, forcing, obs, ws);
 }
 
-const void *fast_kernel_runs(FastKernel k)
-{
-    switch (k) {
-    case kRunsExits:
-        return reinterpret_cast<const void *>(&smart_fast_runs_exits);
-    case kRuns:
-        return reinterpret_cast<const void *>(&smart_fast_runs);
-    case kRunsStates:
-        return reinterpret_cast<const void *>(&smart_fast_runs_states);
-    default:
-        return nullptr;
-    }
-}
-
 } // namespace smart

@@ -24,18 +24,4 @@ SMART_FAST_KERNEL(smart_fast_plain)
         run_ensemble<FastModel<false, false>, false>(a, forcing, obs, ws, nullptr, w.block, w.c);
 }
 
-const void *fast_kernel_steps(FastKernel k)
-{
-    switch (k) {
-    case kSteps:
-        return reinterpret_cast<const void *>(&smart_fast_steps);
-    case kStepsStates:
-        return reinterpret_cast<const void *>(&smart_fast_steps_states);
-    case kPlain:
-        return reinterpret_cast<const void *>(&smart_fast_plain);
-    default:
-        return nullptr;
-    }
-}
-
 } // namespace smart

@@ -207,11 +207,11 @@ def _define(name):
     return int(re.search(r'#define %s (\d+)' % name, text).group(1))
 
 
-def fast_kernel_names():
-    """the names the library itself lists (kFastKernelNames in smart_capi.hip)"""
-    text = open(os.path.join(HERE, 'csrc', 'smart_capi.hip')).read()
-    table = re.search(r'kFastKernelNames\[kNumFastKernels\] = \{(.*?)\};', text, re.S).group(1)
-    return re.findall(r'"(smart_fast_\w+)"', table)
+def fast_kernel_table():
+    """{name: is it one of a time-sliced family} as the library itself lists its fast kernels (SMART_FAST_KERNELS in
+    smart_fast_entry.h)"""
+    text = open(os.path.join(HERE, 'csrc', 'smart_fast_entry.h')).read()
+    return {name: sliced == 'true' for name, sliced in re.findall(r'^\s*X\(k\w+, (smart_fast_\w+), \d, (true|false), ', text, re.M)}
 
 
 # ---- pair blocks ----------------------------------------------------------------------------------------------------
@@ -391,9 +391,10 @@ def lint_handover(lib=None, kernel=None):
             _need(j < len(insts) and 'sc1' in insts[j]['args'], '%s: no buffer_inv sc1 behind the poll' % name)
             _need(_is_wait_vm0(insts[j - 1]), '%s: buffer_inv without its wait' % name)
     if kernel is None:
-        names = fast_kernel_names()
-        _need(len(names) >= 12 and set(SLICED) <= set(names), 'the list of sliced kernels does not match the library\'s')
-        for name in names:
+        table = fast_kernel_table()
+        _need(len(table) >= 12 and set(SLICED) == {n for n, sliced in table.items() if sliced},
+              'the list of sliced kernels does not match the library\'s')
+        for name in table:
             publishes = any(x['op'] == 'buffer_wbl2' for x in dis.kernel(name))
             _need(publishes == (name in SLICED), '%s publishes but is not linted as a sliced kernel (or the reverse)' % name)
 
