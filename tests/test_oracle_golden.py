@@ -183,3 +183,30 @@ def test_g4_objective_functions_pinned_by_example_database(example):
                        example['params'], example['extra'], so.REPORT_SUMMARY, 24)
     o = objfn_oracle.objective_functions(d0, example['flow_obs'])
     assert abs(o[0] - 0.390445) < 1e-6 and abs(o[1] - 0.252085) < 1e-6 and abs(o[6] - 4.31063) < 1e-5
+
+
+def test_finite_forcing_with_the_sign_bit_set_bit_exact():
+    """Negative and -0.0 rain and evaporation (tests/golden/make_forcing_signs.py has the table and says why): what the
+    reference's run() gives for six rows -- the daily value on every hour, 6-hourly values and values that vary inside
+    the day, under a daily summary after a 48-step warm-up, raw reports of gap 24, a report every step and ragged raw
+    reports of gap 7; daily steps on regular, stiff, guarded and ill-conditioned rows -- and the oracle reproduces every
+    bit of discharge, groundwater ratio and final row.  The link "oracle = reference" that tests/
+    test_gpu_forcing_signs.py relies on when it holds the fast kernels to the oracle on this forcing."""
+    import importlib.util
+    import os
+    spec = importlib.util.spec_from_file_location(
+        'make_forcing_signs', os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden', 'make_forcing_signs.py'))
+    cases = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(cases)
+    g = cases.load_fixture()
+    keys = []
+    for key, f, dt, n_warm, params, report, gap in cases.pin_cases():
+        assert np.signbit(f).any() and np.isfinite(f).all() and len(params) == cases.PIN_ROWS
+        dis, gw, fin = cases.oracle_run(so, f, n_warm, params, report, gap, dt=dt)
+        assert dis.shape == g[key + '|discharge'].shape == (cases.PIN_ROWS, -(-f.shape[0] // gap)), key
+        for name, got in (('discharge', dis), ('gw', gw), ('final', fin)):
+            want = g[key + '|' + name]
+            assert np.array_equal(got.view(np.int64), want.view(np.int64)), (key, name)
+        assert np.isfinite(dis).all() and np.isfinite(fin).all() and (dis >= 0).all() and (fin[:, 7:] >= 0).all(), key
+        keys += [key + '|discharge', key + '|gw', key + '|final']
+    assert sorted(keys) == sorted(g) and len(keys) == 3 * 13      # nothing in the fixture goes unread
