@@ -385,6 +385,65 @@ int64_t smart_flow_duration_workspace_bytes(int64_t n_reports, int32_t n_windows
 int64_t smart_flow_duration_sort_capacity(void);
 
 /*
+ * Hydrological signatures of an existing discharge matrix, per sample and per window of report steps: the scores that
+ * depend on the ORDER of the report steps within a window, which no other analysis of the matrix sees.
+ *   sim[R][ld] sample-minor (the layout smart_run_ensemble_hip writes), obs[R] or NULL (NaN = missing), window[R] int32
+ *   or NULL with the convention of smart_objfn_windows_hip (-1 = no window, else 0 .. n_windows-1; NULL = one window
+ *   holding every report step, n_windows must be 1), alpha in (0, 1) the filter parameter, pulse[n_windows][2] doubles
+ *   (lo, hi) or NULL, sig[n_windows][SMART_SIGNATURE_COLS][N] (sample-minor: the stores coalesce, and a column of a
+ *   window is a contiguous [N] vector): device pointers.  Asynchronous on stream; allocates nothing.
+ * For window w and sample n write x_r = sim[r][n].  A row r is VALID iff window[r] == w and, where obs is given, obs[r] is
+ * not NaN; m is the number of valid rows.  There is a PAIR at r iff r >= 1 and rows r-1 and r are both valid; p is the
+ * number of pairs.  Validity belongs to the row, not to the sample.  Everything is walked in ascending r.
+ *   MEAN           sum x_r / m over the valid rows
+ *   BFI            sum (x_r - f_r) / sum x_r over the valid rows, f the ONE-PASS Lyne-Hollick quick flow: f_r = 0 at a
+ *                  valid row without a pair, else f_r = min(max(alpha f_{r-1} + (1 + alpha) / 2 (x_r - x_{r-1}), 0), x_r);
+ *                  NaN if sum x is 0.  One forward pass only: the three-pass form of the filter needs the intermediate
+ *                  series of every sample, which is a second matrix
+ *   FLASHINESS     Richards-Baker: sum over the pairs |x_r - x_{r-1}| / sum over the pairs x_r; NaN if p is 0 or the
+ *                  denominator is 0
+ *   AC1            Pearson correlation of (x_{r-1}, x_r) over the pairs; NaN if p < 2 or either variance is <= 0
+ *   RLD            rising limb density: a RISING pair has x_r > x_{r-1}; a limb starts at a rising pair at r when there
+ *                  is no rising pair at r-1; limbs / rising pairs, NaN if there is no rising pair
+ *   RECESSION      the mean of ln(x_r / x_{r-1}) over the pairs with 0 < x_r < x_{r-1}; NaN if there is none
+ *   PEAK           the maximum of x over the valid rows
+ *   PEAK_ROW       the smallest r attaining it, as a double (the caller turns it into a stamp or a timing error)
+ *   HIGH_COUNT     the number of runs above hi: a run starts at a valid row with x_r > hi that has no pair, or whose
+ *                  x_{r-1} <= hi
+ *   HIGH_DURATION  rows with x_r > hi divided by runs; NaN with no run
+ *   LOW_COUNT, LOW_DURATION   the same with x_r < lo
+ * Rules: m == 0 gives NaN in all twelve columns; a valid row that holds a value that is not finite gives NaN in all twelve
+ * columns of that (window, sample) -- one test of sum x at the end, as smart_objfn_windows_hip: a sum of finite values
+ * that overflows counts the same way; pulse NULL, or a NaN threshold, gives NaN in the two columns that threshold feeds; a
+ * missing observation or a window boundary breaks a pair, a run and a limb, and restarts the filter; comparisons are
+ * strict and made on the matrix values themselves; -0.0 and +0.0 are one value.
+ * Rows that are not valid are never read, and every element of a valid row is loaded once.  Deterministic: no atomics, the
+ * association of every sum is the row order, two launches give the same bits.
+ * Errors (all found before the device is touched): SMART_E_NULL sim or sig missing; SMART_E_SIZE a size < 1, ld <
+ * n_samples, n_reports >= 2^31, n_windows > smart_objfn_max_windows() or != 1 without a window array, alpha outside
+ * (0, 1) or not finite; then SMART_E_NO_DEVICE without a HIP device.
+ */
+#define SMART_SIGNATURE_COLS 12
+#define SMART_SIG_MEAN 0
+#define SMART_SIG_BFI 1
+#define SMART_SIG_FLASHINESS 2
+#define SMART_SIG_AC1 3
+#define SMART_SIG_RLD 4
+#define SMART_SIG_RECESSION 5
+#define SMART_SIG_PEAK 6
+#define SMART_SIG_PEAK_ROW 7
+#define SMART_SIG_HIGH_COUNT 8
+#define SMART_SIG_HIGH_DURATION 9
+#define SMART_SIG_LOW_COUNT 10
+#define SMART_SIG_LOW_DURATION 11
+int smart_signatures_hip(int64_t n_samples, int64_t n_reports, const double *sim, int64_t ld, const double *obs,
+                         const int32_t *window, int32_t n_windows, double alpha, const double *pulse,
+                         double *sig, void *stream);
+
+/* SMART_SIGNATURE_COLS as the library was built (12).  Needs no device. */
+int32_t smart_signature_cols(void);
+
+/*
  * Sobol sensitivity indices of the rows of a matrix whose columns are a Saltelli design in block-major order
  * (smartpy_amd.sampling.saltelli_design): first-order indices after Saltelli 2010, total indices after Jansen, and their
  * standard deviation over bootstrap replicates.

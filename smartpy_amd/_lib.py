@@ -27,6 +27,9 @@ QUANTILES_MAX_PROBS = 16
 TRANSFORMS = {'none': 0, 'sqrt': 1, 'log': 2, 'inverse': 3}     # SMART_TRANSFORM_*
 OBJFN_WINDOW_COLS = 7
 FDC_METHODS = {'auto': 0, 'sort': 1, 'select': 2}              # SMART_FDC_*
+SIGNATURE_NAMES = ['MEAN', 'BFI', 'FLASHINESS', 'AC1', 'RLD', 'RECESSION', 'PEAK', 'PEAK_ROW', 'HIGH_COUNT',
+                   'HIGH_DURATION', 'LOW_COUNT', 'LOW_DURATION']     # SMART_SIG_*, in column order
+SIGNATURE_COLS = len(SIGNATURE_NAMES)
 SOBOL_MAX_PARAMS = 16
 PARETO_MAX_OBJECTIVES = 16
 PARETO_DIRECTIONS = {'max': 0, 'min': 1, 'target': 2}           # SMART_PARETO_*
@@ -78,6 +81,9 @@ SYMBOLS = {
                                                _dp, ctypes.c_int64, ctypes.c_int32, _dp]),
     'smart_flow_duration_workspace_bytes': (ctypes.c_int64, [ctypes.c_int64, ctypes.c_int32, ctypes.c_int32]),
     'smart_flow_duration_sort_capacity': (ctypes.c_int64, []),
+    'smart_signatures_hip': (ctypes.c_int, [ctypes.c_int64, ctypes.c_int64, _dp, ctypes.c_int64, _dp, _dp, ctypes.c_int32,
+                                            ctypes.c_double, _dp, _dp, _dp]),
+    'smart_signature_cols': (ctypes.c_int32, []),
     'smart_sobol_indices_hip': (ctypes.c_int, [ctypes.c_int64, ctypes.c_int32, ctypes.c_int64, _dp, ctypes.c_int64, _dp,
                                                _dp, _dp, _dp, ctypes.c_int32, _dp, _dp, _dp, ctypes.c_int64, _dp]),
     'smart_sobol_workspace_bytes': (ctypes.c_int64, [ctypes.c_int64, ctypes.c_int32, ctypes.c_int64, ctypes.c_int32]),

@@ -1,8 +1,8 @@
 """The analyses of a stored [R, N] discharge matrix (row r = every sample's discharge of report step r), each one launch
 through the C ABI (csrc/smart_analysis_capi.hip): objective functions, weighted quantiles over the samples, objective
-functions per window of report steps, flow duration curves, Sobol indices -- and the Pareto selection over the scores
-they leave, [N, C] with a row per sample.  torch tensors in, torch tensors out, as in
-engine.py -- which imports this module and re-exports every public name of it (engine.flow_duration and the others are
+functions per window of report steps, flow duration curves, hydrological signatures, Sobol indices -- and the Pareto
+selection over the scores they leave, [N, C] with a row per sample.  torch tensors in, torch tensors out, as in engine.py
+-- which imports this module and re-exports every public name of it (engine.flow_duration and the others are
 these functions); what they share on the way to the launch are the private helpers at the top.
 """
 import ctypes
@@ -220,6 +220,54 @@ def flow_duration(discharge_report_major, probs, obs=None, windows=None, n_windo
                                              quant.data_ptr(), code, float(eps), lo, hi, _ptr(scores), _ptr(work), need,
                                              how, _stream(sim.device)))
     return quant, scores
+
+
+SIGNATURE_NAMES = list(_lib.SIGNATURE_NAMES)
+
+
+def signatures(discharge_report_major, obs=None, windows=None, n_windows=None, alpha=0.925, thresholds=None):
+    """Hydrological signatures of every column of a stored [R, N] discharge matrix, per window of report steps -> device
+    tensor [W, 12, N] float64, the columns in the order of SIGNATURE_NAMES: the mean, and the scores that depend on the
+    ORDER of the report steps -- baseflow index (one forward pass of the Lyne-Hollick filter with `alpha`), Richards-Baker
+    flashiness, lag-1 autocorrelation, rising limb density, mean log recession rate, the peak and its row, and the number
+    and mean length of the runs above thresholds[w][1] and below thresholds[w][0].  out[w, c] is a contiguous [N] vector.
+    obs: [R] or None -- a report step without an observation (NaN) is left out and breaks the series there; windows: [R]
+    integers as for objective_functions_windows, or None for one window holding every step; thresholds: [W, 2] (lo, hi),
+    host or device, or None (the four pulse columns are then NaN, as they are for a NaN threshold).  A (window, sample)
+    without a row, or with a value that is not finite, is NaN (include/smart_amd.h: smart_signatures_hip)."""
+    alpha = float(alpha)
+    if not (0.0 < alpha < 1.0):
+        raise SmartEngineError(-2, "signatures: alpha {} must lie inside (0, 1).".format(alpha))
+    sim = discharge_report_major
+    if windows is None:
+        win, W = None, 1
+        if n_windows is not None and int(n_windows) != 1:
+            raise SmartEngineError(-2, "signatures: n_windows = {} without windows.".format(n_windows))
+    else:
+        win, W = _checked_windows('signatures', windows, n_windows)
+        if len(sim.shape) != 2 or sim.shape[0] != len(win):
+            raise SmartEngineError(-2, "signatures: {} window ids for a matrix of shape {}."
+                                   .format(len(win), tuple(sim.shape)))
+    if len(sim.shape) != 2:
+        raise SmartEngineError(-2, "signatures: a matrix [R, N] is needed, not shape {}.".format(tuple(sim.shape)))
+    if thresholds is not None and tuple(thresholds.shape if hasattr(thresholds, 'shape')
+                                        else np.shape(thresholds)) != (W, 2):
+        raise SmartEngineError(-2, "signatures: thresholds must be (lo, hi) per window, shape ({}, 2), not {}."
+                               .format(W, tuple(np.shape(thresholds))))
+    L = _lib.lib()
+    sim, R, N, ld = _matrix(sim)
+    if obs is not None:
+        obs = _as_device(obs, sim.device, (R,))
+    if win is not None:
+        win = _window_ids(win, sim.device)
+    pulse = None if thresholds is None else _as_device(thresholds, sim.device, (W, 2))
+    out = torch.empty((W, _lib.SIGNATURE_COLS, N), dtype=torch.float64, device=sim.device)
+    if N == 0:
+        return out
+    with torch.cuda.device(sim.device):
+        _lib.check(L.smart_signatures_hip(N, R, sim.data_ptr(), ld, _ptr(obs), _ptr(win), W, alpha, _ptr(pulse),
+                                          out.data_ptr(), _stream(sim.device)))
+    return out
 
 
 def sobol_max_resamples():

@@ -36,6 +36,9 @@ UNITS = {
     # flow duration curves (order statistics along time, per sample): default flags, NaNs honoured -- a NaN value has a
     # place in the order, and a non-finite transformed flow has to reach the sums
     'smart_flow_duration.hip': [],
+    # hydrological signatures (a recurrence along time, per sample): default flags, NaNs honoured -- a value that is not
+    # finite has to reach the one sum that finds it
+    'smart_signatures.hip': [],
     # Sobol sensitivity indices of a Saltelli design (point estimates and bootstrap): default flags, NaNs honoured -- a
     # value that is not finite has to reach the one sum that finds it
     'smart_sobol.hip': [],

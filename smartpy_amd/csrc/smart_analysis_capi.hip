@@ -1,5 +1,5 @@
 // smart_analysis_capi.hip -- the C ABI of the analyses of a stored discharge matrix sim[R][ld] (include/smart_amd.h):
-// objective functions, weighted quantiles, objective functions per window, flow duration curves, Sobol indices, and of
+// objective functions, weighted quantiles, objective functions per window, flow duration curves, hydrological signatures, Sobol indices, and of
 // the Pareto selection over the scores they leave, with their capacity and workspace entries -- validation and launch --
 // and the one kernel among them that has no unit of its own, smart_objfn_matrix.  Every refusal comes before the device is asked for; the rules the entries share are the
 // static helpers below, which take the entry's name for the text.
@@ -322,6 +322,29 @@ int64_t smart_flow_duration_workspace_bytes(int64_t n_reports, int32_t n_windows
 }
 
 int64_t smart_flow_duration_sort_capacity(void) { return flow_duration_sort_capacity(); }
+
+int smart_signatures_hip(int64_t n_samples, int64_t n_reports, const double *sim, int64_t ld, const double *obs,
+                         const int32_t *window, int32_t n_windows, double alpha, const double *pulse, double *sig,
+                         void *stream)
+{
+    static const char entry[] = "smart_signatures_hip";
+    int rc;
+    if (!sim || !sig)
+        return fail(SMART_E_NULL, "%s: sim and sig are required (%s is NULL)", entry, !sim ? "sim" : "sig");
+    if ((rc = windowed_sizes(entry, n_samples, n_reports, ld, n_windows, nullptr)))
+        return rc;
+    if (!window && n_windows != 1)
+        return fail(SMART_E_SIZE, "%s: n_windows %d without a window array (NULL is one window)", entry, (int)n_windows);
+    if (!(alpha > 0.0 && alpha < 1.0))
+        return fail(SMART_E_SIZE, "%s: alpha %g must lie inside (0, 1)", entry, alpha);
+    if ((rc = device_ready()))
+        return rc;
+    launch_signatures((long)n_samples, (long)n_reports, sim, (long)ld, obs, window, (int)n_windows, alpha, pulse, sig,
+                      (hipStream_t)stream);
+    return launched();
+}
+
+int32_t smart_signature_cols(void) { return SMART_SIGNATURE_COLS; }
 
 int smart_sobol_indices_hip(int64_t n_base, int32_t n_params, int64_t n_rows, const double *y, int64_t ld, double *s1,
                             double *st, double *moments, const uint16_t *counts, int32_t n_resamples, double *s1_std,

@@ -45,6 +45,10 @@ void launch_flow_duration(long N, long R, const double *sim, long ld, const doub
                           const double *probs, int K, double *quant, int transform, double eps, double seg_lo,
                           double seg_hi, double *objfn, double *ws, bool sort, hipStream_t s);
 
+// ---- smart_signatures.hip
+void launch_signatures(long N, long R, const double *sim, long ld, const double *obs, const int *window, int W,
+                       double alpha, const double *pulse, double *sig, hipStream_t s);
+
 // ---- smart_sobol.hip
 long sobol_lds_capacity();
 int sobol_max_resamples();

@@ -297,6 +297,59 @@ class MonteCarlo(object):
         """`<out>/<catchment>.SMART.<func>.fdc`: beside the sampling database, whatever its format."""
         return self._side_file('.fdc')
 
+    # ---- hydrological signatures -------------------------------------------------------------------------
+    def hydrological_signatures(self, windows='all', alpha=None, high=3.0, low=0.2, thresholds=None, start_month=10,
+                                split=None, write=False):
+        """The hydrological signatures of every row of the sample PER WINDOW of report steps -- the scores that depend on
+        the ORDER of the report steps: MEAN, BFI (baseflow index, one forward pass of the Lyne-Hollick filter),
+        FLASHINESS (Richards-Baker), AC1 (lag-1 autocorrelation), RLD (rising limb density), RECESSION (mean ln(Q_r /
+        Q_r-1) of the falling steps), PEAK and PEAK_ROW (the report step of the peak), HIGH_COUNT / HIGH_DURATION and
+        LOW_COUNT / LOW_DURATION (number and mean length of the runs above `hi` and below `lo`) -- and the same twelve
+        of the observations, by the same kernel.  Report steps without an observation are left out and break the
+        series there.  alpha=None: 0.925 ** (report step in days), 0.925 for daily means; the value used is on the
+        result.  The thresholds of a window default to hi = high x the median and lo = low x the mean of its non-missing
+        observations; a ready [W, 2] array of (lo, hi) passed as thresholds= overrides them.  windows / start_month /
+        split as for window_objective_functions.  One launch of its own over the sample; the [R, N] matrix stays on
+        the device and only [W, 12, N] comes back.  write=True also writes `<out>/<catchment>.SMART.<func>.signatures`
+        (one line per sample in the sample's order, the float32 '%.6e' of the sampling database; header MEAN@<label>,
+        BFI@<label>,... window by window).  Under torch.distributed every rank that calls this computes all rows itself
+        (no collective); rank 0 alone writes.  -> windows.Signatures"""
+        from .. import engine, windows as swin
+        ids, labels = self._resolve_windows(windows, start_month, split)
+        n = self._sample.shape[0]
+        self._check_observations()
+        W = len(labels)
+        if alpha is None:
+            alpha = swin.default_alpha(self.model.delta_save.total_seconds() / 86400.0)
+        obs = np.asarray(self.model.nd_flow, dtype=np.float64)
+        if thresholds is None:
+            thresholds = swin.pulse_thresholds(obs, ids, W, high=high, low=low)
+        thresholds = np.ascontiguousarray(thresholds, dtype=np.float64)
+        if thresholds.shape != (W, 2):
+            raise Exception("The pulse thresholds must be (lo, hi) per window, shape ({}, 2), not {}."
+                            .format(W, thresholds.shape))
+        if n == 0:      # e.g. GLUE with no behavioural set: nothing to launch
+            on_device, values = None, np.empty((W, len(swin.SIGNATURE_NAMES), 0))
+            observed = np.full((W, len(swin.SIGNATURE_NAMES)), np.nan)
+        else:
+            out, on_obs = self._launch_stored()
+            on_device = engine.signatures(out.discharge_report_major, obs=on_obs, windows=ids, n_windows=W, alpha=alpha,
+                                          thresholds=thresholds)
+            values = on_device.cpu().numpy()
+            # the observations as an [R, 1] matrix under the same mask: one definition serves both
+            observed = engine.signatures(obs.reshape(-1, 1), obs=obs, windows=ids, n_windows=W, alpha=alpha,
+                                         thresholds=thresholds).cpu().numpy()[:, :, 0]
+        path = None
+        if write and sdist.rank_world()[0] == 0:
+            path = self.signatures_file
+            _write_signatures_file(path, labels, values)
+        return swin.Signatures(labels, alpha, thresholds, values, on_device, observed, path)
+
+    @property
+    def signatures_file(self):
+        """`<out>/<catchment>.SMART.<func>.signatures`: beside the sampling database, whatever its format."""
+        return self._side_file('.signatures')
+
     # ---- the per-sample protocol of the reference (spotpy setup class) ------------------------------------
     def parameters(self):
         return np.array([p() for p in self.params])
@@ -348,6 +401,18 @@ def _write_windows_file(path, labels, transform, values):
     if n == 0:
         return
     append_float32_rows(path, np.ascontiguousarray(np.transpose(values, (1, 0, 2)).reshape(n, W * k).astype(np.float32)))
+
+
+def _write_signatures_file(path, labels, values):
+    """values [W, 12, N] -> header line + one line per sample, window by window (the sampling database's float32
+    '%.6e', formatted by the library)."""
+    from .. import windows as swin
+    with open(path, 'w', newline='', encoding='utf8') as f:
+        f.write(swin.signatures_header_line(labels))
+    W, k, n = values.shape
+    if n == 0:
+        return
+    append_float32_rows(path, np.ascontiguousarray(np.transpose(values, (2, 0, 1)).reshape(n, W * k).astype(np.float32)))
 
 
 def _write_fdc_file(path, exceedance, labels, transform, curves, values):

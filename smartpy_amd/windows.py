@@ -1,7 +1,8 @@
 """Evaluation windows over the report stamps: which report step belongs to which hydrological year, season, month or
 period of a split-sample test.  Pure host code; the ids go to engine.objective_functions_windows
 (MonteCarlo.window_objective_functions), which scores every sample per window on the GPU, and to engine.flow_duration
-(MonteCarlo.flow_duration_curves), which sorts every sample's flows per window there.
+(MonteCarlo.flow_duration_curves), which sorts every sample's flows per window there, and to engine.signatures
+(MonteCarlo.hydrological_signatures), which walks every sample's flows of a window in time order there.
 """
 from bisect import bisect_right
 from datetime import datetime
@@ -143,3 +144,53 @@ class FlowDuration(object):
         self.curves, self.observed = curves, observed
         self.transform, self.eps, self.segment = transform, eps, (float(segment[0]), float(segment[1]))
         self.values, self.device_values, self.file = values, device_values, file
+
+
+# ---- hydrological signatures ----------------------------------------------------------------------------------------
+from ._lib import SIGNATURE_NAMES       # noqa: E402 -- the twelve columns of a window, SMART_SIG_* (names only: no library is loaded)
+
+
+def default_alpha(report_days):
+    """The Lyne-Hollick filter parameter of a report step of `report_days` days: 0.925 for daily means (Nathan and
+    McMahon 1990, Water Resour. Res. 26), the same decay per day for any other step."""
+    return 0.925 ** float(report_days)
+
+
+def pulse_thresholds(obs, ids, n_windows, high=3.0, low=0.2):
+    """The default pulse thresholds of MonteCarlo.hydrological_signatures -> [W, 2] float64, (lo, hi) per window from the
+    window's non-missing observations: hi = high x their median, lo = low x their mean; NaN for a window without any."""
+    obs, ids = np.asarray(obs, dtype=np.float64), np.asarray(ids)
+    out = np.full((n_windows, 2), np.nan)
+    for w in range(n_windows):
+        x = obs[(ids == w) & ~np.isnan(obs)]
+        if x.size:
+            out[w] = (float(low) * float(np.mean(x)), float(high) * float(np.median(x)))
+    return out
+
+
+def signatures_header_line(labels):
+    """The header of a `.signatures` file: MEAN@<label>, BFI@<label>, ... window by window."""
+    return header_line(labels, names=SIGNATURE_NAMES)
+
+
+class Signatures(object):
+    """What MonteCarlo.hydrological_signatures returns: `names` (the twelve signatures), `labels` (one per window),
+    `alpha` (the filter parameter used), `thresholds` ([W, 2]: the (lo, hi) of the pulse columns), `values` (numpy
+    [W, 12, N] float64, in the order of the sample's rows), `device_values` (the same as a device tensor, or None for an
+    empty sample: device_values[w, c] is a contiguous [N] vector that goes to selection.pareto_rows / Pareto(extra=) as
+    it is), `observed` ([W, 12]: the same signatures of the observations, by the same kernel; NaN for an empty sample,
+    which launches nothing) and `path` (the file written, or None)."""
+
+    def __init__(self, labels, alpha, thresholds, values, device_values, observed, path=None):
+        self.names = list(SIGNATURE_NAMES)
+        self.labels, self.alpha = list(labels), float(alpha)
+        self.thresholds = np.asarray(thresholds, dtype=np.float64)
+        self.values, self.device_values, self.observed, self.path = values, device_values, observed, path
+
+    def relative_error(self):
+        """(values - observed) / |observed| -> [W, 12, N]: the signed relative error of every signature of every sample
+        (PEAK_ROW included: its difference is the timing error in report steps, which a caller reads from
+        values - observed instead)."""
+        with np.errstate(all='ignore'):
+            ref = self.observed[:, :, None]
+            return (self.values - ref) / np.abs(ref)
