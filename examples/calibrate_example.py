@@ -83,6 +83,10 @@ def main():
     # the flow duration curve of every behavioural set (Q5, Q50, Q95) and the fit of its top 2 %: one launch each
     fdc = glue.flow_duration_curves(exceedance=(0.05, 0.5, 0.95), windows='all', write=True)
     high_flow = glue.flow_duration_curves(exceedance=(0.05,), windows='all', segment=(0.98, 1.0))
+    # how much of those scores is noise of the years that lie in the period: block bootstrap over the hydrological years
+    # and a leave-one-year-out jackknife, one launch and two reads of the matrix; unsure.device_stats[1, 2] is the 5 % bound
+    # of KGE of every set, on the GPU
+    unsure = glue.score_uncertainty('hydro_year', resamples=1000, seed=0, write=True)
     top = Best('Catchment', root, 'csv', 'csv', target='KGE', nb_best=10, constraining={'GW': ('equal', (1.0,))})
     top.model.extra = EXTRA
     top.run()
@@ -106,6 +110,10 @@ def main():
                   % (', '.join('%.3g' % v for v in np.nanmedian(fdc.curves[0], axis=1)),
                      ', '.join('%.3g' % v for v in fdc.observed[0]), fdc.file))
             print('      volume bias of the top 2 %% of the curve: smallest |PBias| %.2f %%' % np.nanmin(np.abs(high_flow.values[0][:, 5])))
+            print('      KGE of the best set %.3f, standard error %.3f (bootstrap) / %.3f (jackknife), 5 .. 95 %%: %.3f .. %.3f -> %s'
+                  % tuple([x[1, int(np.nanargmax(unsure.point[:, 1]))] for x in (unsure.point.T, unsure.se_boot, unsure.se_jack,
+                                                                                  unsure.quantiles[:, 0], unsure.quantiles[:, 2])]
+                          + [unsure.path]))
         order = np.argsort(-sens.ST[0])
         print('Sobol: total indices of NSE: %s -> %s'
               % (', '.join('%s %.2f +- %.2f' % (sens.parameters[j], sens.ST[0, j], sens.ST_conf[0, j]) for j in order[:4]), sens.file))

@@ -486,6 +486,72 @@ int32_t smart_sobol_max_resamples(void);
 int64_t smart_sobol_lds_capacity(void);
 
 /*
+ * Score uncertainty: the seven objective functions of an existing discharge matrix under resampling of WINDOWS of report
+ * steps -- a block bootstrap over hydrological years, a leave-one-year-out jackknife (Clark et al. 2021, Water Resour.
+ * Res. 57) -- for every sample: the point value, the replicates' mean, standard deviation and order statistics.
+ *   sim[R][ld] sample-minor (the layout smart_run_ensemble_hip writes), obs[R] (NaN = missing), window[R] int32 with the
+ *   convention of smart_objfn_windows_hip (-1 = no window, else 0 .. n_windows-1), counts[n_resamples][n_windows] uint16,
+ *   point[N][SMART_OBJFN_WINDOW_COLS], stats[SMART_OBJFN_WINDOW_COLS][2 + n_probs][N] (sample-minor: stats[s][c] is a
+ *   contiguous [N] vector), replicates[n_resamples][SMART_OBJFN_WINDOW_COLS][N] or NULL, workspace: device pointers;
+ *   probs[n_probs]: HOST pointer, read before the call returns, each in (0, 1], n_probs <= SMART_QUANTILES_MAX_PROBS;
+ *   transform / eps as for smart_objfn_windows_hip.  Asynchronous on stream; allocates nothing: the workspace is the
+ *   caller's, smart_bootstrap_workspace_bytes says how much.
+ * The valid rows of window w are { r : window[r] == w, obs[r] not NaN }.  Replicate b is the multiset union over w of the
+ * valid rows of window w, each taken counts[b][w] times; its seven values NSE, KGE, KGEc, KGEa, KGEb, PBias, RMSE are the
+ * formulas of montecarlo.py:193-209 (smart_objfn_hip's) on (f(sim), f(obs)) over that multiset, f the transform.  The
+ * POINT value is the replicate with every count 1.  The entry does not know what a year is: a bootstrap and a jackknife
+ * differ in counts only.  Rules:
+ *   - a replicate with fewer than two rows is NaN in all seven columns, for every sample;
+ *   - a (sample, window) that meets a transformed value that is not finite (smart_objfn_windows_hip's list; sums of finite
+ *     values that overflow count the same way) makes NaN every replicate of that sample whose count for that window is
+ *     not 0; a replicate with count 0 there is not affected;
+ *   - a non-finite f(obs[r]) in window w does the same for every sample.
+ * Outputs:
+ *   point[n][s]                      the point value
+ *   stats[s][SMART_BOOT_MEAN][n]     the mean over the n_resamples replicates
+ *   stats[s][SMART_BOOT_STD][n]      their standard deviation, ddof = 1; NaN for n_resamples < 2
+ *                                    (both are NaN if any replicate of that (sample, score) is NaN)
+ *   stats[s][2 + k][n]               the max(1, ceil(probs[k] * n_resamples))-th smallest of the replicate values:
+ *                                    numpy.quantile(..., method='inverted_cdf'), an element of the set, NaN sorts last
+ *   replicates[b][s][n]              every replicate, where the caller wants them (tests, small n_resamples, the whole
+ *                                    distribution); stats are the same bits with and without
+ * n_resamples == 0 is allowed: point only; counts, probs and stats may be NULL and stats is not touched.
+ * The matrix is read once: per (window, sample) five one-pass moments about constants of the whole launch (the mean of
+ * the finite f(obs), and the sample's transformed value in the first valid row), which add across windows; a replicate is
+ * counts x moments (smartpy_amd/csrc/smart_bootstrap.hip).  Mean and standard deviation accumulate in replicate order in
+ * the one-pass form about the point value.  Deterministic: no floating-point atomics, every sum has one association for a
+ * given (n_samples, n_reports, window array, n_resamples): two launches give the same bits, whatever ld.
+ * Errors (all found before the device is touched, every output left as it was): SMART_E_NULL sim, obs, window or point
+ * missing, counts, probs or stats missing with n_resamples > 0, workspace missing; SMART_E_SIZE n_samples or n_reports < 1
+ * or >= 2^31, ld < n_samples, n_windows outside 1 .. smart_bootstrap_max_windows(), n_resamples outside
+ * 0 .. smart_bootstrap_max_resamples(), n_probs outside 1 .. 16 or a probability outside (0, 1] with n_resamples > 0, eps
+ * negative or not finite, workspace_bytes too small; SMART_E_MODE unknown transform; then SMART_E_NO_DEVICE.
+ */
+#define SMART_BOOT_MEAN 0
+#define SMART_BOOT_STD 1
+int smart_objfn_bootstrap_hip(int64_t n_samples, int64_t n_reports, const double *sim, int64_t ld, const double *obs,
+                              const int32_t *window, int32_t n_windows, int32_t transform, double eps,
+                              const uint16_t *counts, int32_t n_resamples, const double *probs, int32_t n_probs,
+                              double *point, double *stats, double *replicates, void *workspace, int64_t workspace_bytes,
+                              void *stream);
+
+/* The workspace smart_objfn_bootstrap_hip needs, in bytes: the moments of every (window, sample), 40 * n_windows *
+ * n_samples bytes, and the replicates and order statistics of one CHUNK of samples -- the entry walks the samples in chunks
+ * of a multiple of 64 (at least 64, at most 16,384) whose 7 * n_resamples values per sample stay below 128 MiB, so the
+ * second part does not grow with n_samples.  with_replicates (the caller passes a replicates buffer) does not change the
+ * answer in this version: the chunk is where the order statistics are taken; the argument is part of the entry so that a
+ * version that takes them in the caller's buffer needs no new ABI.  A negative SMART_E_SIZE for sizes the entry refuses.
+ * Needs no device. */
+int64_t smart_bootstrap_workspace_bytes(int64_t n_samples, int32_t n_windows, int32_t n_resamples, int32_t with_replicates);
+
+/* The largest n_windows of smart_objfn_bootstrap_hip (64: one lane of a wavefront per window holds a replicate's counts).
+ * Needs no device. */
+int32_t smart_bootstrap_max_windows(void);
+
+/* The largest n_resamples of one call (4,096, inside the sort capacity of the order statistics).  Needs no device. */
+int32_t smart_bootstrap_max_resamples(void);
+
+/*
  * Pareto selection: for every row of a score matrix, the number of rows that dominate it over n_objectives selected
  * columns, each with a direction.  0 = the row is on the Pareto front (no row beats it on every selected score at once).
  *   scores[n_rows][ld] (row-major: a row's scores together, ld > the largest selected column), eligible [n_rows] bytes

@@ -30,6 +30,7 @@ FDC_METHODS = {'auto': 0, 'sort': 1, 'select': 2}              # SMART_FDC_*
 SIGNATURE_NAMES = ['MEAN', 'BFI', 'FLASHINESS', 'AC1', 'RLD', 'RECESSION', 'PEAK', 'PEAK_ROW', 'HIGH_COUNT',
                    'HIGH_DURATION', 'LOW_COUNT', 'LOW_DURATION']     # SMART_SIG_*, in column order
 SIGNATURE_COLS = len(SIGNATURE_NAMES)
+BOOT_MEAN, BOOT_STD = 0, 1                                       # SMART_BOOT_*: the rows of stats in front of the quantiles
 SOBOL_MAX_PARAMS = 16
 PARETO_MAX_OBJECTIVES = 16
 PARETO_DIRECTIONS = {'max': 0, 'min': 1, 'target': 2}           # SMART_PARETO_*
@@ -89,6 +90,13 @@ SYMBOLS = {
     'smart_sobol_workspace_bytes': (ctypes.c_int64, [ctypes.c_int64, ctypes.c_int32, ctypes.c_int64, ctypes.c_int32]),
     'smart_sobol_max_resamples': (ctypes.c_int32, []),
     'smart_sobol_lds_capacity': (ctypes.c_int64, []),
+    'smart_objfn_bootstrap_hip': (ctypes.c_int, [ctypes.c_int64, ctypes.c_int64, _dp, ctypes.c_int64, _dp, _dp,
+                                                 ctypes.c_int32, ctypes.c_int32, ctypes.c_double, _dp, ctypes.c_int32,
+                                                 ctypes.POINTER(ctypes.c_double), ctypes.c_int32, _dp, _dp, _dp, _dp,
+                                                 ctypes.c_int64, _dp]),
+    'smart_bootstrap_workspace_bytes': (ctypes.c_int64, [ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32]),
+    'smart_bootstrap_max_windows': (ctypes.c_int32, []),
+    'smart_bootstrap_max_resamples': (ctypes.c_int32, []),
     'smart_pareto_counts_hip': (ctypes.c_int, [ctypes.c_int64, _dp, ctypes.c_int64, ctypes.POINTER(ctypes.c_int32),
                                                ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_double),
                                                ctypes.c_int32, _dp, _dp, _dp, ctypes.c_int64, _dp]),

@@ -353,6 +353,131 @@ def sobol_indices(values, n_base, n_params, counts=None):
     return SobolResult(S1, ST, moments, S1_std, ST_std)
 
 
+def bootstrap_max_windows():
+    """The largest number of windows objective_functions_bootstrap takes in one call (no device needed)."""
+    return int(_lib.lib().smart_bootstrap_max_windows())
+
+
+def bootstrap_max_resamples():
+    """The largest number of replicates of one objective_functions_bootstrap call (no device needed)."""
+    return int(_lib.lib().smart_bootstrap_max_resamples())
+
+
+def _eligible_windows(who, n_windows, eligible):
+    """-> the indices of the eligible windows among 0 .. n_windows-1 (every window for None), ascending"""
+    W = int(n_windows)
+    if W < 1:
+        raise SmartEngineError(-2, "{}: n_windows must be at least 1 (got {}).".format(who, n_windows))
+    if eligible is None:
+        return W, np.arange(W)
+    mask = np.asarray(eligible)
+    if mask.shape != (W,):
+        raise SmartEngineError(-2, "{}: eligible has shape {} where one entry per window ({},) is expected."
+                               .format(who, mask.shape, W))
+    return W, np.flatnonzero(mask != 0)
+
+
+def bootstrap_counts(n_windows, resamples, seed=None, eligible=None):
+    """The block-bootstrap counts of objective_functions_bootstrap -> [resamples, n_windows] uint16 on the host.  With E
+    eligible windows (all of them for eligible=None, else the nonzero entries of the [n_windows] mask, ascending) replicate
+    b draws E of them with replacement: numpy.random.Generator(PCG64(seed)).integers(E, size=(resamples, E)), draw j of
+    row b naming the j-th eligible window, and counts[b, w] is how often replicate b drew window w.  Every row sums to E;
+    the column of a window that is not eligible is 0."""
+    W, idx = _eligible_windows('bootstrap_counts', n_windows, eligible)
+    B, E = int(resamples), len(idx)
+    if B < 0 or B > bootstrap_max_resamples():
+        raise SmartEngineError(-2, "bootstrap_counts: {} resamples, between 0 and {} per call."
+                               .format(resamples, bootstrap_max_resamples()))
+    if E < 1:
+        raise SmartEngineError(-2, "bootstrap_counts: no window is eligible.")
+    if E > 65535:
+        raise SmartEngineError(-2, "bootstrap_counts: a count of {} does not fit the uint16 of the kernel.".format(E))
+    draws = np.random.Generator(np.random.PCG64(seed)).integers(E, size=(B, E))
+    counts = np.zeros((B, W), dtype=np.int64)
+    for b in range(B):
+        counts[b, idx] = np.bincount(draws[b], minlength=E)
+    return np.ascontiguousarray(counts.astype(np.uint16))
+
+
+def jackknife_counts(n_windows, eligible=None):
+    """The leave-one-window-out counts of objective_functions_bootstrap -> [E, n_windows] uint16 on the host: row i holds
+    1 for every eligible window but the i-th of them, which it leaves out, and 0 for the windows that are not eligible."""
+    W, idx = _eligible_windows('jackknife_counts', n_windows, eligible)
+    counts = np.zeros((len(idx), W), dtype=np.uint16)
+    counts[:, idx] = 1
+    counts[np.arange(len(idx)), idx] = 0
+    return counts
+
+
+class BootstrapResult(object):
+    """Device tensors of one objective_functions_bootstrap call: point [N, 7]; stats [7, 2 + K, N] -- per score the mean
+    and the standard deviation (ddof = 1) over the replicates, then the K quantiles, stats[s, c] a contiguous [N] vector --
+    or None without replicates (counts with no row); replicates [B, 7, N] or None; probs, the K probabilities."""
+
+    def __init__(self, point, stats, replicates, probs):
+        self.point, self.stats, self.replicates, self.probs = point, stats, replicates, probs
+
+
+def objective_functions_bootstrap(discharge_report_major, obs, windows, counts, probs=(0.05, 0.5, 0.95), n_windows=None,
+                                  transform='none', eps=0.0, replicates=False):
+    """The seven objective functions NSE, KGE, KGEc, KGEa, KGEb, PBias, RMSE of every column of a stored [R, N] discharge
+    matrix under resampling of WINDOWS of report steps -> BootstrapResult.  windows: [R] integers as for
+    objective_functions_windows; counts: [B, W] uint16 from bootstrap_counts or jackknife_counts (or a device tensor of
+    those 16-bit patterns, uint16 or int16) -- replicate b takes the observed report steps of window w counts[b, w] times;
+    the point value takes every window once.  probs: K <= 16 probabilities in (0, 1]: numpy's 'inverted_cdf' quantiles of
+    the B replicate values, an element of the set.  transform / eps as for objective_functions_windows.  replicates=True
+    also returns every replicate, [B, 7, N].  A replicate with fewer than two report steps is NaN; a (window, sample) that
+    meets a transformed value that is not finite makes NaN the replicates that draw that window, and no other; mean and
+    standard deviation are NaN where a replicate is.  The matrix is read once; the workspace of the call is sized and
+    owned here (include/smart_amd.h: smart_objfn_bootstrap_hip)."""
+    who = 'objective_functions_bootstrap'
+    L = _lib.lib()
+    code = _code(who, 'transform', _lib.TRANSFORMS, transform)
+    win, W = _checked_windows(who, windows, n_windows)
+    sim = discharge_report_major
+    if len(sim.shape) != 2 or sim.shape[0] != len(win):
+        raise SmartEngineError(-2, "{}: {} window ids for a matrix of shape {}.".format(who, len(win), tuple(sim.shape)))
+    if W > bootstrap_max_windows():
+        raise SmartEngineError(-2, "{}: {} windows, at most {} per call.".format(who, W, bootstrap_max_windows()))
+    if not hasattr(counts, 'shape') or len(counts.shape) != 2 or counts.shape[1] != W or \
+            str(counts.dtype).split('.')[-1] not in (('uint16', 'int16') if isinstance(counts, torch.Tensor) else ('uint16',)):
+        raise SmartEngineError(-2, "{}: counts must be uint16 [resamples, {}] (engine.bootstrap_counts, "
+                                   "engine.jackknife_counts), not {} {}."
+                               .format(who, W, getattr(counts, 'dtype', type(counts).__name__),
+                                       tuple(getattr(counts, 'shape', ()))))
+    B = int(counts.shape[0])
+    if B > bootstrap_max_resamples():
+        raise SmartEngineError(-2, "{}: {} resamples, at most {} per call.".format(who, B, bootstrap_max_resamples()))
+    q, q_ptr = _probs(probs)
+    K = q.size
+    if K < 1 or K > _lib.QUANTILES_MAX_PROBS or not np.all((q > 0.0) & (q <= 1.0)):
+        raise SmartEngineError(-2, "{}: the probabilities must be 1 .. {} values in (0, 1], not {}."
+                               .format(who, _lib.QUANTILES_MAX_PROBS, q.tolist()))
+    eps = float(eps)
+    if not (eps >= 0.0) or np.isinf(eps):
+        raise SmartEngineError(-2, "{}: eps {} must be finite and >= 0.".format(who, eps))
+    # ---- from here on the device
+    sim, R, N, ld = _matrix(sim)
+    dev = sim.device
+    obs = _as_device(obs, dev, (R,))
+    win = _window_ids(win, dev)
+    point = torch.empty((N, _lib.OBJFN_WINDOW_COLS), dtype=torch.float64, device=dev)
+    stats = torch.empty((_lib.OBJFN_WINDOW_COLS, 2 + K, N), dtype=torch.float64, device=dev) if B else None
+    reps = torch.empty((B, _lib.OBJFN_WINDOW_COLS, N), dtype=torch.float64, device=dev) if replicates and B else None
+    if N == 0:
+        return BootstrapResult(point, stats, reps, q)
+    if B:
+        if not isinstance(counts, torch.Tensor):
+            counts = torch.from_numpy(np.ascontiguousarray(counts).view(np.int16))     # (the same 16 bits)
+        counts = counts.to(dev).contiguous()
+    work, need = _workspace(int(L.smart_bootstrap_workspace_bytes(N, W, B, 1 if reps is not None else 0)), dev)
+    with torch.cuda.device(dev):
+        _lib.check(L.smart_objfn_bootstrap_hip(N, R, sim.data_ptr(), ld, obs.data_ptr(), win.data_ptr(), W, code, eps,
+                                               counts.data_ptr() if B else None, B, q_ptr, K, point.data_ptr(),
+                                               _ptr(stats), _ptr(reps), _ptr(work), need, _stream(dev)))
+    return BootstrapResult(point, stats, reps, q)
+
+
 def pareto_max_objectives():
     """The largest number of objectives of one pareto_counts call (no device needed)."""
     return int(_lib.lib().smart_pareto_max_objectives())

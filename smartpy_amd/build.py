@@ -42,6 +42,10 @@ UNITS = {
     # Sobol sensitivity indices of a Saltelli design (point estimates and bootstrap): default flags, NaNs honoured -- a
     # value that is not finite has to reach the one sum that finds it
     'smart_sobol.hip': [],
+    # block bootstrap and jackknife of the objective functions (per-window moments, counts x moments per replicate):
+    # default flags, NaNs honoured -- a value that is not finite has to reach the sums of its window, and a NaN replicate
+    # the mean and the standard deviation
+    'smart_bootstrap.hip': [],
     # Pareto selection over the scores of the analyses (dominance counts): default flags, NaNs honoured -- the keys are
     # compared as IEEE says
     'smart_pareto.hip': [],

@@ -1,5 +1,5 @@
 // smart_analysis_capi.hip -- the C ABI of the analyses of a stored discharge matrix sim[R][ld] (include/smart_amd.h):
-// objective functions, weighted quantiles, objective functions per window, flow duration curves, hydrological signatures, Sobol indices, and of
+// objective functions, weighted quantiles, objective functions per window, flow duration curves, hydrological signatures, Sobol indices, the block bootstrap of the objective functions, and of
 // the Pareto selection over the scores they leave, with their capacity and workspace entries -- validation and launch --
 // and the one kernel among them that has no unit of its own, smart_objfn_matrix.  Every refusal comes before the device is asked for; the rules the entries share are the
 // static helpers below, which take the entry's name for the text.
@@ -173,6 +173,20 @@ static const char *sobol_sizes(int64_t n_base, int32_t n_params, int64_t n_rows,
         snprintf(text, len, "n_rows %lld must be in 1 .. 2^31 - 1", (long long)n_rows);
     else if (n_resamples < 0 || n_resamples > sobol_max_resamples())
         snprintf(text, len, "n_resamples %d must be in 0 .. %d", (int)n_resamples, sobol_max_resamples());
+    else
+        return nullptr;
+    return text;
+}
+
+// the size rules of smart_objfn_bootstrap_hip, shared with smart_bootstrap_workspace_bytes; 0 or the text of the refusal
+static const char *bootstrap_sizes(int64_t n_samples, int32_t n_windows, int32_t n_resamples, char *text, size_t len)
+{
+    if (n_samples < 1 || n_samples > 0x7fffffffll)
+        snprintf(text, len, "n_samples %lld must be in 1 .. 2^31 - 1", (long long)n_samples);
+    else if (n_windows < 1 || n_windows > bootstrap_max_windows())
+        snprintf(text, len, "n_windows %d must be in 1 .. %d", (int)n_windows, bootstrap_max_windows());
+    else if (n_resamples < 0 || n_resamples > bootstrap_max_resamples())
+        snprintf(text, len, "n_resamples %d must be in 0 .. %d", (int)n_resamples, bootstrap_max_resamples());
     else
         return nullptr;
     return text;
@@ -383,6 +397,59 @@ int64_t smart_sobol_workspace_bytes(int64_t n_base, int32_t n_params, int64_t n_
 int32_t smart_sobol_max_resamples(void) { return sobol_max_resamples(); }
 
 int64_t smart_sobol_lds_capacity(void) { return sobol_lds_capacity(); }
+
+int smart_objfn_bootstrap_hip(int64_t n_samples, int64_t n_reports, const double *sim, int64_t ld, const double *obs,
+                              const int32_t *window, int32_t n_windows, int32_t transform, double eps,
+                              const uint16_t *counts, int32_t n_resamples, const double *probs, int32_t n_probs,
+                              double *point, double *stats, double *replicates, void *workspace, int64_t workspace_bytes,
+                              void *stream)
+{
+    static const char entry[] = "smart_objfn_bootstrap_hip";
+    int rc;
+    if (!sim || !obs || !window || !point)
+        return fail(SMART_E_NULL, "%s: sim, obs, window and point are required (%s is NULL)", entry,
+                    !sim ? "sim" : (!obs ? "obs" : (!window ? "window" : "point")));
+    if (n_resamples > 0 && (!counts || !probs || !stats))
+        return fail(SMART_E_NULL, "%s: n_resamples %d needs counts, probs and stats (%s is NULL)", entry, (int)n_resamples,
+                    !counts ? "counts" : (!probs ? "probs" : "stats"));
+    char text[160];
+    if (bootstrap_sizes(n_samples, n_windows, n_resamples, text, sizeof text))
+        return fail(SMART_E_SIZE, "%s: %s", entry, text);
+    if (n_reports < 1)
+        return fail(SMART_E_SIZE, "%s: need n_reports >= 1 (got %lld)", entry, (long long)n_reports);
+    if (ld < n_samples)
+        return fail(SMART_E_SIZE, "%s: ld %lld is less than n_samples %lld", entry, (long long)ld, (long long)n_samples);
+    if ((rc = reports_fit(entry, n_reports)))
+        return rc;
+    if (n_resamples > 0) {
+        if (n_probs < 1 || n_probs > SMART_QUANTILES_MAX_PROBS)
+            return fail(SMART_E_SIZE, "%s: n_probs %d must be in 1 .. %d", entry, (int)n_probs, SMART_QUANTILES_MAX_PROBS);
+        if ((rc = probs_inside(entry, probs, n_probs, /*zero_too=*/false)))
+            return rc;
+    }
+    if ((rc = eps_usable(entry, eps)) || (rc = transform_known(entry, transform)) ||
+        (rc = workspace_fits(entry, /*for_objfn=*/false, workspace, workspace_bytes,
+                             bootstrap_workspace_bytes((long)n_samples, (int)n_windows, (int)n_resamples,
+                                                       replicates != nullptr))) ||
+        (rc = device_ready()))
+        return rc;
+    launch_bootstrap((long)n_samples, (long)n_reports, sim, (long)ld, obs, window, (int)n_windows, (int)transform, eps,
+                     counts, (int)n_resamples, probs, n_resamples > 0 ? (int)n_probs : 0, point, stats, replicates,
+                     (double *)workspace, (hipStream_t)stream);
+    return launched();
+}
+
+int64_t smart_bootstrap_workspace_bytes(int64_t n_samples, int32_t n_windows, int32_t n_resamples, int32_t with_replicates)
+{
+    char text[160];
+    if (bootstrap_sizes(n_samples, n_windows, n_resamples, text, sizeof text))
+        return SMART_E_SIZE;
+    return bootstrap_workspace_bytes((long)n_samples, (int)n_windows, (int)n_resamples, with_replicates != 0);
+}
+
+int32_t smart_bootstrap_max_windows(void) { return bootstrap_max_windows(); }
+
+int32_t smart_bootstrap_max_resamples(void) { return bootstrap_max_resamples(); }
 
 int smart_pareto_counts_hip(int64_t n_rows, const double *scores, int64_t ld, const int32_t *columns,
                             const int32_t *direction, const double *target, int32_t n_objectives, const uint8_t *eligible,

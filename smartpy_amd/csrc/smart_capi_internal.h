@@ -56,6 +56,14 @@ long sobol_workspace_bytes();
 void launch_sobol(long n, int k, long M, const double *y, long ld, double *s1, double *st, double *moments,
                   const unsigned short *counts, int B, double *s1_std, double *st_std, hipStream_t s);
 
+// ---- smart_bootstrap.hip
+int bootstrap_max_windows();
+int bootstrap_max_resamples();
+long bootstrap_workspace_bytes(long N, int W, int B, bool with_replicates);
+void launch_bootstrap(long N, long R, const double *sim, long ld, const double *obs, const int *window, int W,
+                      int transform, double eps, const unsigned short *counts, int B, const double *probs, int K,
+                      double *point, double *stats, double *replicates, double *ws, hipStream_t s);
+
 // ---- smart_pareto.hip
 long pareto_workspace_bytes(long N, int M);
 void launch_pareto(long N, const double *scores, long ld, const int *columns, const int *direction, const double *target,

@@ -565,6 +565,8 @@ from .analysis import (objective_functions, quantiles_sort_capacity, weighted_qu
                        objfn_max_windows, objective_functions_windows, flow_duration_sort_capacity, flow_duration,
                        SIGNATURE_NAMES, signatures,
                        sobol_max_resamples, sobol_lds_capacity, sobol_counts, SobolResult, sobol_indices,
+                       bootstrap_max_windows, bootstrap_max_resamples, bootstrap_counts, jackknife_counts,
+                       BootstrapResult, objective_functions_bootstrap,
                        pareto_max_objectives, pareto_counts, pareto_ranks)
 
 

@@ -350,6 +350,67 @@ class MonteCarlo(object):
         """`<out>/<catchment>.SMART.<func>.signatures`: beside the sampling database, whatever its format."""
         return self._side_file('.signatures')
 
+    # ---- score uncertainty ---------------------------------------------------------------------------------
+    def score_uncertainty(self, windows='hydro_year', resamples=1000, seed=None, quantiles=(0.05, 0.5, 0.95),
+                          transform='none', eps=None, min_steps=None, start_month=10, split=None, write=False):
+        """How much of NSE, KGE, KGEc, KGEa, KGEb, PBias and RMSE of every row of the sample is sampling noise of the
+        windows that happen to lie in the evaluation period: a block bootstrap over the windows (hydrological years)
+        with a leave-one-window-out jackknife, after Clark et al. 2021 (Water Resour. Res. 57).  The eligible windows
+        are those with at least `min_steps` observed report steps (None: 1 with fewer than 3 windows, else 90 % of the
+        longest window's observed count); report steps of the other windows take no part, in the point value either;
+        fewer than three eligible windows is an error.  Each of `resamples` replicates draws as many windows as are
+        eligible, with replacement (engine.bootstrap_counts with `seed`); the scores of a replicate are those of its
+        report steps pooled.  -> windows.ScoreUncertainty: point value, mean, standard error (se_boot) and `quantiles`
+        (numpy 'inverted_cdf', at most 16) of the replicates, and the jackknife standard error (se_jack).  windows /
+        start_month / split / transform / eps as for window_objective_functions.  One launch of its own over the sample,
+        then two calls on the [R, N] matrix where it lies, which read it once each.  write=True also writes
+        `<out>/<catchment>.SMART.<func>.uncertainty` (one line per sample in the sample's order, the float32 '%.6e' of
+        the sampling database; header NSE,NSE_se,NSE_jse,NSE_q0.05,... score by score).  Under torch.distributed every
+        rank that calls this computes all rows itself (no collective); rank 0 alone writes."""
+        from .. import engine, windows as swin
+        self._check_transform(transform)
+        ids, labels = self._resolve_windows(windows, start_month, split)
+        n = self._sample.shape[0]
+        self._check_observations()
+        W = len(labels)
+        probs = [float(q) for q in np.atleast_1d(np.asarray(quantiles, dtype=np.float64))]
+        if eps is None:
+            eps = swin.default_eps(transform, self.model.nd_flow)
+        eligible, min_steps = swin.eligible_windows(self.model.nd_flow, ids, W, min_steps)
+        E = int(eligible.sum())
+        if E < 3:
+            raise Exception("The uncertainty of the scores needs at least three windows with {:g} or more observed report "
+                            "steps to resample; {} of the {} windows have that many.".format(min_steps, E, W))
+        boot = engine.bootstrap_counts(W, resamples, seed=seed, eligible=eligible)
+        jack = engine.jackknife_counts(W, eligible=eligible)
+        used = np.where(eligible[np.maximum(ids, 0)] & (ids >= 0), ids, -1).astype(np.int32)
+        k, K = len(swin.OBJ_FN_NAMES), len(probs)
+        if n == 0:      # e.g. GLUE with no behavioural set: nothing to launch
+            on_device, point = None, np.empty((0, k))
+            mean = se_boot = se_jack = np.empty((k, 0))
+            quant = np.empty((k, K, 0))
+        else:
+            out, obs = self._launch_stored()
+            b = engine.objective_functions_bootstrap(out.discharge_report_major, obs, used, boot, probs=probs, n_windows=W,
+                                                     transform=transform, eps=eps)
+            j = engine.objective_functions_bootstrap(out.discharge_report_major, obs, used, jack, probs=probs, n_windows=W,
+                                                     transform=transform, eps=eps)
+            on_device, point = b.stats, b.point.cpu().numpy()
+            stats = on_device.cpu().numpy() if on_device is not None else np.full((k, 2 + K, n), np.nan)
+            mean, se_boot, quant = stats[:, 0], stats[:, 1], stats[:, 2:]
+            se_jack = swin.jackknife_factor(E) * j.stats[:, 1].cpu().numpy()
+        path = None
+        if write and sdist.rank_world()[0] == 0:
+            path = self.uncertainty_file
+            _write_uncertainty_file(path, probs, point, se_boot, se_jack, quant)
+        return swin.ScoreUncertainty(labels, eligible, min_steps, transform, float(eps), probs, point, mean, se_boot, quant,
+                                     se_jack, on_device, path, seed, int(resamples))
+
+    @property
+    def uncertainty_file(self):
+        """`<out>/<catchment>.SMART.<func>.uncertainty`: beside the sampling database, whatever its format."""
+        return self._side_file('.uncertainty')
+
     # ---- the per-sample protocol of the reference (spotpy setup class) ------------------------------------
     def parameters(self):
         return np.array([p() for p in self.params])
@@ -413,6 +474,21 @@ def _write_signatures_file(path, labels, values):
     if n == 0:
         return
     append_float32_rows(path, np.ascontiguousarray(np.transpose(values, (2, 0, 1)).reshape(n, W * k).astype(np.float32)))
+
+
+def _write_uncertainty_file(path, probs, point, se_boot, se_jack, quant):
+    """point [N, 7], se_boot and se_jack [7, N], quant [7, K, N] -> header line + one line per sample, score by score:
+    the point value, its bootstrap and jackknife standard errors, the K quantiles (the sampling database's float32
+    '%.6e', formatted by the library)."""
+    from .. import windows as swin
+    with open(path, 'w', newline='', encoding='utf8') as f:
+        f.write(swin.uncertainty_header_line(probs))
+    n, k = point.shape
+    if n == 0:
+        return
+    table = np.concatenate([point[:, :, None], se_boot.T[:, :, None], se_jack.T[:, :, None],
+                            np.transpose(quant, (2, 0, 1))], axis=2).reshape(n, k * (3 + quant.shape[1]))
+    append_float32_rows(path, np.ascontiguousarray(table.astype(np.float32)))
 
 
 def _write_fdc_file(path, exceedance, labels, transform, curves, values):

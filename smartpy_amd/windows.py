@@ -146,8 +146,55 @@ class FlowDuration(object):
         self.values, self.device_values, self.file = values, device_values, file
 
 
+# ---- score uncertainty ----------------------------------------------------------------------------------------------
+def eligible_windows(obs, ids, n_windows, min_steps=None):
+    """Which windows take part in MonteCarlo.score_uncertainty -> (bool mask [W], the threshold used): those with at least
+    `min_steps` observed (non-missing) report steps.  min_steps=None: 1 if there are fewer than 3 windows, otherwise 90 %
+    of the longest window's observed count -- the "complete years" rule of Clark et al. 2021 (Water Resour. Res. 57)."""
+    obs, ids = np.asarray(obs, dtype=np.float64), np.asarray(ids)
+    observed = np.array([int(np.sum((ids == w) & ~np.isnan(obs))) for w in range(n_windows)], dtype=np.int64)
+    if min_steps is None:
+        min_steps = 1 if n_windows < 3 else 0.9 * float(observed.max())
+    return observed >= min_steps, float(min_steps)
+
+
+def jackknife_factor(n_eligible):
+    """se_jack = jackknife_factor(E) x std(ddof=1) of the E leave-one-out values = sqrt((E - 1) / E x sum (t_i - mean)^2)"""
+    E = float(n_eligible)
+    return np.sqrt((E - 1.0) ** 2 / E)
+
+
+def uncertainty_header_columns(quantiles, names=OBJ_FN_NAMES):
+    """The column names of a `.uncertainty` file, score by score: NSE, NSE_se, NSE_jse, NSE_q0.05, ..."""
+    return [col for name in names for col in
+            [name, name + '_se', name + '_jse'] + ['{}_q{:g}'.format(name, q) for q in quantiles]]
+
+
+def uncertainty_header_line(quantiles, names=OBJ_FN_NAMES):
+    return ','.join(uncertainty_header_columns(quantiles, names)) + '\n'
+
+
+class ScoreUncertainty(object):
+    """What MonteCarlo.score_uncertainty returns: `names` (the seven objective functions), `labels` (one per window),
+    `eligible` (bool [W]: the windows that were resampled), `min_steps`, `transform`, `eps`, `probs` (the K quantile
+    probabilities), `point` (numpy [N, 7], every eligible window once), `mean` and `se_boot` ([7, N]: mean and standard
+    deviation, ddof = 1, over the bootstrap replicates), `quantiles` ([7, K, N]), `se_jack` ([7, N]: the jackknife
+    standard error sqrt((E - 1) / E x sum (t_i - mean)^2) over the E leave-one-window-out values), `device_stats` (the
+    bootstrap call's [7, 2 + K, N] device tensor, or None for an empty sample: device_stats[s, c] is a contiguous [N]
+    vector that goes to selection.condition_mask / pareto_rows / Pareto(extra=) as it is), `path` (the file written, or
+    None), `seed` and `resamples`."""
+
+    def __init__(self, labels, eligible, min_steps, transform, eps, probs, point, mean, se_boot, quantiles, se_jack,
+                 device_stats, path, seed, resamples):
+        self.names = list(OBJ_FN_NAMES)
+        self.labels, self.eligible, self.min_steps = list(labels), np.asarray(eligible, dtype=bool), min_steps
+        self.transform, self.eps, self.probs = transform, eps, [float(q) for q in probs]
+        self.point, self.mean, self.se_boot, self.quantiles, self.se_jack = point, mean, se_boot, quantiles, se_jack
+        self.device_stats, self.path, self.seed, self.resamples = device_stats, path, seed, resamples
+
+
 # ---- hydrological signatures ----------------------------------------------------------------------------------------
-from ._lib import SIGNATURE_NAMES       # noqa: E402 -- the twelve columns of a window, SMART_SIG_* (names only: no library is loaded)
+from ._lib import SIGNATURE_NAMES      # noqa: E402 -- the twelve columns of a window, SMART_SIG_* (names only: no library is loaded)
 
 
 def default_alpha(report_days):
