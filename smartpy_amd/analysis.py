@@ -35,7 +35,9 @@ def _matrix(sim):
 
 
 def _window_ids(win, device):
-    """checked window ids (_checked_windows) -> contiguous int32 tensor on the device"""
+    """checked window ids (_windows) -> contiguous int32 tensor on the device; None (one window) stays None"""
+    if win is None:
+        return None
     if not isinstance(win, torch.Tensor):
         win = torch.from_numpy(np.ascontiguousarray(win.astype(np.int32)))
     return win.to(device=device, dtype=torch.int32).contiguous()
@@ -115,27 +117,48 @@ def weighted_quantiles(discharge_report_major, probs, weights=None, method='auto
     return out
 
 
-def _checked_windows(who, windows, n_windows):
-    """The window ids of a call, checked where they lie (host array or device tensor), before anything is moved or
-    launched -> (flat ids, W)."""
+def _windows(who, sim, windows, n_windows, optional=False):
+    """The windows= argument of a call on the matrix `sim`, checked where the ids lie (host array or device tensor),
+    before anything is moved or launched -> (flat ids, W).  Where it is `optional`, None is one window holding every
+    row -> (None, 1)."""
+    shape = tuple(sim.shape)
+    if windows is None and optional:
+        if n_windows is not None and int(n_windows) != 1:
+            raise SmartEngineError(-2, "{}: n_windows = {} without windows.".format(who, n_windows))
+        if len(shape) != 2:
+            raise SmartEngineError(-2, "{}: a matrix [R, N] is needed, not shape {}.".format(who, shape))
+        return None, 1
     if isinstance(windows, torch.Tensor):
         win = windows.reshape(-1)
-        if win.dtype.is_floating_point or win.dtype == torch.bool:
-            raise SmartEngineError(-2, "{}: windows must be integers.".format(who))
-        top = int(win.max()) if win.numel() else -1
+        integers = not (win.dtype.is_floating_point or win.dtype == torch.bool)
     else:
         win = np.asarray(windows).reshape(-1)
-        if win.dtype.kind not in 'iu':
-            raise SmartEngineError(-2, "{}: windows must be integers.".format(who))
-        top = int(win.max()) if win.size else -1
-    W = top + 1 if n_windows is None else int(n_windows)
+        integers = win.dtype.kind in 'iu'
+    if not integers:
+        raise SmartEngineError(-2, "{}: windows must be integers.".format(who))
+    W = (int(win.max()) + 1 if len(win) else 0) if n_windows is None else int(n_windows)
     if W < 1:
         raise SmartEngineError(-2, "{}: no window (n_windows = {}).".format(who, W))
     bad = int(((win < -1) | (win >= W)).sum())
     if bad:
         raise SmartEngineError(-2, "{}: {} of the {} window ids are outside -1 .. {}."
                                .format(who, bad, len(win), W - 1))
+    if len(shape) != 2 or shape[0] != len(win):
+        raise SmartEngineError(-2, "{}: {} window ids for a matrix of shape {}.".format(who, len(win), shape))
     return win, W
+
+
+def _counts16(who, counts, axis, size, layout):
+    """The counts= argument of a call: 16-bit counts [., .] with `size` entries along `axis` -- uint16 on the host, uint16
+    or int16 (the same 16 bits) on a device -> a tensor where they lie, a host array as its int16 view."""
+    shape = tuple(getattr(counts, 'shape', ()))
+    kinds = ('uint16', 'int16') if isinstance(counts, torch.Tensor) else ('uint16',)
+    if len(shape) != 2 or shape[axis] != size or str(getattr(counts, 'dtype', '')).split('.')[-1] not in kinds:
+        raise SmartEngineError(-2, "{}: counts must be uint16 {}, not {} {}."
+                               .format(who, layout, getattr(counts, 'dtype', type(counts).__name__), shape))
+    if not isinstance(counts, torch.Tensor):
+        counts = torch.from_numpy(np.ascontiguousarray(counts).view(np.int16))
+    return counts
 
 
 def objfn_max_windows():
@@ -152,12 +175,8 @@ def objective_functions_windows(discharge_report_major, obs, windows, n_windows=
     that meets a transformed value that is not finite is NaN (include/smart_amd.h: smart_objfn_windows_hip)."""
     L = _lib.lib()
     code = _code('objective_functions_windows', 'transform', _lib.TRANSFORMS, transform)
-    win, W = _checked_windows('objective_functions_windows', windows, n_windows)
-    sim = discharge_report_major
-    if len(sim.shape) != 2 or sim.shape[0] != len(win):
-        raise SmartEngineError(-2, "objective_functions_windows: {} window ids for a matrix of shape {}."
-                               .format(len(win), tuple(sim.shape)))
-    sim, R, N, ld = _matrix(sim)
+    win, W = _windows('objective_functions_windows', discharge_report_major, windows, n_windows)
+    sim, R, N, ld = _matrix(discharge_report_major)
     obs = _as_device(obs, sim.device, (R,))
     win = _window_ids(win, sim.device)
     out = torch.empty((W, N, _lib.OBJFN_WINDOW_COLS), dtype=torch.float64, device=sim.device)
@@ -191,25 +210,13 @@ def flow_duration(discharge_report_major, probs, obs=None, windows=None, n_windo
     how = _code('flow_duration', 'method', _lib.FDC_METHODS, method)
     if objfn and obs is None:
         raise SmartEngineError(-1, "flow_duration: the objective functions of the curve need obs.")
-    sim = discharge_report_major
-    if windows is None:
-        win, W = None, 1
-        if n_windows is not None and int(n_windows) != 1:
-            raise SmartEngineError(-2, "flow_duration: n_windows = {} without windows.".format(n_windows))
-    else:
-        win, W = _checked_windows('flow_duration', windows, n_windows)
-        if len(sim.shape) != 2 or sim.shape[0] != len(win):
-            raise SmartEngineError(-2, "flow_duration: {} window ids for a matrix of shape {}."
-                                   .format(len(win), tuple(sim.shape)))
-    if len(sim.shape) != 2:
-        raise SmartEngineError(-2, "flow_duration: a matrix [R, N] is needed, not shape {}.".format(tuple(sim.shape)))
-    sim, R, N, ld = _matrix(sim)
+    win, W = _windows('flow_duration', discharge_report_major, windows, n_windows, optional=True)
+    sim, R, N, ld = _matrix(discharge_report_major)
     q, q_ptr = _probs(probs)
     lo, hi = (float(x) for x in segment)
     if obs is not None:
         obs = _as_device(obs, sim.device, (R,))
-    if win is not None:
-        win = _window_ids(win, sim.device)
+    win = _window_ids(win, sim.device)
     quant = torch.empty((W, q.size, N), dtype=torch.float64, device=sim.device)
     scores = torch.empty((W, N, _lib.OBJFN_WINDOW_COLS), dtype=torch.float64, device=sim.device) if objfn else None
     if N == 0:
@@ -238,28 +245,16 @@ def signatures(discharge_report_major, obs=None, windows=None, n_windows=None, a
     alpha = float(alpha)
     if not (0.0 < alpha < 1.0):
         raise SmartEngineError(-2, "signatures: alpha {} must lie inside (0, 1).".format(alpha))
-    sim = discharge_report_major
-    if windows is None:
-        win, W = None, 1
-        if n_windows is not None and int(n_windows) != 1:
-            raise SmartEngineError(-2, "signatures: n_windows = {} without windows.".format(n_windows))
-    else:
-        win, W = _checked_windows('signatures', windows, n_windows)
-        if len(sim.shape) != 2 or sim.shape[0] != len(win):
-            raise SmartEngineError(-2, "signatures: {} window ids for a matrix of shape {}."
-                                   .format(len(win), tuple(sim.shape)))
-    if len(sim.shape) != 2:
-        raise SmartEngineError(-2, "signatures: a matrix [R, N] is needed, not shape {}.".format(tuple(sim.shape)))
+    win, W = _windows('signatures', discharge_report_major, windows, n_windows, optional=True)
     if thresholds is not None and tuple(thresholds.shape if hasattr(thresholds, 'shape')
                                         else np.shape(thresholds)) != (W, 2):
         raise SmartEngineError(-2, "signatures: thresholds must be (lo, hi) per window, shape ({}, 2), not {}."
                                .format(W, tuple(np.shape(thresholds))))
     L = _lib.lib()
-    sim, R, N, ld = _matrix(sim)
+    sim, R, N, ld = _matrix(discharge_report_major)
     if obs is not None:
         obs = _as_device(obs, sim.device, (R,))
-    if win is not None:
-        win = _window_ids(win, sim.device)
+    win = _window_ids(win, sim.device)
     pulse = None if thresholds is None else _as_device(thresholds, sim.device, (W, 2))
     out = torch.empty((W, _lib.SIGNATURE_COLS, N), dtype=torch.float64, device=sim.device)
     if N == 0:
@@ -325,10 +320,7 @@ def sobol_indices(values, n_base, n_params, counts=None):
                                    "n_params = {} in 1 .. {}.".format(y.shape[1], n_base, n_params, _lib.SOBOL_MAX_PARAMS))
     B = 0
     if counts is not None:
-        if len(counts.shape) != 2 or counts.shape[0] != n or \
-                str(counts.dtype).split('.')[-1] not in (('uint16', 'int16') if isinstance(counts, torch.Tensor) else ('uint16',)):
-            raise SmartEngineError(-2, "sobol_indices: counts must be uint16 [n_base, resamples] (engine.sobol_counts), "
-                                       "not {} {}.".format(counts.dtype, tuple(counts.shape)))
+        counts = _counts16('sobol_indices', counts, 0, n, '[n_base, resamples] (engine.sobol_counts)')
         B = int(counts.shape[1])
         if B > sobol_max_resamples():
             raise SmartEngineError(-2, "sobol_indices: {} resamples, at most {} per call.".format(B, sobol_max_resamples()))
@@ -341,8 +333,6 @@ def sobol_indices(values, n_base, n_params, counts=None):
     if M == 0:
         return SobolResult(S1, ST, moments, None, None)
     if B > 0:
-        if not isinstance(counts, torch.Tensor):
-            counts = torch.from_numpy(np.ascontiguousarray(counts).view(np.int16))     # (the same 16 bits)
         counts = counts.to(dev).contiguous()
         S1_std, ST_std = torch.empty_like(S1), torch.empty_like(ST)
     work, need = _workspace(int(L.smart_sobol_workspace_bytes(n, k, M, B)), dev)
@@ -433,18 +423,11 @@ def objective_functions_bootstrap(discharge_report_major, obs, windows, counts, 
     who = 'objective_functions_bootstrap'
     L = _lib.lib()
     code = _code(who, 'transform', _lib.TRANSFORMS, transform)
-    win, W = _checked_windows(who, windows, n_windows)
-    sim = discharge_report_major
-    if len(sim.shape) != 2 or sim.shape[0] != len(win):
-        raise SmartEngineError(-2, "{}: {} window ids for a matrix of shape {}.".format(who, len(win), tuple(sim.shape)))
+    win, W = _windows(who, discharge_report_major, windows, n_windows)
     if W > bootstrap_max_windows():
         raise SmartEngineError(-2, "{}: {} windows, at most {} per call.".format(who, W, bootstrap_max_windows()))
-    if not hasattr(counts, 'shape') or len(counts.shape) != 2 or counts.shape[1] != W or \
-            str(counts.dtype).split('.')[-1] not in (('uint16', 'int16') if isinstance(counts, torch.Tensor) else ('uint16',)):
-        raise SmartEngineError(-2, "{}: counts must be uint16 [resamples, {}] (engine.bootstrap_counts, "
-                                   "engine.jackknife_counts), not {} {}."
-                               .format(who, W, getattr(counts, 'dtype', type(counts).__name__),
-                                       tuple(getattr(counts, 'shape', ()))))
+    counts = _counts16(who, counts, 1, W,
+                       '[resamples, {}] (engine.bootstrap_counts, engine.jackknife_counts)'.format(W))
     B = int(counts.shape[0])
     if B > bootstrap_max_resamples():
         raise SmartEngineError(-2, "{}: {} resamples, at most {} per call.".format(who, B, bootstrap_max_resamples()))
@@ -457,7 +440,7 @@ def objective_functions_bootstrap(discharge_report_major, obs, windows, counts, 
     if not (eps >= 0.0) or np.isinf(eps):
         raise SmartEngineError(-2, "{}: eps {} must be finite and >= 0.".format(who, eps))
     # ---- from here on the device
-    sim, R, N, ld = _matrix(sim)
+    sim, R, N, ld = _matrix(discharge_report_major)
     dev = sim.device
     obs = _as_device(obs, dev, (R,))
     win = _window_ids(win, dev)
@@ -467,8 +450,6 @@ def objective_functions_bootstrap(discharge_report_major, obs, windows, counts, 
     if N == 0:
         return BootstrapResult(point, stats, reps, q)
     if B:
-        if not isinstance(counts, torch.Tensor):
-            counts = torch.from_numpy(np.ascontiguousarray(counts).view(np.int16))     # (the same 16 bits)
         counts = counts.to(dev).contiguous()
     work, need = _workspace(int(L.smart_bootstrap_workspace_bytes(N, W, B, 1 if reps is not None else 0)), dev)
     with torch.cuda.device(dev):

@@ -62,7 +62,7 @@ __global__ __launch_bounds__(WX *WR *kWave) void smart_objfn_matrix(long N, long
     for (; r < R; r += WR)
         add(obs[r], col[r * ld]);
     double m[5] = {A, B, C1, C2, C3};
-    if (WR > 1) {
+    if (WR > 1) { // (sum_wave_moments of smart_window_rows.h is this; called here it moved the kernel's instructions)
 #pragma unroll
         for (int k = 0; k < 5; ++k)
             part[wr][k][lane] = m[k];
@@ -114,6 +114,14 @@ static int windowed_sizes(const char *entry, int64_t n_samples, int64_t n_report
         return rc;
     if (n_windows > objfn_max_windows())
         return fail(SMART_E_SIZE, "%s: n_windows %d, at most %d per call", entry, (int)n_windows, objfn_max_windows());
+    return SMART_OK;
+}
+
+// where the window array is optional: without one there is one window
+static int window_array_given(const char *entry, const int32_t *window, int32_t n_windows)
+{
+    if (!window && n_windows != 1)
+        return fail(SMART_E_SIZE, "%s: n_windows %d without a window array (NULL is one window)", entry, (int)n_windows);
     return SMART_OK;
 }
 
@@ -294,10 +302,9 @@ int smart_flow_duration_hip(int64_t n_samples, int64_t n_reports, const double *
                     !sim ? "sim" : (!probs ? "probs" : "quant"));
     if (objfn && !obs)
         return fail(SMART_E_NULL, "%s: objfn needs obs (obs is NULL)", entry);
-    if ((rc = windowed_sizes(entry, n_samples, n_reports, ld, n_windows, &n_probs)))
+    if ((rc = windowed_sizes(entry, n_samples, n_reports, ld, n_windows, &n_probs)) ||
+        (rc = window_array_given(entry, window, n_windows)))
         return rc;
-    if (!window && n_windows != 1)
-        return fail(SMART_E_SIZE, "%s: n_windows %d without a window array (NULL is one window)", entry, (int)n_windows);
     if (n_probs > SMART_QUANTILES_MAX_PROBS)
         return fail(SMART_E_SIZE, "%s: n_probs %d, at most %d probabilities per call", entry, (int)n_probs,
                     SMART_QUANTILES_MAX_PROBS);
@@ -345,10 +352,9 @@ int smart_signatures_hip(int64_t n_samples, int64_t n_reports, const double *sim
     int rc;
     if (!sim || !sig)
         return fail(SMART_E_NULL, "%s: sim and sig are required (%s is NULL)", entry, !sim ? "sim" : "sig");
-    if ((rc = windowed_sizes(entry, n_samples, n_reports, ld, n_windows, nullptr)))
+    if ((rc = windowed_sizes(entry, n_samples, n_reports, ld, n_windows, nullptr)) ||
+        (rc = window_array_given(entry, window, n_windows)))
         return rc;
-    if (!window && n_windows != 1)
-        return fail(SMART_E_SIZE, "%s: n_windows %d without a window array (NULL is one window)", entry, (int)n_windows);
     if (!(alpha > 0.0 && alpha < 1.0))
         return fail(SMART_E_SIZE, "%s: alpha %g must lie inside (0, 1)", entry, alpha);
     if ((rc = device_ready()))

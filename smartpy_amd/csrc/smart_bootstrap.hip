@@ -28,9 +28,10 @@
 //
 // 1. smart_bootstrap_observed, grid W: every workgroup forms g and r0 with the same fixed-order tree (the same bits in
 //    each), workgroup w the four observation sums of window w.
-// 2. smart_bootstrap_moments, grid (ceil(N / 64), W): the geometry and the in-order LDS row compaction of
-//    smart_objfn_windows (8 wavefronts on the same 64 samples, rows of no window or without an observation never read,
-//    every element of a listed row loaded once), writing the five moments to the workspace [W][5][N] instead of finishing.
+// 2. smart_bootstrap_moments, grid (ceil(N / 64), W): the geometry of smart_objfn_windows and its list, walk and
+//    reduction, all from smart_window_rows.h (8 wavefronts on the same 64 samples, rows of no window or without an
+//    observation never read, every element of a listed row loaded once); the two kernels differ in the observation
+//    reference (g), in where the shift comes from (c_n) and in the end: the five moments go to the workspace [W][5][N].
 // 3. smart_bootstrap_scores, one lane per sample, grid (ceil(cn / 64), up to 32): the wavefronts of the grid's y split the
 //    replicates round-robin (at least four each).  counts[b][.] is wave-uniform: lane w loads counts[b][w] -- one
 //    coalesced read per replicate -- and the count of a window is then a lane read (v_readlane) into a scalar register; a
@@ -56,14 +57,13 @@
 // window array, B): two launches give the same bits, whatever ld.
 #include "smart_capi_internal.h"
 #include "smart_device.h"
+#include "smart_window_rows.h"
 
 namespace smart {
 
-constexpr int kBsWaves = 8;                     // wavefronts per workgroup (moments: on the same 64 samples; scores: over b)
+// (smart_bootstrap_moments has the kWin* geometry of smart_window_rows.h)
+constexpr int kBsWaves = 8;                     // wavefronts per workgroup of _observed and _scores (there: over b)
 constexpr int kBsThreads = kBsWaves * kWave;
-constexpr int kBsChunk = 1024;                  // rows of window[] looked at per compaction
-constexpr int kBsSub = kBsChunk / kBsThreads;   // ... rows per thread in it
-constexpr int kBsUnroll = 4;                    // row segments in flight per lane
 constexpr int kBsMaxWindows = kWave;            // one lane per window holds a replicate's counts
 constexpr int kBsMaxResamples = 4096;
 constexpr int kBsHead = 8;                      // doubles in front of the workspace: g, r0 (-1: no valid row)
@@ -165,16 +165,16 @@ __global__ __launch_bounds__(kBsThreads) void smart_bootstrap_observed(long R, c
 
 // ---- 2. the five moments of every (window, sample) about g and c_n ---------------------------------------------------------
 template <int T>
-__global__ __launch_bounds__(kBsThreads) void smart_bootstrap_moments(long N, long R, const double *__restrict__ sim, long ld,
-                                                                     const double *__restrict__ obs,
-                                                                     const int *__restrict__ window, double eps,
-                                                                     const double *__restrict__ head,
-                                                                     double *__restrict__ mom)
+__global__ __launch_bounds__(kWinThreads) void smart_bootstrap_moments(long N, long R, const double *__restrict__ sim, long ld,
+                                                                      const double *__restrict__ obs,
+                                                                      const int *__restrict__ window, double eps,
+                                                                      const double *__restrict__ head,
+                                                                      double *__restrict__ mom)
 {
-    __shared__ int cnt[kBsSub][kBsWaves];
-    __shared__ int rows[kBsChunk];
-    __shared__ double fes[kBsChunk];
-    __shared__ double part[kBsWaves][5][kWave];
+    __shared__ int cnt[kWinSub][kWinWaves];
+    __shared__ int rows[kWinChunk];
+    __shared__ double fes[kWinChunk];
+    __shared__ double part[kWinWaves][5][kWave];
     const int w = blockIdx.y;
     const int tid = threadIdx.x, lane = tid & (kWave - 1);
     const int wr = __builtin_amdgcn_readfirstlane(tid / kWave);
@@ -200,77 +200,33 @@ __global__ __launch_bounds__(kBsThreads) void smart_bootstrap_moments(long N, lo
         C2 += u * u;
         C3 += (e - g) * u;
     };
-    for (long c0 = 0; c0 < R; c0 += kBsChunk) {
-        bool in[kBsSub];
-        double fe[kBsSub];
-        unsigned long long votes[kBsSub];
-#pragma unroll
-        for (int k = 0; k < kBsSub; ++k) {
-            const long r = c0 + k * kBsThreads + tid;
-            in[k] = false;
-            fe[k] = 0.0;
-            if (r < R && window[r] == w) {
+    for (long c0 = 0; c0 < R; c0 += kWinChunk) {
+        double fe[kWinSub] = {}; // f(obs) of this thread's rows, for the list
+        const int m = list_rows<kWinWaves, kWinSub>(
+            c0, R, wr, cnt,
+            [&](long r, int k) {
+                if (window[r] != w)
+                    return false;
                 const double e = obs[r];
-                if (!is_nan_bits(e)) {
-                    in[k] = true;
-                    fe[k] = flow_transform(T, e, eps);
-                }
-            }
-            votes[k] = __ballot(in[k]);
-            if (lane == 0)
-                cnt[k][wr] = __popcll(votes[k]);
-        }
-        __syncthreads();
-        int m = 0; // list entries so far: sub-chunk after sub-chunk, wavefront after wavefront, lane after lane = row order
-#pragma unroll
-        for (int k = 0; k < kBsSub; ++k) {
-            int before = 0, all = 0;
-#pragma unroll
-            for (int v = 0; v < kBsWaves; ++v) {
-                const int c = cnt[k][v];
-                all += c;
-                before += v < wr ? c : 0;
-            }
-            if (in[k]) {
-                const int pos = m + before + __popcll(votes[k] & ((1ull << lane) - 1ull));
-                rows[pos] = (int)(c0 + k * kBsThreads + tid);
+                if (is_nan_bits(e))
+                    return false;
+                fe[k] = flow_transform(T, e, eps);
+                return true;
+            },
+            [&](int pos, long r, int k) {
+                rows[pos] = (int)r;
                 fes[pos] = fe[k];
-            }
-            m += all;
-        }
-        __syncthreads();
-        m = __builtin_amdgcn_readfirstlane(m);
-        int j = wr;
-        for (; j + (kBsUnroll - 1) * kBsWaves < m; j += kBsUnroll * kBsWaves) {
-            double s[kBsUnroll];
-#pragma unroll
-            for (int k = 0; k < kBsUnroll; ++k)
-                s[k] = col[(long)__builtin_amdgcn_readfirstlane(rows[j + k * kBsWaves]) * ld];
-#pragma unroll
-            for (int k = 0; k < kBsUnroll; ++k)
-                add(fes[j + k * kBsWaves], flow_transform(T, s[k], eps));
-        }
-        for (; j < m; j += kBsWaves)
-            add(fes[j], flow_transform(T, col[(long)__builtin_amdgcn_readfirstlane(rows[j]) * ld], eps));
-        // (the next chunk's barrier behind its counts stands between these reads of the list and its next writes)
+            });
+        walk_listed_rows<T>(wr, m, rows, fes, col, ld, eps, add);
     }
 
     // the wavefronts' partial moments, added in wavefront order
     double mo[5] = {A, B, C1, C2, C3};
-#pragma unroll
-    for (int k = 0; k < 5; ++k)
-        part[wr][k][lane] = mo[k];
-    __syncthreads();
-    if (wr != 0 || !live)
+    if (!sum_wave_moments<kWinWaves>(mo, part, wr, lane, live))
         return;
 #pragma unroll
-    for (int k = 0; k < 5; ++k) {
-        double t = part[0][k][lane];
-#pragma unroll
-        for (int v = 1; v < kBsWaves; ++v)
-            t += part[v][k][lane];
-        mom[((long)w * 5 + k) * N + n] = t;
-    }
+    for (int k = 0; k < 5; ++k)
+        mom[((long)w * 5 + k) * N + n] = mo[k];
 }
 
 // ---- 3. the replicates: counts x moments, the seven scores -----------------------------------------------------------------
@@ -389,7 +345,7 @@ static void launch_bootstrap_moments(long N, long R, const double *sim, long ld,
                                      double eps, double *ws, double *mom, hipStream_t s)
 {
     hipLaunchKernelGGL(smart_bootstrap_observed<T>, dim3((unsigned)W), dim3(kBsThreads), 0, s, R, obs, window, W, eps, ws);
-    hipLaunchKernelGGL(smart_bootstrap_moments<T>, dim3((unsigned)((N + kWave - 1) / kWave), (unsigned)W), dim3(kBsThreads),
+    hipLaunchKernelGGL(smart_bootstrap_moments<T>, dim3((unsigned)((N + kWave - 1) / kWave), (unsigned)W), dim3(kWinThreads),
                        0, s, N, R, sim, ld, obs, window, eps, ws, mom);
 }
 
@@ -399,19 +355,9 @@ void launch_bootstrap(long N, long R, const double *sim, long ld, const double *
 {
     const BootstrapLayout l = bootstrap_layout(N, W, B);
     double *const mom = ws + l.mom;
-    switch (transform) {
-    case SMART_TRANSFORM_SQRT:
-        launch_bootstrap_moments<SMART_TRANSFORM_SQRT>(N, R, sim, ld, obs, window, W, eps, ws, mom, s);
-        break;
-    case SMART_TRANSFORM_LOG:
-        launch_bootstrap_moments<SMART_TRANSFORM_LOG>(N, R, sim, ld, obs, window, W, eps, ws, mom, s);
-        break;
-    case SMART_TRANSFORM_INVERSE:
-        launch_bootstrap_moments<SMART_TRANSFORM_INVERSE>(N, R, sim, ld, obs, window, W, eps, ws, mom, s);
-        break;
-    default:
-        launch_bootstrap_moments<SMART_TRANSFORM_NONE>(N, R, sim, ld, obs, window, W, eps, ws, mom, s);
-    }
+    with_transform(transform, [&](auto t) {
+        launch_bootstrap_moments<decltype(t)::value>(N, R, sim, ld, obs, window, W, eps, ws, mom, s);
+    });
     const long step = B > 0 ? l.chunk : (N < kBsMaxChunk ? N : kBsMaxChunk);
     // wavefronts over the replicates: at least four replicates each, at most 32 workgroups deep
     int deep = (B + 4 * kBsWaves - 1) / (4 * kBsWaves);

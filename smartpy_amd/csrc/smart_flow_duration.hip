@@ -14,7 +14,7 @@
 //
 // SORT FORM (R <= 16,384).  A workgroup of 1,024 threads takes COLS adjacent samples of one window, grid =
 // (ceil(N / COLS), W).  It walks window[] / obs[] in chunks of 1,024 rows, compacts its window's rows in row order into an
-// LDS list (ballot + prefix counts, no atomics: smart_objfn_windows.hip) and loads the COLS-wide pieces of those rows as
+// LDS list (ballot + prefix counts, no atomics: smart_window_rows.h) and loads the COLS-wide pieces of those rows as
 // KEYS into LDS -- 8 bytes per element, 16,384 elements = 128 KiB in every instance (CAP rows x COLS = 1,024 x 16 ..
 // 16,384 x 1), 12 KiB more for the row list and the reduction: 140 of the 160 KiB a gfx950 workgroup may open.
 //   LDS LAYOUT.  Interleaved: rank i of column c lies at flat position i * COLS + c.  A compare-exchange at row distance
@@ -45,6 +45,7 @@
 #include "smart_capi_internal.h"
 #include "smart_device.h"
 #include "smart_order_keys.h"
+#include "smart_window_rows.h"
 #include <cstdlib>
 
 namespace smart {
@@ -57,33 +58,15 @@ constexpr long kFdcCapacity = 16384;     // rows of the sort form: the COLS = 1 
 constexpr int kFdcHead = 8;              // doubles in front of a window's sorted f(obs) in the workspace:
                                          // m, i0, i1, mean, sum, sum (e - mean)^2, sum (e - mean), usable (1 / 0)
 
-// the rows of window w among [c0, c0 + kFdcChunk), in row order, into rows[]; -> how many (the same in every thread).
-// The caller puts a barrier between its last read of rows[] and the next call.
-// (The compaction inside smart_objfn_windows is the same idea written for its own shape -- two rows per thread, f(obs)
-// carried along into the list -- and stays apart.)
-__device__ inline int fdc_compact(long c0, long R, const double *__restrict__ obs, const int *__restrict__ window, int w,
-                                  int *cnt, int *rows)
+// the rows of window w among [c0, c0 + kFdcChunk), in row order, into rows[]; -> how many (list_rows, smart_window_rows.h:
+// one row per thread, no payload).  The caller puts a barrier between its last read of rows[] and the next call.
+__device__ __forceinline__ int fdc_compact(long c0, long R, const double *__restrict__ obs,
+                                           const int *__restrict__ window, int w, int (*cnt)[kFdcWaves], int *rows)
 {
-    const int tid = threadIdx.x, lane = tid & (kWave - 1), wr = tid / kWave;
-    const long r = c0 + tid;
-    bool in = r < R && (!window || window[r] == w);
-    if (in && obs)
-        in = !is_nan_bits(obs[r]);
-    const unsigned long long votes = __ballot(in);
-    if (lane == 0)
-        cnt[wr] = __popcll(votes);
-    __syncthreads();
-    int before = 0, all = 0;
-#pragma unroll
-    for (int v = 0; v < kFdcWaves; ++v) {
-        const int c = cnt[v];
-        all += c;
-        before += v < wr ? c : 0;
-    }
-    if (in)
-        rows[before + __popcll(votes & ((1ull << lane) - 1ull))] = (int)r;
-    __syncthreads();
-    return all;
+    const int wr = threadIdx.x / kWave;  // (a vector value: the sixteen compares of list_rows measured faster so)
+    return list_rows<kFdcWaves, 1>(
+        c0, R, wr, cnt, [&](long r, int) { return (!window || window[r] == w) && (!obs || !is_nan_bits(obs[r])); },
+        [&](int pos, long r, int) { rows[pos] = (int)r; });
 }
 
 // rows of the network for m rows: a power of two >= max(m, 2) with at least one wavefront of flat positions
@@ -161,7 +144,7 @@ __global__ __launch_bounds__(kFdcThreads) void smart_fdc_observed(long R, const 
     __shared__ unsigned long long keys[kFdcElems];
     __shared__ double sh[kFdcThreads];
     __shared__ int rows[kFdcChunk];
-    __shared__ int cnt[kFdcWaves];
+    __shared__ int cnt[1][kFdcWaves];
     const int w = blockIdx.x, tid = threadIdx.x;
     int m = 0;
     for (long c0 = 0; c0 < R; c0 += kFdcChunk) {
@@ -226,7 +209,7 @@ __global__ __launch_bounds__(kFdcThreads) void smart_fdc_sort(long N, long R, co
     __shared__ unsigned long long keys[kFdcElems];
     __shared__ double sh[kFdcThreads];
     __shared__ int rows[kFdcChunk];
-    __shared__ int cnt[kFdcWaves];
+    __shared__ int cnt[1][kFdcWaves];
     const int w = blockIdx.y, tid = threadIdx.x;
     long bx = blockIdx.x;
     if (remap) {

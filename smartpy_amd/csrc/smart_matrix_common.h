@@ -1,6 +1,8 @@
 // smart_matrix_common.h -- what the kernels that read a stored discharge matrix sim[R][ld] share (smart_objfn_matrix,
-// smart_objfn_windows, smart_fdc_*, smart_quantiles_*, smart_sobol_*), and the few constants and bit tests every kernel
-// of the library takes from ONE definition (smart_device.h includes this file).  No arithmetic of the model lives here.
+// smart_objfn_windows, smart_fdc_*, smart_signatures, smart_quantiles_*, smart_sobol_*, smart_bootstrap_*), and the few
+// constants and bit tests every kernel of the library takes from ONE definition (smart_device.h includes this file).  No
+// arithmetic of the model lives here.  What the kernels that walk the rows of a WINDOW share on top of it -- the in-order
+// row list, the walk over it, the reduction of the partial moments -- is smart_window_rows.h.
 #pragma once
 
 #include "../../include/smart_amd.h"

@@ -14,13 +14,11 @@
 // geometry of smart_objfn_matrix).  A workgroup
 //   1. forms the window's observation statistics (count, mean, sum, sum of squared deviations) in two passes over
 //      window[] and obs[] -- R * 12 bytes, L2-resident -- with a fixed-order LDS tree;
-//   2. walks window[] in chunks of kWinChunk rows: every thread tests rows of its own, the rows that belong to the window
-//      and carry an observation are compacted IN ROW ORDER into an LDS list (row, f(obs[row])) -- ballot + prefix counts,
-//      no atomics -- and the wavefronts take the list entries round-robin, kWinUnroll row segments (512 contiguous bytes
-//      each) in flight per lane.  Rows of no window, of another window, or without an observation are never read;
+//   2. walks window[] in chunks of kWinChunk rows: the rows that belong to the window and carry an observation are listed
+//      IN ROW ORDER as (row, f(obs[row])) in LDS (list_rows, smart_window_rows.h) and the wavefronts take the list entries
+//      round-robin (walk_listed_rows).  Rows of no window, of another window, or without an observation are never read;
 //      every element of a listed row is loaded once, by one lane of one wavefront;
-//   3. adds the wavefronts' partial moments through LDS in wavefront order and finishes.
-// The row of a list entry is wave-uniform (readfirstlane): the address arithmetic of a load is scalar.
+//   3. adds the wavefronts' partial moments through LDS in wavefront order (sum_wave_moments) and finishes.
 //
 // Moments: the one-pass form of smart_objfn_matrix about the window's observation mean and a per-sample shift, the
 // sample's FIRST in-window transformed value (loaded by wavefront 0, handed to the others through LDS, and accumulated by
@@ -33,14 +31,10 @@
 // window array): two launches give the same bits.
 #include "smart_capi_internal.h"
 #include "smart_device.h"
+#include "smart_window_rows.h"
 
 namespace smart {
 
-constexpr int kWinWaves = 8;                      // wavefronts per workgroup, all on the same 64 samples
-constexpr int kWinThreads = kWinWaves * kWave;
-constexpr int kWinChunk = 1024;                   // rows of window[] looked at per compaction
-constexpr int kWinSub = kWinChunk / kWinThreads;  // ... rows per thread in it
-constexpr int kWinUnroll = 4;                     // row segments in flight per lane
 // each workgroup re-reads window[] and obs[] (R * 12 bytes, three times): W times per 64 samples over the launch.  The
 // bound keeps that beside the matrix traffic for windows of a useful length, and the grid's y inside its 65,535.
 constexpr int kWinMaxWindows = 1024;
@@ -124,8 +118,7 @@ __global__ __launch_bounds__(kWinThreads) void smart_objfn_windows(long N, long 
     }
     const double ebar = st[1];
 
-    // ---- 2. the rows of the window, chunk by chunk (the compaction is the idea of fdc_compact, smart_flow_duration.hip,
-    // which takes one row per thread and lists rows alone; the two stay apart)
+    // ---- 2. the rows of the window, chunk by chunk
     const double *const col = sim + n;
     double shift = 0.0;
     bool have_shift = false; // (the same in every thread of the workgroup)
@@ -139,45 +132,22 @@ __global__ __launch_bounds__(kWinThreads) void smart_objfn_windows(long N, long 
         C3 += (e - ebar) * u;
     };
     for (long c0 = 0; c0 < R; c0 += kWinChunk) {
-        bool in[kWinSub];
-        double fe[kWinSub];
-        unsigned long long votes[kWinSub];
-#pragma unroll
-        for (int k = 0; k < kWinSub; ++k) {
-            const long r = c0 + k * kWinThreads + tid;
-            in[k] = false;
-            fe[k] = 0.0;
-            if (r < R && window[r] == w) {
+        double fe[kWinSub] = {}; // f(obs) of this thread's rows, for the list
+        const int m = list_rows<kWinWaves, kWinSub>(
+            c0, R, wr, cnt,
+            [&](long r, int k) {
+                if (window[r] != w)
+                    return false;
                 const double e = obs[r];
-                if (!is_nan_bits(e)) {
-                    in[k] = true;
-                    fe[k] = flow_transform(T, e, eps);
-                }
-            }
-            votes[k] = __ballot(in[k]);
-            if (lane == 0)
-                cnt[k][wr] = __popcll(votes[k]);
-        }
-        __syncthreads();
-        int m = 0; // list entries so far: sub-chunk after sub-chunk, wavefront after wavefront, lane after lane = row order
-#pragma unroll
-        for (int k = 0; k < kWinSub; ++k) {
-            int before = 0, all = 0;
-#pragma unroll
-            for (int v = 0; v < kWinWaves; ++v) {
-                const int c = cnt[k][v];
-                all += c;
-                before += v < wr ? c : 0;
-            }
-            if (in[k]) {
-                const int pos = m + before + __popcll(votes[k] & ((1ull << lane) - 1ull));
-                rows[pos] = (int)(c0 + k * kWinThreads + tid);
+                if (is_nan_bits(e))
+                    return false;
+                fe[k] = flow_transform(T, e, eps);
+                return true;
+            },
+            [&](int pos, long r, int k) {
+                rows[pos] = (int)r;
                 fes[pos] = fe[k];
-            }
-            m += all;
-        }
-        __syncthreads();
-        m = __builtin_amdgcn_readfirstlane(m);
+            });
         if (m == 0)
             continue;
         int j = wr;
@@ -195,35 +165,13 @@ __global__ __launch_bounds__(kWinThreads) void smart_objfn_windows(long N, long 
                 j += kWinWaves;
             }
         }
-        for (; j + (kWinUnroll - 1) * kWinWaves < m; j += kWinUnroll * kWinWaves) {
-            double s[kWinUnroll];
-#pragma unroll
-            for (int k = 0; k < kWinUnroll; ++k)
-                s[k] = col[(long)__builtin_amdgcn_readfirstlane(rows[j + k * kWinWaves]) * ld];
-#pragma unroll
-            for (int k = 0; k < kWinUnroll; ++k)
-                add(fes[j + k * kWinWaves], flow_transform(T, s[k], eps));
-        }
-        for (; j < m; j += kWinWaves)
-            add(fes[j], flow_transform(T, col[(long)__builtin_amdgcn_readfirstlane(rows[j]) * ld], eps));
+        walk_listed_rows<T>(j, m, rows, fes, col, ld, eps, add);
     }
 
     // ---- 3. the wavefronts' partial moments, added in wavefront order
     double mo[5] = {A, B, C1, C2, C3};
-#pragma unroll
-    for (int k = 0; k < 5; ++k)
-        part[wr][k][lane] = mo[k];
-    __syncthreads();
-    if (wr != 0 || !live)
+    if (!sum_wave_moments<kWinWaves>(mo, part, wr, lane, live))
         return;
-#pragma unroll
-    for (int k = 0; k < 5; ++k) {
-        double t = part[0][k][lane];
-#pragma unroll
-        for (int v = 1; v < kWinWaves; ++v)
-            t += part[v][k][lane];
-        mo[k] = t;
-    }
     double o[8];
     finish_objectives(st, mo[0], mo[1], mo[2], mo[3], mo[4], 0.0, quiet_nan(), o);
     const bool ok = is_finite_bits(mo[2]); // some f(sim) of this sample was not finite (header comment)
@@ -238,23 +186,10 @@ void launch_objfn_windows(long N, long R, const double *sim, long ld, const doub
                           int transform, double eps, double *objfn, hipStream_t s)
 {
     const dim3 grid((unsigned)((N + kWave - 1) / kWave), (unsigned)W), block(kWinThreads);
-    switch (transform) {
-    case SMART_TRANSFORM_SQRT:
-        hipLaunchKernelGGL(smart_objfn_windows<SMART_TRANSFORM_SQRT>, grid, block, 0, s, N, R, sim, ld, obs, window, eps,
+    with_transform(transform, [&](auto t) {
+        hipLaunchKernelGGL(smart_objfn_windows<decltype(t)::value>, grid, block, 0, s, N, R, sim, ld, obs, window, eps,
                            objfn);
-        break;
-    case SMART_TRANSFORM_LOG:
-        hipLaunchKernelGGL(smart_objfn_windows<SMART_TRANSFORM_LOG>, grid, block, 0, s, N, R, sim, ld, obs, window, eps,
-                           objfn);
-        break;
-    case SMART_TRANSFORM_INVERSE:
-        hipLaunchKernelGGL(smart_objfn_windows<SMART_TRANSFORM_INVERSE>, grid, block, 0, s, N, R, sim, ld, obs, window, eps,
-                           objfn);
-        break;
-    default:
-        hipLaunchKernelGGL(smart_objfn_windows<SMART_TRANSFORM_NONE>, grid, block, 0, s, N, R, sim, ld, obs, window, eps,
-                           objfn);
-    }
+    });
 }
 
 } // namespace smart

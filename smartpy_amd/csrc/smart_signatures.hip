@@ -6,9 +6,8 @@
 // Geometry.  One lane per sample, grid = (ceil(N / 256), W), a workgroup = kSigWaves wavefronts over 256 ADJACENT samples
 // of the same window.  The clamped Lyne-Hollick filter is a true recurrence along time: a lane walks every row of its
 // sample, in ascending row order.  A workgroup
-//   1. walks window[] and obs[] in chunks of kSigChunk rows: every thread tests rows of its own, and the window's valid rows
-//      are compacted IN ROW ORDER into an LDS list of (row, has-pair flag) in one word -- ballot + prefix counts, no atomics
-//      (the idea of smart_objfn_windows and of fdc_compact; the copies stay apart, as those files say);
+//   1. walks window[] and obs[] in chunks of kSigChunk rows: the window's valid rows are listed IN ROW ORDER -- the time
+//      order of the recurrences -- as (row, has-pair flag) in one word in LDS (list_rows, smart_window_rows.h);
 //   2. every wavefront walks the WHOLE list, each for its own 64 samples, kSigUnroll row segments (512 contiguous bytes
 //      each) in flight per lane.  Rows of no window, of another window, or without an observation are never read; every
 //      element of a listed row is loaded once.
@@ -22,7 +21,7 @@
 // of its own: the sum of x never becomes finite again, and ONE test of it at the end empties the (window, sample).
 //
 // State: sixteen doubles and eleven 32-bit counts and flags per lane, in registers for the whole walk.  With the loads in
-// flight and the logarithm's temporaries hipcc takes 115 VGPRs and no scratch under __launch_bounds__(256, 4): four
+// flight and the logarithm's temporaries hipcc takes 113 VGPRs and no scratch under __launch_bounds__(256, 4): four
 // wavefronts per SIMD (left alone it takes 154, three wavefronts).  The pair is an `if` WITHOUT an else -- what a row
 // without a pair restarts is set before it: an if / else on the uniform flag makes hipcc keep the old and the new
 // state side by side (51 VGPRs spilled).
@@ -32,7 +31,7 @@
 // Not built: a split of the time axis across wavefronts.  The associative form of the clamped filter composes clamp-affine
 // maps, which changes the bits and needs two sweeps.
 #include "smart_capi_internal.h"
-#include "smart_matrix_common.h"
+#include "smart_window_rows.h"
 
 namespace smart {
 
@@ -50,9 +49,8 @@ __global__ __launch_bounds__(kSigThreads, kSigWavesPerSimd) void smart_signature
     __shared__ int cnt[kSigSub][kSigWaves];
     __shared__ unsigned rows[kSigChunk]; // (row << 1) | has-pair: a row is below 2^31
     const int w = blockIdx.y;
-    const int tid = threadIdx.x, lane = tid & (kWave - 1);
-    const int wr = __builtin_amdgcn_readfirstlane(tid / kWave);
-    long n = (long)blockIdx.x * kSigThreads + tid;
+    const int wr = __builtin_amdgcn_readfirstlane(threadIdx.x / kWave);
+    long n = (long)blockIdx.x * kSigThreads + threadIdx.x;
     const bool live = n < N;
     if (!live)
         n = N - 1;
@@ -116,36 +114,16 @@ __global__ __launch_bounds__(kSigThreads, kSigWavesPerSimd) void smart_signature
     };
 
     for (long c0 = 0; c0 < R; c0 += kSigChunk) {
-        bool in[kSigSub], pair[kSigSub];
-        unsigned long long votes[kSigSub];
-#pragma unroll
-        for (int k = 0; k < kSigSub; ++k) {
-            const long r = c0 + k * kSigThreads + tid;
-            in[k] = r < R && valid(r);
-            pair[k] = in[k] && r >= 1 && valid(r - 1);
-            votes[k] = __ballot(in[k]);
-            if (lane == 0)
-                cnt[k][wr] = __popcll(votes[k]);
-        }
-        __syncthreads();
-        int listed = 0; // list entries so far: sub-chunk after sub-chunk, wavefront after wavefront, lane after lane = row order
-#pragma unroll
-        for (int k = 0; k < kSigSub; ++k) {
-            int before = 0, all = 0;
-#pragma unroll
-            for (int v = 0; v < kSigWaves; ++v) {
-                const int c = cnt[k][v];
-                all += c;
-                before += v < wr ? c : 0;
-            }
-            if (in[k]) {
-                const int pos = listed + before + __popcll(votes[k] & ((1ull << lane) - 1ull));
-                rows[pos] = ((unsigned)(c0 + k * kSigThreads + tid) << 1) | (pair[k] ? 1u : 0u);
-            }
-            listed += all;
-        }
-        __syncthreads();
-        listed = __builtin_amdgcn_readfirstlane(listed);
+        bool pair[kSigSub] = {}; // row r - 1 is valid too, for the list
+        const int listed = list_rows<kSigWaves, kSigSub>(
+            c0, R, wr, cnt,
+            [&](long r, int k) {
+                if (!valid(r))
+                    return false;
+                pair[k] = r >= 1 && valid(r - 1);
+                return true;
+            },
+            [&](int pos, long r, int k) { rows[pos] = ((unsigned)r << 1) | (pair[k] ? 1u : 0u); });
         int j = 0;
         if (!have_shift && listed > 0) { // entry 0 of the first chunk that has one: the sample's shift
             const unsigned e = __builtin_amdgcn_readfirstlane(rows[0]);

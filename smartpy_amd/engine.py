@@ -561,7 +561,7 @@ class SingleRun(object):
 
 
 # the analyses of a stored discharge matrix live in analysis.py; every name of them is a name of this module as well
-from .analysis import (objective_functions, quantiles_sort_capacity, weighted_quantiles, _checked_windows,  # noqa: E402,F401
+from .analysis import (objective_functions, quantiles_sort_capacity, weighted_quantiles,  # noqa: E402,F401
                        objfn_max_windows, objective_functions_windows, flow_duration_sort_capacity, flow_duration,
                        SIGNATURE_NAMES, signatures,
                        sobol_max_resamples, sobol_lds_capacity, sobol_counts, SobolResult, sobol_indices,
