@@ -76,6 +76,9 @@ def main():
     # what a GLUE analysis is run for: the likelihood-weighted prediction bounds of the behavioural ensemble at every
     # report step (one launch of its own; the [R, N] matrix stays on the GPU, only the [3, R] bounds come back)
     bounds = glue.prediction_bounds(quantiles=(0.05, 0.5, 0.95), likelihood='NSE', write=True)
+    # ... and whether the predictive distribution behind them is any good: CRPS, spread and the PIT of every report step
+    # (one launch of its own, only [5, R] comes back), skill against climatology, PIT histogram and reliability index
+    verified = glue.ensemble_verification(likelihood='NSE', bins=10, write=True)
     # split-sample and low-flow scores of the behavioural sets: KGE per hydrological year and the NSE of ln(Q + eps), one
     # launch each; the [W, N, 7] values stay on the GPU (per_year.device_values) for conditioning on every year
     per_year = glue.window_objective_functions('hydro_year', write=True)
@@ -101,6 +104,9 @@ def main():
         print('GLUE: %d behavioural sets -> %s' % (len(glue.behavioural_params), glue.db_file))
         print('      5 / 50 / 95 %% prediction bounds hold %.1f %% of the observations -> %s'
               % (100 * bounds.containment, bounds.file))
+        print('      mean CRPS %.4g (spread %.4g), skill against climatology %.3f, reliability %.3f, PIT histogram %s -> %s'
+              % (verified.mean_crps, verified.mean_spread, verified.skill, verified.reliability,
+                 ' '.join('%.0f' % c for c in verified.pit_histogram), verified.file))
         if len(glue.behavioural_params):
             print('      KGE per hydrological year, median over the sets: %s -> %s'
                   % (', '.join('%s: %.3f' % (y, np.nanmedian(per_year.values[w][:, 1])) for w, y in enumerate(per_year.labels)),

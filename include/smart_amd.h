@@ -588,6 +588,59 @@ int64_t smart_pareto_workspace_bytes(int64_t n_rows, int32_t n_objectives);
 int smart_pareto_max_objectives(void);
 
 /*
+ * Ensemble verification along the SAMPLE axis, per report step: is the predictive distribution of the (behavioural,
+ * likelihood-weighted) ensemble any good against the observation.  For one report step with members x_n = sim[r][n],
+ * weights w_n >= 0 (NULL: all 1) and the observation y = obs[r]: the members with w_n == 0 take no part at all -- they
+ * are dropped when the step is loaded, a NaN or an infinity of weight zero decides nothing.  With the live members
+ * sorted ascending x_(1) <= ... <= x_(M), W their total weight, A_i = sum of w_(j) over j <= i (prefix sums, left to
+ * right), B_i = sum of w_(j) over j > i (suffix sums, right to left; never 1 - A_i / W), P_i = A_i / W, Q_i = B_i / W:
+ *   SMART_ENS_CRPS      the integral of (F(x) - 1[x >= y])^2 dx = max(x_(1) - y, 0) + max(y - x_(M), 0) +
+ *                       sum over i < M of (m_i - x_(i)) P_i^2 + (x_(i+1) - m_i) Q_i^2, m_i = min(max(y, x_(i)), x_(i+1))
+ *   SMART_ENS_SPREAD    the integral of F (1 - F) dx = sum over i < M of (x_(i+1) - x_(i)) P_i Q_i  (= E|X - X'| / 2, so
+ *                       CRPS = E|X - y| - SPREAD; computed as this sum of non-negative terms, not as that difference)
+ *   SMART_ENS_PIT_LOW   sum of w over { x < y } / W         SMART_ENS_PIT_HIGH   sum of w over { x <= y } / W
+ *   SMART_ENS_MEAN      sum of w x / W, added in sorted order
+ * -0.0 and +0.0 are one value.  W == 0, or a live member that is a NaN or an infinity: all five NaN for that step.  An
+ * observation that is not finite (missing), or obs == NULL (every one missing): CRPS and both PITs NaN; SPREAD and MEAN
+ * do not depend on it.  The weights MUST be finite and >= 0: a precondition, not checked on the device.
+ *   sim[R][ld] sample-minor (the layout smart_run_ensemble_hip writes), weights[N] or NULL, obs[R] or NULL,
+ *   out[SMART_ENSEMBLE_SCORE_COLS][R] (every column a contiguous [R] vector): device pointers.  Asynchronous on stream;
+ *   allocates nothing: the workspace is the caller's.
+ * One workgroup per report step, in one of two forms (smartpy_amd/csrc/smart_ensemble_scores.hip):
+ *   SMART_ENS_LDS     the step sorted in LDS, both scans and the terms in registers; no workspace;
+ *                     n_samples <= smart_ensemble_scores_lds_capacity(), else SMART_E_SIZE
+ *   SMART_ENS_GLOBAL  any n_samples <= 2^24: the step sorted in the workspace (long stages there, short ones block by
+ *                     block in LDS); the report steps go in batches of as many as the workspace holds, one launch each
+ *   SMART_ENS_AUTO    LDS within its capacity, global beyond
+ * Deterministic: no floating-point atomics, every sum has one association for a given (n_samples, form), so two launches
+ * give the same bits -- whatever the batches.  The two forms associate differently and agree to rounding only.
+ * Errors (all found before the device is touched): SMART_E_NULL sim or out missing, the global form without a workspace;
+ * SMART_E_SIZE a size < 1, ld < n_samples, n_reports >= 2^31, n_samples > 2^24, the LDS form beyond its capacity, a
+ * workspace that does not hold one step; SMART_E_MODE unknown method; then SMART_E_NO_DEVICE without a HIP device.
+ */
+#define SMART_ENSEMBLE_SCORE_COLS 5
+#define SMART_ENS_CRPS 0
+#define SMART_ENS_SPREAD 1
+#define SMART_ENS_PIT_LOW 2
+#define SMART_ENS_PIT_HIGH 3
+#define SMART_ENS_MEAN 4
+#define SMART_ENS_AUTO 0
+#define SMART_ENS_LDS 1
+#define SMART_ENS_GLOBAL 2
+int smart_ensemble_scores_hip(int64_t n_samples, int64_t n_reports, const double *sim, int64_t ld, const double *weights,
+                              const double *obs, double *out, int32_t method, void *workspace, int64_t workspace_bytes,
+                              void *stream);
+
+/* The workspace smart_ensemble_scores_hip asks for, in bytes: 0 for the LDS form (and for AUTO within its capacity); for
+ * the global form one step is n_samples rounded up to a power of two (at least 4096) times 16 bytes with weights, 8
+ * without, and the answer holds min(n_reports, as many steps as fit in 256 MiB, at least one).  The entry itself takes
+ * any workspace that holds one step.  A negative SMART_E_* code for what the entry refuses.  Needs no device. */
+int64_t smart_ensemble_scores_workspace_bytes(int64_t n_samples, int64_t n_reports, int32_t weighted, int32_t method);
+
+/* The largest n_samples SMART_ENS_LDS takes: 8192 (10 bytes per sorted element in LDS).  Needs no device. */
+int64_t smart_ensemble_scores_lds_capacity(void);
+
+/*
  * Sampling database, CSV flavour -- the rows MonteCarlo.save writes one by one (montecarlo.py:211-231): every value
  * cast to float32 and printed '%.6e', comma separated, one '\n'-terminated line per sample.  HOST pointers, no
  * device involved.  Appends n_rows lines of n_cols values (row-major float32 table: objective functions, parameters,

@@ -34,6 +34,9 @@ BOOT_MEAN, BOOT_STD = 0, 1                                       # SMART_BOOT_*:
 SOBOL_MAX_PARAMS = 16
 PARETO_MAX_OBJECTIVES = 16
 PARETO_DIRECTIONS = {'max': 0, 'min': 1, 'target': 2}           # SMART_PARETO_*
+ENSEMBLE_SCORE_NAMES = ['CRPS', 'SPREAD', 'PIT_LOW', 'PIT_HIGH', 'MEAN']     # SMART_ENS_*, in column order
+ENSEMBLE_SCORE_COLS = len(ENSEMBLE_SCORE_NAMES)
+ENSEMBLE_METHODS = {'auto': 0, 'lds': 1, 'global': 2}           # SMART_ENS_*
 
 _dp = ctypes.c_void_p   # device or host address, passed as an integer
 
@@ -102,6 +105,11 @@ SYMBOLS = {
                                                ctypes.c_int32, _dp, _dp, _dp, ctypes.c_int64, _dp]),
     'smart_pareto_workspace_bytes': (ctypes.c_int64, [ctypes.c_int64, ctypes.c_int32]),
     'smart_pareto_max_objectives': (ctypes.c_int, []),
+    'smart_ensemble_scores_hip': (ctypes.c_int, [ctypes.c_int64, ctypes.c_int64, _dp, ctypes.c_int64, _dp, _dp, _dp,
+                                                 ctypes.c_int32, _dp, ctypes.c_int64, _dp]),
+    'smart_ensemble_scores_workspace_bytes': (ctypes.c_int64, [ctypes.c_int64, ctypes.c_int64, ctypes.c_int32,
+                                                               ctypes.c_int32]),
+    'smart_ensemble_scores_lds_capacity': (ctypes.c_int64, []),
     'smart_db_append_rows': (ctypes.c_int, [ctypes.c_char_p, ctypes.POINTER(ctypes.c_float), ctypes.c_int64,
                                             ctypes.c_int64, ctypes.c_int32]),
     'smart_db_parse_rows': (ctypes.c_int64, [ctypes.c_char_p, ctypes.c_int64, ctypes.c_int64,

@@ -1,9 +1,10 @@
 """The analyses of a stored [R, N] discharge matrix (row r = every sample's discharge of report step r), each one launch
 through the C ABI (csrc/smart_analysis_capi.hip): objective functions, weighted quantiles over the samples, objective
-functions per window of report steps, flow duration curves, hydrological signatures, Sobol indices -- and the Pareto
-selection over the scores they leave, [N, C] with a row per sample.  torch tensors in, torch tensors out, as in engine.py
--- which imports this module and re-exports every public name of it (engine.flow_duration and the others are
-these functions); what they share on the way to the launch are the private helpers at the top.
+functions per window of report steps, flow duration curves, hydrological signatures, Sobol indices, ensemble
+verification scores -- and the Pareto selection over the scores they leave, [N, C] with a row per sample.  torch tensors
+in, torch tensors out, as in engine.py -- which imports this module and re-exports every public name of it
+(engine.flow_duration and the others are these functions); what they share on the way to the launch are the private
+helpers at the top.
 """
 import ctypes
 
@@ -581,3 +582,45 @@ def pareto_ranks(scores, directions, targets=None, columns=None, eligible=None, 
         if int(left.sum()) == 0:        # the one read of this front
             break
     return ranks
+
+
+ENSEMBLE_SCORE_NAMES = list(_lib.ENSEMBLE_SCORE_NAMES)
+
+
+def ensemble_scores_lds_capacity():
+    """The largest number of samples the LDS form of ensemble_scores takes (no device needed)."""
+    return int(_lib.lib().smart_ensemble_scores_lds_capacity())
+
+
+def ensemble_scores(discharge_report_major, obs=None, weights=None, method='auto'):
+    """Verification scores of the ensemble of a stored [R, N] discharge matrix, per report step -> device tensor [5, R]
+    float64, the rows in the order of ENSEMBLE_SCORE_NAMES: the continuous ranked probability score of the weighted
+    ensemble against obs[r] (as the integral of (F - 1[x >= y])^2: a sum of non-negative terms), the ensemble's spread
+    (the integral of F (1 - F) = E|X - X'| / 2), the probability integral transform of the observation from below
+    (sum of w over x < y, / W) and from above (x <= y), and the weighted mean.  obs: [R] or None -- a step without a
+    finite observation has NaN for CRPS and both PITs; weights: [N], finite and >= 0, or None for equal weights -- a
+    member of weight zero takes no part, whatever its value; a step whose weights sum to zero, or with a live member that
+    is not finite, is NaN in all five.  method: 'auto' (by size), 'lds' (N <= ensemble_scores_lds_capacity()) or
+    'global' (N <= 2**24).  The workspace of the call is sized and owned here (include/smart_amd.h:
+    smart_ensemble_scores_hip)."""
+    L = _lib.lib()
+    code = _code('ensemble_scores', 'method', _lib.ENSEMBLE_METHODS, method)
+    sim, R, N, ld = _matrix(discharge_report_major)
+    if obs is not None:
+        obs = _as_device(obs, sim.device, (R,))
+    if weights is not None:
+        weights = _as_device(weights, sim.device, (N,))
+        bad = int((~(torch.isfinite(weights) & (weights >= 0))).sum())
+        if bad:
+            raise SmartEngineError(-2, "ensemble_scores: {} of the {} weights are negative or not finite."
+                                   .format(bad, N))
+    out = torch.empty((_lib.ENSEMBLE_SCORE_COLS, R), dtype=torch.float64, device=sim.device)
+    if R == 0:
+        return out
+    # (sizes the helper refuses get no workspace: the entry refuses them too, with its text)
+    work, need = _workspace(max(0, int(L.smart_ensemble_scores_workspace_bytes(N, R, 1 if weights is not None else 0,
+                                                                               code))), sim.device)
+    with torch.cuda.device(sim.device):
+        _lib.check(L.smart_ensemble_scores_hip(N, R, sim.data_ptr(), ld, _ptr(weights), _ptr(obs), out.data_ptr(), code,
+                                               _ptr(work), need, _stream(sim.device)))
+    return out

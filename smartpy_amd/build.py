@@ -49,6 +49,9 @@ UNITS = {
     # Pareto selection over the scores of the analyses (dominance counts): default flags, NaNs honoured -- the keys are
     # compared as IEEE says
     'smart_pareto.hip': [],
+    # ensemble verification per report step (CRPS, spread, PIT, mean across the samples): default flags, NaNs honoured --
+    # a live member that is not finite is found by its key, and a missing observation by its bits
+    'smart_ensemble_scores.hip': [],
     'smart_capi.hip': [],
     # the C entries of the matrix analyses, and smart_objfn_matrix: the flags smart_capi.hip had it compiled with
     'smart_analysis_capi.hip': [],

@@ -1,6 +1,6 @@
 // smart_analysis_capi.hip -- the C ABI of the analyses of a stored discharge matrix sim[R][ld] (include/smart_amd.h):
 // objective functions, weighted quantiles, objective functions per window, flow duration curves, hydrological signatures, Sobol indices, the block bootstrap of the objective functions, and of
-// the Pareto selection over the scores they leave, with their capacity and workspace entries -- validation and launch --
+// the Pareto selection over the scores they leave, and the ensemble verification scores per report step, with their capacity and workspace entries -- validation and launch --
 // and the one kernel among them that has no unit of its own, smart_objfn_matrix.  Every refusal comes before the device is asked for; the rules the entries share are the
 // static helpers below, which take the entry's name for the text.
 #include "smart_capi_internal.h"
@@ -210,6 +210,29 @@ static const char *pareto_sizes(int64_t n_rows, int32_t n_objectives, char *text
     else
         return nullptr;
     return text;
+}
+
+// the size and method rules of smart_ensemble_scores_hip, shared with smart_ensemble_scores_workspace_bytes; SMART_OK, or
+// the code of the refusal with its text
+static int ensemble_sizes(int64_t n_samples, int64_t n_reports, int32_t method, char *text, size_t len)
+{
+    int code = SMART_E_SIZE;
+    if (n_samples < 1 || n_reports < 1)
+        snprintf(text, len, "need n_samples, n_reports >= 1 (got %lld, %lld)", (long long)n_samples, (long long)n_reports);
+    else if (n_reports > 0x7fffffffll)
+        snprintf(text, len, "n_reports %lld is more than one launch takes (2^31 - 1)", (long long)n_reports);
+    else if (n_samples > ensemble_scores_max_samples())
+        snprintf(text, len, "n_samples %lld, at most %lld (2^24)", (long long)n_samples,
+                 (long long)ensemble_scores_max_samples());
+    else if (method != SMART_ENS_AUTO && method != SMART_ENS_LDS && method != SMART_ENS_GLOBAL) {
+        snprintf(text, len, "method '%d' unknown.", (int)method);
+        code = SMART_E_MODE;
+    } else if (method == SMART_ENS_LDS && n_samples > ensemble_scores_lds_capacity())
+        snprintf(text, len, "the LDS form takes at most %lld samples, not %lld", (long long)ensemble_scores_lds_capacity(),
+                 (long long)n_samples);
+    else
+        return SMART_OK;
+    return code;
 }
 
 } // namespace smart
@@ -507,5 +530,41 @@ int64_t smart_pareto_workspace_bytes(int64_t n_rows, int32_t n_objectives)
 }
 
 int smart_pareto_max_objectives(void) { return SMART_PARETO_MAX_OBJECTIVES; }
+
+int smart_ensemble_scores_hip(int64_t n_samples, int64_t n_reports, const double *sim, int64_t ld, const double *weights,
+                              const double *obs, double *out, int32_t method, void *workspace, int64_t workspace_bytes,
+                              void *stream)
+{
+    static const char entry[] = "smart_ensemble_scores_hip";
+    int rc;
+    if (!sim || !out)
+        return fail(SMART_E_NULL, "%s: sim and out are required (%s is NULL)", entry, !sim ? "sim" : "out");
+    char text[160];
+    if ((rc = ensemble_sizes(n_samples, n_reports, method, text, sizeof text)))
+        return fail(rc, "%s: %s", entry, text);
+    if (ld < n_samples)
+        return fail(SMART_E_SIZE, "%s: ld %lld is less than n_samples %lld", entry, (long long)ld, (long long)n_samples);
+    const bool lds = method == SMART_ENS_LDS || (method == SMART_ENS_AUTO && n_samples <= ensemble_scores_lds_capacity());
+    if (!lds && (rc = workspace_fits(entry, /*for_objfn=*/false, workspace, workspace_bytes,
+                                     ensemble_scores_step_bytes((long)n_samples, weights != nullptr))))
+        return rc;
+    if ((rc = device_ready()))
+        return rc;
+    launch_ensemble_scores((long)n_samples, (long)n_reports, sim, (long)ld, weights, obs, out, lds, workspace,
+                           (long)workspace_bytes, (hipStream_t)stream);
+    return launched();
+}
+
+int64_t smart_ensemble_scores_workspace_bytes(int64_t n_samples, int64_t n_reports, int32_t weighted, int32_t method)
+{
+    char text[160];
+    if (int rc = ensemble_sizes(n_samples, n_reports, method, text, sizeof text))
+        return rc;
+    if (method == SMART_ENS_LDS || (method == SMART_ENS_AUTO && n_samples <= ensemble_scores_lds_capacity()))
+        return 0;
+    return ensemble_scores_workspace_bytes((long)n_samples, (long)n_reports, weighted != 0);
+}
+
+int64_t smart_ensemble_scores_lds_capacity(void) { return ensemble_scores_lds_capacity(); }
 
 } // extern "C"

@@ -69,4 +69,12 @@ long pareto_workspace_bytes(long N, int M);
 void launch_pareto(long N, const double *scores, long ld, const int *columns, const int *direction, const double *target,
                    int M, const unsigned char *eligible, int *dominated_by, void *workspace, hipStream_t s);
 
+// ---- smart_ensemble_scores.hip
+long ensemble_scores_lds_capacity();
+long ensemble_scores_max_samples();
+long ensemble_scores_step_bytes(long N, bool weighted);
+long ensemble_scores_workspace_bytes(long N, long R, bool weighted);
+void launch_ensemble_scores(long N, long R, const double *sim, long ld, const double *weights, const double *obs,
+                            double *out, bool lds, void *workspace, long workspace_bytes, hipStream_t s);
+
 } // namespace smart

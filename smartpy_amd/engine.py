@@ -567,7 +567,8 @@ from .analysis import (objective_functions, quantiles_sort_capacity, weighted_qu
                        sobol_max_resamples, sobol_lds_capacity, sobol_counts, SobolResult, sobol_indices,
                        bootstrap_max_windows, bootstrap_max_resamples, bootstrap_counts, jackknife_counts,
                        BootstrapResult, objective_functions_bootstrap,
-                       pareto_max_objectives, pareto_counts, pareto_ranks)
+                       pareto_max_objectives, pareto_counts, pareto_ranks,
+                       ENSEMBLE_SCORE_NAMES, ensemble_scores_lds_capacity, ensemble_scores)
 
 
 def allsteps(area_m2, delta_sec, length_simu, nd_rain, nd_peva, nd_parameters, nd_initial, report_type, report_gap):

@@ -1,6 +1,7 @@
 """GLUE conditioning run (counterpart of smartpy/montecarlo/glue.py): keep the behavioural sets of a previous
 LHS sampling, re-simulate them (typically on another period) -- and, beyond the reference, hand out what a GLUE
-analysis is run for: the likelihood-weighted prediction bounds of the behavioural ensemble (prediction_bounds)."""
+analysis is run for: the likelihood-weighted prediction bounds of the behavioural ensemble (prediction_bounds), and
+how good that predictive distribution is against the observations (ensemble_verification)."""
 from csv import writer
 
 import numpy as np
@@ -8,6 +9,7 @@ import numpy as np
 from .montecarlo import MonteCarlo
 from .selection import condition_mask, check_shapes, SecondStage
 from .. import distributed as sdist
+from ..verification import EnsembleVerification
 
 
 class PredictionBounds(object):
@@ -118,3 +120,33 @@ class GLUE(SecondStage, MonteCarlo):
                 w.writerow(['DateTime'] + ['q%g' % p for p in q])
                 w.writerows([dt] + ['%e' % v for v in column] for dt, column in zip(stamps, bounds.T))
         return PredictionBounds(q, bounds, stamps, containment, path)
+
+    # ---- ensemble verification --------------------------------------------------------------------------
+    def ensemble_verification(self, likelihood=None, bins=10, write=False):
+        """How good the predictive distribution of the behavioural ensemble is: at every report step the CRPS of the
+        likelihood-weighted ensemble against the observation, the ensemble's spread, the PIT of the observation from
+        below and from above and the weighted mean (engine.ensemble_scores), and over the steps that have all of them
+        the mean CRPS and spread, the skill against climatology, the non-randomised PIT histogram over `bins` bins and
+        the reliability index (smartpy_amd.verification).  One launch of its own over the behavioural rows; the [R, N]
+        matrix stays on the device and only the [5, R] scores come back.  likelihood: as for prediction_bounds.
+        write=True also writes `<out>/<catchment>.SMART.glue.verification` (CSV: DateTime,crps,spread,pit_low,pit_high,
+        mean with the dates and the '%e' of the modelled flow file).  Under torch.distributed every rank that calls this
+        computes all rows itself (no collective); rank 0 alone writes.  -> EnsembleVerification"""
+        from .. import engine
+        stamps = self.model.timeseries_report[1:]
+        weights = self._likelihood_weights(likelihood)
+        flow = self.model.nd_flow
+        if self._sample.shape[0] == 0:      # no behavioural set: nothing to launch
+            scores = np.full((5, len(stamps)), np.nan)
+        else:
+            out, obs = self._launch_stored()
+            scores = engine.ensemble_scores(out.discharge_report_major, obs, weights).cpu().numpy()
+        path = None
+        if write and sdist.rank_world()[0] == 0:
+            path = self._side_file('.verification')
+            with open(path, 'w', newline='', encoding='utf8') as f:
+                w = writer(f, delimiter=',')
+                w.writerow(['DateTime', 'crps', 'spread', 'pit_low', 'pit_high', 'mean'])
+                w.writerows([dt] + ['%e' % v for v in column] for dt, column in zip(stamps, scores.T))
+        return EnsembleVerification(scores, None if flow is None else np.asarray(flow, dtype=np.float64), stamps, bins,
+                                    path)
