@@ -90,6 +90,10 @@ def main():
     # and a leave-one-year-out jackknife, one launch and two reads of the matrix; unsure.device_stats[1, 2] is the 5 % bound
     # of KGE of every set, on the GPU
     unsure = glue.score_uncertainty('hydro_year', resamples=1000, seed=0, write=True)
+    # WHEN in the record each parameter is identifiable (DYNIA): per report step the best tenth of the LHS sample over a
+    # moving window of +- 15 days, spread over 20 bins of every parameter's range; one launch of its own, [R, 10, 20] comes
+    # back; dynia.information[r, p] is near 1 where the data of that period pin parameter p down
+    dynia = lhs.dynamic_identifiability(half_width=15, fraction=0.1, bins=20, write=True)
     top = Best('Catchment', root, 'csv', 'csv', target='KGE', nb_best=10, constraining={'GW': ('equal', (1.0,))})
     top.model.extra = EXTRA
     top.run()
@@ -101,6 +105,8 @@ def main():
     sens = sob.sensitivity(targets=['NSE', 'KGE'], resamples=128, write=True)
     in_time = sob.sensitivity_series(write=True)
     if rank == 0:
+        print('DYNIA: mean information content over the record: %s -> %s'
+              % (', '.join('%s %.2f' % (p, v) for p, v in zip(dynia.names, np.nanmean(dynia.information, axis=0))), dynia.file))
         print('GLUE: %d behavioural sets -> %s' % (len(glue.behavioural_params), glue.db_file))
         print('      5 / 50 / 95 %% prediction bounds hold %.1f %% of the observations -> %s'
               % (100 * bounds.containment, bounds.file))

@@ -641,6 +641,65 @@ int64_t smart_ensemble_scores_workspace_bytes(int64_t n_samples, int64_t n_repor
 int64_t smart_ensemble_scores_lds_capacity(void);
 
 /*
+ * Dynamic identifiability analysis (DYNIA, Wagener et al. 2003, Hydrol. Process. 17): WHEN in the record does the sample
+ * the caller already has constrain each factor.  Inputs: sim[R][ld] sample-minor (the layout smart_run_ensemble_hip
+ * writes); obs[R], a value that is not finite is missing; a half width h >= 0 in report steps, the window being
+ * w = 2 h + 1 steps; 1 <= min_valid <= w; fraction in (0, 1]; a category table cat[P][N] of uint8 -- the bin of row n on
+ * factor p, 255: the row takes no part in this factor (a value in n_bins .. 254 does the same) --, P <=
+ * SMART_DYNIA_MAX_FACTORS, n_bins B <= SMART_DYNIA_MAX_BINS; support SMART_DYNIA_EQUAL or SMART_DYNIA_LINEAR.
+ * Per report step r:
+ *   1. V_r = { s : |s - r| <= h, 0 <= s < R, obs[s] finite }: the window is cut at both ends of the record.
+ *      count[r] = |V_r|.
+ *   2. count[r] < min_valid: the step is not assessed -- cut[r] and every share of the step are NaN, retained[r] = 0, and
+ *      the step's row of err is NaN where err is asked for.
+ *   3. Otherwise E[r][n] = sum over s in V_r of |sim[s][n] - obs[s]|: the window's SUM of absolute errors, not its mean --
+ *      the count is the same for every sample of a step, so neither the ranks nor the normalised supports depend on it,
+ *      and one rounding is saved (divide by count[r] for display).  A sim value that is not finite makes E not finite.
+ *   4. The rows with a finite E[r][n] are eligible, M_r of them; M_r == 0 is treated like a step not assessed.
+ *      k = max(1, (int64) ceil(fraction * (double) M_r)), in double arithmetic exactly as written.
+ *   5. cut[r] = the k-th smallest eligible E (compared as order-preserving keys: -0.0 and +0.0 are one value).  Retained:
+ *      every eligible row with E <= cut[r] -- every tie at the cut stays in, retained[r] >= k.
+ *   6. The support of a retained row: EQUAL s_n = 1; LINEAR s_n = cut[r] - E[r][n], one subtraction, >= 0.  S = the sum of
+ *      s_n over the retained rows; S == 0 (every retained row ties at the cut) falls back to s_n = 1.
+ *   7. shares[r][p][b] = (the sum of s_n over the retained n with cat[p][n] == b) / S.  A factor with rows of category
+ *      255 sums to less than one.
+ * Outputs, device pointers: shares[R][P][B], cut[R], retained[R] and count[R] (int32), and err[R][ld_err] holding the E
+ * sums, or NULL where they are not wanted.  Asynchronous on stream; allocates nothing: the workspace is the caller's.  The
+ * E sums of a batch of steps live there as [batch][N] doubles (in err itself where it is given); the entry takes any
+ * workspace that holds one step, n_samples * 8 bytes.
+ * The window sums use additions only (no running sum that subtracts the outgoing term): time is tiled in blocks of w rows
+ * at absolute positions, a window is a suffix sum of one block plus a prefix sum of the next, at most w - 1 additions of
+ * non-negative terms (smartpy_amd/csrc/smart_dynia.hip).  A share adds its supports in ascending sample order.
+ * Deterministic: no floating-point atomics, every sum has one association for a given (n_samples, n_reports, h), so two
+ * launches give the same bits -- whatever the batches.
+ * Errors (all found before the device is touched): SMART_E_NULL a required pointer missing (err alone may be NULL);
+ * SMART_E_SIZE a size < 1, n_samples or n_reports >= 2^31, h beyond smart_dynia_max_half_width(), P or B beyond the
+ * macros, ld or ld_err < n_samples, min_valid outside 1 .. w, fraction outside (0, 1] or NaN, a workspace that does not
+ * hold one step; SMART_E_MODE unknown support; then SMART_E_NO_DEVICE without a HIP device.
+ */
+#define SMART_DYNIA_MAX_FACTORS 16
+#define SMART_DYNIA_MAX_BINS 64
+#define SMART_DYNIA_EQUAL 0
+#define SMART_DYNIA_LINEAR 1
+int smart_dynia_hip(int64_t n_samples, int64_t n_reports, const double *sim, int64_t ld, const double *obs,
+                    int32_t half_width, int32_t min_valid, double fraction, const uint8_t *cat, int32_t n_factors,
+                    int32_t n_bins, int32_t support, double *shares, double *cut, int32_t *retained, int32_t *count,
+                    double *err, int64_t ld_err, void *workspace, int64_t workspace_bytes, void *stream);
+
+/* The workspace smart_dynia_hip asks for, in bytes: one step is n_samples * 8 bytes, and the answer holds
+ * min(n_reports, as many steps as fit in 256 MiB, at least one).  SMART_E_SIZE (negative) for sizes the entry refuses.
+ * Needs no device. */
+int64_t smart_dynia_workspace_bytes(int64_t n_samples, int64_t n_reports, int32_t half_width, int32_t n_factors,
+                                    int32_t n_bins);
+
+/* The largest half width smart_dynia_hip takes: 63 (a window of 127 steps per lane in LDS).  Needs no device. */
+int32_t smart_dynia_max_half_width(void);
+
+/* The largest n_samples whose step smart_dynia_hip keeps in LDS for the selection: 16384 (up to 2048 in a smaller
+ * instance); beyond, the step is re-read from the batch's row.  Needs no device. */
+int64_t smart_dynia_lds_capacity(void);
+
+/*
  * Sampling database, CSV flavour -- the rows MonteCarlo.save writes one by one (montecarlo.py:211-231): every value
  * cast to float32 and printed '%.6e', comma separated, one '\n'-terminated line per sample.  HOST pointers, no
  * device involved.  Appends n_rows lines of n_cols values (row-major float32 table: objective functions, parameters,

@@ -1,7 +1,7 @@
 """The analyses of a stored [R, N] discharge matrix (row r = every sample's discharge of report step r), each one launch
 through the C ABI (csrc/smart_analysis_capi.hip): objective functions, weighted quantiles over the samples, objective
 functions per window of report steps, flow duration curves, hydrological signatures, Sobol indices, ensemble
-verification scores -- and the Pareto selection over the scores they leave, [N, C] with a row per sample.  torch tensors
+verification scores, the dynamic identifiability analysis -- and the Pareto selection over the scores they leave, [N, C] with a row per sample.  torch tensors
 in, torch tensors out, as in engine.py -- which imports this module and re-exports every public name of it
 (engine.flow_duration and the others are these functions); what they share on the way to the launch are the private
 helpers at the top.
@@ -624,3 +624,69 @@ def ensemble_scores(discharge_report_major, obs=None, weights=None, method='auto
         _lib.check(L.smart_ensemble_scores_hip(N, R, sim.data_ptr(), ld, _ptr(weights), _ptr(obs), out.data_ptr(), code,
                                                _ptr(work), need, _stream(sim.device)))
     return out
+
+
+def dynia_max_half_width():
+    """The largest half width dynamic_identifiability takes, in report steps (no device needed)."""
+    return int(_lib.lib().smart_dynia_max_half_width())
+
+
+def dynia_lds_capacity():
+    """The largest number of samples whose step dynamic_identifiability keeps in LDS for the selection (no device
+    needed)."""
+    return int(_lib.lib().smart_dynia_lds_capacity())
+
+
+class DyniaResult(object):
+    """Device tensors of one dynamic_identifiability call: shares [R, P, B] float64, cut [R] float64 (the window's SUM of
+    absolute errors at the cut), retained [R] and count [R] int32, errors [R, N] float64 (the sums) or None."""
+
+    def __init__(self, shares, cut, retained, count, errors):
+        self.shares, self.cut, self.retained, self.count, self.errors = shares, cut, retained, count, errors
+
+
+def dynamic_identifiability(discharge_report_major, obs, categories, n_bins, half_width, fraction=0.1, min_valid=None,
+                            support='linear', keep_errors=False):
+    """Dynamic identifiability analysis (DYNIA, Wagener et al. 2003) of a stored [R, N] discharge matrix -> DyniaResult.
+    Per report step r the samples are scored by the sum of |sim - obs| over the observed steps of the moving window
+    |s - r| <= half_width (cut at both ends of the record), the best `fraction` of the rows with a finite sum is retained
+    -- k = max(1, ceil(fraction * M)), every tie at the cut stays in -- and shares[r, p, b] is the retained rows' support
+    that falls into bin b of factor p, over the support of them all.  categories: [P, N] uint8, host or device, the bin
+    of row n on factor p (identifiability.bin_table makes one), 255 = the row takes no part in the factor; P <= 16,
+    n_bins <= 64.  support: 'equal' (every retained row 1) or 'linear' (cut - sum; 1 where every retained row ties).
+    min_valid: the observed steps a window needs, None = (w + 1) // 2 with w = 2 * half_width + 1; a step with fewer
+    is NaN in cut and shares, 0 in retained.  keep_errors=True also returns the sums, [R, N].  The workspace of the call
+    is sized and owned here (include/smart_amd.h: smart_dynia_hip)."""
+    who = 'dynamic_identifiability'
+    L = _lib.lib()
+    code = _code(who, 'support', _lib.DYNIA_SUPPORTS, support)
+    h, B = int(half_width), int(n_bins)
+    w = 2 * h + 1
+    min_valid = (w + 1) // 2 if min_valid is None else int(min_valid)
+    shape = tuple(getattr(categories, 'shape', ()))
+    n_cols = tuple(discharge_report_major.shape)[-1]
+    if len(shape) != 2 or shape[1] != n_cols or str(getattr(categories, 'dtype', '')).split('.')[-1] != 'uint8':
+        raise SmartEngineError(-2, "{}: categories must be uint8 [factors, {}] (identifiability.bin_table), not {} {}."
+                               .format(who, n_cols, getattr(categories, 'dtype', type(categories).__name__), shape))
+    P = shape[0]
+    # ---- from here on the device
+    sim, R, N, ld = _matrix(discharge_report_major)
+    dev = sim.device
+    obs = _as_device(obs, dev, (R,))
+    if not isinstance(categories, torch.Tensor):
+        categories = torch.from_numpy(np.ascontiguousarray(categories))
+    cat = categories.to(dev).contiguous()
+    shares = torch.empty((R, P, B), dtype=torch.float64, device=dev)
+    cut = torch.empty((R,), dtype=torch.float64, device=dev)
+    retained = torch.empty((R,), dtype=torch.int32, device=dev)
+    count = torch.empty((R,), dtype=torch.int32, device=dev)
+    errors = torch.empty((R, N), dtype=torch.float64, device=dev) if keep_errors else None
+    if R == 0 or N == 0:
+        return DyniaResult(shares, cut, retained, count, errors)
+    # (sizes the helper refuses get no workspace: the entry refuses them too, with its text)
+    work, need = _workspace(max(0, int(L.smart_dynia_workspace_bytes(N, R, h, P, B))), dev)
+    with torch.cuda.device(dev):
+        _lib.check(L.smart_dynia_hip(N, R, sim.data_ptr(), ld, obs.data_ptr(), h, min_valid, float(fraction),
+                                     cat.data_ptr(), P, B, code, shares.data_ptr(), cut.data_ptr(), retained.data_ptr(),
+                                     count.data_ptr(), _ptr(errors), N, _ptr(work), need, _stream(dev)))
+    return DyniaResult(shares, cut, retained, count, errors)

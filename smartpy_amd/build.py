@@ -52,6 +52,10 @@ UNITS = {
     # ensemble verification per report step (CRPS, spread, PIT, mean across the samples): default flags, NaNs honoured --
     # a live member that is not finite is found by its key, and a missing observation by its bits
     'smart_ensemble_scores.hip': [],
+    # dynamic identifiability analysis (moving-window error sums along time, selection and shares across the samples):
+    # default flags, NaNs honoured -- a value that is not finite has to reach the window sums it lies in, and is found
+    # there by its key
+    'smart_dynia.hip': [],
     'smart_capi.hip': [],
     # the C entries of the matrix analyses, and smart_objfn_matrix: the flags smart_capi.hip had it compiled with
     'smart_analysis_capi.hip': [],

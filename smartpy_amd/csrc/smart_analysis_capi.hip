@@ -1,6 +1,6 @@
 // smart_analysis_capi.hip -- the C ABI of the analyses of a stored discharge matrix sim[R][ld] (include/smart_amd.h):
 // objective functions, weighted quantiles, objective functions per window, flow duration curves, hydrological signatures, Sobol indices, the block bootstrap of the objective functions, and of
-// the Pareto selection over the scores they leave, and the ensemble verification scores per report step, with their capacity and workspace entries -- validation and launch --
+// the Pareto selection over the scores they leave, the ensemble verification scores and the dynamic identifiability analysis per report step, with their capacity and workspace entries -- validation and launch --
 // and the one kernel among them that has no unit of its own, smart_objfn_matrix.  Every refusal comes before the device is asked for; the rules the entries share are the
 // static helpers below, which take the entry's name for the text.
 #include "smart_capi_internal.h"
@@ -233,6 +233,27 @@ static int ensemble_sizes(int64_t n_samples, int64_t n_reports, int32_t method, 
     else
         return SMART_OK;
     return code;
+}
+
+// the size rules of smart_dynia_hip, shared with smart_dynia_workspace_bytes; 0 or the text of the refusal
+static const char *dynia_sizes(int64_t n_samples, int64_t n_reports, int32_t half_width, int32_t n_factors, int32_t n_bins,
+                               char *text, size_t len)
+{
+    if (n_samples < 1 || n_reports < 1)
+        snprintf(text, len, "need n_samples, n_reports >= 1 (got %lld, %lld)", (long long)n_samples, (long long)n_reports);
+    else if (n_samples > 0x7fffffffll)
+        snprintf(text, len, "n_samples %lld must be in 1 .. 2^31 - 1", (long long)n_samples);
+    else if (n_reports > 0x7fffffffll)
+        snprintf(text, len, "n_reports %lld is more than one launch takes (2^31 - 1)", (long long)n_reports);
+    else if (half_width < 0 || half_width > dynia_max_half_width())
+        snprintf(text, len, "half_width %d must be in 0 .. %d", (int)half_width, dynia_max_half_width());
+    else if (n_factors < 1 || n_factors > SMART_DYNIA_MAX_FACTORS)
+        snprintf(text, len, "n_factors %d must be in 1 .. %d", (int)n_factors, SMART_DYNIA_MAX_FACTORS);
+    else if (n_bins < 1 || n_bins > SMART_DYNIA_MAX_BINS)
+        snprintf(text, len, "n_bins %d must be in 1 .. %d", (int)n_bins, SMART_DYNIA_MAX_BINS);
+    else
+        return nullptr;
+    return text;
 }
 
 } // namespace smart
@@ -566,5 +587,54 @@ int64_t smart_ensemble_scores_workspace_bytes(int64_t n_samples, int64_t n_repor
 }
 
 int64_t smart_ensemble_scores_lds_capacity(void) { return ensemble_scores_lds_capacity(); }
+
+int smart_dynia_hip(int64_t n_samples, int64_t n_reports, const double *sim, int64_t ld, const double *obs,
+                    int32_t half_width, int32_t min_valid, double fraction, const uint8_t *cat, int32_t n_factors,
+                    int32_t n_bins, int32_t support, double *shares, double *cut, int32_t *retained, int32_t *count,
+                    double *err, int64_t ld_err, void *workspace, int64_t workspace_bytes, void *stream)
+{
+    static const char entry[] = "smart_dynia_hip";
+    int rc;
+    if (!sim || !obs || !cat || !shares || !cut || !retained || !count)
+        return fail(SMART_E_NULL, "%s: sim, obs, cat, shares, cut, retained and count are required (%s is NULL)", entry,
+                    !sim ? "sim"
+                         : (!obs ? "obs"
+                                 : (!cat ? "cat" : (!shares ? "shares" : (!cut ? "cut" : (!retained ? "retained" : "count"))))));
+    char text[160];
+    if (dynia_sizes(n_samples, n_reports, half_width, n_factors, n_bins, text, sizeof text))
+        return fail(SMART_E_SIZE, "%s: %s", entry, text);
+    if (ld < n_samples)
+        return fail(SMART_E_SIZE, "%s: ld %lld is less than n_samples %lld", entry, (long long)ld, (long long)n_samples);
+    if (err && ld_err < n_samples)
+        return fail(SMART_E_SIZE, "%s: ld_err %lld is less than n_samples %lld", entry, (long long)ld_err,
+                    (long long)n_samples);
+    if (min_valid < 1 || min_valid > 2 * half_width + 1)
+        return fail(SMART_E_SIZE, "%s: min_valid %d must be in 1 .. %d (the window)", entry, (int)min_valid,
+                    2 * (int)half_width + 1);
+    if (!(fraction > 0.0 && fraction <= 1.0))
+        return fail(SMART_E_SIZE, "%s: fraction %g is outside (0, 1]", entry, fraction);
+    if (support != SMART_DYNIA_EQUAL && support != SMART_DYNIA_LINEAR)
+        return fail(SMART_E_MODE, "%s: support '%d' unknown.", entry, (int)support);
+    if ((rc = workspace_fits(entry, /*for_objfn=*/false, workspace, workspace_bytes, dynia_step_bytes((long)n_samples))) ||
+        (rc = device_ready()))
+        return rc;
+    launch_dynia((long)n_samples, (long)n_reports, sim, (long)ld, obs, (int)half_width, (int)min_valid, fraction, cat,
+                 (int)n_factors, (int)n_bins, (int)support, shares, cut, retained, count, err, (long)ld_err, workspace,
+                 (long)workspace_bytes, (hipStream_t)stream);
+    return launched();
+}
+
+int64_t smart_dynia_workspace_bytes(int64_t n_samples, int64_t n_reports, int32_t half_width, int32_t n_factors,
+                                    int32_t n_bins)
+{
+    char text[160];
+    if (dynia_sizes(n_samples, n_reports, half_width, n_factors, n_bins, text, sizeof text))
+        return SMART_E_SIZE;
+    return dynia_workspace_bytes((long)n_samples, (long)n_reports);
+}
+
+int32_t smart_dynia_max_half_width(void) { return dynia_max_half_width(); }
+
+int64_t smart_dynia_lds_capacity(void) { return dynia_lds_capacity(); }
 
 } // extern "C"

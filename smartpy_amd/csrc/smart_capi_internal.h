@@ -77,4 +77,13 @@ long ensemble_scores_workspace_bytes(long N, long R, bool weighted);
 void launch_ensemble_scores(long N, long R, const double *sim, long ld, const double *weights, const double *obs,
                             double *out, bool lds, void *workspace, long workspace_bytes, hipStream_t s);
 
+// ---- smart_dynia.hip
+int dynia_max_half_width();
+long dynia_lds_capacity();
+long dynia_step_bytes(long N);
+long dynia_workspace_bytes(long N, long R);
+void launch_dynia(long N, long R, const double *sim, long ld, const double *obs, int h, int min_valid, double fraction,
+                  const unsigned char *cat, int P, int B, int support, double *shares, double *cut, int *retained,
+                  int *count, double *err, long ld_err, void *workspace, long workspace_bytes, hipStream_t s);
+
 } // namespace smart

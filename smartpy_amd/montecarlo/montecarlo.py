@@ -411,6 +411,60 @@ class MonteCarlo(object):
         """`<out>/<catchment>.SMART.<func>.uncertainty`: beside the sampling database, whatever its format."""
         return self._side_file('.uncertainty')
 
+    # ---- dynamic identifiability --------------------------------------------------------------------------
+    def dynamic_identifiability(self, half_width=None, fraction=0.1, bins=20, support='linear', min_valid=None, level=0.9,
+                                ranges=None, write=False):
+        """WHEN in the record each parameter is identifiable (DYNIA, Wagener et al. 2003, Hydrol. Process. 17), from the
+        sample as it is: per report step every row is scored by its absolute error over the observed steps of the moving
+        window of `half_width` report steps to either side (None: the report steps of 15 days), the best `fraction` of
+        the rows is retained, and their support ('linear': the distance to the cut; 'equal': 1 each) is shared out over
+        `bins` equal bins of every parameter's range.  From the shares: the `level` confidence limits of every parameter
+        and its information content 1 - width / range (smartpy_amd.identifiability) -- near 1 where the data of that
+        period pin the parameter down.  ranges=None: the ranges the sample was drawn from (model.parameters.ranges: for a
+        GLUE object the prior ranges, not the extent of the behavioural rows); a dict name -> (lo, hi) or [P, 2] overrides
+        them.  A window with fewer than `min_valid` observed steps (None: half of it) is NaN.  One launch of its own over
+        the sample; the [R, N] matrix stays on the device and only [R, P, bins] comes back.  write=True also writes
+        `<out>/<catchment>.SMART.<func>.dynia` (header DateTime,IC@<name>,LO@<name>,HI@<name>,...; one line per report
+        step, '%.6e').  Under torch.distributed every rank that calls this computes all rows itself (no collective);
+        rank 0 alone writes.  -> identifiability.DynamicIdentifiability"""
+        from .. import engine, identifiability as ident
+        stamps = self.model.timeseries_report[1:]
+        names = list(self.param_names)
+        if half_width is None:
+            half_width = int(15 * 86400 // self.model.delta_save.total_seconds())
+        half_width, bins = int(half_width), int(bins)
+        if min_valid is None:
+            min_valid = half_width + 1
+        if ranges is None:
+            ranges = self.model.parameters.ranges
+        self._check_observations()
+        n, R, P = self._sample.shape[0], len(stamps), len(names)
+        on_device = None
+        if n == 0:      # e.g. GLUE with no behavioural set: nothing to launch
+            shares = np.full((R, P, bins), np.nan)
+            cut, retained, count = np.full(R, np.nan), np.zeros(R, dtype=np.int32), np.zeros(R, dtype=np.int32)
+        else:
+            rows = self._device_sample if self._device_sample is not None else self._sample
+            cat = ident.bin_table(rows, ident._ranges(ranges, names), bins)
+            out, obs = self._launch_stored()
+            res = engine.dynamic_identifiability(out.discharge_report_major, obs, cat, bins, half_width, fraction=fraction,
+                                                 min_valid=min_valid, support=support)
+            on_device = res.shares
+            shares, cut = on_device.cpu().numpy(), res.cut.cpu().numpy()
+            retained, count = res.retained.cpu().numpy(), res.count.cpu().numpy()
+        result = ident.DynamicIdentifiability(stamps, names, ranges, shares, cut, retained, count, level=level,
+                                              half_width=half_width, fraction=float(fraction), support=support,
+                                              min_valid=int(min_valid), device_shares=on_device)
+        if write and sdist.rank_world()[0] == 0:
+            result.file = self.dynia_file
+            ident.write_file(result.file, stamps, names, result.information, result.limits)
+        return result
+
+    @property
+    def dynia_file(self):
+        """`<out>/<catchment>.SMART.<func>.dynia`: beside the sampling database, whatever its format."""
+        return self._side_file('.dynia')
+
     # ---- the per-sample protocol of the reference (spotpy setup class) ------------------------------------
     def parameters(self):
         return np.array([p() for p in self.params])
