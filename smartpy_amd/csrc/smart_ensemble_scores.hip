@@ -25,6 +25,9 @@
 //           hand-over between workgroups, no atomics).  The scan runs block by block: block totals first, chained into
 //           carries in both directions, then the same register scan per block on top of its carries.
 //
+// The network in LDS (bitonic_merge_lds) and the scan (block_scan) are those of smart_order_stats.h, which says why the
+// long stages on the workspace and the sum of ens_finish are spelled out here.
+//
 // DETERMINISM.  No floating-point atomics, every sum has ONE association for a given (N, form): the scans chain the
 // elements of a thread, then the lanes of a wavefront, then the wavefronts (left to right for A, right to left for B);
 // the terms are added per thread in position order, joined by a fixed butterfly over the lanes and a fixed chain over
@@ -34,7 +37,7 @@
 // Weights must be finite and >= 0 (checked by the caller, not here).
 #include "smart_capi_internal.h"
 #include "smart_matrix_common.h"
-#include "smart_order_keys.h"
+#include "smart_order_stats.h"
 #include <cstdint>
 
 namespace smart {
@@ -48,73 +51,6 @@ constexpr unsigned long long kKeyPlusInf = 0xfff0000000000000ull;   // value_key
 constexpr unsigned long long kKeyMinusInf = 0x000fffffffffffffull;  // value_key(-inf)
 static_assert(kEnsCapacity <= 65536, "sample indices are kept as 16-bit numbers");
 
-// ---- the network --------------------------------------------------------------------------------------------------
-// the stages j = j_first, j_first / 2, ... 1 of the merge k on CAP elements in LDS that stand at g0 .. g0 + CAP of the
-// whole sequence (the direction of a pair is a bit of its position in the WHOLE sequence).  The payload follows its key.
-// TWO STAGES A PASS: a thread holds the four elements that the stages j and j / 2 pair among themselves -- (0, 2), (1, 3),
-// then (0, 1), (2, 3) -- at base + {0, j / 2, j, j + j / 2}, base running over the positions whose bits j and j / 2 are
-// clear (k > j: one direction for all four).  Every element is read once and written once for two stages, and half the
-// barriers are gone; a last stage j = 1 that has no partner runs alone.
-template <int CAP, int THREADS, bool PAYLOAD, typename T>
-__device__ inline void ens_merge_lds(unsigned long long *keys, T *pay, int k, int j_first, int g0)
-{
-    int j = j_first;
-    for (; j >= 2; j >>= 2) {
-        const int h = j >> 1;
-        for (int t = threadIdx.x; t < CAP / 4; t += THREADS) {
-            const int low = t & (h - 1);
-            const int base = ((t - low) << 2) | low;
-            const bool up = ((g0 + base) & k) == 0;
-            const int at[4] = {base, base + h, base + j, base + j + h};
-            unsigned long long key[4];
-            T pv[4];
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                key[e] = keys[at[e]];
-                if constexpr (PAYLOAD)
-                    pv[e] = pay[at[e]];
-            }
-            auto exchange = [&](int a, int b) {
-                if ((key[a] > key[b]) == up) {
-                    const unsigned long long kt = key[a];
-                    key[a] = key[b];
-                    key[b] = kt;
-                    if constexpr (PAYLOAD) {
-                        const T pt = pv[a];
-                        pv[a] = pv[b];
-                        pv[b] = pt;
-                    }
-                }
-            };
-            exchange(0, 2), exchange(1, 3), exchange(0, 1), exchange(2, 3);
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                keys[at[e]] = key[e];
-                if constexpr (PAYLOAD)
-                    pay[at[e]] = pv[e];
-            }
-        }
-        __syncthreads();
-    }
-    if (j == 1) {
-        for (int t = threadIdx.x; t < CAP / 2; t += THREADS) {
-            const int i = 2 * t;
-            const bool up = ((g0 + i) & k) == 0;
-            const unsigned long long a = keys[i], b = keys[i + 1];
-            if ((a > b) == up) {
-                keys[i] = b;
-                keys[i + 1] = a;
-                if constexpr (PAYLOAD) {
-                    const T pa = pay[i];
-                    pay[i] = pay[i + 1];
-                    pay[i + 1] = pa;
-                }
-            }
-        }
-        __syncthreads();
-    }
-}
-
 // the first position of sorted keys[0 .. n) that holds the padding = the number of live members
 __device__ inline int ens_live(const unsigned long long *keys, int n)
 {
@@ -127,62 +63,6 @@ __device__ inline int ens_live(const unsigned long long *keys, int n)
             lo = mid + 1;
     }
     return lo;
-}
-
-// ---- the scans ----------------------------------------------------------------------------------------------------
-// a[e] holds the weight at position threadIdx.x * E + e of a block.  On return a[e] is the INCLUSIVE prefix sum of the
-// block at that position (chained left to right) and b[e] the EXCLUSIVE suffix sum (chained right to left); tot_l and
-// tot_r are the block's total in either direction, the same bits in every thread.
-template <int E, int WAVES>
-__device__ inline void ens_scan(double (&a)[E], double (&b)[E], double *wave_l, double *wave_r, double &tot_l, double &tot_r)
-{
-    const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
-    double back = 0.0, fwd = 0.0;
-#pragma unroll
-    for (int e = E - 1; e >= 0; --e) {
-        b[e] = back;
-        back += a[e];
-    }
-#pragma unroll
-    for (int e = 0; e < E; ++e) {
-        fwd += a[e];
-        a[e] = fwd;
-    }
-    double before = 0.0, after = 0.0;
-    for (int j = 0; j < kWave - 1; ++j) {           // the lanes to the left, chained left to right
-        const double tj = __shfl(fwd, j, kWave);
-        if (lane > j)
-            before += tj;
-    }
-    for (int j = kWave - 1; j > 0; --j) {           // the lanes to the right, chained right to left
-        const double tj = __shfl(back, j, kWave);
-        if (lane < j)
-            after += tj;
-    }
-    if (lane == kWave - 1)
-        wave_l[wave] = before + fwd;
-    if (lane == 0)
-        wave_r[wave] = after + back;
-    __syncthreads();
-    double ahead = 0.0, behind = 0.0;
-    tot_l = 0.0;
-    tot_r = 0.0;
-    for (int v = 0; v < WAVES; ++v) {
-        if (v == wave)
-            ahead = tot_l;
-        tot_l += wave_l[v];
-    }
-    for (int v = WAVES - 1; v >= 0; --v) {
-        if (v == wave)
-            behind = tot_r;
-        tot_r += wave_r[v];
-    }
-#pragma unroll
-    for (int e = 0; e < E; ++e) {
-        a[e] = ahead + (before + a[e]);
-        b[e] = behind + (after + b[e]);
-    }
-    __syncthreads();    // wave_l and wave_r may be written again
 }
 
 // ---- the terms ----------------------------------------------------------------------------------------------------
@@ -286,7 +166,7 @@ __global__ __launch_bounds__(THREADS) void smart_ensemble_scores_lds(int N, long
         pit[0] = pit[1] = 0.0;
     __syncthreads();
     for (int k = 2; k <= CAP; k <<= 1)
-        ens_merge_lds<CAP, THREADS, WEIGHTED, unsigned short>(keys, idx, k, k >> 1, 0);
+        bitonic_merge_lds<CAP, THREADS, WEIGHTED, unsigned short>(keys, idx, k, k >> 1, 0);
     if (tid == 0)
         live = WEIGHTED ? ens_live(keys, CAP) : N;
     __syncthreads();
@@ -306,7 +186,7 @@ __global__ __launch_bounds__(THREADS) void smart_ensemble_scores_lds(int N, long
     }
     if constexpr (WEIGHTED) {
         double tot_r;
-        ens_scan<E, WAVES>(a, b, wave_l, wave_r, W, tot_r);
+        block_scan<E, WAVES, true>(a, b, wave_l, wave_r, W, tot_r);
     } else {
         W = (double)M;
 #pragma unroll
@@ -378,7 +258,7 @@ __global__ __launch_bounds__(kEnsGlobalThreads) void smart_ensemble_scores_globa
         }
         __syncthreads();
         for (int k = 2; k <= kEnsBlock; k <<= 1)
-            ens_merge_lds<kEnsBlock, THREADS, WEIGHTED, double>(lk, lw, k, k >> 1, g0);
+            bitonic_merge_lds<kEnsBlock, THREADS, WEIGHTED, double>(lk, lw, k, k >> 1, g0);
         for (int t = tid; t < kEnsBlock; t += THREADS) {
             kg[g0 + t] = lk[t];
             if constexpr (WEIGHTED)
@@ -455,7 +335,7 @@ __global__ __launch_bounds__(kEnsGlobalThreads) void smart_ensemble_scores_globa
                     lw[t] = wg[g0 + t];
             }
             __syncthreads();
-            ens_merge_lds<kEnsBlock, THREADS, WEIGHTED, double>(lk, lw, k, kEnsBlock >> 1, g0);
+            bitonic_merge_lds<kEnsBlock, THREADS, WEIGHTED, double>(lk, lw, k, kEnsBlock >> 1, g0);
             for (int t = tid; t < kEnsBlock; t += THREADS) {
                 kg[g0 + t] = lk[t];
                 if constexpr (WEIGHTED)
@@ -484,7 +364,7 @@ __global__ __launch_bounds__(kEnsGlobalThreads) void smart_ensemble_scores_globa
                 const int i = c * kEnsBlock + tid * E + e;
                 a[e] = i < M ? wg[i] : 0.0;
             }
-            ens_scan<E, WAVES>(a, b, wave_l, wave_r, tot_l, tot_r);
+            block_scan<E, WAVES, true>(a, b, wave_l, wave_r, tot_l, tot_r);
             if (tid == 0) {
                 carry_l[c] = tot_l;
                 carry_r[c] = tot_r;
@@ -523,7 +403,7 @@ __global__ __launch_bounds__(kEnsGlobalThreads) void smart_ensemble_scores_globa
         }
         if constexpr (WEIGHTED) {
             double tot_l, tot_r;
-            ens_scan<E, WAVES>(a, b, wave_l, wave_r, tot_l, tot_r);
+            block_scan<E, WAVES, true>(a, b, wave_l, wave_r, tot_l, tot_r);
 #pragma unroll
             for (int e = 0; e < E; ++e) {
                 a[e] = carry_l[c] + a[e];

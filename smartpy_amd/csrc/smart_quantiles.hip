@@ -18,12 +18,13 @@
 //   select  any N.  No sort: all probabilities bisect the key space together, between the smallest and the largest key
 //           of the row; a round reads the row once and forms S_k = sum of [key_n <= mid_k] * w_n for every k.
 //
+// The network and the scan of the sort form are those of smart_order_stats.h.
+//
 // DETERMINISM.  No floating-point atomics.  Every sum has ONE association for a given (N, form):
-//   scan    thread t owns E consecutive sorted positions and adds them left to right; the lanes of a wavefront are
-//           chained left to right, the wavefronts of the workgroup likewise -- cum[i] = A_wave + (B_lane + L_i), where
-//           each prefix IS the running value at the end of what precedes it.  Hence cum[i] >= cum[i-1] always and
-//           cum[i] == cum[i-1] where w_i == 0 (adding a non-negative term never lowers a rounded sum): the binary search
-//           is well defined and a sample of weight zero never decides a result.  W = cum[N-1], so q <= 1 is always reached.
+//   scan    block_scan: thread t owns E consecutive sorted positions, cum[i] = A_wave + (B_lane + L_i).  Hence cum[i] >=
+//           cum[i-1] always and cum[i] == cum[i-1] where w_i == 0 (adding a non-negative term never lowers a rounded
+//           sum): the binary search is well defined and a sample of weight zero never decides a result.  W = cum[N-1], so
+//           q <= 1 is always reached.
 //   select  thread t adds its elements n = t, t + T, ... in that order; a fixed butterfly joins the lanes, a fixed
 //           chain the wavefronts.  The shape does not depend on mid, every term [key <= mid] * w is monotone in mid and a
 //           rounded sum of non-negative terms is monotone in each: S(mid) is monotone, which the bisection relies on.
@@ -32,7 +33,7 @@
 // Weights must be finite and >= 0 (checked by the caller, not here); weights == nullptr means equal weights.
 #include "smart_capi_internal.h"
 #include "smart_matrix_common.h"
-#include "smart_order_keys.h"
+#include "smart_order_stats.h"
 #include <cstdint>
 
 namespace smart {
@@ -77,55 +78,20 @@ __global__ __launch_bounds__(THREADS) void smart_quantiles_sort(int N, long R, c
     __syncthreads();
 
     // bitonic network over CAP elements, ascending; the padding (above every key of the row) ends up at [N, CAP)
-    for (int k = 2; k <= CAP; k <<= 1) {
-        for (int j = k >> 1; j > 0; j >>= 1) {
-            for (int t = tid; t < CAP / 2; t += THREADS) {
-                const int i = 2 * t - (t & (j - 1));
-                const int l = i + j;
-                const bool up = (i & k) == 0;
-                const unsigned long long a = keys[i], b = keys[l];
-                if ((a > b) == up) {
-                    keys[i] = b;
-                    keys[l] = a;
-                    const unsigned short ia = idx[i];
-                    idx[i] = idx[l];
-                    idx[l] = ia;
-                }
-            }
-            __syncthreads();
-        }
-    }
+    for (int k = 2; k <= CAP; k <<= 1)
+        bitonic_merge_lds<CAP, THREADS, true>(keys, idx, k, k >> 1, 0);
 
     // inclusive scan of the weights in sorted order (header: DETERMINISM)
     double w[E];
-    double total = 0.0;
 #pragma unroll
     for (int e = 0; e < E; ++e) {
         const int i = tid * E + e;
         w[e] = i < N ? (weights ? weights[idx[i]] : 1.0) : 0.0;
-        total = e == 0 ? w[0] : total + w[e];
-        w[e] = total;
     }
-    double before = 0.0;    // B_lane: the lanes to the left, chained
-    const int lane = tid & (kWave - 1), wave = tid / kWave;
-    for (int j = 0; j < kWave - 1; ++j) {
-        const double tj = __shfl(total, j, kWave);
-        if (j == 0)
-            before = lane > 0 ? tj : 0.0;
-        else if (lane > j)
-            before += tj;
-    }
-    if (lane == kWave - 1)
-        wave_total[wave] = lane > 0 ? before + total : total;
-    __syncthreads();
-    double ahead = 0.0;     // A_wave: the wavefronts to the left, chained
-    for (int v = 0; v < wave; ++v)
-        ahead = v == 0 ? wave_total[0] : ahead + wave_total[v];
+    block_scan<E, WAVES>(w, wave_total);
 #pragma unroll
-    for (int e = 0; e < E; ++e) {
-        const double in_wave = lane > 0 ? before + w[e] : w[e];
-        cum[tid * E + e] = wave > 0 ? ahead + in_wave : in_wave;
-    }
+    for (int e = 0; e < E; ++e)
+        cum[tid * E + e] = w[e];
     __syncthreads();
 
     if (tid < K) {
