@@ -700,6 +700,59 @@ int32_t smart_dynia_max_half_width(void);
 int64_t smart_dynia_lds_capacity(void);
 
 /*
+ * PAWN sensitivity from the sample at hand (Pianosi & Wagener 2015, Environ. Model. Softw. 67; the given-data form, 2018,
+ * Environ. Model. Softw. 108): HOW MUCH does the distribution of an output move when a factor is confined to one bin of
+ * its range -- the Kolmogorov-Smirnov distance between the unconditional empirical CDF and the conditional one, per
+ * output, factor and bin.  Inputs: y[R][ld] sample-minor (the discharge matrix where smart_run_ensemble_hip left it, or
+ * any [M][N] table of per-row values); a category table cat[P][N] of uint8 exactly as smart_dynia_hip takes it --
+ * cat[p][n] the bin of row n on factor p, 255 or any value >= B: in no bin of this factor --, P <= SMART_PAWN_MAX_FACTORS,
+ * n_bins B <= SMART_PAWN_MAX_BINS, N <= 2^24.
+ * Per call: counts[p][b] = the number of rows n < N with cat[p][n] == b (int32).
+ * Per row r of the matrix:
+ *   1. The N values sorted ascending, compared as order-preserving keys: -0.0 and +0.0 are one value.
+ *   2. Position i (0-based) is an EVALUATION POINT iff i == N - 1 or key[i] != key[i + 1]: the end of a run of ties.
+ *   3. For factor p and bin b with n_b = counts[p][b] > 0, c_b(i) the number of positions <= i whose row lies in bin b:
+ *        num[r][p][b] = max over the evaluation points i of |(i + 1) n_b - c_b(i) N|     (integers below 2^48)
+ *        ks[r][p][b]  = (double) num / ((double) N * (double) n_b)      (the product is exact: ONE correctly rounded division)
+ *   4. n_b == 0: NaN.
+ *   5. A value of the row that is not finite (NaN, +-inf): every ks[r][.][.] is NaN.
+ * This is sup over x of |F(x) - F_b(x)| of the two right-continuous empirical CDFs: both are constant between sample
+ * values, so the supremum is taken at a sample value, after all its ties.  Rows of category 255 belong to the
+ * unconditional sample and to no bin.
+ * Outputs, device pointers: ks[R][P][B] (double) and counts[P][B] (int32).  Asynchronous on stream; allocates nothing: the
+ * workspace is the caller's.  No atomics of any kind.  Everything is integers until the one division (held exactly in
+ * doubles: smartpy_amd/csrc/smart_pawn.hip), so the result does not depend on the launch, the batches or the form: the
+ * two forms agree BIT FOR BIT, and with the definition as written.
+ * One workgroup per row, in one of two forms:
+ *   SMART_PAWN_LDS     the row sorted in LDS with 16-bit sample indices; no workspace;
+ *                      n_samples <= smart_pawn_lds_capacity(), else SMART_E_SIZE
+ *   SMART_PAWN_GLOBAL  any n_samples <= 2^24: (key, 32-bit index) pairs sorted in the workspace (long stages there, short
+ *                      ones block by block in LDS); the rows go in batches of as many as the workspace holds
+ *   SMART_PAWN_AUTO    LDS within its capacity, global beyond
+ * Errors (all found before the device is touched; the first offending argument wins): SMART_E_NULL y, cat, ks or counts
+ * missing; SMART_E_SIZE a size < 1, n_samples > 2^24, n_rows >= 2^31, ld < n_samples, n_factors outside 1 .. 16, n_bins
+ * outside 1 .. 64; SMART_E_MODE unknown method; SMART_E_SIZE the LDS form beyond its capacity; SMART_E_NULL the global form
+ * without a workspace, SMART_E_SIZE a workspace that does not hold one step; then SMART_E_NO_DEVICE without a HIP device.
+ */
+#define SMART_PAWN_MAX_FACTORS 16
+#define SMART_PAWN_MAX_BINS 64
+#define SMART_PAWN_AUTO 0
+#define SMART_PAWN_LDS 1
+#define SMART_PAWN_GLOBAL 2
+int smart_pawn_ks_hip(int64_t n_samples, int64_t n_rows, const double *y, int64_t ld, const uint8_t *cat, int32_t n_factors,
+                      int32_t n_bins, double *ks, int32_t *counts, int32_t method, void *workspace, int64_t workspace_bytes,
+                      void *stream);
+
+/* The workspace smart_pawn_ks_hip asks for, in bytes: 0 for the LDS form (and for AUTO within its capacity); for the
+ * global form one step is n_samples rounded up to a power of two (at least 4096) times 12 bytes, and the answer holds
+ * min(n_rows, as many steps as fit in 256 MiB, at least one).  The entry itself takes any workspace that holds one step.
+ * A negative SMART_E_* code for what the entry refuses.  Needs no device. */
+int64_t smart_pawn_workspace_bytes(int64_t n_samples, int64_t n_rows, int32_t method);
+
+/* The largest n_samples SMART_PAWN_LDS takes: 8192 (10 bytes per sorted element in LDS).  Needs no device. */
+int64_t smart_pawn_lds_capacity(void);
+
+/*
  * Sampling database, CSV flavour -- the rows MonteCarlo.save writes one by one (montecarlo.py:211-231): every value
  * cast to float32 and printed '%.6e', comma separated, one '\n'-terminated line per sample.  HOST pointers, no
  * device involved.  Appends n_rows lines of n_cols values (row-major float32 table: objective functions, parameters,

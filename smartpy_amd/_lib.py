@@ -39,6 +39,8 @@ ENSEMBLE_SCORE_COLS = len(ENSEMBLE_SCORE_NAMES)
 ENSEMBLE_METHODS = {'auto': 0, 'lds': 1, 'global': 2}           # SMART_ENS_*
 DYNIA_MAX_FACTORS, DYNIA_MAX_BINS = 16, 64
 DYNIA_SUPPORTS = {'equal': 0, 'linear': 1}                      # SMART_DYNIA_*
+PAWN_MAX_FACTORS, PAWN_MAX_BINS = 16, 64
+PAWN_METHODS = {'auto': 0, 'lds': 1, 'global': 2}               # SMART_PAWN_*
 
 _dp = ctypes.c_void_p   # device or host address, passed as an integer
 
@@ -119,6 +121,10 @@ SYMBOLS = {
                                                      ctypes.c_int32]),
     'smart_dynia_max_half_width': (ctypes.c_int32, []),
     'smart_dynia_lds_capacity': (ctypes.c_int64, []),
+    'smart_pawn_ks_hip': (ctypes.c_int, [ctypes.c_int64, ctypes.c_int64, _dp, ctypes.c_int64, _dp, ctypes.c_int32,
+                                         ctypes.c_int32, _dp, _dp, ctypes.c_int32, _dp, ctypes.c_int64, _dp]),
+    'smart_pawn_workspace_bytes': (ctypes.c_int64, [ctypes.c_int64, ctypes.c_int64, ctypes.c_int32]),
+    'smart_pawn_lds_capacity': (ctypes.c_int64, []),
     'smart_db_append_rows': (ctypes.c_int, [ctypes.c_char_p, ctypes.POINTER(ctypes.c_float), ctypes.c_int64,
                                             ctypes.c_int64, ctypes.c_int32]),
     'smart_db_parse_rows': (ctypes.c_int64, [ctypes.c_char_p, ctypes.c_int64, ctypes.c_int64,

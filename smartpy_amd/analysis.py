@@ -1,7 +1,7 @@
 """The analyses of a stored [R, N] discharge matrix (row r = every sample's discharge of report step r), each one launch
 through the C ABI (csrc/smart_analysis_capi.hip): objective functions, weighted quantiles over the samples, objective
 functions per window of report steps, flow duration curves, hydrological signatures, Sobol indices, ensemble
-verification scores, the dynamic identifiability analysis -- and the Pareto selection over the scores they leave, [N, C] with a row per sample.  torch tensors
+verification scores, the dynamic identifiability analysis, the PAWN sensitivity -- and the Pareto selection over the scores they leave, [N, C] with a row per sample.  torch tensors
 in, torch tensors out, as in engine.py -- which imports this module and re-exports every public name of it
 (engine.flow_duration and the others are these functions); what they share on the way to the launch are the private
 helpers at the top.
@@ -690,3 +690,56 @@ def dynamic_identifiability(discharge_report_major, obs, categories, n_bins, hal
                                      cat.data_ptr(), P, B, code, shares.data_ptr(), cut.data_ptr(), retained.data_ptr(),
                                      count.data_ptr(), _ptr(errors), N, _ptr(work), need, _stream(dev)))
     return DyniaResult(shares, cut, retained, count, errors)
+
+
+def pawn_lds_capacity():
+    """The largest number of samples the LDS form of pawn_ks takes (no device needed)."""
+    return int(_lib.lib().smart_pawn_lds_capacity())
+
+
+class PawnResult(object):
+    """Device tensors of one pawn_ks call: ks [R, P, B] float64 and counts [P, B] int32; numpy() gives both on the host."""
+
+    def __init__(self, ks, counts):
+        self.ks, self.counts = ks, counts
+
+    def numpy(self):
+        return self.ks.cpu().numpy(), self.counts.cpu().numpy()
+
+
+def pawn_ks(values_row_major, categories, n_bins, method='auto'):
+    """The Kolmogorov-Smirnov distances of PAWN (Pianosi & Wagener 2015, 2018) on the sample at hand -> PawnResult.
+    values_row_major: [R, N], a row per output -- the stored discharge matrix, or any table of per-sample values; per row
+    its N values are sorted (-0.0 and +0.0 one value) and ks[r, p, b] is the largest distance between the empirical CDF
+    of them all and that of the rows in bin b of factor p, taken at the end of every run of ties: a ratio of integers,
+    the same bits as the numpy statement of the definition, whatever the form.  categories: [P, N] uint8, host or device
+    (identifiability.bin_table, pawn.dummy_table), 255 = in no bin of the factor; P <= 16, n_bins <= 64.  counts[p, b]
+    is the number of rows in the bin; an empty bin is NaN, and so is every ks of a row that holds a value that is not
+    finite.  method: 'auto' (by size), 'lds' (N <= pawn_lds_capacity()) or 'global' (N <= 2**24).  The workspace of the
+    call is sized and owned here (include/smart_amd.h: smart_pawn_ks_hip)."""
+    who = 'pawn_ks'
+    L = _lib.lib()
+    code = _code(who, 'method', _lib.PAWN_METHODS, method)
+    B = int(n_bins)
+    shape = tuple(getattr(categories, 'shape', ()))
+    n_cols = tuple(values_row_major.shape)[-1]
+    if len(shape) != 2 or shape[1] != n_cols or str(getattr(categories, 'dtype', '')).split('.')[-1] != 'uint8':
+        raise SmartEngineError(-2, "{}: categories must be uint8 [factors, {}] (identifiability.bin_table), not {} {}."
+                               .format(who, n_cols, getattr(categories, 'dtype', type(categories).__name__), shape))
+    P = shape[0]
+    # ---- from here on the device
+    y, R, N, ld = _matrix(values_row_major)
+    dev = y.device
+    if not isinstance(categories, torch.Tensor):
+        categories = torch.from_numpy(np.ascontiguousarray(categories))
+    cat = categories.to(dev).contiguous()
+    ks = torch.empty((R, P, B), dtype=torch.float64, device=dev)
+    counts = torch.empty((P, B), dtype=torch.int32, device=dev)
+    if R == 0 or N == 0:
+        return PawnResult(ks, counts)
+    # (sizes the helper refuses get no workspace: the entry refuses them too, with its text)
+    work, need = _workspace(max(0, int(L.smart_pawn_workspace_bytes(N, R, code))), dev)
+    with torch.cuda.device(dev):
+        _lib.check(L.smart_pawn_ks_hip(N, R, y.data_ptr(), ld, cat.data_ptr(), P, B, ks.data_ptr(), counts.data_ptr(), code,
+                                       _ptr(work), need, _stream(dev)))
+    return PawnResult(ks, counts)

@@ -56,6 +56,9 @@ UNITS = {
     # default flags, NaNs honoured -- a value that is not finite has to reach the window sums it lies in, and is found
     # there by its key
     'smart_dynia.hip': [],
+    # PAWN sensitivity (Kolmogorov-Smirnov distances across the samples, per row of a matrix): default flags, NaNs
+    # honoured -- a value that is not finite is found by its key, and the integers held in doubles are exact either way
+    'smart_pawn.hip': [],
     'smart_capi.hip': [],
     # the C entries of the matrix analyses, and smart_objfn_matrix: the flags smart_capi.hip had it compiled with
     'smart_analysis_capi.hip': [],

@@ -1,6 +1,6 @@
 // smart_analysis_capi.hip -- the C ABI of the analyses of a stored discharge matrix sim[R][ld] (include/smart_amd.h):
 // objective functions, weighted quantiles, objective functions per window, flow duration curves, hydrological signatures, Sobol indices, the block bootstrap of the objective functions, and of
-// the Pareto selection over the scores they leave, the ensemble verification scores and the dynamic identifiability analysis per report step, with their capacity and workspace entries -- validation and launch --
+// the Pareto selection over the scores they leave, the ensemble verification scores, the dynamic identifiability analysis and the PAWN sensitivity per report step, with their capacity and workspace entries -- validation and launch --
 // and the one kernel among them that has no unit of its own, smart_objfn_matrix.  Every refusal comes before the device is asked for; the rules the entries share are the
 // static helpers below, which take the entry's name for the text.
 #include "smart_capi_internal.h"
@@ -254,6 +254,35 @@ static const char *dynia_sizes(int64_t n_samples, int64_t n_reports, int32_t hal
     else
         return nullptr;
     return text;
+}
+
+// the size and method rules of smart_pawn_ks_hip that smart_pawn_workspace_bytes shares (ld, the factors and the bins lie
+// between the sizes and the method in the entry); SMART_OK, or the code of the refusal with its text
+static int pawn_sizes(int64_t n_samples, int64_t n_rows, char *text, size_t len)
+{
+    if (n_samples < 1 || n_rows < 1)
+        snprintf(text, len, "need n_samples, n_rows >= 1 (got %lld, %lld)", (long long)n_samples, (long long)n_rows);
+    else if (n_samples > pawn_max_samples())
+        snprintf(text, len, "n_samples %lld, at most %lld (2^24)", (long long)n_samples, (long long)pawn_max_samples());
+    else if (n_rows > 0x7fffffffll)
+        snprintf(text, len, "n_rows %lld is more than one launch takes (2^31 - 1)", (long long)n_rows);
+    else
+        return SMART_OK;
+    return SMART_E_SIZE;
+}
+
+static int pawn_method(int64_t n_samples, int32_t method, char *text, size_t len)
+{
+    if (method != SMART_PAWN_AUTO && method != SMART_PAWN_LDS && method != SMART_PAWN_GLOBAL) {
+        snprintf(text, len, "method '%d' unknown.", (int)method);
+        return SMART_E_MODE;
+    }
+    if (method == SMART_PAWN_LDS && n_samples > pawn_lds_capacity()) {
+        snprintf(text, len, "the LDS form takes at most %lld samples, not %lld", (long long)pawn_lds_capacity(),
+                 (long long)n_samples);
+        return SMART_E_SIZE;
+    }
+    return SMART_OK;
 }
 
 } // namespace smart
@@ -636,5 +665,48 @@ int64_t smart_dynia_workspace_bytes(int64_t n_samples, int64_t n_reports, int32_
 int32_t smart_dynia_max_half_width(void) { return dynia_max_half_width(); }
 
 int64_t smart_dynia_lds_capacity(void) { return dynia_lds_capacity(); }
+
+int smart_pawn_ks_hip(int64_t n_samples, int64_t n_rows, const double *y, int64_t ld, const uint8_t *cat, int32_t n_factors,
+                      int32_t n_bins, double *ks, int32_t *counts, int32_t method, void *workspace, int64_t workspace_bytes,
+                      void *stream)
+{
+    static const char entry[] = "smart_pawn_ks_hip";
+    int rc;
+    if (!y || !cat || !ks || !counts)
+        return fail(SMART_E_NULL, "%s: y, cat, ks and counts are required (%s is NULL)", entry,
+                    !y ? "y" : (!cat ? "cat" : (!ks ? "ks" : "counts")));
+    char text[160];
+    if ((rc = pawn_sizes(n_samples, n_rows, text, sizeof text)))
+        return fail(rc, "%s: %s", entry, text);
+    if (ld < n_samples)
+        return fail(SMART_E_SIZE, "%s: ld %lld is less than n_samples %lld", entry, (long long)ld, (long long)n_samples);
+    if (n_factors < 1 || n_factors > SMART_PAWN_MAX_FACTORS)
+        return fail(SMART_E_SIZE, "%s: n_factors %d must be in 1 .. %d", entry, (int)n_factors, SMART_PAWN_MAX_FACTORS);
+    if (n_bins < 1 || n_bins > SMART_PAWN_MAX_BINS)
+        return fail(SMART_E_SIZE, "%s: n_bins %d must be in 1 .. %d", entry, (int)n_bins, SMART_PAWN_MAX_BINS);
+    if ((rc = pawn_method(n_samples, method, text, sizeof text)))
+        return fail(rc, "%s: %s", entry, text);
+    const bool lds = method == SMART_PAWN_LDS || (method == SMART_PAWN_AUTO && n_samples <= pawn_lds_capacity());
+    if (!lds && (rc = workspace_fits(entry, /*for_objfn=*/false, workspace, workspace_bytes, pawn_step_bytes((long)n_samples))))
+        return rc;
+    if ((rc = device_ready()))
+        return rc;
+    launch_pawn((long)n_samples, (long)n_rows, y, (long)ld, cat, (int)n_factors, (int)n_bins, ks, counts, lds, workspace,
+                (long)workspace_bytes, (hipStream_t)stream);
+    return launched();
+}
+
+int64_t smart_pawn_workspace_bytes(int64_t n_samples, int64_t n_rows, int32_t method)
+{
+    char text[160];
+    int rc;
+    if ((rc = pawn_sizes(n_samples, n_rows, text, sizeof text)) || (rc = pawn_method(n_samples, method, text, sizeof text)))
+        return rc;
+    if (method == SMART_PAWN_LDS || (method == SMART_PAWN_AUTO && n_samples <= pawn_lds_capacity()))
+        return 0;
+    return pawn_workspace_bytes((long)n_samples, (long)n_rows);
+}
+
+int64_t smart_pawn_lds_capacity(void) { return pawn_lds_capacity(); }
 
 } // extern "C"

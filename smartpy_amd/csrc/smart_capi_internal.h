@@ -86,4 +86,12 @@ void launch_dynia(long N, long R, const double *sim, long ld, const double *obs,
                   const unsigned char *cat, int P, int B, int support, double *shares, double *cut, int *retained,
                   int *count, double *err, long ld_err, void *workspace, long workspace_bytes, hipStream_t s);
 
+// ---- smart_pawn.hip
+long pawn_lds_capacity();
+long pawn_max_samples();
+long pawn_step_bytes(long N);
+long pawn_workspace_bytes(long N, long R);
+void launch_pawn(long N, long R, const double *y, long ld, const unsigned char *cat, int P, int B, double *ks, int *counts,
+                 bool lds, void *workspace, long workspace_bytes, hipStream_t s);
+
 } // namespace smart

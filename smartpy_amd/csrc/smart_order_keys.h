@@ -1,8 +1,8 @@
 // smart_order_keys.h -- doubles as ORDER-PRESERVING 64-BIT KEYS: unsigned order of the keys = numeric order of the
 // doubles, every NaN one key above +inf, both zeros one key, and one key above them all for padding.  What the kernels
-// that sort or select compare: smart_quantiles.hip, smart_ensemble_scores.hip and smart_dynia.hip along the sample axis
-// (with smart_order_stats.h, the network and the scan of those that sort, and smart_key_select.h, the k-th key by
-// bisection), smart_flow_duration.hip along time.
+// that sort or select compare: smart_quantiles.hip, smart_ensemble_scores.hip, smart_dynia.hip and smart_pawn.hip along
+// the sample axis (with smart_order_stats.h, the network and the scan of those that sort, and smart_key_select.h, the
+// k-th key by bisection), smart_flow_duration.hip along time.
 #pragma once
 #include <hip/hip_runtime.h>
 

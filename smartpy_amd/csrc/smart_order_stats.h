@@ -1,8 +1,9 @@
 // smart_order_stats.h -- the WORKGROUP PRIMITIVES that the kernels which SORT along the sample axis share, each defined
 // ONCE: the bitonic network in LDS over 64-bit keys (smart_order_keys.h) with a payload, and the scan of the weights in
 // sorted order.  Their order of operations is what the determinism of those kernels rests on.  Users:
-// smart_quantiles_sort (network, forward scan) and smart_ensemble_scores_lds / _global (network, scan in both
-// directions).  One workgroup of THREADS threads calls these together.
+// smart_quantiles_sort (network, forward scan), smart_ensemble_scores_lds / _global (network, scan in both
+// directions) and smart_pawn_lds / _global (network with the sample index as payload; the long stages of a merge on a
+// workspace, bitonic_long_stages).  One workgroup of THREADS threads calls these together.
 //
 // NOT HERE, on purpose:
 //   fdc_sort (smart_flow_duration.hip) sorts along TIME, one column per lane group: it interleaves the columns in LDS and
@@ -81,6 +82,66 @@ __device__ inline void bitonic_merge_lds(unsigned long long *keys, T *pay, int k
                     pay[i] = pay[i + 1];
                     pay[i + 1] = pa;
                 }
+            }
+        }
+        __syncthreads();
+    }
+}
+
+// the LONG stages j = k / 2, k / 4, ... BLOCK of the merge k on P elements in memory (kg: keys, pg: the payload that
+// follows its key), for a network whose shorter stages run block by block in LDS (bitonic_merge_lds from BLOCK / 2 on).
+// Two stages in one pass while both reach past a block, the four-element exchange of bitonic_merge_lds; a last one alone.
+// ONE workgroup owns the buffer: __syncthreads() is the only ordering.  User: smart_pawn_global (32-bit sample indices);
+// the ensemble kernels keep their own text of these stages (above).
+template <int BLOCK, int THREADS, typename T>
+__device__ inline void bitonic_long_stages(unsigned long long *kg, T *pg, int P, int k)
+{
+    int j = k >> 1;
+    for (; (j >> 1) >= BLOCK; j >>= 2) {
+        const int h = j >> 1;
+        for (int t = threadIdx.x; t < P / 4; t += THREADS) {
+            const int low = t & (h - 1);
+            const int base = ((t - low) << 2) | low;
+            const bool up = (base & k) == 0;
+            const int at[4] = {base, base + h, base + j, base + j + h};
+            unsigned long long key[4];
+            T pv[4];
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                key[e] = kg[at[e]];
+                pv[e] = pg[at[e]];
+            }
+            auto exchange = [&](int a, int b) {
+                if ((key[a] > key[b]) == up) {
+                    const unsigned long long kt = key[a];
+                    key[a] = key[b];
+                    key[b] = kt;
+                    const T pt = pv[a];
+                    pv[a] = pv[b];
+                    pv[b] = pt;
+                }
+            };
+            exchange(0, 2), exchange(1, 3), exchange(0, 1), exchange(2, 3);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                kg[at[e]] = key[e];
+                pg[at[e]] = pv[e];
+            }
+        }
+        __syncthreads();
+    }
+    for (; j >= BLOCK; j >>= 1) {
+        for (int t = threadIdx.x; t < P / 2; t += THREADS) {
+            const int i = 2 * t - (t & (j - 1));
+            const int l = i + j;
+            const bool up = (i & k) == 0;
+            const unsigned long long ka = kg[i], kb = kg[l];
+            if ((ka > kb) == up) {
+                kg[i] = kb;
+                kg[l] = ka;
+                const T pa = pg[i];
+                pg[i] = pg[l];
+                pg[l] = pa;
             }
         }
         __syncthreads();

@@ -465,6 +465,98 @@ class MonteCarlo(object):
         """`<out>/<catchment>.SMART.<func>.dynia`: beside the sampling database, whatever its format."""
         return self._side_file('.dynia')
 
+    # ---- PAWN sensitivity ---------------------------------------------------------------------------------
+    def pawn_sensitivity(self, of='discharge', bins=10, statistic='median', dummies=3, seed=0, min_count=None, ranges=None,
+                         method='auto', write=False):
+        """HOW MUCH every parameter moves the distribution of an output (PAWN, Pianosi & Wagener 2015; the given-data
+        form, 2018), from the sample as it is -- no design of its own.  Per output the Kolmogorov-Smirnov distance between
+        the CDF over all rows and the CDF over the rows whose parameter lies in one of `bins` equal bins of its range;
+        the index of a parameter is the `statistic` ('median', 'mean', 'max') of those distances over the bins that hold
+        at least `min_count` rows (None: max(10, N // (4 bins))).  of='discharge': every report step, from the [R, N]
+        matrix where a launch of its own leaves it (time-varying sensitivity); of='objective_functions': NSE, KGE, KGEc,
+        KGEa, KGEb, PBias, RMSE and the groundwater ratio of every row ([8, N]; those of the last run() where there was
+        one); an array or tensor [M, N]: any per-row values of the caller's.  `dummies` factors that influence nothing by
+        construction (random partitions of the rows into `bins` groups, numpy.random.default_rng(seed)) travel through
+        the same launch: the largest index among them is the noise floor `dummy`, and `influential` = index > dummy.
+        ranges=None: the ranges the sample was drawn from, as dynamic_identifiability takes them.  The distances are
+        ratios of integers: the same bits as the definition in numpy, whatever `method` ('auto', 'lds', 'global').
+        write=True also writes `<out>/<catchment>.SMART.<func>.pawn` (header DateTime,<name>,...,dummy; one line per
+        output, '%.6e').  Under torch.distributed every rank that calls this computes all rows itself (no collective);
+        rank 0 alone writes.  -> pawn.PawnSensitivity"""
+        from .. import _lib, engine, identifiability as ident, pawn
+        names = list(self.param_names)
+        bins, dummies = int(bins), int(dummies)
+        n, P = self._sample.shape[0], len(names)
+        if not 0 <= dummies <= _lib.PAWN_MAX_FACTORS - P:
+            raise SmartEngineError(-2, "pawn_sensitivity: dummies {} must be in 0 .. {} ({} factors a launch, {} of them "
+                                       "parameters).".format(dummies, _lib.PAWN_MAX_FACTORS - P,
+                                                             _lib.PAWN_MAX_FACTORS, P))
+        if statistic not in pawn.STATISTICS:
+            raise SmartEngineError(-7, "pawn_sensitivity: statistic '{}' unknown.".format(statistic))
+        if ranges is None:
+            ranges = self.model.parameters.ranges
+        if min_count is None:
+            min_count = pawn.default_min_count(n, bins)
+        values = None
+        if isinstance(of, str):
+            if of not in ('discharge', 'objective_functions'):
+                raise SmartEngineError(-7, "pawn_sensitivity: of '{}' unknown.".format(of))
+            stamps = self.model.timeseries_report[1:] if of == 'discharge' else OBJ_FN_NAMES + ['GW_RATIO']
+        else:
+            values = of
+            if len(values.shape) != 2 or values.shape[1] != n:
+                raise SmartEngineError(-2, "pawn_sensitivity: the values must be [M, {}] (a column per row of the sample), "
+                                           "not {}.".format(n, tuple(values.shape)))
+            stamps = list(range(values.shape[0]))
+        on_device = None
+        if n == 0:      # e.g. GLUE with no behavioural set: nothing to launch
+            ks = np.full((len(stamps), P + dummies, bins), np.nan)
+            counts = np.zeros((P + dummies, bins), dtype=np.int32)
+            table = np.empty((P + dummies, 0), dtype=np.uint8)
+        else:
+            rows = self._device_sample if self._device_sample is not None else self._sample
+            cat = ident.bin_table(rows, ident._ranges(ranges, names), bins)
+            extra = pawn.dummy_table(n, bins, dummies, seed)
+            if ident._is_tensor(cat):
+                import torch
+                cat = torch.cat([cat, torch.from_numpy(extra).to(cat.device)], dim=0)
+            else:
+                cat = np.concatenate([cat, extra], axis=0)
+            if values is None and of == 'discharge':
+                values = self._launch_stored()[0].discharge_report_major
+            elif values is None:
+                values = self._score_table()
+            res = engine.pawn_ks(values, cat, bins, method=method)
+            on_device = res.ks
+            ks, counts = res.numpy()
+            table = cat.cpu().numpy() if ident._is_tensor(cat) else cat
+        result = pawn.PawnSensitivity(stamps, names, ks, counts, statistic=statistic, min_count=min_count,
+                                      categories=table, device_ks=on_device)
+        if write and sdist.rank_world()[0] == 0:
+            result.file = self.pawn_file
+            pawn.write_file(result.file, stamps, names, result.index, result.dummy)
+        return result
+
+    def _score_table(self):
+        """[8, N] on the device: the seven objective functions and the groundwater ratio of every row of the sample --
+        those of the last run(), or of a launch of its own where there was none"""
+        import torch
+        n = self._sample.shape[0]
+        if self.device_obj_fns is not None and self.device_obj_fns.shape[0] == n:
+            scores, gw = self.device_obj_fns, self.device_gw
+        else:
+            self._check_observations()
+            rows = self._device_sample if self._device_sample is not None else self._sample
+            out = self.model.simulate_ensemble(rows, objective_functions=True, gw_constraint=self.constraints['gw'],
+                                               math_mode=self.math_mode)
+            scores, gw = out.objfn[:n], out.gw[:n]
+        return torch.cat([scores[:, :len(OBJ_FN_NAMES)], gw.unsqueeze(1)], dim=1).t().contiguous()
+
+    @property
+    def pawn_file(self):
+        """`<out>/<catchment>.SMART.<func>.pawn`: beside the sampling database, whatever its format."""
+        return self._side_file('.pawn')
+
     # ---- the per-sample protocol of the reference (spotpy setup class) ------------------------------------
     def parameters(self):
         return np.array([p() for p in self.params])
