@@ -29,6 +29,7 @@ __global__ __launch_bounds__(WX *WR *kWave) void smart_objfn_matrix(long N, long
     __shared__ double part[WR > 1 ? WR : 1][5][kWave];
     obs_stats<false>(obs, R, st, nullptr, sh); // every thread stores the same five values to st
     __syncthreads();
+    const long r1 = first_observed_row(obs, R, sh);
     const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
     const int wx = wave % WX, wr = wave / WX;
     long n = ((long)blockIdx.x * WX + wx) * kWave + lane;
@@ -37,7 +38,10 @@ __global__ __launch_bounds__(WX *WR *kWave) void smart_objfn_matrix(long N, long
         n = N - 1;
     const double ebar = st[1];
     const double *col = sim + n;
-    const double shift = col[0]; // any constant per sample works (finish_objectives); the first value keeps the digits
+    // any constant per sample works (finish_objectives); the sample's value at the first OBSERVED report keeps the
+    // digits: it is one of the summed values.  Row 0, where it carries no observation, is none of them -- a flood before
+    // the gauge begins, a start-up value, a NaN that add() would never have seen
+    const double shift = col[r1 * ld];
     double A = 0.0, B = 0.0, C1 = 0.0, C2 = 0.0, C3 = 0.0;
     auto add = [&](double e, double s) {
         if (!is_nan_bits(e)) { // montecarlo.py:195-196

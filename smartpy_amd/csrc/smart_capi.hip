@@ -40,8 +40,11 @@ __global__ __launch_bounds__(256) void smart_obs_prepare(const double *obs, long
     const long c = blockIdx.x;
     double *w = ws + c * (kWsHead + R);
     obs_stats<true>(obs + c * R, R, st, w + kWsHead, sh);
+    const long r1 = first_observed_row(obs + c * R, R, sh);
     if (threadIdx.x < 5)
         w[threadIdx.x] = st[threadIdx.x];
+    if (threadIdx.x == 5)
+        w[kWsFirst] = (double)r1; // the report whose value is the constant of the fused moments (Reporter, smart_device.h)
 }
 
 // ---- small kernels around the launch -------------------------------------------------------------------------

@@ -150,14 +150,21 @@ __device__ __forceinline__ void raise_status(const KArgs &a, int bit)
 #endif
 
 constexpr int kIllCondWaves = 16; // workgroups per block of 64 samples of the kernels that take one sample per DPP row
-constexpr int kWsHead = 8;
+constexpr int kWsHead = 8;  // doubles in front of a catchment's deviations: obs_stats' five, then
+constexpr int kWsFirst = 5; // ... the number of the first report that carries an observation (smart_obs_prepare)
 
 // objective functions from the one-pass moments (montecarlo.py:193-209; formulas of spotpy's nashsutcliffe,
 // kge(return_all=True), pbias, rmse).  Moments are taken about the observation mean, known before the run:
 //   A = sum(s - e)   B = sum((s - e)^2)   C1 = sum(s - c)   C2 = sum((s - c)^2)   C3 = sum((e - ebar)(s - c))
-// with ebar the observation mean and c ANY constant per sample (variance and covariance do not depend on it); the
-// kernels take c = the sample's own first reported discharge: a simulated series that barely moves (std 1e-4 of its
-// mean) then keeps its variance through the one-pass form, where c = ebar lost half the digits (KGEa off by 2e-7)
+// with ebar the observation mean and c ANY constant per sample (variance and covariance do not depend on it).  What c
+// costs is digits: var_s = C2 / n - (C1 / n)^2 is off by about n 2^-53 kappa of itself, kappa = 1 + ((c - mean s) / std s)^2.
+// A simulated series that barely moves (std 1e-4 of its mean) lost half of them with c = ebar (KGEa off by 2e-7); with c
+// ONE OF THE SUMMED VALUES kappa is at most about n.  So the constant of a sample is its value at the FIRST REPORT THAT
+// CARRIES AN OBSERVATION: report r1 of the catchment (smart_objfn_matrix: first_observed_row; the fused moments: Reporter
+// below, r1 left in the workspace head by smart_obs_prepare), the first listed row of the window (smart_objfn_windows),
+// the launch's first valid row (smart_bootstrap_moments).  Report 0, where it carries no observation, is none of the
+// summed values -- a flood before the gauge begins, a start-up value -- and kappa about it has no bound
+// (tests/test_objfn_truth_host.py).  With report 0 observed, r1 = 0 and every kernel does what it always did.
 __device__ inline void finish_objectives(const double *st, double A, double B, double C1, double C2, double C3,
                                          double gw_sim, double gw_obs, double *o)
 {
@@ -608,7 +615,8 @@ __device__ __forceinline__ void init_model(const KArgs &a, const LaneCtx &x, Mod
 struct Reporter {
     const double *__restrict__ obs; // this catchment's observations | null
     const double *__restrict__ ws;  // this catchment's workspace (statistics + e - mean) | null
-    double shift; // c above: this sample's discharge of report step 0
+    double shift; // c above: this sample's discharge of the first report step that carries an observation
+    long r1;      // ... the number of that report (smart_obs_prepare; 0 where there are no observations)
     bool want_obj;
     double A = 0.0, B = 0.0, C1 = 0.0, C2 = 0.0, C3 = 0.0;
 
@@ -619,7 +627,12 @@ struct Reporter {
         ws = ws_all ? ws_all + x.c * (kWsHead + a.R) : nullptr;
         obs = obs_all ? obs_all + x.c * a.R : nullptr;
         shift = 0.0;
+        r1 = want_obj && ws ? (long)__builtin_amdgcn_readfirstlane((int)ws[kWsFirst]) : 0; // (wave-uniform: one catchment)
     }
+
+    // Is report r one that (re)sets the constant?  No moment is added before r1, so "every report up to r1 sets it, the
+    // last assignment wins" is "report r1 sets it" -- without a test for equality on a number the asm does not carry.
+    __device__ __forceinline__ bool sets_shift(long r) const { return r <= r1; }
 
     // one report with an observation: `e` the observation, `w` its deviation from the observation mean
     __device__ __forceinline__ void add_moments(double val, double e, double w)
@@ -639,7 +652,7 @@ struct Reporter {
             __builtin_nontemporal_store(val, &a.discharge[(x.c * a.R + r) * a.ld + x.n]);
         if (want_obj) {
             const double e = obs[r];
-            if (r == 0)
+            if (sets_shift(r))
                 shift = val;
             if (!is_nan_bits(e)) { // montecarlo.py:195-196 (add_moments() written out: through the method the code of
                                    // smart_fast_stiff, _guard, _plain and smart_ensemble_literal comes out different)
@@ -677,7 +690,7 @@ struct Reporter {
         prime(a, r + 1);
         if (a.discharge && x.live)
             __builtin_nontemporal_store(val, &a.discharge[(x.c * a.R + r) * a.ld + x.n]);
-        if (want_obj && r == 0)
+        if (want_obj && sets_shift(r))
             shift = val;
         if (want_obj && !is_nan_bits(e)) // montecarlo.py:195-196
             add_moments(val, e, w);
@@ -702,9 +715,9 @@ struct Reporter {
     // The report of the interval engine (run_ensemble_merged over piecewise-constant forcing): what emit() does, operation
     // for operation, in the form of the streamed step loop above -- the row pointer (begin_rows), no test for the lanes
     // beyond the batch, a missing observation told by the mark in its deviation (one 32-bit scalar compare: e and w are in
-    // scalar registers, requested an interval ahead by interval_loop_obs) -- and with report 0, the one that sets `shift`,
-    // looked for only where the caller says it may be (MAY_BE_FIRST: the intervals interval_loop takes on their own;
-    // `first`: this is report 0).  OBJ: the caller has observations (Reporter::want_obj, decided outside its loop).
+    // scalar registers, requested an interval ahead by interval_loop_obs) -- and with the reports up to r1, the ones that set
+    // `shift`, looked for only where the caller says they may be (MAY_BE_FIRST: the intervals interval_loop takes on their
+    // own; `first`: sets_shift(this report)).  OBJ: the caller has observations (Reporter::want_obj, decided outside its loop).
     template <bool OBJ, bool MAY_BE_FIRST, bool NONTEMPORAL>
     __device__ __forceinline__ void emit_interval(bool store, long ld, bool first, double val, double e, double w)
     {
@@ -850,9 +863,10 @@ __device__ __forceinline__ void run_ensemble(const KArgs &a, const double2 *__re
                         rep.add_moments(val, e, w);
                 }
             };
-            if (a.T > 0) {
-                time_loop(m, f, 1, [&](const double2 v, const double ex) { step_and_report(v, ex, std::true_type()); });
-                time_loop(m, f + 1, a.T - 1,
+            if (a.T > 0) { // the reports up to the first observed one set the constant (report 0 alone where it is observed)
+                const long lead = rep.r1 + 1 < a.T ? rep.r1 + 1 : a.T;
+                time_loop(m, f, lead, [&](const double2 v, const double ex) { step_and_report(v, ex, std::true_type()); });
+                time_loop(m, f + lead, a.T - lead,
                           [&](const double2 v, const double ex) { step_and_report(v, ex, std::false_type()); });
             }
             write_results(a, x, m, rep, num1 / den1, nullptr);
@@ -1054,8 +1068,8 @@ constexpr int kGroup = 4;
 //
 // body(k, v, e, w, lead_tag): k the interval's number within the stretch; lead_tag says at compile time whether the
 // call is one of the `lead` intervals taken on their own ahead of the groups (or of the n % kGroup behind them: the
-// same code) -- the run proper takes report 0 there, the one report that sets Reporter::shift, so that the groups
-// carry no test for it.
+// same code) -- the run proper takes the reports up to the first observed one there, the ones that set Reporter::shift,
+// so that the groups carry no test for it.
 template <bool OBS, class Body>
 __device__ __forceinline__ void interval_walk(const double2 *__restrict__ f, const double *obs_, const double *dev_,
                                               long i0, long i1, long gap, int lead, Body &&body)
@@ -1136,7 +1150,7 @@ __device__ __forceinline__ void interval_loop(const double2 *__restrict__ f, lon
 }
 
 // The same walk for the run proper, with the observation of each interval and its deviation from the mean
-// (Reporter::emit_interval); `lead`: 1 where the stretch starts with report 0.
+// (Reporter::emit_interval); `lead`: how many of the stretch's first reports may set Reporter::shift (those up to r1).
 template <class Body>
 __device__ __forceinline__ void interval_loop_obs(const double2 *__restrict__ f, const double *obs, const double *dev,
                                                   long i0, long i1, long gap, int lead, Body &&body)
@@ -1422,9 +1436,10 @@ __device__ __forceinline__ void run_ensemble_merged(const KArgs &a, const double
     constexpr bool deferring = !piecewise; // is an evaporation demand carried in `pend`?  (the step loop's lazy dry steps)
     // The report of the interval engine: the row of the discharge matrix at a per-lane pointer that moves on by ld (the
     // lanes beyond the batch carry its last sample and store that sample's value where its own lane does: no EXEC mask
-    // around the store), report 0 -- only the slice with ra == 0 has it -- among the intervals interval_loop takes on
-    // their own, the last report interval (where the SPLIT models park their state) as a count within the slice.
-    [[maybe_unused]] const bool first_slice = ra == 0;
+    // around the store), the reports up to the first observed one -- those that may set the constant; report 0 alone, in
+    // the slice with ra == 0, where it is observed -- among the intervals interval_loop takes on their own (n_lead of
+    // this slice's), the last report interval (where the SPLIT models park their state) as a count within the slice.
+    [[maybe_unused]] const int n_lead = (int)(rep.r1 + 1 > ra ? (rep.r1 + 1 < rb ? rep.r1 + 1 - ra : rb - ra) : 0);
     [[maybe_unused]] int store = __builtin_amdgcn_readfirstlane((int)(a.discharge != nullptr));
     asm("" : "+s"(store)); // (an integer in a scalar register, as above)
     [[maybe_unused]] const int k_park = Model::kSplit && ra <= a.R - 1 && a.R - 1 < rb ? (int)(a.R - 1 - ra) : -1;
@@ -1456,12 +1471,12 @@ __device__ __forceinline__ void run_ensemble_merged(const KArgs &a, const double
         if (starts_run)
             m.begin_run();
         if (rep.want_obj) {
-            interval_loop_obs(f, rep.obs, rep.ws + kWsHead, ra, rb, gap, first_slice ? 1 : 0,
+            interval_loop_obs(f, rep.obs, rep.ws + kWsHead, ra, rb, gap, n_lead,
                               [&](int k, const double2 v, const double e, const double w, auto lead_tag) {
                                   double qo, qg, qi;
                                   interval_last(v, qo, qg, qi);
                                   rep.template emit_interval<true, decltype(lead_tag)::value, false>(
-                                      store, a.ld, first_slice && k == 0, qo, e, w);
+                                      store, a.ld, rep.sets_shift(ra + k), qo, e, w);
                                   num_raw += qg;
                                   den_raw += qi;
                               });
@@ -1479,14 +1494,14 @@ __device__ __forceinline__ void run_ensemble_merged(const KArgs &a, const double
         if (starts_run)
             m.begin_run();
         if (rep.want_obj) {
-            interval_loop_obs(f, rep.obs, rep.ws + kWsHead, ra, rb, gap, first_slice ? 1 : 0,
+            interval_loop_obs(f, rep.obs, rep.ws + kWsHead, ra, rb, gap, n_lead,
                               [&](int k, const double2 v, const double e, const double w, auto lead_tag) {
                                   if (Model::kSplit && k == k_park)
                                       park_state();
                                   double acc = 0.0;
                                   interval(v, acc, num, den);
                                   rep.template emit_interval<true, decltype(lead_tag)::value, false>(
-                                      store, a.ld, first_slice && k == 0, acc * inv_gap, e, w);
+                                      store, a.ld, rep.sets_shift(ra + k), acc * inv_gap, e, w);
                                   q_out_total += acc;
                               });
         } else {
@@ -1569,11 +1584,13 @@ __device__ __forceinline__ void run_ensemble_merged(const KArgs &a, const double
                         auto run_steps = [&](auto store_tag, auto obs_tag) {
                             constexpr bool OBS = decltype(obs_tag)::value;
                             long first = i0;
-                            if (i0 == 0 && i1 > 0) { // report 0 on its own: it sets the constant the moments are taken about
-                                m.template step_arms<Q, true>(f[0], acc);
+                            // the reports up to the first observed one on their own: they set the constant the moments
+                            // are taken about (report 0 alone where it is observed)
+                            for (; first < i1 && rep.sets_shift(first); ++first) {
+                                const long t = __builtin_amdgcn_readfirstlane((int)first); // (the forcing: scalar loads)
+                                m.template step_arms<Q, true>(f[t], acc);
                                 rep.shift = acc;
-                                report_every(store_tag, obs_tag, OBS ? obs_c[0] : 0.0, OBS ? dev_c[0] : 0.0);
-                                first = 1;
+                                report_every(store_tag, obs_tag, OBS ? obs_c[t] : 0.0, OBS ? dev_c[t] : 0.0);
                             }
                             auto each = [&](long from, long n) __attribute__((always_inline)) {
                                 time_loop_arms_each<Q, OBS>(m, f + from, OBS ? obs_c + from : nullptr,
@@ -1644,7 +1661,7 @@ __device__ __forceinline__ void run_ensemble_merged(const KArgs &a, const double
                                 m.template stream_gap<REPORT == kReportLast>(
                                     a.estream + (x.c * every_pairs(a.T) + first / 2) * 8,
                                     a.ecodes + x.c * every_pairs(a.T) + first / 2, (int)(n_stream * gap / 4), reporting,
-                                    a.discharge != nullptr, rep.want_obj, r == 0, inv_gap, acc, rep.A, rep.B, rep.C1, rep.C2,
+                                    a.discharge != nullptr, rep.want_obj, rep.want_obj && rep.sets_shift(r), inv_gap, acc, rep.A, rep.B, rep.C1, rep.C2,
                                     rep.C3, rep.shift, REPORT == kReportLast ? num_raw : q_out_total,
                                     REPORT == kReportLast ? den_raw : unused, rep.row, a.ld);
                                 if (reporting)
@@ -1670,7 +1687,7 @@ __device__ __forceinline__ void run_ensemble_merged(const KArgs &a, const double
                                     f_asm + i0 * gap, codes_c + i0 * cpi, fetch ? a.obs + x.c * a.R + i0 : nullptr,
                                     fetch ? a.ws + x.c * (kWsHead + a.R) + kWsHead + i0 : nullptr, n_stream,
                                     (int)(ODD ? cpi : cpi / 2), ((i0 * cpi) & 1) != 0, reporting, a.discharge != nullptr,
-                                    r == 0, inv_gap, acc, rep.A, rep.B, rep.C1, rep.C2, rep.C3, rep.shift,
+                                    rep.want_obj && rep.sets_shift(r), inv_gap, acc, rep.A, rep.B, rep.C1, rep.C2, rep.C3, rep.shift,
                                     REPORT == kReportLast ? num_raw : q_out_total,
                                     REPORT == kReportLast ? den_raw : unused, rep.row, a.ld);
                             };

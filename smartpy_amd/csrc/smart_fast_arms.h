@@ -313,7 +313,7 @@
 //   s68, s69 / s70, s71            their code words (first pair, second pair)
 //   s72 counter (pairs of chunks of the interval, counts up to zero), s75 the same for the intervals of the stretch,
 //   s73 / s74 byte offsets of the last request into forcing / codes, s84 of the observation at hand (s[80:83]: it and
-//   its deviation), s85: is the next report number 0?, s[76:77] jump target, s[78:79] address of block 0
+//   its deviation), s85: is the first observed report still ahead?, s[76:77] jump target, s[78:79] address of block 0
 #ifndef SMART_P_STRIDE
 #error "SMART_P_STRIDE comes from smart_device.h"
 #endif
@@ -388,10 +388,12 @@
                                SMART_A_DRY(route, p2, dry_split) SMART_A_DRY(route, p3, dry_split) tail)
 // The moments of a report about value `val` with observation e, deviation w (upper word whi: the missing mark): Reporter's
 // (smart_device.h: emit / report_every), operation for operation
-#define SMART_R_MOMENTS(val, e, w, whi)                                                                                \
+#define SMART_R_MOMENTS(val, e, w, whi) SMART_R_MOMENTS_X(val, e, w, whi, "")
+// (seen: what a report that carries an observation does besides -- SMART_P_REPORT_X ends its search for the first one)
+#define SMART_R_MOMENTS_X(val, e, w, whi, seen)                                                                        \
     "s_cmp_eq_u32 " whi ", 0x7ff8dead\n\t"                                                                             \
     "s_cbranch_scc1 50f\n\t"                                                                                           \
-    "s_nop 0\n\t"                                                                                                      \
+    "s_nop 0\n\t" seen                                                                                                 \
     "v_add_f64 %[rd], " val ", -" e "\n\t"                                                                             \
     "v_add_f64 %[ru], " val ", -%[shift]\n\t"                                                                          \
     "v_add_f64 %[mA], %[mA], %[rd]\n\t"                                                                                \
@@ -401,8 +403,10 @@
     "v_fma_f64 %[mC3], " w ", %[ru], %[mC3]\n\t"                                                                       \
     "50:\n\t"
 // The report at the end of an interval, in the asm (one copy per asm, reached from the tails of the last pair's blocks):
-// nothing during the warm-up (%[rep] = 0); the value (value: the instruction that puts it into %[rv]); report 0 sets the
-// constant the moments are taken about (s85: is the next report number 0?); the discharge through the lane's row pointer;
+// nothing during the warm-up (%[rep] = 0); the value (value: the instruction that puts it into %[rv]); every report up to
+// the first that carries an observation sets the constant the moments are taken about (s85: has none been seen yet?  set
+// where the stretch starts at or before that report, cleared behind the missing-observation test: with report 0 observed
+// the instructions a report executes are the ones it always did); the discharge through the lane's row pointer;
 // the moments (e, w in s[80:83], requested when the interval began); `after`: what the run keeps of the interval.
 #define SMART_P_REPORT(value, after) SMART_P_REPORT_X(value, after, "s[80:81]", "s[82:83]", "s83")
 // (the discharge matrix is written once and read by another kernel, if at all: `nt` keeps it from displacing what the L2
@@ -413,7 +417,6 @@
     "s_cbranch_scc1 96f\n\t" value "s_cmp_eq_u32 s85, 0\n\t"                                                           \
     "s_cbranch_scc1 93f\n\t"                                                                                           \
     "v_mov_b64_e64 %[shift], %[rv]\n\t"                                                                                \
-    "s_mov_b32 s85, 0\n\t"                                                                                             \
     "93:\n\t"                                                                                                          \
     "s_cmp_eq_u32 %[sto], 0\n\t"                                                                                       \
     "s_cbranch_scc1 97f\n\t"                                                                                           \
@@ -421,7 +424,7 @@
     "v_lshl_add_u64 %[row], %[ld], 3, %[row]\n\t"                                                                      \
     "97:\n\t"                                                                                                          \
     "s_cmp_eq_u32 %[hob], 0\n\t"                                                                                       \
-    "s_cbranch_scc1 98f\n\t" SMART_R_MOMENTS("%[rv]", e, w, whi) "98:\n\t" after "96:\n\t"
+    "s_cbranch_scc1 98f\n\t" SMART_R_MOMENTS_X("%[rv]", e, w, whi, "s_mov_b32 s85, 0\n\t") "98:\n\t" after "96:\n\t"
 #define SMART_P_VALUE_MEAN "v_mul_f64 %[rv], %[acc], %[ig]\n\t"
 #define SMART_P_AFTER_MEAN "v_add_f64 %[qtot], %[qtot], %[acc]\n\tv_mov_b64_e64 %[acc], 0\n\t"
 #define SMART_P_VALUE_LAST "v_mov_b64_e64 %[rv], %[acc]\n\t"

@@ -903,7 +903,9 @@ struct FastModel {
     // f_asm / codes: the first interval's first chunk in the forcing (through a pointer that hipcc does not take for the
     // __restrict__ one: smart_device.h) and its code words (smart_forcing_scan); obs_p / dev_p: the first interval's
     // observation and deviation (null: none, or the warm-up -- reporting: false).  first_is_0: the stretch's first report
-    // is report 0, which sets the constant the moments are taken about.  sum_a / sum_b: the sum of the outflows (means;
+    // may set the constant the moments are taken about -- it is a report up to the first observed one (Reporter::
+    // sets_shift; report 0 where that carries an observation), and the asm goes on setting it until a report carries an
+    // observation (s85, smart_fast_arms.h).  sum_a / sum_b: the sum of the outflows (means;
     // sum_b unused) or the two sums of the raw groundwater ratio (LAST).  QUICK waves only; the asm requests two chunks
     // beyond the stretch: the caller keeps the last interval of the forcing array away from it.
     // ODD: intervals of any whole number of chunks (half = that number; the stretch may start in either register buffer:
@@ -1018,8 +1020,8 @@ struct FastModel {
     }
 
     // `quads` x 4 steps of a run whose report gap is not a whole number of chunks, through the blocks of SMART_A_GAP_STREAM:
-    // the stream of records and code words of stream_every(), the interval's report (stream_stretch()'s: flags, report 0's
-    // constant, row pointer, moments, sums) behind the arms whose steps end an interval -- the code words know which.
+    // the stream of records and code words of stream_every(), the interval's report (stream_stretch()'s: flags, the constant
+    // of the first observed report, row pointer, moments, sums) behind the arms whose steps end an interval -- the code words know which.
     // The steps are whole intervals (the caller sees to it); acc, the interval's sum, is zero going in and coming out.
     template <bool LAST>
     __device__ __forceinline__ void stream_gap(const double *records, const unsigned *codes, int quads, bool reporting,

@@ -115,4 +115,30 @@ __device__ inline void obs_stats(const double *obs, long R, double *st, double *
     st[4] = s1;
 }
 
+// the first report step that carries an observation (0 where none does): the row whose value is the constant of a
+// sample's one-pass moments (finish_objectives, smart_device.h).  Every thread of the workgroup gets the same answer.  The
+// workgroup looks at blockDim.x rows at a time -- one round finds it unless that many leading reports are all missing --
+// every wavefront names the first of its 64 by a ballot, and the smallest of those goes through LDS (an index held in a
+// double is exact; a minimum does not depend on the order it is taken in): two barriers a round, where a tree over the
+// threads would take ten.  blockDim.x is a multiple of 64, sh holds one double per wavefront.  (With R < 1 there is no
+// round and no barrier: a caller that relies on one for its own shared values places it itself.)
+__device__ inline long first_observed_row(const double *obs, long R, double *sh)
+{
+    const int tid = threadIdx.x, lane = tid & (kWave - 1), wave = tid / kWave, waves = blockDim.x / kWave;
+    for (long base = 0; base < R; base += blockDim.x) {
+        const long r = base + tid;
+        const unsigned long long seen = __ballot(r < R && !is_nan_bits(obs[r]));
+        if (lane == 0)
+            sh[wave] = seen ? (double)(base + wave * kWave + __builtin_ctzll(seen)) : (double)R;
+        __syncthreads();
+        double first = sh[0];
+        for (int w = 1; w < waves; ++w)
+            first = sh[w] < first ? sh[w] : first;
+        __syncthreads(); // (sh is free again)
+        if (first < (double)R)
+            return (long)first;
+    }
+    return 0;
+}
+
 } // namespace smart
