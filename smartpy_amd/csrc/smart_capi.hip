@@ -188,6 +188,8 @@ struct Overrides {
                             // is 0 (n <= 0 counts as 1); 0: unset, plan_time_slices decides
     int illcond_form = SMART_LITERAL_FORM_AUTO; // SMART_ILLCOND_FORM=rows|lanes: the class-3 kernel when
                                                 // SmartEnsemble.literal_form is _AUTO; anything else: illcond_form decides
+    bool taper = true;      // SMART_SLICE_TAPER=0: equal time slices instead of the tapered ones (smart_slice_cuts.h): the A/B
+                            // of the two on one library, and the tests that hold one against the other
     int exits = -1;         // SMART_EXITS=0|1: the interval engine without / with early exits; -1: unset, from the load
     long max_polls = kDefaultMaxPolls; // SMART_DEBUG_MAX_POLLS=n > 0: bound of a slice's wait for its predecessor (tests)
     int drop_slice = 0;     // SMART_DEBUG_DROP_SLICE=1: slice 0 of block 0 never publishes (tests)
@@ -202,6 +204,8 @@ static Overrides read_overrides()
         o.pair_blocks = atoi(v) != 0;
     if (const char *v = getenv("SMART_TIME_SLICES"))
         o.time_slices = atoi(v) <= 0 ? 1 : atoi(v);
+    if (const char *v = getenv("SMART_SLICE_TAPER"))
+        o.taper = atoi(v) != 0;
     if (const char *v = getenv("SMART_ILLCOND_FORM"))
         o.illcond_form = !strcmp(v, "rows")    ? SMART_LITERAL_FORM_ROWS
                          : !strcmp(v, "lanes") ? SMART_LITERAL_FORM_LANES
@@ -297,6 +301,9 @@ struct Layout {
                                        // over whole intervals of whole chunks) -- or, for a report every step and gaps that
                                        // are not whole chunks, the records [C][every_pairs(T)][8] doubles and at
     size_t ecodes_off = 0;             // ... ecodes_off their code words [C][every_pairs(T)]; rounded up to 256 bytes
+#ifdef SMART_SLICE_TIMELINE
+    size_t timeline_off = 0, timeline = 0; // measurement build: the slice timeline [blocks * kTimelineSlices][5], last of all
+#endif
     size_t total = 0;                  // what smart_workspace_bytes asks for (0: the sizes of the call make no sense)
     size_t handover() const { return state + flags; }
 };
@@ -338,6 +345,12 @@ static Layout layout(const SmartEnsemble *e, bool sliced)
     }
     l.codes = (l.codes + 255) / 256 * 256;
     l.total = l.codes_off + l.codes;
+#ifdef SMART_SLICE_TIMELINE
+    l.timeline_off = l.total;
+    if (sliced)
+        l.timeline = blocks * kTimelineSlices * kTimelineFields * sizeof(unsigned long long);
+    l.total += l.timeline;
+#endif
     return l;
 }
 
@@ -467,6 +480,9 @@ struct Workspace {
     double *stats = nullptr;
     char *state = nullptr; // hand-over of a sliced launch, its slice flags behind it; null means a plain launch
     char *codes = nullptr; // code words or records
+#ifdef SMART_SLICE_TIMELINE
+    char *timeline = nullptr;
+#endif
 };
 
 static Workspace carve(const SmartEnsemble *e, const Overrides &ov)
@@ -487,6 +503,10 @@ static Workspace carve(const SmartEnsemble *e, const Overrides &ov)
     // serves a sliced launch, which then runs its threaded chunks
     if (l.codes && bytes >= l.total)
         w.codes = base + l.codes_off;
+#ifdef SMART_SLICE_TIMELINE
+    if (l.timeline && bytes >= l.total)
+        w.timeline = base + l.timeline_off;
+#endif
     return w;
 }
 
@@ -732,10 +752,16 @@ static int run(const SmartEnsemble *e, const Overrides &ov, bool literal_rows = 
     KArgs a_sliced = a;
     if (n_seg > 1) {
         a_sliced.n_seg = n_seg;
+        // the library's own choice of slices or a forced count alike: long slices first, short ones at the end, wherever
+        // the axis is long enough for that (the kernels take the host's word: one test, made here)
+        a_sliced.taper = ov.taper && slice_taper_applies(a.W / a.gap + a.R, n_seg);
         a_sliced.seg_state = (double *)w.state;
         a_sliced.seg_flag = (int *)(w.state + (w.lay.flags_off - w.lay.state_off));
         a_sliced.max_polls = ov.max_polls;
         a_sliced.debug_drop = ov.drop_slice;
+#ifdef SMART_SLICE_TIMELINE
+        a_sliced.timeline = (unsigned long long *)w.timeline;
+#endif
     }
     if (w.hdr) {
         reset_workspace(w, e->n_catchments, a_sliced.seg_flag, n_seg > 1 ? a.seg_blocks : 0, s);

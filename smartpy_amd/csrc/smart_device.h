@@ -19,6 +19,7 @@
 //   SMART_STEPS_PHASE, SMART_EVERY_PHASE    loop placement   tools/gpu_round.sh phases-every
 #pragma once
 
+#include "smart_slice_cuts.h"    // where a sliced launch cuts the time axis
 #include "smart_matrix_common.h" // kWave, is_nan_bits, kMissingObs, quiet_nan: one definition for every kernel
 
 #include <hip/hip_runtime.h>
@@ -71,6 +72,8 @@ struct KArgs {
     int div[kMaxDiv] = {};
     // time-sliced launch (n_seg > 1): see "time-sliced launch" below
     int n_seg = 1;            // workgroups per block of 64 samples, each advancing one slice of the time axis
+    int taper = 0;            // the slices' cuts: 0 equal, 1 tapered towards the end of the axis (smart_slice_cuts.h; the
+                              // host sets it only where slice_taper_applies)
     long n_catch = 1;         // C
     long n_blocks = 0;        // ceil(N / 64), blocks per catchment
     long seg_blocks = 0;      // C * n_blocks
@@ -78,7 +81,22 @@ struct KArgs {
     int *seg_flag = nullptr;     // [seg_blocks] slices completed (negative: the chain is poisoned, see wait_for_slice)
     long max_polls = 0;          // bound of a slice's wait for its predecessor, in polls of ~3 us
     int debug_drop = 0;          // test knob: slice 0 of block 0 never publishes (its successors must time out)
+#ifdef SMART_SLICE_TIMELINE
+    // measurement build only (tools/slice_timeline.py; never the installed library): per ticket of a sliced launch
+    // kTimelineFields words -- ticket, hardware id (HW_ID, XCC_ID << 32), s_memrealtime at the start, after the wait for
+    // the predecessor (0: slice 0 waits for nobody) and at the end -- behind everything else in the workspace
+    unsigned long long *timeline = nullptr; // [seg_blocks * kTimelineSlices][kTimelineFields] | null
+#endif
 };
+#ifdef SMART_SLICE_TIMELINE
+constexpr int kTimelineFields = 5, kTimelineSlices = 64; // (launches of more slices record the first 64 of each chain)
+__device__ __forceinline__ void timeline_note(const KArgs &a, long block, long c, int seg, int field,
+                                              unsigned long long value)
+{
+    if (a.timeline && a.n_seg > 1 && seg < kTimelineSlices && seg < a.n_seg && threadIdx.x == 0)
+        a.timeline[((long)seg * a.seg_blocks + c * a.n_blocks + block) * kTimelineFields + field] = value;
+}
+#endif
 
 // the fields of a block's hand-over between two time slices (KArgs::seg_state), 64 doubles each
 enum SegField : int {
@@ -1163,7 +1181,10 @@ __device__ __forceinline__ void interval_loop_obs(const double2 *__restrict__ f,
 // the SIMDs that hold ceil(B / S) of them while the others idle (1e5 samples: 1,563 blocks on 1,024 SIMDs, 539 SIMDs
 // with two).  Here the time axis of every block is cut into n_seg slices and each (block, slice) is its own
 // workgroup, handed out as slots free up, so a SIMD that finishes early simply gets more slices.  Slice s of a block
-// starts from the state slice s - 1 left in `seg_state` and waits for `seg_flag[slot] >= s`.
+// starts from the state slice s - 1 left in `seg_state` and waits for `seg_flag[slot] >= s`.  The slices are long at
+// the start of the axis and short at its end wherever the axis is long enough (KArgs::taper, smart_slice_cuts.h): the
+// chains advance together, so the SIMDs run dry over the wall time of the last slice -- 2.6 % of the headline launch
+// idle with 24 equal slices, 0.6 % tapered (profiles/slice_taper.txt).
 //
 // Which (block, slice) a workgroup runs comes from a TICKET it draws when it starts (one atomic add on a counter in
 // the workspace header), not from its workgroup id: ticket t is slice t / seg_blocks of block t % seg_blocks, so the
@@ -1355,7 +1376,8 @@ __device__ __forceinline__ void run_ensemble_merged(const KArgs &a, const double
     // this workgroup's slice [g0, g1) of the W / gap warm-up intervals followed by the R report intervals
     // (n_seg == 1: everything).  Summary reports need W % gap == 0 (checked on the host, structure.py:190).
     const long n_warm = a.W / gap, n_all = n_warm + a.R;
-    const long g0 = n_all * seg / a.n_seg, g1 = n_all * (seg + 1) / a.n_seg;
+    const long g0 = a.taper ? slice_cut_tapered(n_all, seg, a.n_seg) : n_all * seg / a.n_seg;
+    const long g1 = a.taper ? slice_cut_tapered(n_all, seg + 1, a.n_seg) : n_all * (seg + 1) / a.n_seg;
     const long wa = g0 < n_warm ? g0 : n_warm, wb = g1 < n_warm ? g1 : n_warm;
     const long ra = g0 > n_warm ? g0 - n_warm : 0, rb = g1 > n_warm ? g1 - n_warm : 0;
     const bool last = seg == a.n_seg - 1;
@@ -1397,6 +1419,9 @@ __device__ __forceinline__ void run_ensemble_merged(const KArgs &a, const double
             }
             return;
         }
+#ifdef SMART_SLICE_TIMELINE
+        timeline_note(a, block, catchment, seg, 3, __builtin_amdgcn_s_memrealtime());
+#endif
         m.load_state(hand, kWave);
         if constexpr (REPORT == kReportLast) {
             num_raw = hand[kSegOutflows * kWave];

@@ -125,7 +125,17 @@ __device__ __forceinline__ void merged_kernel(const KArgs &a, const double2 *__r
         if (!forcing_is_mine<FORCING>(a, fflags, w))
             return;
     }
+#ifdef SMART_SLICE_TIMELINE
+    timeline_note(a, w.block, w.c, w.seg, 0, (unsigned long long)(w.seg * a.seg_blocks + w.c * a.n_blocks + w.block));
+    timeline_note(a, w.block, w.c, w.seg, 1,
+                  (unsigned long long)__builtin_amdgcn_s_getreg(63492) // HW_ID [31:0]
+                      | (unsigned long long)__builtin_amdgcn_s_getreg(63508) << 32); // XCC_ID [31:0]
+    timeline_note(a, w.block, w.c, w.seg, 2, __builtin_amdgcn_s_memrealtime());
+#endif
     run_ensemble_merged<Model, FORCING, REPORT>(a, forcing, obs, ws, w.block, w.c, w.seg, fflags);
+#ifdef SMART_SLICE_TIMELINE
+    timeline_note(a, w.block, w.c, w.seg, 4, __builtin_amdgcn_s_memrealtime());
+#endif
 }
 
 } // namespace smart
