@@ -53,10 +53,40 @@ def _code(who, what, table, name):
 
 
 def _workspace(need, device):
-    """What a *_workspace_bytes entry answered -> (scratch tensor or None, bytes); a refusal (negative) is raised."""
-    if need < 0:
-        _lib.check(need)
+    """What a *_workspace_bytes entry answered -> (scratch tensor or None, bytes).  Sizes the query refuses (a negative
+    answer; smart_pareto_workspace_bytes answers 0) get no workspace: the entry refuses them too, with its own text."""
+    need = max(0, int(need))
     return (torch.empty(need, dtype=torch.uint8, device=device) if need else None), need
+
+
+def _launch(device, entry, *args):
+    """Call a *_hip entry on `device` and on torch's current stream there -- the stream is the entry's last argument,
+    after `args` -- and raise what it refuses."""
+    with torch.cuda.device(device):
+        _lib.check(entry(*args, torch.cuda.current_stream(device).cuda_stream))
+
+
+def _weights(who, weights, device, n):
+    """The weights= argument of a call: [n], finite and >= 0 -> float64 tensor on the device; None (equal weights) stays"""
+    if weights is None:
+        return None
+    weights = _as_device(weights, device, (n,))
+    bad = int((~(torch.isfinite(weights) & (weights >= 0))).sum())
+    if bad:
+        raise SmartEngineError(-2, "{}: {} of the {} weights are negative or not finite.".format(who, bad, n))
+    return weights
+
+
+def _categories(who, categories, n_cols):
+    """The categories= argument of a call: uint8 [factors, n_cols], host or device, checked before anything is moved
+    -> a tensor where they lie (its first dimension is the number of factors)"""
+    shape = tuple(getattr(categories, 'shape', ()))
+    if len(shape) != 2 or shape[1] != n_cols or str(getattr(categories, 'dtype', '')).split('.')[-1] != 'uint8':
+        raise SmartEngineError(-2, "{}: categories must be uint8 [factors, {}] (identifiability.bin_table), not {} {}."
+                               .format(who, n_cols, getattr(categories, 'dtype', type(categories).__name__), shape))
+    if not isinstance(categories, torch.Tensor):
+        categories = torch.from_numpy(np.ascontiguousarray(categories))
+    return categories
 
 
 def _ptr(t):
@@ -69,10 +99,6 @@ def _probs(probs):
     return q, q.ctypes.data_as(ctypes.POINTER(ctypes.c_double))
 
 
-def _stream(device):
-    return torch.cuda.current_stream(device).cuda_stream
-
-
 def objective_functions(discharge_report_major, obs, gw_sim=None, gw_obs=None):
     """montecarlo.py:193-209 for every column of a stored [R, N] discharge matrix (one pass over it, HBM-bound)."""
     L = _lib.lib()
@@ -80,10 +106,8 @@ def objective_functions(discharge_report_major, obs, gw_sim=None, gw_obs=None):
     obs = _as_device(obs, sim.device, (R,))
     gw_sim = _as_device(gw_sim, sim.device, (N,)) if gw_sim is not None else None
     out = torch.empty((N, 8), dtype=torch.float64, device=sim.device)
-    with torch.cuda.device(sim.device):
-        _lib.check(L.smart_objfn_hip(N, R, sim.data_ptr(), ld, obs.data_ptr(), _ptr(gw_sim),
-                                     float('nan') if gw_obs is None else float(gw_obs), out.data_ptr(),
-                                     _stream(sim.device)))
+    _launch(sim.device, L.smart_objfn_hip, N, R, sim.data_ptr(), ld, obs.data_ptr(), _ptr(gw_sim),
+            float('nan') if gw_obs is None else float(gw_obs), out.data_ptr())
     return out
 
 
@@ -105,16 +129,10 @@ def weighted_quantiles(discharge_report_major, probs, weights=None, method='auto
     code = _code('weighted_quantiles', 'method', _QUANTILE_METHODS, method)
     sim, R, N, ld = _matrix(discharge_report_major)
     q, q_ptr = _probs(probs)
-    if weights is not None:
-        weights = _as_device(weights, sim.device, (N,))
-        bad = int((~(torch.isfinite(weights) & (weights >= 0))).sum())
-        if bad:
-            raise SmartEngineError(-2, "weighted_quantiles: {} of the {} weights are negative or not finite."
-                                   .format(bad, N))
+    weights = _weights('weighted_quantiles', weights, sim.device, N)
     out = torch.empty((q.size, R), dtype=torch.float64, device=sim.device)
-    with torch.cuda.device(sim.device):
-        _lib.check(L.smart_weighted_quantiles_hip(N, R, sim.data_ptr(), ld, _ptr(weights), q_ptr, q.size,
-                                                  out.data_ptr(), code, _stream(sim.device)))
+    _launch(sim.device, L.smart_weighted_quantiles_hip, N, R, sim.data_ptr(), ld, _ptr(weights), q_ptr, q.size,
+            out.data_ptr(), code)
     return out
 
 
@@ -183,9 +201,8 @@ def objective_functions_windows(discharge_report_major, obs, windows, n_windows=
     out = torch.empty((W, N, _lib.OBJFN_WINDOW_COLS), dtype=torch.float64, device=sim.device)
     if N == 0:
         return out
-    with torch.cuda.device(sim.device):
-        _lib.check(L.smart_objfn_windows_hip(N, R, sim.data_ptr(), ld, obs.data_ptr(), win.data_ptr(), W, code,
-                                             float(eps), out.data_ptr(), _stream(sim.device)))
+    _launch(sim.device, L.smart_objfn_windows_hip, N, R, sim.data_ptr(), ld, obs.data_ptr(), win.data_ptr(), W, code,
+            float(eps), out.data_ptr())
     return out
 
 
@@ -222,11 +239,11 @@ def flow_duration(discharge_report_major, probs, obs=None, windows=None, n_windo
     scores = torch.empty((W, N, _lib.OBJFN_WINDOW_COLS), dtype=torch.float64, device=sim.device) if objfn else None
     if N == 0:
         return quant, scores
-    work, need = _workspace(int(L.smart_flow_duration_workspace_bytes(R, W, 1 if objfn else 0)), sim.device)
-    with torch.cuda.device(sim.device):
-        _lib.check(L.smart_flow_duration_hip(N, R, sim.data_ptr(), ld, _ptr(obs), _ptr(win), W, q_ptr, q.size,
-                                             quant.data_ptr(), code, float(eps), lo, hi, _ptr(scores), _ptr(work), need,
-                                             how, _stream(sim.device)))
+    work, need = _workspace(L.smart_flow_duration_workspace_bytes(R, W, 1 if objfn else 0), sim.device)
+    # (torch gives a matrix without a report step no address, and NULL would be the entry's first refusal: such a matrix
+    # gets an address that is never followed, so that the entry refuses what its workspace query refused -- the size)
+    _launch(sim.device, L.smart_flow_duration_hip, N, R, sim.data_ptr() or 0x1000, ld, _ptr(obs), _ptr(win), W, q_ptr,
+            q.size, quant.data_ptr(), code, float(eps), lo, hi, _ptr(scores), _ptr(work), need, how)
     return quant, scores
 
 
@@ -260,9 +277,8 @@ def signatures(discharge_report_major, obs=None, windows=None, n_windows=None, a
     out = torch.empty((W, _lib.SIGNATURE_COLS, N), dtype=torch.float64, device=sim.device)
     if N == 0:
         return out
-    with torch.cuda.device(sim.device):
-        _lib.check(L.smart_signatures_hip(N, R, sim.data_ptr(), ld, _ptr(obs), _ptr(win), W, alpha, _ptr(pulse),
-                                          out.data_ptr(), _stream(sim.device)))
+    _launch(sim.device, L.smart_signatures_hip, N, R, sim.data_ptr(), ld, _ptr(obs), _ptr(win), W, alpha, _ptr(pulse),
+            out.data_ptr())
     return out
 
 
@@ -336,11 +352,9 @@ def sobol_indices(values, n_base, n_params, counts=None):
     if B > 0:
         counts = counts.to(dev).contiguous()
         S1_std, ST_std = torch.empty_like(S1), torch.empty_like(ST)
-    work, need = _workspace(int(L.smart_sobol_workspace_bytes(n, k, M, B)), dev)
-    with torch.cuda.device(dev):
-        _lib.check(L.smart_sobol_indices_hip(n, k, M, y.data_ptr(), ld, S1.data_ptr(), ST.data_ptr(), moments.data_ptr(),
-                                             counts.data_ptr() if B else None, B, _ptr(S1_std), _ptr(ST_std), _ptr(work),
-                                             need, _stream(dev)))
+    work, need = _workspace(L.smart_sobol_workspace_bytes(n, k, M, B), dev)
+    _launch(dev, L.smart_sobol_indices_hip, n, k, M, y.data_ptr(), ld, S1.data_ptr(), ST.data_ptr(), moments.data_ptr(),
+            counts.data_ptr() if B else None, B, _ptr(S1_std), _ptr(ST_std), _ptr(work), need)
     return SobolResult(S1, ST, moments, S1_std, ST_std)
 
 
@@ -452,11 +466,9 @@ def objective_functions_bootstrap(discharge_report_major, obs, windows, counts, 
         return BootstrapResult(point, stats, reps, q)
     if B:
         counts = counts.to(dev).contiguous()
-    work, need = _workspace(int(L.smart_bootstrap_workspace_bytes(N, W, B, 1 if reps is not None else 0)), dev)
-    with torch.cuda.device(dev):
-        _lib.check(L.smart_objfn_bootstrap_hip(N, R, sim.data_ptr(), ld, obs.data_ptr(), win.data_ptr(), W, code, eps,
-                                               counts.data_ptr() if B else None, B, q_ptr, K, point.data_ptr(),
-                                               _ptr(stats), _ptr(reps), _ptr(work), need, _stream(dev)))
+    work, need = _workspace(L.smart_bootstrap_workspace_bytes(N, W, B, 1 if reps is not None else 0), dev)
+    _launch(dev, L.smart_objfn_bootstrap_hip, N, R, sim.data_ptr(), ld, obs.data_ptr(), win.data_ptr(), W, code, eps,
+            counts.data_ptr() if B else None, B, q_ptr, K, point.data_ptr(), _ptr(stats), _ptr(reps), _ptr(work), need)
     return BootstrapResult(point, stats, reps, q)
 
 
@@ -526,7 +538,7 @@ class _ParetoCall(object):
         self.device = self.scores.device
         self.eligible = None if eligible is None else self.mask(eligible)
         self.work, self.need = (None, 0) if N == 0 else \
-            _workspace(int(self.L.smart_pareto_workspace_bytes(N, M)), self.device)
+            _workspace(self.L.smart_pareto_workspace_bytes(N, M), self.device)
 
     def mask(self, flags):
         """flags [N] (bool or numbers, host or device) -> contiguous uint8 device tensor, 1 where not zero"""
@@ -540,11 +552,9 @@ class _ParetoCall(object):
         if self.N == 0:
             return out
         i32, f64 = ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_double)
-        with torch.cuda.device(self.device):
-            _lib.check(self.L.smart_pareto_counts_hip(self.N, self.scores.data_ptr(), self.ld, self.cols.ctypes.data_as(i32),
-                                                      self.code.ctypes.data_as(i32), self.target.ctypes.data_as(f64),
-                                                      self.M, _ptr(eligible), out.data_ptr(), _ptr(self.work), self.need,
-                                                      _stream(self.device)))
+        _launch(self.device, self.L.smart_pareto_counts_hip, self.N, self.scores.data_ptr(), self.ld,
+                self.cols.ctypes.data_as(i32), self.code.ctypes.data_as(i32), self.target.ctypes.data_as(f64), self.M,
+                _ptr(eligible), out.data_ptr(), _ptr(self.work), self.need)
         return out
 
 
@@ -608,21 +618,14 @@ def ensemble_scores(discharge_report_major, obs=None, weights=None, method='auto
     sim, R, N, ld = _matrix(discharge_report_major)
     if obs is not None:
         obs = _as_device(obs, sim.device, (R,))
-    if weights is not None:
-        weights = _as_device(weights, sim.device, (N,))
-        bad = int((~(torch.isfinite(weights) & (weights >= 0))).sum())
-        if bad:
-            raise SmartEngineError(-2, "ensemble_scores: {} of the {} weights are negative or not finite."
-                                   .format(bad, N))
+    weights = _weights('ensemble_scores', weights, sim.device, N)
     out = torch.empty((_lib.ENSEMBLE_SCORE_COLS, R), dtype=torch.float64, device=sim.device)
     if R == 0:
         return out
-    # (sizes the helper refuses get no workspace: the entry refuses them too, with its text)
-    work, need = _workspace(max(0, int(L.smart_ensemble_scores_workspace_bytes(N, R, 1 if weights is not None else 0,
-                                                                               code))), sim.device)
-    with torch.cuda.device(sim.device):
-        _lib.check(L.smart_ensemble_scores_hip(N, R, sim.data_ptr(), ld, _ptr(weights), _ptr(obs), out.data_ptr(), code,
-                                               _ptr(work), need, _stream(sim.device)))
+    work, need = _workspace(L.smart_ensemble_scores_workspace_bytes(N, R, 1 if weights is not None else 0, code),
+                            sim.device)
+    _launch(sim.device, L.smart_ensemble_scores_hip, N, R, sim.data_ptr(), ld, _ptr(weights), _ptr(obs), out.data_ptr(),
+            code, _ptr(work), need)
     return out
 
 
@@ -663,18 +666,12 @@ def dynamic_identifiability(discharge_report_major, obs, categories, n_bins, hal
     h, B = int(half_width), int(n_bins)
     w = 2 * h + 1
     min_valid = (w + 1) // 2 if min_valid is None else int(min_valid)
-    shape = tuple(getattr(categories, 'shape', ()))
-    n_cols = tuple(discharge_report_major.shape)[-1]
-    if len(shape) != 2 or shape[1] != n_cols or str(getattr(categories, 'dtype', '')).split('.')[-1] != 'uint8':
-        raise SmartEngineError(-2, "{}: categories must be uint8 [factors, {}] (identifiability.bin_table), not {} {}."
-                               .format(who, n_cols, getattr(categories, 'dtype', type(categories).__name__), shape))
-    P = shape[0]
+    categories = _categories(who, categories, tuple(discharge_report_major.shape)[-1])
+    P = categories.shape[0]
     # ---- from here on the device
     sim, R, N, ld = _matrix(discharge_report_major)
     dev = sim.device
     obs = _as_device(obs, dev, (R,))
-    if not isinstance(categories, torch.Tensor):
-        categories = torch.from_numpy(np.ascontiguousarray(categories))
     cat = categories.to(dev).contiguous()
     shares = torch.empty((R, P, B), dtype=torch.float64, device=dev)
     cut = torch.empty((R,), dtype=torch.float64, device=dev)
@@ -683,12 +680,10 @@ def dynamic_identifiability(discharge_report_major, obs, categories, n_bins, hal
     errors = torch.empty((R, N), dtype=torch.float64, device=dev) if keep_errors else None
     if R == 0 or N == 0:
         return DyniaResult(shares, cut, retained, count, errors)
-    # (sizes the helper refuses get no workspace: the entry refuses them too, with its text)
-    work, need = _workspace(max(0, int(L.smart_dynia_workspace_bytes(N, R, h, P, B))), dev)
-    with torch.cuda.device(dev):
-        _lib.check(L.smart_dynia_hip(N, R, sim.data_ptr(), ld, obs.data_ptr(), h, min_valid, float(fraction),
-                                     cat.data_ptr(), P, B, code, shares.data_ptr(), cut.data_ptr(), retained.data_ptr(),
-                                     count.data_ptr(), _ptr(errors), N, _ptr(work), need, _stream(dev)))
+    work, need = _workspace(L.smart_dynia_workspace_bytes(N, R, h, P, B), dev)
+    _launch(dev, L.smart_dynia_hip, N, R, sim.data_ptr(), ld, obs.data_ptr(), h, min_valid, float(fraction),
+            cat.data_ptr(), P, B, code, shares.data_ptr(), cut.data_ptr(), retained.data_ptr(), count.data_ptr(),
+            _ptr(errors), N, _ptr(work), need)
     return DyniaResult(shares, cut, retained, count, errors)
 
 
@@ -721,25 +716,17 @@ def pawn_ks(values_row_major, categories, n_bins, method='auto'):
     L = _lib.lib()
     code = _code(who, 'method', _lib.PAWN_METHODS, method)
     B = int(n_bins)
-    shape = tuple(getattr(categories, 'shape', ()))
-    n_cols = tuple(values_row_major.shape)[-1]
-    if len(shape) != 2 or shape[1] != n_cols or str(getattr(categories, 'dtype', '')).split('.')[-1] != 'uint8':
-        raise SmartEngineError(-2, "{}: categories must be uint8 [factors, {}] (identifiability.bin_table), not {} {}."
-                               .format(who, n_cols, getattr(categories, 'dtype', type(categories).__name__), shape))
-    P = shape[0]
+    categories = _categories(who, categories, tuple(values_row_major.shape)[-1])
+    P = categories.shape[0]
     # ---- from here on the device
     y, R, N, ld = _matrix(values_row_major)
     dev = y.device
-    if not isinstance(categories, torch.Tensor):
-        categories = torch.from_numpy(np.ascontiguousarray(categories))
     cat = categories.to(dev).contiguous()
     ks = torch.empty((R, P, B), dtype=torch.float64, device=dev)
     counts = torch.empty((P, B), dtype=torch.int32, device=dev)
     if R == 0 or N == 0:
         return PawnResult(ks, counts)
-    # (sizes the helper refuses get no workspace: the entry refuses them too, with its text)
-    work, need = _workspace(max(0, int(L.smart_pawn_workspace_bytes(N, R, code))), dev)
-    with torch.cuda.device(dev):
-        _lib.check(L.smart_pawn_ks_hip(N, R, y.data_ptr(), ld, cat.data_ptr(), P, B, ks.data_ptr(), counts.data_ptr(), code,
-                                       _ptr(work), need, _stream(dev)))
+    work, need = _workspace(L.smart_pawn_workspace_bytes(N, R, code), dev)
+    _launch(dev, L.smart_pawn_ks_hip, N, R, y.data_ptr(), ld, cat.data_ptr(), P, B, ks.data_ptr(), counts.data_ptr(), code,
+            _ptr(work), need)
     return PawnResult(ks, counts)

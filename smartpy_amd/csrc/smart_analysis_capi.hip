@@ -1,13 +1,16 @@
 // smart_analysis_capi.hip -- the C ABI of the analyses of a stored discharge matrix sim[R][ld] (include/smart_amd.h):
 // objective functions, weighted quantiles, objective functions per window, flow duration curves, hydrological signatures, Sobol indices, the block bootstrap of the objective functions, and of
 // the Pareto selection over the scores they leave, the ensemble verification scores, the dynamic identifiability analysis and the PAWN sensitivity per report step, with their capacity and workspace entries -- validation and launch --
-// and the one kernel among them that has no unit of its own, smart_objfn_matrix.  Every refusal comes before the device is asked for; the rules the entries share are the
-// static helpers below, which take the entry's name for the text.
+// and the one kernel among them that has no unit of its own, smart_objfn_matrix.  Every refusal comes before the device is asked for; every rule is stated once, as a
+// method of the Check below, which carries the entry's name for the text.
 #include "smart_capi_internal.h"
 #include "smart_device.h"
 
 #include <cmath>
+#include <cstdarg>
 #include <cstdio>
+#include <cstring>
+#include <initializer_list>
 
 namespace smart {
 
@@ -93,78 +96,186 @@ __global__ __launch_bounds__(WX *WR *kWave) void smart_objfn_matrix(long N, long
     }
 }
 
-// ---- the rules the entries share ------------------------------------------------------------------------------------
-static int reports_fit(const char *entry, int64_t n_reports)
-{
-    if (n_reports > 0x7fffffffll)
-        return fail(SMART_E_SIZE, "%s: n_reports %lld is more than one launch takes (2^31 - 1)", entry,
-                    (long long)n_reports);
-    return SMART_OK;
-}
+// ---- the rules of the entries ---------------------------------------------------------------------------------------
+// One Check per call, the rules in the entry's own order (the order is part of the ABI: it says which refusal wins).  The
+// first rule that is broken decides: it sets the code and, where the Check carries the entry's name, the thread's text
+// through fail(); every rule after it is passed over, so a rule may rely on the ones before it.  A workspace query states
+// the same rules to a Check without a name: the code alone, the thread's text untouched.
+struct Named {
+    const char *name;
+    const void *ptr;
+};
+#define NAMED(p) Named{#p, p}
+struct Count {
+    const char *name;
+    long long value;
+};
+#define COUNT(n) Count{#n, (long long)(n)}
 
-// the sizes of a matrix read per window: every count >= 1 (n_probs where the entry has one), ld, 2^31, the window cap
-static int windowed_sizes(const char *entry, int64_t n_samples, int64_t n_reports, int64_t ld, int32_t n_windows,
-                          const int32_t *n_probs)
-{
-    if (n_probs && (n_samples < 1 || n_reports < 1 || n_windows < 1 || *n_probs < 1))
-        return fail(SMART_E_SIZE, "%s: need n_samples, n_reports, n_windows, n_probs >= 1 (got %lld, %lld, %d, %d)", entry,
-                    (long long)n_samples, (long long)n_reports, (int)n_windows, (int)*n_probs);
-    if (n_samples < 1 || n_reports < 1 || n_windows < 1)
-        return fail(SMART_E_SIZE, "%s: need n_samples, n_reports, n_windows >= 1 (got %lld, %lld, %d)", entry,
-                    (long long)n_samples, (long long)n_reports, (int)n_windows);
-    if (ld < n_samples)
-        return fail(SMART_E_SIZE, "%s: ld %lld is less than n_samples %lld", entry, (long long)ld, (long long)n_samples);
-    if (int rc = reports_fit(entry, n_reports))
-        return rc;
-    if (n_windows > objfn_max_windows())
-        return fail(SMART_E_SIZE, "%s: n_windows %d, at most %d per call", entry, (int)n_windows, objfn_max_windows());
-    return SMART_OK;
-}
+constexpr long long kInt32Max = 0x7fffffffll;
 
-// where the window array is optional: without one there is one window
-static int window_array_given(const char *entry, const int32_t *window, int32_t n_windows)
+class Check
 {
-    if (!window && n_windows != 1)
-        return fail(SMART_E_SIZE, "%s: n_windows %d without a window array (NULL is one window)", entry, (int)n_windows);
-    return SMART_OK;
-}
+  public:
+    explicit Check(const char *entry) : entry_(entry) {}
+    int rc = SMART_OK;
+    bool ok() const { return rc == SMART_OK; }
+    int ready() const { return rc ? rc : device_ready(); } // before the launch: the refusal, or whether there is a device
 
-// every probability inside (0, 1], or [0, 1] where rank 1 has a probability of its own (a NaN is outside both)
-static int probs_inside(const char *entry, const double *probs, int32_t n_probs, bool zero_too)
-{
-    for (int32_t k = 0; k < n_probs; ++k)
-        if (!((zero_too ? probs[k] >= 0.0 : probs[k] > 0.0) && probs[k] <= 1.0))
-            return fail(SMART_E_SIZE, "%s: probability %d is %g, outside %s", entry, (int)k, probs[k],
-                        zero_too ? "[0, 1]" : "(0, 1]");
-    return SMART_OK;
-}
+    __attribute__((format(printf, 3, 4))) void refuse(int code, const char *fmt, ...)
+    {
+        if (rc)
+            return;
+        rc = code;
+        if (!entry_)
+            return;
+        char text[384];
+        va_list ap;
+        va_start(ap, fmt);
+        vsnprintf(text, sizeof text, fmt, ap);
+        va_end(ap);
+        fail(code, "%s: %s", entry_, text);
+    }
 
-static int eps_usable(const char *entry, double eps)
-{
-    if (!(eps >= 0.0) || std::isinf(eps))
-        return fail(SMART_E_SIZE, "%s: eps %g must be finite and >= 0", entry, eps);
-    return SMART_OK;
-}
+    // pointers an entry cannot do without: the first that is NULL is named (the two oldest entries name none)
+    void required(std::initializer_list<Named> ptrs, bool name_it = true)
+    {
+        const char *missing = first_null(ptrs);
+        if (missing && name_it)
+            refuse(SMART_E_NULL, "%s are required (%s is NULL)", names(ptrs, " and ").s, missing);
+        else if (missing)
+            refuse(SMART_E_NULL, "%s are required", names(ptrs, " and ").s);
+    }
+    // ... and those it cannot do without once `count` is above zero
+    void needs(const char *what, int count, std::initializer_list<Named> ptrs)
+    {
+        const char *missing = count > 0 ? first_null(ptrs) : nullptr;
+        if (missing)
+            refuse(SMART_E_NULL, "%s %d needs %s (%s is NULL)", what, count, names(ptrs, " and ").s, missing);
+    }
+    void at_least_one(std::initializer_list<Count> counts)
+    {
+        bool bad = false;
+        for (const Count &c : counts)
+            bad |= c.value < 1;
+        if (!bad)
+            return;
+        Text got;
+        for (const Count &c : counts)
+            got.add(got.s[0] ? ", " : "").add(c.value);
+        refuse(SMART_E_SIZE, "need %s >= 1 (got %s)", names(counts, ", ").s, got.s);
+    }
+    void in_range(const char *name, long long v, long long lo, long long hi, const char *suffix = "")
+    {
+        if (v < lo || v > hi)
+            refuse(SMART_E_SIZE, "%s %lld must be in %lld .. %s%s", name, v, lo,
+                   hi == kInt32Max ? "2^31 - 1" : Text().add(hi).s, suffix);
+    }
+    void ld_holds(const char *name, long long ld, long long n_samples)
+    {
+        if (ld < n_samples)
+            refuse(SMART_E_SIZE, "%s %lld is less than n_samples %lld", name, ld, n_samples);
+    }
+    void one_launch(const char *name, long long steps) // a grid dimension
+    {
+        if (steps > kInt32Max)
+            refuse(SMART_E_SIZE, "%s %lld is more than one launch takes (2^31 - 1)", name, steps);
+    }
+    void samples_at_most(long long n_samples, long long most) // where sample indices are kept in 24 bits
+    {
+        if (n_samples > most)
+            refuse(SMART_E_SIZE, "n_samples %lld, at most %lld (2^24)", n_samples, most);
+    }
+    void method_known(int method)
+    {
+        if (!smart::method_known(method))
+            refuse(SMART_E_MODE, "method '%d' unknown.", method);
+    }
+    void form_fits(int method, const char *form, long long n_samples, long long capacity)
+    {
+        if (method == kMethodCapacity && n_samples > capacity)
+            refuse(SMART_E_SIZE, "the %s form takes at most %lld samples, not %lld", form, capacity, n_samples);
+    }
+    // the sizes of a matrix read per window: every count >= 1 (n_probs where the entry has one), ld, 2^31, the window cap
+    void windowed_sizes(int64_t n_samples, int64_t n_reports, int64_t ld, int32_t n_windows, const int32_t *n_probs)
+    {
+        if (n_probs)
+            at_least_one({COUNT(n_samples), COUNT(n_reports), COUNT(n_windows), Count{"n_probs", *n_probs}});
+        else
+            at_least_one({COUNT(n_samples), COUNT(n_reports), COUNT(n_windows)});
+        ld_holds("ld", ld, n_samples);
+        one_launch("n_reports", n_reports);
+        if (n_windows > objfn_max_windows())
+            refuse(SMART_E_SIZE, "n_windows %d, at most %d per call", (int)n_windows, objfn_max_windows());
+    }
+    // where the window array is optional: without one there is one window
+    void window_array_given(const int32_t *window, int32_t n_windows)
+    {
+        if (!window && n_windows != 1)
+            refuse(SMART_E_SIZE, "n_windows %d without a window array (NULL is one window)", (int)n_windows);
+    }
+    // every probability inside (0, 1], or [0, 1] where rank 1 has a probability of its own (a NaN is outside both)
+    void probs_inside(const double *probs, int32_t n_probs, bool zero_too)
+    {
+        for (int32_t k = 0; ok() && k < n_probs; ++k)
+            if (!((zero_too ? probs[k] >= 0.0 : probs[k] > 0.0) && probs[k] <= 1.0))
+                refuse(SMART_E_SIZE, "probability %d is %g, outside %s", (int)k, probs[k], zero_too ? "[0, 1]" : "(0, 1]");
+    }
+    void eps_usable(double eps)
+    {
+        if (!(eps >= 0.0) || std::isinf(eps))
+            refuse(SMART_E_SIZE, "eps %g must be finite and >= 0", eps);
+    }
+    void transform_known(int32_t transform)
+    {
+        if (transform < SMART_TRANSFORM_NONE || transform > SMART_TRANSFORM_INVERSE)
+            refuse(SMART_E_MODE, "transform '%d' unknown.", (int)transform);
+    }
+    // a workspace of `need` bytes: present where any are needed, and large enough
+    void workspace_fits(bool for_objfn, const void *workspace, int64_t workspace_bytes, long need)
+    {
+        if (need > 0 && !workspace)
+            refuse(SMART_E_NULL,
+                   for_objfn ? "objfn needs a workspace of %ld bytes (workspace is NULL)"
+                             : "a workspace of %ld bytes is needed (workspace is NULL)",
+                   need);
+        else if (workspace_bytes < (workspace ? need : 0))
+            refuse(SMART_E_SIZE, "workspace_bytes %lld, need %ld", (long long)workspace_bytes, need);
+    }
 
-static int transform_known(const char *entry, int32_t transform)
-{
-    if (transform < SMART_TRANSFORM_NONE || transform > SMART_TRANSFORM_INVERSE)
-        return fail(SMART_E_MODE, "%s: transform '%d' unknown.", entry, (int)transform);
-    return SMART_OK;
-}
-
-// a workspace of `need` bytes: present where any are needed, and large enough
-static int workspace_fits(const char *entry, bool for_objfn, const void *workspace, int64_t workspace_bytes, long need)
-{
-    if (need > 0 && !workspace)
-        return fail(SMART_E_NULL,
-                    for_objfn ? "%s: objfn needs a workspace of %ld bytes (workspace is NULL)"
-                              : "%s: a workspace of %ld bytes is needed (workspace is NULL)",
-                    entry, need);
-    if (workspace_bytes < (workspace ? need : 0))
-        return fail(SMART_E_SIZE, "%s: workspace_bytes %lld, need %ld", entry, (long long)workspace_bytes, need);
-    return SMART_OK;
-}
+  private:
+    struct Text { // the lists inside a refusal
+        char s[128] = "";
+        Text &add(const char *piece)
+        {
+            strncat(s, piece, sizeof s - strlen(s) - 1);
+            return *this;
+        }
+        Text &add(long long v)
+        {
+            const size_t at = strlen(s);
+            snprintf(s + at, sizeof s - at, "%lld", v);
+            return *this;
+        }
+    };
+    template <class Item>
+    static Text names(std::initializer_list<Item> items, const char *before_last) // "a, b and c", "a, b, c"
+    {
+        Text t;
+        size_t i = 0;
+        for (const Item &x : items)
+            t.add(i++ == 0 ? "" : (i == items.size() ? before_last : ", ")).add(x.name);
+        return t;
+    }
+    static const char *first_null(std::initializer_list<Named> ptrs)
+    {
+        for (const Named &p : ptrs)
+            if (!p.ptr)
+                return p.name;
+        return nullptr;
+    }
+    const char *entry_; // null: a workspace query
+};
 
 // the end of every entry, after its launch
 static int launched()
@@ -174,119 +285,60 @@ static int launched()
     return SMART_OK;
 }
 
-// the size rules of smart_sobol_indices_hip, shared with smart_sobol_workspace_bytes; 0 or the text of the refusal
-static const char *sobol_sizes(int64_t n_base, int32_t n_params, int64_t n_rows, int32_t n_resamples, char *text, size_t len)
+// ---- the size rules an entry shares with its workspace query ---------------------------------------------------------
+static void sobol_sizes(Check &c, int64_t n_base, int32_t n_params, int64_t n_rows, int32_t n_resamples)
 {
-    if (n_base < 1 || n_base > 0x7fffffffll)
-        snprintf(text, len, "n_base %lld must be in 1 .. 2^31 - 1", (long long)n_base);
-    else if (n_params < 1 || n_params > SMART_SOBOL_MAX_PARAMS)
-        snprintf(text, len, "n_params %d must be in 1 .. %d", (int)n_params, SMART_SOBOL_MAX_PARAMS);
-    else if (n_rows < 1 || n_rows > 0x7fffffffll)
-        snprintf(text, len, "n_rows %lld must be in 1 .. 2^31 - 1", (long long)n_rows);
-    else if (n_resamples < 0 || n_resamples > sobol_max_resamples())
-        snprintf(text, len, "n_resamples %d must be in 0 .. %d", (int)n_resamples, sobol_max_resamples());
-    else
-        return nullptr;
-    return text;
+    c.in_range("n_base", n_base, 1, kInt32Max);
+    c.in_range("n_params", n_params, 1, SMART_SOBOL_MAX_PARAMS);
+    c.in_range("n_rows", n_rows, 1, kInt32Max);
+    c.in_range("n_resamples", n_resamples, 0, sobol_max_resamples());
 }
 
-// the size rules of smart_objfn_bootstrap_hip, shared with smart_bootstrap_workspace_bytes; 0 or the text of the refusal
-static const char *bootstrap_sizes(int64_t n_samples, int32_t n_windows, int32_t n_resamples, char *text, size_t len)
+static void bootstrap_sizes(Check &c, int64_t n_samples, int32_t n_windows, int32_t n_resamples)
 {
-    if (n_samples < 1 || n_samples > 0x7fffffffll)
-        snprintf(text, len, "n_samples %lld must be in 1 .. 2^31 - 1", (long long)n_samples);
-    else if (n_windows < 1 || n_windows > bootstrap_max_windows())
-        snprintf(text, len, "n_windows %d must be in 1 .. %d", (int)n_windows, bootstrap_max_windows());
-    else if (n_resamples < 0 || n_resamples > bootstrap_max_resamples())
-        snprintf(text, len, "n_resamples %d must be in 0 .. %d", (int)n_resamples, bootstrap_max_resamples());
-    else
-        return nullptr;
-    return text;
+    c.in_range("n_samples", n_samples, 1, kInt32Max);
+    c.in_range("n_windows", n_windows, 1, bootstrap_max_windows());
+    c.in_range("n_resamples", n_resamples, 0, bootstrap_max_resamples());
 }
 
-// the size rules of smart_pareto_counts_hip, shared with smart_pareto_workspace_bytes; 0 or the text of the refusal
-static const char *pareto_sizes(int64_t n_rows, int32_t n_objectives, char *text, size_t len)
+static void pareto_sizes(Check &c, int64_t n_rows, int32_t n_objectives)
 {
-    if (n_rows < 1 || n_rows > 0x7fffffffll)
-        snprintf(text, len, "n_rows %lld must be in 1 .. 2^31 - 1", (long long)n_rows);
-    else if (n_objectives < 1 || n_objectives > SMART_PARETO_MAX_OBJECTIVES)
-        snprintf(text, len, "n_objectives %d must be in 1 .. %d", (int)n_objectives, SMART_PARETO_MAX_OBJECTIVES);
-    else
-        return nullptr;
-    return text;
+    c.in_range("n_rows", n_rows, 1, kInt32Max);
+    c.in_range("n_objectives", n_objectives, 1, SMART_PARETO_MAX_OBJECTIVES);
 }
 
-// the size and method rules of smart_ensemble_scores_hip, shared with smart_ensemble_scores_workspace_bytes; SMART_OK, or
-// the code of the refusal with its text
-static int ensemble_sizes(int64_t n_samples, int64_t n_reports, int32_t method, char *text, size_t len)
+// (the method belongs to the sizes here: the entry tests it before ld)
+static void ensemble_sizes(Check &c, int64_t n_samples, int64_t n_reports, int32_t method)
 {
-    int code = SMART_E_SIZE;
-    if (n_samples < 1 || n_reports < 1)
-        snprintf(text, len, "need n_samples, n_reports >= 1 (got %lld, %lld)", (long long)n_samples, (long long)n_reports);
-    else if (n_reports > 0x7fffffffll)
-        snprintf(text, len, "n_reports %lld is more than one launch takes (2^31 - 1)", (long long)n_reports);
-    else if (n_samples > ensemble_scores_max_samples())
-        snprintf(text, len, "n_samples %lld, at most %lld (2^24)", (long long)n_samples,
-                 (long long)ensemble_scores_max_samples());
-    else if (method != SMART_ENS_AUTO && method != SMART_ENS_LDS && method != SMART_ENS_GLOBAL) {
-        snprintf(text, len, "method '%d' unknown.", (int)method);
-        code = SMART_E_MODE;
-    } else if (method == SMART_ENS_LDS && n_samples > ensemble_scores_lds_capacity())
-        snprintf(text, len, "the LDS form takes at most %lld samples, not %lld", (long long)ensemble_scores_lds_capacity(),
-                 (long long)n_samples);
-    else
-        return SMART_OK;
-    return code;
+    c.at_least_one({COUNT(n_samples), COUNT(n_reports)});
+    c.one_launch("n_reports", n_reports);
+    c.samples_at_most(n_samples, ensemble_scores_max_samples());
+    c.method_known(method);
+    c.form_fits(method, "LDS", n_samples, ensemble_scores_lds_capacity());
 }
 
-// the size rules of smart_dynia_hip, shared with smart_dynia_workspace_bytes; 0 or the text of the refusal
-static const char *dynia_sizes(int64_t n_samples, int64_t n_reports, int32_t half_width, int32_t n_factors, int32_t n_bins,
-                               char *text, size_t len)
+static void dynia_sizes(Check &c, int64_t n_samples, int64_t n_reports, int32_t half_width, int32_t n_factors, int32_t n_bins)
 {
-    if (n_samples < 1 || n_reports < 1)
-        snprintf(text, len, "need n_samples, n_reports >= 1 (got %lld, %lld)", (long long)n_samples, (long long)n_reports);
-    else if (n_samples > 0x7fffffffll)
-        snprintf(text, len, "n_samples %lld must be in 1 .. 2^31 - 1", (long long)n_samples);
-    else if (n_reports > 0x7fffffffll)
-        snprintf(text, len, "n_reports %lld is more than one launch takes (2^31 - 1)", (long long)n_reports);
-    else if (half_width < 0 || half_width > dynia_max_half_width())
-        snprintf(text, len, "half_width %d must be in 0 .. %d", (int)half_width, dynia_max_half_width());
-    else if (n_factors < 1 || n_factors > SMART_DYNIA_MAX_FACTORS)
-        snprintf(text, len, "n_factors %d must be in 1 .. %d", (int)n_factors, SMART_DYNIA_MAX_FACTORS);
-    else if (n_bins < 1 || n_bins > SMART_DYNIA_MAX_BINS)
-        snprintf(text, len, "n_bins %d must be in 1 .. %d", (int)n_bins, SMART_DYNIA_MAX_BINS);
-    else
-        return nullptr;
-    return text;
+    c.at_least_one({COUNT(n_samples), COUNT(n_reports)});
+    c.in_range("n_samples", n_samples, 1, kInt32Max);
+    c.one_launch("n_reports", n_reports);
+    c.in_range("half_width", half_width, 0, dynia_max_half_width());
+    c.in_range("n_factors", n_factors, 1, SMART_DYNIA_MAX_FACTORS);
+    c.in_range("n_bins", n_bins, 1, SMART_DYNIA_MAX_BINS);
 }
 
-// the size and method rules of smart_pawn_ks_hip that smart_pawn_workspace_bytes shares (ld, the factors and the bins lie
-// between the sizes and the method in the entry); SMART_OK, or the code of the refusal with its text
-static int pawn_sizes(int64_t n_samples, int64_t n_rows, char *text, size_t len)
+// (ld, the factors and the bins lie between the sizes and the method in the entry: two helpers)
+static void pawn_sizes(Check &c, int64_t n_samples, int64_t n_rows)
 {
-    if (n_samples < 1 || n_rows < 1)
-        snprintf(text, len, "need n_samples, n_rows >= 1 (got %lld, %lld)", (long long)n_samples, (long long)n_rows);
-    else if (n_samples > pawn_max_samples())
-        snprintf(text, len, "n_samples %lld, at most %lld (2^24)", (long long)n_samples, (long long)pawn_max_samples());
-    else if (n_rows > 0x7fffffffll)
-        snprintf(text, len, "n_rows %lld is more than one launch takes (2^31 - 1)", (long long)n_rows);
-    else
-        return SMART_OK;
-    return SMART_E_SIZE;
+    c.at_least_one({COUNT(n_samples), COUNT(n_rows)});
+    c.samples_at_most(n_samples, pawn_max_samples());
+    c.one_launch("n_rows", n_rows);
 }
 
-static int pawn_method(int64_t n_samples, int32_t method, char *text, size_t len)
+static void pawn_method(Check &c, int64_t n_samples, int32_t method)
 {
-    if (method != SMART_PAWN_AUTO && method != SMART_PAWN_LDS && method != SMART_PAWN_GLOBAL) {
-        snprintf(text, len, "method '%d' unknown.", (int)method);
-        return SMART_E_MODE;
-    }
-    if (method == SMART_PAWN_LDS && n_samples > pawn_lds_capacity()) {
-        snprintf(text, len, "the LDS form takes at most %lld samples, not %lld", (long long)pawn_lds_capacity(),
-                 (long long)n_samples);
-        return SMART_E_SIZE;
-    }
-    return SMART_OK;
+    c.method_known(method);
+    c.form_fits(method, "LDS", n_samples, pawn_lds_capacity());
 }
 
 } // namespace smart
@@ -298,11 +350,11 @@ extern "C" {
 int smart_objfn_hip(int64_t n_samples, int64_t n_reports, const double *sim, int64_t ld, const double *obs,
                     const double *gw_sim, double gw_obs, double *objfn, void *stream)
 {
-    if (!sim || !obs || !objfn)
-        return fail(SMART_E_NULL, "smart_objfn_hip: sim, obs and objfn are required");
+    Check c("smart_objfn_hip");
+    c.required({NAMED(sim), NAMED(obs), NAMED(objfn)}, /*name_it=*/false);
     if (n_samples < 1 || n_reports < 1 || ld < n_samples)
-        return fail(SMART_E_SIZE, "smart_objfn_hip: need n_samples, n_reports >= 1 and ld >= n_samples");
-    if (int rc = device_ready())
+        c.refuse(SMART_E_SIZE, "need n_samples, n_reports >= 1 and ld >= n_samples");
+    if (int rc = c.ready())
         return rc;
     if (n_samples >= 4 * 65536) // >= 4 wavefronts per SIMD even with one lane per sample
         hipLaunchKernelGGL((smart_objfn_matrix<4, 1, 8>), dim3((unsigned)((n_samples + 4 * kWave - 1) / (4 * kWave))),
@@ -319,30 +371,20 @@ int smart_weighted_quantiles_hip(int64_t n_samples, int64_t n_reports, const dou
                                  const double *weights, const double *probs, int32_t n_probs, double *out,
                                  int32_t method, void *stream)
 {
-    static const char entry[] = "smart_weighted_quantiles_hip";
-    int rc;
-    if (!sim || !probs || !out)
-        return fail(SMART_E_NULL, "%s: sim, probs and out are required", entry);
+    Check c("smart_weighted_quantiles_hip");
+    c.required({NAMED(sim), NAMED(probs), NAMED(out)}, /*name_it=*/false);
     if (n_samples < 1 || n_reports < 1 || n_probs < 1 || ld < n_samples)
-        return fail(SMART_E_SIZE, "%s: need n_samples, n_reports, n_probs >= 1 and ld >= n_samples", entry);
-    if ((rc = reports_fit(entry, n_reports)))
-        return rc;
+        c.refuse(SMART_E_SIZE, "need n_samples, n_reports, n_probs >= 1 and ld >= n_samples");
+    c.one_launch("n_reports", n_reports);
     if (n_probs > SMART_QUANTILES_MAX_PROBS)
-        return fail(SMART_E_SIZE, "%s: %d probabilities, at most %d per call", entry, (int)n_probs,
-                    SMART_QUANTILES_MAX_PROBS);
-    if ((rc = probs_inside(entry, probs, n_probs, /*zero_too=*/false)))
+        c.refuse(SMART_E_SIZE, "%d probabilities, at most %d per call", (int)n_probs, SMART_QUANTILES_MAX_PROBS);
+    c.probs_inside(probs, n_probs, /*zero_too=*/false);
+    c.method_known(method);
+    c.form_fits(method, "sort", n_samples, quantiles_sort_capacity());
+    if (int rc = c.ready())
         return rc;
-    if (method != SMART_QUANTILES_AUTO && method != SMART_QUANTILES_SORT && method != SMART_QUANTILES_SELECT)
-        return fail(SMART_E_MODE, "%s: method '%d' unknown.", entry, (int)method);
-    if (method == SMART_QUANTILES_SORT && n_samples > quantiles_sort_capacity())
-        return fail(SMART_E_SIZE, "%s: the sort form takes at most %lld samples, not %lld", entry,
-                    (long long)quantiles_sort_capacity(), (long long)n_samples);
-    if ((rc = device_ready()))
-        return rc;
-    const bool sort = method == SMART_QUANTILES_SORT ||
-                      (method == SMART_QUANTILES_AUTO && n_samples <= quantiles_sort_capacity());
-    launch_quantiles((long)n_samples, (long)n_reports, sim, (long)ld, weights, probs, (int)n_probs, out, sort,
-                     (hipStream_t)stream);
+    launch_quantiles((long)n_samples, (long)n_reports, sim, (long)ld, weights, probs, (int)n_probs, out,
+                     capacity_form(method, (long)n_samples, quantiles_sort_capacity()), (hipStream_t)stream);
     return launched();
 }
 
@@ -352,13 +394,12 @@ int smart_objfn_windows_hip(int64_t n_samples, int64_t n_reports, const double *
                             const int32_t *window, int32_t n_windows, int32_t transform, double eps, double *objfn,
                             void *stream)
 {
-    static const char entry[] = "smart_objfn_windows_hip";
-    int rc;
-    if (!sim || !obs || !window || !objfn)
-        return fail(SMART_E_NULL, "%s: sim, obs, window and objfn are required (%s is NULL)", entry,
-                    !sim ? "sim" : (!obs ? "obs" : (!window ? "window" : "objfn")));
-    if ((rc = windowed_sizes(entry, n_samples, n_reports, ld, n_windows, nullptr)) || (rc = eps_usable(entry, eps)) ||
-        (rc = transform_known(entry, transform)) || (rc = device_ready()))
+    Check c("smart_objfn_windows_hip");
+    c.required({NAMED(sim), NAMED(obs), NAMED(window), NAMED(objfn)});
+    c.windowed_sizes(n_samples, n_reports, ld, n_windows, nullptr);
+    c.eps_usable(eps);
+    c.transform_known(transform);
+    if (int rc = c.ready())
         return rc;
     launch_objfn_windows((long)n_samples, (long)n_reports, sim, (long)ld, obs, window, (int)n_windows, (int)transform, eps,
                          objfn, (hipStream_t)stream);
@@ -372,49 +413,41 @@ int smart_flow_duration_hip(int64_t n_samples, int64_t n_reports, const double *
                             double *quant, int32_t transform, double eps, double seg_lo, double seg_hi, double *objfn,
                             void *workspace, int64_t workspace_bytes, int32_t method, void *stream)
 {
-    static const char entry[] = "smart_flow_duration_hip";
-    int rc;
-    if (!sim || !probs || !quant)
-        return fail(SMART_E_NULL, "%s: sim, probs and quant are required (%s is NULL)", entry,
-                    !sim ? "sim" : (!probs ? "probs" : "quant"));
+    Check c("smart_flow_duration_hip");
+    c.required({NAMED(sim), NAMED(probs), NAMED(quant)});
     if (objfn && !obs)
-        return fail(SMART_E_NULL, "%s: objfn needs obs (obs is NULL)", entry);
-    if ((rc = windowed_sizes(entry, n_samples, n_reports, ld, n_windows, &n_probs)) ||
-        (rc = window_array_given(entry, window, n_windows)))
-        return rc;
+        c.refuse(SMART_E_NULL, "objfn needs obs (obs is NULL)");
+    c.windowed_sizes(n_samples, n_reports, ld, n_windows, &n_probs);
+    c.window_array_given(window, n_windows);
     if (n_probs > SMART_QUANTILES_MAX_PROBS)
-        return fail(SMART_E_SIZE, "%s: n_probs %d, at most %d probabilities per call", entry, (int)n_probs,
-                    SMART_QUANTILES_MAX_PROBS);
-    if ((rc = probs_inside(entry, probs, n_probs, /*zero_too=*/true)) || (rc = eps_usable(entry, eps)))
-        return rc;
+        c.refuse(SMART_E_SIZE, "n_probs %d, at most %d probabilities per call", (int)n_probs, SMART_QUANTILES_MAX_PROBS);
+    c.probs_inside(probs, n_probs, /*zero_too=*/true);
+    c.eps_usable(eps);
     if (!(seg_lo >= 0.0 && seg_lo < seg_hi && seg_hi <= 1.0))
-        return fail(SMART_E_SIZE, "%s: the segment (%g, %g) is not 0 <= seg_lo < seg_hi <= 1", entry, seg_lo, seg_hi);
-    if ((rc = transform_known(entry, transform)))
-        return rc;
-    if (method != SMART_FDC_AUTO && method != SMART_FDC_SORT && method != SMART_FDC_SELECT)
-        return fail(SMART_E_MODE, "%s: method '%d' unknown.", entry, (int)method);
+        c.refuse(SMART_E_SIZE, "the segment (%g, %g) is not 0 <= seg_lo < seg_hi <= 1", seg_lo, seg_hi);
+    c.transform_known(transform);
+    c.method_known(method);
     if (objfn && method == SMART_FDC_SELECT)
-        return fail(SMART_E_MODE, "%s: the select form gives order statistics only (objfn given)", entry);
+        c.refuse(SMART_E_MODE, "the select form gives order statistics only (objfn given)");
     const long capacity = flow_duration_sort_capacity();
     if (n_reports > capacity && (objfn || method == SMART_FDC_SORT))
-        return fail(SMART_E_SIZE, "%s: %s at most %ld report steps (the sort capacity), not %lld", entry,
-                    objfn ? "the objective functions of the curve take" : "the sort form takes", capacity,
-                    (long long)n_reports);
-    if (objfn && (rc = workspace_fits(entry, /*for_objfn=*/true, workspace, workspace_bytes,
-                                      flow_duration_workspace_bytes((long)n_reports, (int)n_windows, true))))
+        c.refuse(SMART_E_SIZE, "%s at most %ld report steps (the sort capacity), not %lld",
+                 objfn ? "the objective functions of the curve take" : "the sort form takes", capacity,
+                 (long long)n_reports);
+    if (c.ok() && objfn)
+        c.workspace_fits(/*for_objfn=*/true, workspace, workspace_bytes,
+                         flow_duration_workspace_bytes((long)n_reports, (int)n_windows, true));
+    if (int rc = c.ready())
         return rc;
-    if ((rc = device_ready()))
-        return rc;
-    const bool sort = method != SMART_FDC_SELECT && n_reports <= capacity;
     launch_flow_duration((long)n_samples, (long)n_reports, sim, (long)ld, obs, window, (int)n_windows, probs, (int)n_probs,
-                         quant, (int)transform, eps, seg_lo, seg_hi, objfn, (double *)workspace, sort,
-                         (hipStream_t)stream);
+                         quant, (int)transform, eps, seg_lo, seg_hi, objfn, (double *)workspace,
+                         capacity_form(method, (long)n_reports, capacity), (hipStream_t)stream);
     return launched();
 }
 
 int64_t smart_flow_duration_workspace_bytes(int64_t n_reports, int32_t n_windows, int32_t with_objfn)
 {
-    if (n_reports < 1 || n_reports > 0x7fffffffll || n_windows < 1)
+    if (n_reports < 1 || n_reports > kInt32Max || n_windows < 1) // (its own three arguments, and no more: smart_amd.h)
         return SMART_E_SIZE;
     return flow_duration_workspace_bytes((long)n_reports, (int)n_windows, with_objfn != 0);
 }
@@ -425,16 +458,13 @@ int smart_signatures_hip(int64_t n_samples, int64_t n_reports, const double *sim
                          const int32_t *window, int32_t n_windows, double alpha, const double *pulse, double *sig,
                          void *stream)
 {
-    static const char entry[] = "smart_signatures_hip";
-    int rc;
-    if (!sim || !sig)
-        return fail(SMART_E_NULL, "%s: sim and sig are required (%s is NULL)", entry, !sim ? "sim" : "sig");
-    if ((rc = windowed_sizes(entry, n_samples, n_reports, ld, n_windows, nullptr)) ||
-        (rc = window_array_given(entry, window, n_windows)))
-        return rc;
+    Check c("smart_signatures_hip");
+    c.required({NAMED(sim), NAMED(sig)});
+    c.windowed_sizes(n_samples, n_reports, ld, n_windows, nullptr);
+    c.window_array_given(window, n_windows);
     if (!(alpha > 0.0 && alpha < 1.0))
-        return fail(SMART_E_SIZE, "%s: alpha %g must lie inside (0, 1)", entry, alpha);
-    if ((rc = device_ready()))
+        c.refuse(SMART_E_SIZE, "alpha %g must lie inside (0, 1)", alpha);
+    if (int rc = c.ready())
         return rc;
     launch_signatures((long)n_samples, (long)n_reports, sim, (long)ld, obs, window, (int)n_windows, alpha, pulse, sig,
                       (hipStream_t)stream);
@@ -447,22 +477,15 @@ int smart_sobol_indices_hip(int64_t n_base, int32_t n_params, int64_t n_rows, co
                             double *st, double *moments, const uint16_t *counts, int32_t n_resamples, double *s1_std,
                             double *st_std, void *workspace, int64_t workspace_bytes, void *stream)
 {
-    static const char entry[] = "smart_sobol_indices_hip";
-    int rc;
-    if (!y || !s1 || !st || !moments)
-        return fail(SMART_E_NULL, "%s: y, s1, st and moments are required (%s is NULL)", entry,
-                    !y ? "y" : (!s1 ? "s1" : (!st ? "st" : "moments")));
-    if (n_resamples > 0 && (!counts || !s1_std || !st_std))
-        return fail(SMART_E_NULL, "%s: n_resamples %d needs counts, s1_std and st_std (%s is NULL)", entry,
-                    (int)n_resamples, !counts ? "counts" : (!s1_std ? "s1_std" : "st_std"));
-    char text[160];
-    if (sobol_sizes(n_base, n_params, n_rows, n_resamples, text, sizeof text))
-        return fail(SMART_E_SIZE, "%s: %s", entry, text);
-    if (ld < n_base * (n_params + 2))
-        return fail(SMART_E_SIZE, "%s: ld %lld is less than n_base * (n_params + 2) = %lld", entry, (long long)ld,
-                    (long long)(n_base * (n_params + 2)));
-    if ((rc = workspace_fits(entry, /*for_objfn=*/false, workspace, workspace_bytes, sobol_workspace_bytes())) ||
-        (rc = device_ready()))
+    Check c("smart_sobol_indices_hip");
+    c.required({NAMED(y), NAMED(s1), NAMED(st), NAMED(moments)});
+    c.needs("n_resamples", n_resamples, {NAMED(counts), NAMED(s1_std), NAMED(st_std)});
+    sobol_sizes(c, n_base, n_params, n_rows, n_resamples);
+    if (c.ok() && ld < n_base * (n_params + 2))
+        c.refuse(SMART_E_SIZE, "ld %lld is less than n_base * (n_params + 2) = %lld", (long long)ld,
+                 (long long)(n_base * (n_params + 2)));
+    c.workspace_fits(/*for_objfn=*/false, workspace, workspace_bytes, sobol_workspace_bytes());
+    if (int rc = c.ready())
         return rc;
     launch_sobol((long)n_base, (int)n_params, (long)n_rows, y, (long)ld, s1, st, moments, counts, (int)n_resamples,
                  s1_std, st_std, (hipStream_t)stream);
@@ -471,10 +494,9 @@ int smart_sobol_indices_hip(int64_t n_base, int32_t n_params, int64_t n_rows, co
 
 int64_t smart_sobol_workspace_bytes(int64_t n_base, int32_t n_params, int64_t n_rows, int32_t n_resamples)
 {
-    char text[160];
-    if (sobol_sizes(n_base, n_params, n_rows, n_resamples, text, sizeof text))
-        return SMART_E_SIZE;
-    return sobol_workspace_bytes();
+    Check c(nullptr);
+    sobol_sizes(c, n_base, n_params, n_rows, n_resamples);
+    return c.ok() ? sobol_workspace_bytes() : c.rc;
 }
 
 int32_t smart_sobol_max_resamples(void) { return sobol_max_resamples(); }
@@ -487,34 +509,23 @@ int smart_objfn_bootstrap_hip(int64_t n_samples, int64_t n_reports, const double
                               double *point, double *stats, double *replicates, void *workspace, int64_t workspace_bytes,
                               void *stream)
 {
-    static const char entry[] = "smart_objfn_bootstrap_hip";
-    int rc;
-    if (!sim || !obs || !window || !point)
-        return fail(SMART_E_NULL, "%s: sim, obs, window and point are required (%s is NULL)", entry,
-                    !sim ? "sim" : (!obs ? "obs" : (!window ? "window" : "point")));
-    if (n_resamples > 0 && (!counts || !probs || !stats))
-        return fail(SMART_E_NULL, "%s: n_resamples %d needs counts, probs and stats (%s is NULL)", entry, (int)n_resamples,
-                    !counts ? "counts" : (!probs ? "probs" : "stats"));
-    char text[160];
-    if (bootstrap_sizes(n_samples, n_windows, n_resamples, text, sizeof text))
-        return fail(SMART_E_SIZE, "%s: %s", entry, text);
-    if (n_reports < 1)
-        return fail(SMART_E_SIZE, "%s: need n_reports >= 1 (got %lld)", entry, (long long)n_reports);
-    if (ld < n_samples)
-        return fail(SMART_E_SIZE, "%s: ld %lld is less than n_samples %lld", entry, (long long)ld, (long long)n_samples);
-    if ((rc = reports_fit(entry, n_reports)))
-        return rc;
-    if (n_resamples > 0) {
-        if (n_probs < 1 || n_probs > SMART_QUANTILES_MAX_PROBS)
-            return fail(SMART_E_SIZE, "%s: n_probs %d must be in 1 .. %d", entry, (int)n_probs, SMART_QUANTILES_MAX_PROBS);
-        if ((rc = probs_inside(entry, probs, n_probs, /*zero_too=*/false)))
-            return rc;
+    Check c("smart_objfn_bootstrap_hip");
+    c.required({NAMED(sim), NAMED(obs), NAMED(window), NAMED(point)});
+    c.needs("n_resamples", n_resamples, {NAMED(counts), NAMED(probs), NAMED(stats)});
+    bootstrap_sizes(c, n_samples, n_windows, n_resamples);
+    c.at_least_one({COUNT(n_reports)});
+    c.ld_holds("ld", ld, n_samples);
+    c.one_launch("n_reports", n_reports);
+    if (n_resamples > 0) { // (without replicates neither n_probs nor the probabilities are looked at)
+        c.in_range("n_probs", n_probs, 1, SMART_QUANTILES_MAX_PROBS);
+        c.probs_inside(probs, n_probs, /*zero_too=*/false);
     }
-    if ((rc = eps_usable(entry, eps)) || (rc = transform_known(entry, transform)) ||
-        (rc = workspace_fits(entry, /*for_objfn=*/false, workspace, workspace_bytes,
-                             bootstrap_workspace_bytes((long)n_samples, (int)n_windows, (int)n_resamples,
-                                                       replicates != nullptr))) ||
-        (rc = device_ready()))
+    c.eps_usable(eps);
+    c.transform_known(transform);
+    if (c.ok())
+        c.workspace_fits(/*for_objfn=*/false, workspace, workspace_bytes,
+                         bootstrap_workspace_bytes((long)n_samples, (int)n_windows, (int)n_resamples, replicates != nullptr));
+    if (int rc = c.ready())
         return rc;
     launch_bootstrap((long)n_samples, (long)n_reports, sim, (long)ld, obs, window, (int)n_windows, (int)transform, eps,
                      counts, (int)n_resamples, probs, n_resamples > 0 ? (int)n_probs : 0, point, stats, replicates,
@@ -524,10 +535,9 @@ int smart_objfn_bootstrap_hip(int64_t n_samples, int64_t n_reports, const double
 
 int64_t smart_bootstrap_workspace_bytes(int64_t n_samples, int32_t n_windows, int32_t n_resamples, int32_t with_replicates)
 {
-    char text[160];
-    if (bootstrap_sizes(n_samples, n_windows, n_resamples, text, sizeof text))
-        return SMART_E_SIZE;
-    return bootstrap_workspace_bytes((long)n_samples, (int)n_windows, (int)n_resamples, with_replicates != 0);
+    Check c(nullptr);
+    bootstrap_sizes(c, n_samples, n_windows, n_resamples);
+    return c.ok() ? bootstrap_workspace_bytes((long)n_samples, (int)n_windows, (int)n_resamples, with_replicates != 0) : c.rc;
 }
 
 int32_t smart_bootstrap_max_windows(void) { return bootstrap_max_windows(); }
@@ -538,37 +548,33 @@ int smart_pareto_counts_hip(int64_t n_rows, const double *scores, int64_t ld, co
                             const int32_t *direction, const double *target, int32_t n_objectives, const uint8_t *eligible,
                             int32_t *dominated_by, void *workspace, int64_t workspace_bytes, void *stream)
 {
-    static const char entry[] = "smart_pareto_counts_hip";
-    int rc;
-    if (!scores || !columns || !direction || !dominated_by)
-        return fail(SMART_E_NULL, "%s: scores, columns, direction and dominated_by are required (%s is NULL)", entry,
-                    !scores ? "scores" : (!columns ? "columns" : (!direction ? "direction" : "dominated_by")));
-    char text[160];
-    if (pareto_sizes(n_rows, n_objectives, text, sizeof text))
-        return fail(SMART_E_SIZE, "%s: %s", entry, text);
-    for (int32_t m = 0; m < n_objectives; ++m) {
+    Check c("smart_pareto_counts_hip");
+    c.required({NAMED(scores), NAMED(columns), NAMED(direction), NAMED(dominated_by)});
+    pareto_sizes(c, n_rows, n_objectives);
+    // (the loops below read the arrays: they are walked only while no rule is broken, one objective after the other)
+    for (int32_t m = 0; c.ok() && m < n_objectives; ++m) {
         if (columns[m] < 0 || columns[m] >= ld)
-            return fail(SMART_E_SIZE, "%s: column %d of objective %d is outside 0 .. ld - 1 = %lld", entry, (int)columns[m],
-                        (int)m, (long long)ld - 1);
+            c.refuse(SMART_E_SIZE, "column %d of objective %d is outside 0 .. ld - 1 = %lld", (int)columns[m], (int)m,
+                     (long long)ld - 1);
         for (int32_t k = 0; k < m; ++k)
             if (columns[k] == columns[m])
-                return fail(SMART_E_SIZE, "%s: column %d is named twice (objectives %d and %d)", entry, (int)columns[m],
-                            (int)k, (int)m);
+                c.refuse(SMART_E_SIZE, "column %d is named twice (objectives %d and %d)", (int)columns[m], (int)k, (int)m);
     }
-    for (int32_t m = 0; m < n_objectives; ++m)
+    for (int32_t m = 0; c.ok() && m < n_objectives; ++m)
         if (direction[m] != SMART_PARETO_MAX && direction[m] != SMART_PARETO_MIN && direction[m] != SMART_PARETO_TARGET)
-            return fail(SMART_E_MODE, "%s: direction '%d' of objective %d unknown.", entry, (int)direction[m], (int)m);
-    for (int32_t m = 0; m < n_objectives; ++m) {
+            c.refuse(SMART_E_MODE, "direction '%d' of objective %d unknown.", (int)direction[m], (int)m);
+    for (int32_t m = 0; c.ok() && m < n_objectives; ++m) {
         if (direction[m] != SMART_PARETO_TARGET)
             continue;
         if (!target)
-            return fail(SMART_E_NULL, "%s: objective %d is a TARGET (target is NULL)", entry, (int)m);
-        if (!std::isfinite(target[m]))
-            return fail(SMART_E_SIZE, "%s: target %g of objective %d must be finite", entry, target[m], (int)m);
+            c.refuse(SMART_E_NULL, "objective %d is a TARGET (target is NULL)", (int)m);
+        else if (!std::isfinite(target[m]))
+            c.refuse(SMART_E_SIZE, "target %g of objective %d must be finite", target[m], (int)m);
     }
-    if ((rc = workspace_fits(entry, /*for_objfn=*/false, workspace, workspace_bytes,
-                             pareto_workspace_bytes((long)n_rows, (int)n_objectives))) ||
-        (rc = device_ready()))
+    if (c.ok())
+        c.workspace_fits(/*for_objfn=*/false, workspace, workspace_bytes,
+                         pareto_workspace_bytes((long)n_rows, (int)n_objectives));
+    if (int rc = c.ready())
         return rc;
     launch_pareto((long)n_rows, scores, (long)ld, columns, direction, target, (int)n_objectives, eligible, dominated_by,
                   workspace, (hipStream_t)stream);
@@ -577,10 +583,9 @@ int smart_pareto_counts_hip(int64_t n_rows, const double *scores, int64_t ld, co
 
 int64_t smart_pareto_workspace_bytes(int64_t n_rows, int32_t n_objectives)
 {
-    char text[160];
-    if (pareto_sizes(n_rows, n_objectives, text, sizeof text))
-        return 0;
-    return pareto_workspace_bytes((long)n_rows, (int)n_objectives);
+    Check c(nullptr);
+    pareto_sizes(c, n_rows, n_objectives);
+    return c.ok() ? pareto_workspace_bytes((long)n_rows, (int)n_objectives) : 0; // (0, not the code: smart_amd.h)
 }
 
 int smart_pareto_max_objectives(void) { return SMART_PARETO_MAX_OBJECTIVES; }
@@ -589,20 +594,15 @@ int smart_ensemble_scores_hip(int64_t n_samples, int64_t n_reports, const double
                               const double *obs, double *out, int32_t method, void *workspace, int64_t workspace_bytes,
                               void *stream)
 {
-    static const char entry[] = "smart_ensemble_scores_hip";
-    int rc;
-    if (!sim || !out)
-        return fail(SMART_E_NULL, "%s: sim and out are required (%s is NULL)", entry, !sim ? "sim" : "out");
-    char text[160];
-    if ((rc = ensemble_sizes(n_samples, n_reports, method, text, sizeof text)))
-        return fail(rc, "%s: %s", entry, text);
-    if (ld < n_samples)
-        return fail(SMART_E_SIZE, "%s: ld %lld is less than n_samples %lld", entry, (long long)ld, (long long)n_samples);
-    const bool lds = method == SMART_ENS_LDS || (method == SMART_ENS_AUTO && n_samples <= ensemble_scores_lds_capacity());
-    if (!lds && (rc = workspace_fits(entry, /*for_objfn=*/false, workspace, workspace_bytes,
-                                     ensemble_scores_step_bytes((long)n_samples, weights != nullptr))))
-        return rc;
-    if ((rc = device_ready()))
+    Check c("smart_ensemble_scores_hip");
+    c.required({NAMED(sim), NAMED(out)});
+    ensemble_sizes(c, n_samples, n_reports, method);
+    c.ld_holds("ld", ld, n_samples);
+    const bool lds = capacity_form(method, (long)n_samples, ensemble_scores_lds_capacity());
+    if (c.ok() && !lds)
+        c.workspace_fits(/*for_objfn=*/false, workspace, workspace_bytes,
+                         ensemble_scores_step_bytes((long)n_samples, weights != nullptr));
+    if (int rc = c.ready())
         return rc;
     launch_ensemble_scores((long)n_samples, (long)n_reports, sim, (long)ld, weights, obs, out, lds, workspace,
                            (long)workspace_bytes, (hipStream_t)stream);
@@ -611,12 +611,13 @@ int smart_ensemble_scores_hip(int64_t n_samples, int64_t n_reports, const double
 
 int64_t smart_ensemble_scores_workspace_bytes(int64_t n_samples, int64_t n_reports, int32_t weighted, int32_t method)
 {
-    char text[160];
-    if (int rc = ensemble_sizes(n_samples, n_reports, method, text, sizeof text))
-        return rc;
-    if (method == SMART_ENS_LDS || (method == SMART_ENS_AUTO && n_samples <= ensemble_scores_lds_capacity()))
+    Check c(nullptr);
+    ensemble_sizes(c, n_samples, n_reports, method);
+    if (!c.ok())
+        return c.rc;
+    if (capacity_form(method, (long)n_samples, ensemble_scores_lds_capacity()))
         return 0;
-    return ensemble_scores_workspace_bytes((long)n_samples, (long)n_reports, weighted != 0);
+    return batched_workspace_bytes(ensemble_scores_step_bytes((long)n_samples, weighted != 0), (long)n_reports);
 }
 
 int64_t smart_ensemble_scores_lds_capacity(void) { return ensemble_scores_lds_capacity(); }
@@ -626,30 +627,19 @@ int smart_dynia_hip(int64_t n_samples, int64_t n_reports, const double *sim, int
                     int32_t n_bins, int32_t support, double *shares, double *cut, int32_t *retained, int32_t *count,
                     double *err, int64_t ld_err, void *workspace, int64_t workspace_bytes, void *stream)
 {
-    static const char entry[] = "smart_dynia_hip";
-    int rc;
-    if (!sim || !obs || !cat || !shares || !cut || !retained || !count)
-        return fail(SMART_E_NULL, "%s: sim, obs, cat, shares, cut, retained and count are required (%s is NULL)", entry,
-                    !sim ? "sim"
-                         : (!obs ? "obs"
-                                 : (!cat ? "cat" : (!shares ? "shares" : (!cut ? "cut" : (!retained ? "retained" : "count"))))));
-    char text[160];
-    if (dynia_sizes(n_samples, n_reports, half_width, n_factors, n_bins, text, sizeof text))
-        return fail(SMART_E_SIZE, "%s: %s", entry, text);
-    if (ld < n_samples)
-        return fail(SMART_E_SIZE, "%s: ld %lld is less than n_samples %lld", entry, (long long)ld, (long long)n_samples);
-    if (err && ld_err < n_samples)
-        return fail(SMART_E_SIZE, "%s: ld_err %lld is less than n_samples %lld", entry, (long long)ld_err,
-                    (long long)n_samples);
-    if (min_valid < 1 || min_valid > 2 * half_width + 1)
-        return fail(SMART_E_SIZE, "%s: min_valid %d must be in 1 .. %d (the window)", entry, (int)min_valid,
-                    2 * (int)half_width + 1);
+    Check c("smart_dynia_hip");
+    c.required({NAMED(sim), NAMED(obs), NAMED(cat), NAMED(shares), NAMED(cut), NAMED(retained), NAMED(count)});
+    dynia_sizes(c, n_samples, n_reports, half_width, n_factors, n_bins);
+    c.ld_holds("ld", ld, n_samples);
+    if (err)
+        c.ld_holds("ld_err", ld_err, n_samples);
+    c.in_range("min_valid", min_valid, 1, 2 * (long long)half_width + 1, " (the window)");
     if (!(fraction > 0.0 && fraction <= 1.0))
-        return fail(SMART_E_SIZE, "%s: fraction %g is outside (0, 1]", entry, fraction);
+        c.refuse(SMART_E_SIZE, "fraction %g is outside (0, 1]", fraction);
     if (support != SMART_DYNIA_EQUAL && support != SMART_DYNIA_LINEAR)
-        return fail(SMART_E_MODE, "%s: support '%d' unknown.", entry, (int)support);
-    if ((rc = workspace_fits(entry, /*for_objfn=*/false, workspace, workspace_bytes, dynia_step_bytes((long)n_samples))) ||
-        (rc = device_ready()))
+        c.refuse(SMART_E_MODE, "support '%d' unknown.", (int)support);
+    c.workspace_fits(/*for_objfn=*/false, workspace, workspace_bytes, dynia_step_bytes((long)n_samples));
+    if (int rc = c.ready())
         return rc;
     launch_dynia((long)n_samples, (long)n_reports, sim, (long)ld, obs, (int)half_width, (int)min_valid, fraction, cat,
                  (int)n_factors, (int)n_bins, (int)support, shares, cut, retained, count, err, (long)ld_err, workspace,
@@ -660,10 +650,9 @@ int smart_dynia_hip(int64_t n_samples, int64_t n_reports, const double *sim, int
 int64_t smart_dynia_workspace_bytes(int64_t n_samples, int64_t n_reports, int32_t half_width, int32_t n_factors,
                                     int32_t n_bins)
 {
-    char text[160];
-    if (dynia_sizes(n_samples, n_reports, half_width, n_factors, n_bins, text, sizeof text))
-        return SMART_E_SIZE;
-    return dynia_workspace_bytes((long)n_samples, (long)n_reports);
+    Check c(nullptr);
+    dynia_sizes(c, n_samples, n_reports, half_width, n_factors, n_bins);
+    return c.ok() ? batched_workspace_bytes(dynia_step_bytes((long)n_samples), (long)n_reports) : c.rc;
 }
 
 int32_t smart_dynia_max_half_width(void) { return dynia_max_half_width(); }
@@ -674,26 +663,17 @@ int smart_pawn_ks_hip(int64_t n_samples, int64_t n_rows, const double *y, int64_
                       int32_t n_bins, double *ks, int32_t *counts, int32_t method, void *workspace, int64_t workspace_bytes,
                       void *stream)
 {
-    static const char entry[] = "smart_pawn_ks_hip";
-    int rc;
-    if (!y || !cat || !ks || !counts)
-        return fail(SMART_E_NULL, "%s: y, cat, ks and counts are required (%s is NULL)", entry,
-                    !y ? "y" : (!cat ? "cat" : (!ks ? "ks" : "counts")));
-    char text[160];
-    if ((rc = pawn_sizes(n_samples, n_rows, text, sizeof text)))
-        return fail(rc, "%s: %s", entry, text);
-    if (ld < n_samples)
-        return fail(SMART_E_SIZE, "%s: ld %lld is less than n_samples %lld", entry, (long long)ld, (long long)n_samples);
-    if (n_factors < 1 || n_factors > SMART_PAWN_MAX_FACTORS)
-        return fail(SMART_E_SIZE, "%s: n_factors %d must be in 1 .. %d", entry, (int)n_factors, SMART_PAWN_MAX_FACTORS);
-    if (n_bins < 1 || n_bins > SMART_PAWN_MAX_BINS)
-        return fail(SMART_E_SIZE, "%s: n_bins %d must be in 1 .. %d", entry, (int)n_bins, SMART_PAWN_MAX_BINS);
-    if ((rc = pawn_method(n_samples, method, text, sizeof text)))
-        return fail(rc, "%s: %s", entry, text);
-    const bool lds = method == SMART_PAWN_LDS || (method == SMART_PAWN_AUTO && n_samples <= pawn_lds_capacity());
-    if (!lds && (rc = workspace_fits(entry, /*for_objfn=*/false, workspace, workspace_bytes, pawn_step_bytes((long)n_samples))))
-        return rc;
-    if ((rc = device_ready()))
+    Check c("smart_pawn_ks_hip");
+    c.required({NAMED(y), NAMED(cat), NAMED(ks), NAMED(counts)});
+    pawn_sizes(c, n_samples, n_rows);
+    c.ld_holds("ld", ld, n_samples);
+    c.in_range("n_factors", n_factors, 1, SMART_PAWN_MAX_FACTORS);
+    c.in_range("n_bins", n_bins, 1, SMART_PAWN_MAX_BINS);
+    pawn_method(c, n_samples, method);
+    const bool lds = capacity_form(method, (long)n_samples, pawn_lds_capacity());
+    if (c.ok() && !lds)
+        c.workspace_fits(/*for_objfn=*/false, workspace, workspace_bytes, pawn_step_bytes((long)n_samples));
+    if (int rc = c.ready())
         return rc;
     launch_pawn((long)n_samples, (long)n_rows, y, (long)ld, cat, (int)n_factors, (int)n_bins, ks, counts, lds, workspace,
                 (long)workspace_bytes, (hipStream_t)stream);
@@ -702,15 +682,17 @@ int smart_pawn_ks_hip(int64_t n_samples, int64_t n_rows, const double *y, int64_
 
 int64_t smart_pawn_workspace_bytes(int64_t n_samples, int64_t n_rows, int32_t method)
 {
-    char text[160];
-    int rc;
-    if ((rc = pawn_sizes(n_samples, n_rows, text, sizeof text)) || (rc = pawn_method(n_samples, method, text, sizeof text)))
-        return rc;
-    if (method == SMART_PAWN_LDS || (method == SMART_PAWN_AUTO && n_samples <= pawn_lds_capacity()))
+    Check c(nullptr);
+    pawn_sizes(c, n_samples, n_rows);
+    pawn_method(c, n_samples, method);
+    if (!c.ok())
+        return c.rc;
+    if (capacity_form(method, (long)n_samples, pawn_lds_capacity()))
         return 0;
-    return pawn_workspace_bytes((long)n_samples, (long)n_rows);
+    return batched_workspace_bytes(pawn_step_bytes((long)n_samples), (long)n_rows);
 }
 
 int64_t smart_pawn_lds_capacity(void) { return pawn_lds_capacity(); }
 
 } // extern "C"
+

@@ -7,6 +7,8 @@
 
 #include <hip/hip_runtime.h>
 
+#include <type_traits>
+
 namespace smart {
 
 // ---- smart_capi.hip: the text smart_last_error() returns, per thread
@@ -21,6 +23,67 @@ int device_ready(); // SMART_OK, or SMART_E_NO_DEVICE with its text: every entry
         if (_e != hipSuccess)                                                                                          \
             return hip_fail(_e, #expr);                                                                                \
     } while (0)
+
+// ---- the launch rules the analysis units share (host side): stated here once, used by smart_analysis_capi.hip and by
+// the launch tails of the units
+
+// WHICH FORM RUNS.  Every method argument of the ABI is 0 = AUTO, 1 = the form with a capacity (SORT, LDS), 2 = the form
+// without one (SELECT, GLOBAL); AUTO takes the first wherever the row fits.
+constexpr int kMethodAuto = 0, kMethodCapacity = 1, kMethodOther = 2;
+static_assert(SMART_QUANTILES_AUTO == kMethodAuto && SMART_FDC_AUTO == kMethodAuto && SMART_ENS_AUTO == kMethodAuto &&
+                  SMART_PAWN_AUTO == kMethodAuto && SMART_QUANTILES_SORT == kMethodCapacity &&
+                  SMART_FDC_SORT == kMethodCapacity && SMART_ENS_LDS == kMethodCapacity &&
+                  SMART_PAWN_LDS == kMethodCapacity && SMART_QUANTILES_SELECT == kMethodOther &&
+                  SMART_FDC_SELECT == kMethodOther && SMART_ENS_GLOBAL == kMethodOther && SMART_PAWN_GLOBAL == kMethodOther,
+              "one predicate reads every method argument");
+inline bool method_known(int method) { return method >= kMethodAuto && method <= kMethodOther; }
+inline bool capacity_form(int method, long n, long capacity)
+{
+    return method == kMethodCapacity || (method == kMethodAuto && n <= capacity);
+}
+
+// WHICH INSTANCE OF A KERNEL THAT SORTS A ROW IN LDS RUNS: run(cap, threads) with the elements and the threads of the
+// smallest instance that holds N, both as compile-time constants (cap(), threads()); CAPACITY is the largest instance.
+template <int CAPACITY, class Run>
+inline void sort_instance(long N, Run run)
+{
+    static_assert(CAPACITY > 4096, "the ladder ends above its last rung");
+    if (N <= 1024)
+        run(std::integral_constant<int, 1024>(), std::integral_constant<int, 512>());
+    else if (N <= 2048)
+        run(std::integral_constant<int, 2048>(), std::integral_constant<int, 1024>());
+    else if (N <= 4096)
+        run(std::integral_constant<int, 4096>(), std::integral_constant<int, 1024>());
+    else
+        run(std::integral_constant<int, CAPACITY>(), std::integral_constant<int, 1024>());
+}
+
+// HOW MANY STEPS A WORKSPACE HOLDS, where a kernel keeps step_bytes per report step (or row) and the steps go in
+// batches, one launch per batch: a *_workspace_bytes entry asks for as many steps as fit in kBatchBytes, at least one,
+// at most R; the launch takes as many per batch as the workspace it is given holds (the entry has seen to one).
+constexpr long kBatchBytes = 256l << 20;
+inline long workspace_steps(long workspace_bytes, long step_bytes) { return workspace_bytes / step_bytes; }
+inline long batched_workspace_bytes(long step_bytes, long R)
+{
+    long steps = workspace_steps(kBatchBytes, step_bytes);
+    steps = steps < 1 ? 1 : steps;
+    return (steps < R ? steps : R) * step_bytes;
+}
+template <class Run>
+inline void for_each_batch(long R, long batch, Run run) // run(first step, steps) over [0, R)
+{
+    for (long r0 = 0; r0 < R; r0 += batch)
+        run(r0, R - r0 < batch ? R - r0 : batch);
+}
+
+// a length rounded up to a power of two of at least `block`: what a bitonic network over blocks in LDS sorts
+inline long padded_pow2(long n, long block)
+{
+    long p = block;
+    while (p < n)
+        p *= 2;
+    return p;
+}
 
 // ---- smart_literal.hip
 struct KArgs;
@@ -73,7 +136,6 @@ void launch_pareto(long N, const double *scores, long ld, const int *columns, co
 long ensemble_scores_lds_capacity();
 long ensemble_scores_max_samples();
 long ensemble_scores_step_bytes(long N, bool weighted);
-long ensemble_scores_workspace_bytes(long N, long R, bool weighted);
 void launch_ensemble_scores(long N, long R, const double *sim, long ld, const double *weights, const double *obs,
                             double *out, bool lds, void *workspace, long workspace_bytes, hipStream_t s);
 
@@ -81,7 +143,6 @@ void launch_ensemble_scores(long N, long R, const double *sim, long ld, const do
 int dynia_max_half_width();
 long dynia_lds_capacity();
 long dynia_step_bytes(long N);
-long dynia_workspace_bytes(long N, long R);
 void launch_dynia(long N, long R, const double *sim, long ld, const double *obs, int h, int min_valid, double fraction,
                   const unsigned char *cat, int P, int B, int support, double *shares, double *cut, int *retained,
                   int *count, double *err, long ld_err, void *workspace, long workspace_bytes, hipStream_t s);
@@ -90,7 +151,6 @@ void launch_dynia(long N, long R, const double *sim, long ld, const double *obs,
 long pawn_lds_capacity();
 long pawn_max_samples();
 long pawn_step_bytes(long N);
-long pawn_workspace_bytes(long N, long R);
 void launch_pawn(long N, long R, const double *y, long ld, const unsigned char *cat, int P, int B, double *ks, int *counts,
                  bool lds, void *workspace, long workspace_bytes, hipStream_t s);
 

@@ -42,8 +42,6 @@ constexpr int kDyniaChunk = 8;                  // pass A: blocks of w rows per 
 constexpr long kDyniaSmallCapacity = 2048;      // pass B: 16 KiB of keys, 256 threads
 constexpr long kDyniaLdsCapacity = 16384;       // pass B: 128 KiB of keys, 1024 threads; beyond: the row stays in memory
 constexpr int kDyniaCompact = 10240;            // pass B, global form: retained rows compacted in LDS, 12 bytes each = 120 KiB
-constexpr long kDyniaBatchBytes = 256l << 20;
-constexpr unsigned long long kKeyInf = 0xfff0000000000000ull;   // value_key(+inf): an eligible E lies below
 
 // ---- count[r]: the observed steps of the window, once per step ------------------------------------------------------
 __global__ __launch_bounds__(256) void smart_dynia_count(long R, const double *__restrict__ obs, int h, int *__restrict__ count)
@@ -174,7 +172,7 @@ __global__ __launch_bounds__(THREADS) void smart_dynia_shares(long N, long r0, c
     unsigned long long kmin = kKeyPad, kmax = 0;
     for (long n = tid; n < N; n += THREADS) {
         const unsigned long long key = key_at(n);
-        if (key < kKeyInf) {
+        if (key < kKeyPlusInf) {
             kmin = key < kmin ? key : kmin;
             kmax = key > kmax ? key : kmax;
         }
@@ -188,7 +186,7 @@ __global__ __launch_bounds__(THREADS) void smart_dynia_shares(long N, long r0, c
         ends[0][wave] = kmin;
         ends[1][wave] = kmax;
     }
-    const unsigned M = block_count<THREADS>([&](long n) { return key_at(n) < kKeyInf; }, N, counters); // (publishes ends)
+    const unsigned M = block_count<THREADS>([&](long n) { return key_at(n) < kKeyPlusInf; }, N, counters); // (publishes ends)
     if (M == 0) {
         dynia_not_assessed(r, P, B, shares, cut, retained);
         return;
@@ -314,14 +312,6 @@ long dynia_lds_capacity() { return kDyniaLdsCapacity; }
 
 long dynia_step_bytes(long N) { return N * 8; }
 
-long dynia_workspace_bytes(long N, long R)
-{
-    const long step = dynia_step_bytes(N);
-    long steps = kDyniaBatchBytes / step;
-    steps = steps < 1 ? 1 : steps;
-    return (steps < R ? steps : R) * step;
-}
-
 static long floor_div(long a, long b) { return a >= 0 ? a / b : -((-a + b - 1) / b); }
 
 void launch_dynia(long N, long R, const double *sim, long ld, const double *obs, int h, int min_valid, double fraction,
@@ -333,10 +323,7 @@ void launch_dynia(long N, long R, const double *sim, long ld, const double *obs,
     // the E sums of a batch of steps: in err where it is wanted (every step at once), else in the workspace
     double *E = err ? err : (double *)workspace;
     const long ldE = err ? ld_err : N;
-    long batch = err ? R : workspace_bytes / dynia_step_bytes(N);
-    batch = batch < R ? batch : R;
-    for (long r0 = 0; r0 < R; r0 += batch) {
-        const long nb = R - r0 < batch ? R - r0 : batch;
+    for_each_batch(R, err ? R : workspace_steps(workspace_bytes, dynia_step_bytes(N)), [&](long r0, long nb) {
         const long bb_first = floor_div(r0 - h, w) + 1, bb_last = floor_div(r0 + nb - 1 - h, w) + 1;
         const long blocks = bb_last - bb_first + 1;
         long per_chunk = (blocks + 32767) / 32768;
@@ -354,7 +341,7 @@ void launch_dynia(long N, long R, const double *sim, long ld, const double *obs,
         else
             hipLaunchKernelGGL((smart_dynia_shares<0, 1024>), steps, dim3(1024), 0, s, N, r0, E, ldE, count, min_valid,
                                fraction, cat, P, B, support, shares, cut, retained);
-    }
+    });
 }
 
 } // namespace smart

@@ -46,9 +46,6 @@ constexpr long kEnsCapacity = 8192;             // LDS form: 8192 * (8 + 2) byte
 constexpr int kEnsBlock = 4096;                 // global form: elements of one LDS block, (8 + 8) bytes each = 64 KiB
 constexpr int kEnsGlobalThreads = 1024;
 constexpr long kEnsMaxSamples = 1l << 24;
-constexpr long kEnsBatchBytes = 256l << 20;     // what smart_ensemble_scores_workspace_bytes asks for at most (one step aside)
-constexpr unsigned long long kKeyPlusInf = 0xfff0000000000000ull;   // value_key(+inf); every NaN lies above
-constexpr unsigned long long kKeyMinusInf = 0x000fffffffffffffull;  // value_key(-inf)
 static_assert(kEnsCapacity <= 65536, "sample indices are kept as 16-bit numbers");
 
 // the first position of sorted keys[0 .. n) that holds the padding = the number of live members
@@ -435,63 +432,34 @@ long ensemble_scores_lds_capacity() { return kEnsCapacity; }
 
 long ensemble_scores_max_samples() { return kEnsMaxSamples; }
 
-static long ens_padded(long N)
-{
-    long P = kEnsBlock;
-    while (P < N)
-        P *= 2;
-    return P;
-}
-
-long ensemble_scores_step_bytes(long N, bool weighted) { return ens_padded(N) * (weighted ? 16 : 8); }
-
-long ensemble_scores_workspace_bytes(long N, long R, bool weighted)
-{
-    const long step = ensemble_scores_step_bytes(N, weighted);
-    long steps = kEnsBatchBytes / step;
-    steps = steps < 1 ? 1 : steps;
-    return (steps < R ? steps : R) * step;
-}
-
-template <int CAP, int THREADS>
-static void launch_ens_lds(long N, long R, const double *sim, long ld, const double *weights, const double *obs,
-                           double *out, hipStream_t s)
-{
-    const dim3 grid((unsigned)R);
-    if (weights)
-        hipLaunchKernelGGL((smart_ensemble_scores_lds<CAP, THREADS, true>), grid, dim3(THREADS), 0, s, (int)N, R, sim, ld,
-                           weights, obs, out);
-    else
-        hipLaunchKernelGGL((smart_ensemble_scores_lds<CAP, THREADS, false>), grid, dim3(THREADS), 0, s, (int)N, R, sim, ld,
-                           weights, obs, out);
-}
+long ensemble_scores_step_bytes(long N, bool weighted) { return padded_pow2(N, kEnsBlock) * (weighted ? 16 : 8); }
 
 void launch_ensemble_scores(long N, long R, const double *sim, long ld, const double *weights, const double *obs,
                             double *out, bool lds, void *workspace, long workspace_bytes, hipStream_t s)
 {
     if (lds) {
-        if (N <= 1024)
-            launch_ens_lds<1024, 512>(N, R, sim, ld, weights, obs, out, s);
-        else if (N <= 2048)
-            launch_ens_lds<2048, 1024>(N, R, sim, ld, weights, obs, out, s);
-        else if (N <= 4096)
-            launch_ens_lds<4096, 1024>(N, R, sim, ld, weights, obs, out, s);
-        else
-            launch_ens_lds<(int)kEnsCapacity, 1024>(N, R, sim, ld, weights, obs, out, s);
+        sort_instance<(int)kEnsCapacity>(N, [&](auto cap, auto threads) {
+            const dim3 grid((unsigned)R);
+            if (weights)
+                hipLaunchKernelGGL((smart_ensemble_scores_lds<cap(), threads(), true>), grid, dim3(threads()), 0, s, (int)N,
+                                   R, sim, ld, weights, obs, out);
+            else
+                hipLaunchKernelGGL((smart_ensemble_scores_lds<cap(), threads(), false>), grid, dim3(threads()), 0, s,
+                                   (int)N, R, sim, ld, weights, obs, out);
+        });
         return;
     }
     // report steps in batches of as many as the workspace holds, one launch per batch
-    const long P = ens_padded(N);
-    const long batch = workspace_bytes / ensemble_scores_step_bytes(N, weights != nullptr);
-    for (long r0 = 0; r0 < R; r0 += batch) {
-        const long steps = R - r0 < batch ? R - r0 : batch;
+    const long P = padded_pow2(N, kEnsBlock);
+    const long batch = workspace_steps(workspace_bytes, ensemble_scores_step_bytes(N, weights != nullptr));
+    for_each_batch(R, batch, [&](long r0, long steps) {
         if (weights)
             hipLaunchKernelGGL((smart_ensemble_scores_global<true>), dim3((unsigned)steps), dim3(kEnsGlobalThreads), 0, s,
                                (int)N, (int)P, R, r0, sim, ld, weights, obs, out, (unsigned long long *)workspace);
         else
             hipLaunchKernelGGL((smart_ensemble_scores_global<false>), dim3((unsigned)steps), dim3(kEnsGlobalThreads), 0, s,
                                (int)N, (int)P, R, r0, sim, ld, weights, obs, out, (unsigned long long *)workspace);
-    }
+    });
 }
 
 } // namespace smart

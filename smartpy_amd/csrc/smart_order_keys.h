@@ -9,6 +9,8 @@
 namespace smart {
 
 constexpr unsigned long long kKeyNaN = 0xfff8000000000000ull;  // above +inf (0xfff0...), below the padding
+constexpr unsigned long long kKeyPlusInf = 0xfff0000000000000ull;   // value_key(+inf): a finite value lies below
+constexpr unsigned long long kKeyMinusInf = 0x000fffffffffffffull;  // value_key(-inf): a finite value lies above
 constexpr unsigned long long kKeyPad = 0xffffffffffffffffull;
 constexpr unsigned long long kKeyZero = 0x8000000000000000ull;
 

@@ -39,10 +39,7 @@ constexpr long kPawnCapacity = 8192;            // LDS form: 8192 * (8 + 2) byte
 constexpr int kPawnBlock = 4096;                // global form: elements of one LDS block, (8 + 4) bytes each = 48 KiB
 constexpr int kPawnGlobalThreads = 1024;
 constexpr long kPawnMaxSamples = 1l << 24;
-constexpr long kPawnBatchBytes = 256l << 20;
 constexpr unsigned kPawnEval = 0x80000000u;     // global form: bit 31 of a sorted index = the position is an evaluation point
-constexpr unsigned long long kPawnKeyPlusInf = 0xfff0000000000000ull;   // value_key(+inf); every NaN lies above
-constexpr unsigned long long kPawnKeyMinusInf = 0x000fffffffffffffull;  // value_key(-inf)
 static_assert(kPawnCapacity <= 32768, "sample indices are kept as 16-bit numbers");
 static_assert(SMART_PAWN_MAX_BINS <= kWave, "a lane stands for one bin of one factor");
 
@@ -189,7 +186,7 @@ __global__ __launch_bounds__(THREADS) void smart_pawn_lds(int N, const double *_
     __syncthreads();
     for (int k = 2; k <= CAP; k <<= 1)
         bitonic_merge_lds<CAP, THREADS, true, unsigned short>(keys, idx, k, k >> 1, 0);
-    if (keys[0] <= kPawnKeyMinusInf || keys[N - 1] >= kPawnKeyPlusInf) {    // a value that is not finite (every thread alike)
+    if (keys[0] <= kKeyMinusInf || keys[N - 1] >= kKeyPlusInf) {    // a value that is not finite (every thread alike)
         pawn_row_nan(P, B, out);
         return;
     }
@@ -286,7 +283,7 @@ __global__ __launch_bounds__(kPawnGlobalThreads) void smart_pawn_global(int N, i
             __syncthreads();
         }
     }
-    if (kg[0] <= kPawnKeyMinusInf || kg[N - 1] >= kPawnKeyPlusInf) {      // a value that is not finite (every thread alike)
+    if (kg[0] <= kKeyMinusInf || kg[N - 1] >= kKeyPlusInf) {      // a value that is not finite (every thread alike)
         pawn_row_nan(P, B, out);
         return;
     }
@@ -334,54 +331,25 @@ long pawn_lds_capacity() { return kPawnCapacity; }
 
 long pawn_max_samples() { return kPawnMaxSamples; }
 
-static long pawn_padded(long N)
-{
-    long P2 = kPawnBlock;
-    while (P2 < N)
-        P2 *= 2;
-    return P2;
-}
-
-long pawn_step_bytes(long N) { return pawn_padded(N) * 12; }
-
-long pawn_workspace_bytes(long N, long R)
-{
-    const long step = pawn_step_bytes(N);
-    long steps = kPawnBatchBytes / step;
-    steps = steps < 1 ? 1 : steps;
-    return (steps < R ? steps : R) * step;
-}
-
-template <int CAP, int THREADS>
-static void launch_pawn_lds(long N, long R, const double *y, long ld, const unsigned char *cat, int P, int B, double *ks,
-                            hipStream_t s)
-{
-    hipLaunchKernelGGL((smart_pawn_lds<CAP, THREADS>), dim3((unsigned)R), dim3(THREADS), 0, s, (int)N, y, ld, cat, P, B, ks);
-}
+long pawn_step_bytes(long N) { return padded_pow2(N, kPawnBlock) * 12; }
 
 void launch_pawn(long N, long R, const double *y, long ld, const unsigned char *cat, int P, int B, double *ks, int *counts,
                  bool lds, void *workspace, long workspace_bytes, hipStream_t s)
 {
     hipLaunchKernelGGL(smart_pawn_counts, dim3((unsigned)P), dim3(1024), 0, s, (int)N, cat, B, counts);
     if (lds) {
-        if (N <= 1024)
-            launch_pawn_lds<1024, 512>(N, R, y, ld, cat, P, B, ks, s);
-        else if (N <= 2048)
-            launch_pawn_lds<2048, 1024>(N, R, y, ld, cat, P, B, ks, s);
-        else if (N <= 4096)
-            launch_pawn_lds<4096, 1024>(N, R, y, ld, cat, P, B, ks, s);
-        else
-            launch_pawn_lds<(int)kPawnCapacity, 1024>(N, R, y, ld, cat, P, B, ks, s);
+        sort_instance<(int)kPawnCapacity>(N, [&](auto cap, auto threads) {
+            hipLaunchKernelGGL((smart_pawn_lds<cap(), threads()>), dim3((unsigned)R), dim3(threads()), 0, s, (int)N, y, ld,
+                               cat, P, B, ks);
+        });
         return;
     }
     // rows in batches of as many as the workspace holds, one launch per batch
-    const long P2 = pawn_padded(N);
-    const long batch = workspace_bytes / pawn_step_bytes(N);
-    for (long r0 = 0; r0 < R; r0 += batch) {
-        const long steps = R - r0 < batch ? R - r0 : batch;
+    const long P2 = padded_pow2(N, kPawnBlock);
+    for_each_batch(R, workspace_steps(workspace_bytes, pawn_step_bytes(N)), [&](long r0, long steps) {
         hipLaunchKernelGGL(smart_pawn_global, dim3((unsigned)steps), dim3(kPawnGlobalThreads), 0, s, (int)N, (int)P2, r0, y,
                            ld, cat, P, B, ks, (unsigned char *)workspace);
-    }
+    });
 }
 
 } // namespace smart

@@ -246,18 +246,10 @@ void launch_quantiles(long N, long R, const double *sim, long ld, const double *
         p.q[k] = k < K ? probs[k] : 0.0;
     const dim3 grid((unsigned)R);
     if (sort) {
-        if (N <= 1024)
-            hipLaunchKernelGGL((smart_quantiles_sort<1024, 512>), grid, dim3(512), 0, s, (int)N, R, sim, ld, weights, p, K,
-                               out);
-        else if (N <= 2048)
-            hipLaunchKernelGGL((smart_quantiles_sort<2048, 1024>), grid, dim3(1024), 0, s, (int)N, R, sim, ld, weights, p,
-                               K, out);
-        else if (N <= 4096)
-            hipLaunchKernelGGL((smart_quantiles_sort<4096, 1024>), grid, dim3(1024), 0, s, (int)N, R, sim, ld, weights, p,
-                               K, out);
-        else
-            hipLaunchKernelGGL((smart_quantiles_sort<(int)kSortCapacity, 1024>), grid, dim3(1024), 0, s, (int)N, R, sim,
-                               ld, weights, p, K, out);
+        sort_instance<(int)kSortCapacity>(N, [&](auto cap, auto threads) {
+            hipLaunchKernelGGL((smart_quantiles_sort<cap(), threads()>), grid, dim3(threads()), 0, s, (int)N, R, sim, ld,
+                               weights, p, K, out);
+        });
     } else if (K <= 4) {
         hipLaunchKernelGGL((smart_quantiles_select<4>), grid, dim3(select_threads(4)), 0, s, N, R, sim, ld, weights, p, K, out);
     } else if (K <= 8) {

@@ -8,7 +8,6 @@ import numpy as np
 
 from .montecarlo import MonteCarlo
 from .selection import condition_mask, check_shapes, SecondStage
-from .. import distributed as sdist
 from ..verification import EnsembleVerification
 
 
@@ -113,7 +112,7 @@ class GLUE(SecondStage, MonteCarlo):
                     containment = float(inside.sum()) / float(there.sum())
             bounds = on_device.cpu().numpy()
         path = None
-        if write and sdist.rank_world()[0] == 0:
+        if self._writes(write):
             path = self._side_file('.bounds')
             with open(path, 'w', newline='', encoding='utf8') as f:
                 w = writer(f, delimiter=',')
@@ -142,7 +141,7 @@ class GLUE(SecondStage, MonteCarlo):
             out, obs = self._launch_stored()
             scores = engine.ensemble_scores(out.discharge_report_major, obs, weights).cpu().numpy()
         path = None
-        if write and sdist.rank_world()[0] == 0:
+        if self._writes(write):
             path = self._side_file('.verification')
             with open(path, 'w', newline='', encoding='utf8') as f:
                 w = writer(f, delimiter=',')

@@ -22,7 +22,7 @@ from ..objfunctions import groundwater_constraint
 from .. import distributed as sdist
 from ..engine import SmartEngineError
 from .database import database_for
-from .selection import append_float32_rows
+from .selection import write_float32_table
 
 OBJ_FN_NAMES = ['NSE', 'KGE', 'KGEc', 'KGEa', 'KGEb', 'PBias', 'RMSE']      # montecarlo.py:71-74; 'GW' is appended
                                                                              # when the settings hold a gw_constraint
@@ -95,6 +95,10 @@ class MonteCarlo(object):
     def device_sample(self):
         return self._device_sample
 
+    def _launch_rows(self):
+        """The rows to launch: the device copy where the sample was drawn or selected there, else the host matrix."""
+        return self._device_sample if self._device_sample is not None else self._sample
+
     @property
     def p_map(self):
         """parameter tuple -> row index (lhs.py:117); built on first use (a dict of 1e6 tuples is not free)."""
@@ -136,7 +140,7 @@ class MonteCarlo(object):
             sdist.barrier()
             return
         lo, hi = sdist.shard_bounds(n, world, rank)
-        rows = self._device_sample if self._device_sample is not None else self._sample
+        rows = self._launch_rows()
         # one rank's launch failing -- a status word its repeated launch could not clear, a HIP out-of-memory at
         # save_sim=True, any other exception (round 5 caught SmartEngineError only: advisor) -- must not leave its peers
         # waiting in the gather below: the outcome is agreed over the ranks first, and every rank raises if any did (a
@@ -205,9 +209,13 @@ class MonteCarlo(object):
     def _launch_stored(self):
         """One launch over the sample with the [R, N] discharge matrix kept on the device -> (the launch's result, the
         observations it has left on the device, or None)"""
-        rows = self._device_sample if self._device_sample is not None else self._sample
-        out = self.model.simulate_ensemble(rows, save_discharge=True, math_mode=self.math_mode)
+        out = self.model.simulate_ensemble(self._launch_rows(), save_discharge=True, math_mode=self.math_mode)
         return out, self.model._device_cache[2]
+
+    @staticmethod
+    def _writes(write):
+        """Whether this process writes the side file of a call: write=True, and under torch.distributed rank 0 alone."""
+        return write and sdist.rank_world()[0] == 0
 
     def _side_file(self, suffix):
         """`<out>/<catchment>.SMART.<func><suffix>`: beside the sampling database, whatever its format."""
@@ -240,7 +248,7 @@ class MonteCarlo(object):
                                                            transform=transform, eps=eps)
             values = on_device.cpu().numpy()
         path = None
-        if write and sdist.rank_world()[0] == 0:
+        if self._writes(write):
             path = self.windows_file
             _write_windows_file(path, labels, transform, values)
         return swin.WindowObjectives(labels, transform, float(eps), values, on_device, path)
@@ -286,7 +294,7 @@ class MonteCarlo(object):
             curves, values = quant.cpu().numpy(), on_device.cpu().numpy()
         observed = swin.observed_duration(self.model.nd_flow, ids, W, q)
         path = None
-        if write and sdist.rank_world()[0] == 0:
+        if self._writes(write):
             path = self.fdc_file
             _write_fdc_file(path, exceedance, labels, transform, curves, values)
         return swin.FlowDuration(exceedance, labels, curves, observed, transform, float(eps), segment, values, on_device,
@@ -340,7 +348,7 @@ class MonteCarlo(object):
             observed = engine.signatures(obs.reshape(-1, 1), obs=obs, windows=ids, n_windows=W, alpha=alpha,
                                          thresholds=thresholds).cpu().numpy()[:, :, 0]
         path = None
-        if write and sdist.rank_world()[0] == 0:
+        if self._writes(write):
             path = self.signatures_file
             _write_signatures_file(path, labels, values)
         return swin.Signatures(labels, alpha, thresholds, values, on_device, observed, path)
@@ -400,7 +408,7 @@ class MonteCarlo(object):
             mean, se_boot, quant = stats[:, 0], stats[:, 1], stats[:, 2:]
             se_jack = swin.jackknife_factor(E) * j.stats[:, 1].cpu().numpy()
         path = None
-        if write and sdist.rank_world()[0] == 0:
+        if self._writes(write):
             path = self.uncertainty_file
             _write_uncertainty_file(path, probs, point, se_boot, se_jack, quant)
         return swin.ScoreUncertainty(labels, eligible, min_steps, transform, float(eps), probs, point, mean, se_boot, quant,
@@ -444,8 +452,7 @@ class MonteCarlo(object):
             shares = np.full((R, P, bins), np.nan)
             cut, retained, count = np.full(R, np.nan), np.zeros(R, dtype=np.int32), np.zeros(R, dtype=np.int32)
         else:
-            rows = self._device_sample if self._device_sample is not None else self._sample
-            cat = ident.bin_table(rows, ident._ranges(ranges, names), bins)
+            cat = ident.bin_table(self._launch_rows(), ident._ranges(ranges, names), bins)
             out, obs = self._launch_stored()
             res = engine.dynamic_identifiability(out.discharge_report_major, obs, cat, bins, half_width, fraction=fraction,
                                                  min_valid=min_valid, support=support)
@@ -455,7 +462,7 @@ class MonteCarlo(object):
         result = ident.DynamicIdentifiability(stamps, names, ranges, shares, cut, retained, count, level=level,
                                               half_width=half_width, fraction=float(fraction), support=support,
                                               min_valid=int(min_valid), device_shares=on_device)
-        if write and sdist.rank_world()[0] == 0:
+        if self._writes(write):
             result.file = self.dynia_file
             ident.write_file(result.file, stamps, names, result.information, result.limits)
         return result
@@ -514,8 +521,7 @@ class MonteCarlo(object):
             counts = np.zeros((P + dummies, bins), dtype=np.int32)
             table = np.empty((P + dummies, 0), dtype=np.uint8)
         else:
-            rows = self._device_sample if self._device_sample is not None else self._sample
-            cat = ident.bin_table(rows, ident._ranges(ranges, names), bins)
+            cat = ident.bin_table(self._launch_rows(), ident._ranges(ranges, names), bins)
             extra = pawn.dummy_table(n, bins, dummies, seed)
             if ident._is_tensor(cat):
                 import torch
@@ -532,7 +538,7 @@ class MonteCarlo(object):
             table = cat.cpu().numpy() if ident._is_tensor(cat) else cat
         result = pawn.PawnSensitivity(stamps, names, ks, counts, statistic=statistic, min_count=min_count,
                                       categories=table, device_ks=on_device)
-        if write and sdist.rank_world()[0] == 0:
+        if self._writes(write):
             result.file = self.pawn_file
             pawn.write_file(result.file, stamps, names, result.index, result.dummy)
         return result
@@ -546,9 +552,8 @@ class MonteCarlo(object):
             scores, gw = self.device_obj_fns, self.device_gw
         else:
             self._check_observations()
-            rows = self._device_sample if self._device_sample is not None else self._sample
-            out = self.model.simulate_ensemble(rows, objective_functions=True, gw_constraint=self.constraints['gw'],
-                                               math_mode=self.math_mode)
+            out = self.model.simulate_ensemble(self._launch_rows(), objective_functions=True,
+                                               gw_constraint=self.constraints['gw'], math_mode=self.math_mode)
             scores, gw = out.objfn[:n], out.gw[:n]
         return torch.cat([scores[:, :len(OBJ_FN_NAMES)], gw.unsqueeze(1)], dim=1).t().contiguous()
 
@@ -602,24 +607,16 @@ def _write_windows_file(path, labels, transform, values):
     """values [W, N, 7] -> header line + one line per sample, window by window (the sampling database's float32
     '%.6e', formatted by the library)."""
     from .. import windows as swin
-    with open(path, 'w', newline='', encoding='utf8') as f:
-        f.write(swin.header_line(labels, transform))
     W, n, k = values.shape
-    if n == 0:
-        return
-    append_float32_rows(path, np.ascontiguousarray(np.transpose(values, (1, 0, 2)).reshape(n, W * k).astype(np.float32)))
+    write_float32_table(path, swin.header_line(labels, transform), np.transpose(values, (1, 0, 2)).reshape(n, W * k))
 
 
 def _write_signatures_file(path, labels, values):
     """values [W, 12, N] -> header line + one line per sample, window by window (the sampling database's float32
     '%.6e', formatted by the library)."""
     from .. import windows as swin
-    with open(path, 'w', newline='', encoding='utf8') as f:
-        f.write(swin.signatures_header_line(labels))
     W, k, n = values.shape
-    if n == 0:
-        return
-    append_float32_rows(path, np.ascontiguousarray(np.transpose(values, (2, 0, 1)).reshape(n, W * k).astype(np.float32)))
+    write_float32_table(path, swin.signatures_header_line(labels), np.transpose(values, (2, 0, 1)).reshape(n, W * k))
 
 
 def _write_uncertainty_file(path, probs, point, se_boot, se_jack, quant):
@@ -627,25 +624,17 @@ def _write_uncertainty_file(path, probs, point, se_boot, se_jack, quant):
     the point value, its bootstrap and jackknife standard errors, the K quantiles (the sampling database's float32
     '%.6e', formatted by the library)."""
     from .. import windows as swin
-    with open(path, 'w', newline='', encoding='utf8') as f:
-        f.write(swin.uncertainty_header_line(probs))
     n, k = point.shape
-    if n == 0:
-        return
     table = np.concatenate([point[:, :, None], se_boot.T[:, :, None], se_jack.T[:, :, None],
                             np.transpose(quant, (2, 0, 1))], axis=2).reshape(n, k * (3 + quant.shape[1]))
-    append_float32_rows(path, np.ascontiguousarray(table.astype(np.float32)))
+    write_float32_table(path, swin.uncertainty_header_line(probs), table)
 
 
 def _write_fdc_file(path, exceedance, labels, transform, curves, values):
     """curves [W, K, N] and values [W, N, 7] -> header line + one line per sample: the K flows of every window, then
     the seven objective functions of every window (the sampling database's float32 '%.6e', formatted by the library)."""
     from .. import windows as swin
-    with open(path, 'w', newline='', encoding='utf8') as f:
-        f.write(swin.fdc_header_line(exceedance, labels, transform))
     W, K, n = curves.shape
-    if n == 0:
-        return
     table = np.concatenate([np.transpose(curves, (2, 0, 1)).reshape(n, W * K),
                             np.transpose(values, (1, 0, 2)).reshape(n, W * values.shape[2])], axis=1)
-    append_float32_rows(path, np.ascontiguousarray(table.astype(np.float32)))
+    write_float32_table(path, swin.fdc_header_line(exceedance, labels, transform), table)

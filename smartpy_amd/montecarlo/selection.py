@@ -120,6 +120,33 @@ def append_float32_rows(path, table):
                                                table.shape[0], table.shape[1], 0))
 
 
+def write_float32_table(path, header, table, labels=None):
+    """The side file of an analysis: the header line, then the rows of the [n, k] table as float32, as a sampling database
+    prints them -- nothing after the header for an empty table.  With `labels`, one per row, every line begins `label,`
+    (the library formats the rows into a file of its own beside `path`, which is then removed)."""
+    table = np.ascontiguousarray(np.asarray(table).astype(np.float32))
+    with open(path, 'w', newline='', encoding='utf8') as f:
+        f.write(header)
+    if table.shape[0] == 0:
+        return
+    if labels is None:
+        append_float32_rows(path, table)
+        return
+    raw = path + '.rows'
+    if os.path.exists(raw):
+        os.remove(raw)
+    try:
+        append_float32_rows(raw, table)
+        with open(raw, encoding='utf8') as f:
+            lines = f.read().split('\n')[:-1]
+    finally:
+        if os.path.exists(raw):
+            os.remove(raw)
+    with open(path, 'a', newline='', encoding='utf8') as f:
+        for label, line in zip(labels, lines):
+            f.write(label + ',' + line + '\n')
+
+
 def as_stored(matrix):
     """What a float64 matrix becomes on its way through a sampling database: cast to float32, printed '%.6e', parsed
     back to float32 (montecarlo.py:225-231, :262) -- 7 significant digits, not a float32 round trip.  Done with the

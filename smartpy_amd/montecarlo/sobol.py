@@ -7,14 +7,12 @@ engine.sobol_indices turns the values of the rows -- objective functions, the gr
 report step, anything the caller computed per row -- into first-order (Saltelli 2010) and total (Jansen) indices with
 bootstrap confidence intervals, on the GPU.
 """
-import os
 from statistics import NormalDist
 
 import numpy as np
 
 from .montecarlo import MonteCarlo
-from .selection import append_float32_rows
-from .. import distributed as sdist
+from .selection import write_float32_table
 from ..sampling import saltelli_design
 
 INDICES_HEADER = 'target,parameter,S1,S1_conf,ST,ST_conf\n'
@@ -127,7 +125,7 @@ class Sobol(MonteCarlo):
         names, values = self._target_rows(targets)
         res, S1, ST, S1_conf, ST_conf, mean, variance = self._analyse(values, resamples, conf_level, seed)
         path = None
-        if write and sdist.rank_world()[0] == 0:
+        if self._writes(write):
             path = self.indices_file
             _write_indices_file(path, names, self.vary, S1, S1_conf, ST, ST_conf)
         return SobolIndices(self.vary, names, S1, ST, S1_conf, ST_conf, mean, variance, float(conf_level), int(resamples),
@@ -145,7 +143,7 @@ class Sobol(MonteCarlo):
                                                                       seed)
         stamps = self.model.timeseries_report[1:]
         path = None
-        if write and sdist.rank_world()[0] == 0:
+        if self._writes(write):
             path = self.series_file
             _write_series_file(path, stamps, self.vary, S1, ST)
         return SobolSeries(self.vary, stamps, S1, ST, S1_conf, ST_conf, mean, variance, float(conf_level), int(resamples),
@@ -166,38 +164,16 @@ def series_header_line(parameters):
     return ','.join(['DateTime'] + ['S1_%s' % p for p in parameters] + ['ST_%s' % p for p in parameters]) + '\n'
 
 
-def _write_labelled_rows(path, header, labels, table):
-    """header line, then `label,` + the row of the table as the sampling database prints it (float32 '%.6e', formatted by
-    the library into a file of its own beside `path`, which is then removed)."""
-    table = np.ascontiguousarray(np.asarray(table, dtype=np.float64).astype(np.float32))
-    lines = []
-    if table.shape[0]:
-        raw = path + '.rows'
-        if os.path.exists(raw):
-            os.remove(raw)
-        try:
-            append_float32_rows(raw, table)
-            with open(raw, encoding='utf8') as f:
-                lines = f.read().split('\n')[:-1]
-        finally:
-            if os.path.exists(raw):
-                os.remove(raw)
-    with open(path, 'w', newline='', encoding='utf8') as f:
-        f.write(header)
-        for label, line in zip(labels, lines):
-            f.write(label + ',' + line + '\n')
-
-
 def _write_indices_file(path, targets, parameters, S1, S1_conf, ST, ST_conf):
     """[M, k] arrays -> one line per (target, parameter); confidence half-widths that were not asked for are NaN."""
     M, k = S1.shape
     nan = np.full((M, k), np.nan)
     table = np.stack([S1, nan if S1_conf is None else S1_conf, ST, nan if ST_conf is None else ST_conf], axis=2)
     labels = ['%s,%s' % (t, p) for t in targets for p in parameters]
-    _write_labelled_rows(path, INDICES_HEADER, labels, table.reshape(M * k, 4))
+    write_float32_table(path, INDICES_HEADER, table.reshape(M * k, 4), labels)
 
 
 def _write_series_file(path, stamps, parameters, S1, ST):
     """S1, ST [R, k] -> one line per report step: its stamp, the k first-order and the k total indices."""
     labels = [t.strftime('%Y-%m-%d %H:%M:%S') for t in stamps]
-    _write_labelled_rows(path, series_header_line(parameters), labels, np.concatenate([S1, ST], axis=1))
+    write_float32_table(path, series_header_line(parameters), np.concatenate([S1, ST], axis=1), labels)

@@ -1,12 +1,15 @@
-"""The refusals of the five matrix-analysis entries of the C ABI (smart_objfn_hip, smart_weighted_quantiles_hip,
-smart_objfn_windows_hip, smart_flow_duration_hip, smart_sobol_indices_hip) and of their capacity / workspace entries:
+"""The refusals of seven matrix-analysis entries of the C ABI (smart_objfn_hip, smart_weighted_quantiles_hip,
+smart_objfn_windows_hip, smart_flow_duration_hip, smart_sobol_indices_hip, smart_signatures_hip,
+smart_objfn_bootstrap_hip) and of their capacity / workspace entries (the entries that came later hold theirs in their own
+host tests):
 return code and smart_last_error() text of every refusal branch, as literals.  Validation comes before the device, so
 none of these calls needs one, and none dereferences a device pointer (FAKE is never read; the probability lists, which
 the host reads, are real arrays).
 
 A row is (entry, what differs from the entry's valid call, return code, text).  Rows that break two rules at once pin the
 precedence: which refusal wins.  The pairs were recorded from the library as it stood before the entries moved into a
-unit of their own; they are the contract the move had to keep, byte for byte."""
+unit of their own -- those of the signatures and of the bootstrap before the size rules of the entries were folded into
+one form; they are the contract both moves had to keep, byte for byte."""
 import ctypes
 
 import pytest
@@ -18,8 +21,9 @@ FAKE = 0x1000                       # a non-NULL address that no refusal path re
 NAN, INF = float('nan'), float('inf')
 TWO31 = 2 ** 31
 
-O, Q, W, F, S = ('smart_objfn_hip', 'smart_weighted_quantiles_hip', 'smart_objfn_windows_hip',
-                 'smart_flow_duration_hip', 'smart_sobol_indices_hip')
+O, Q, W, F, S, G, B = ('smart_objfn_hip', 'smart_weighted_quantiles_hip', 'smart_objfn_windows_hip',
+                       'smart_flow_duration_hip', 'smart_sobol_indices_hip', 'smart_signatures_hip',
+                       'smart_objfn_bootstrap_hip')
 
 
 def doubles(*values):
@@ -40,10 +44,18 @@ VALID = {
     'smart_sobol_indices_hip': dict(n_base=8, n_params=2, n_rows=3, y=FAKE, ld=32, s1=FAKE, st=FAKE, moments=FAKE,
                                     counts=None, n_resamples=0, s1_std=None, st_std=None, workspace=None,
                                     workspace_bytes=0, stream=None),
+    'smart_signatures_hip': dict(n_samples=4, n_reports=3, sim=FAKE, ld=4, obs=FAKE, window=FAKE, n_windows=2, alpha=0.925,
+                                 pulse=FAKE, sig=FAKE, stream=None),
+    'smart_objfn_bootstrap_hip': dict(n_samples=4, n_reports=3, sim=FAKE, ld=4, obs=FAKE, window=FAKE, n_windows=2,
+                                      transform=0, eps=0.0, counts=FAKE, n_resamples=4, probs=(0.05, 0.5), n_probs=2,
+                                      point=FAKE, stats=FAKE, replicates=None, workspace=FAKE, workspace_bytes=1 << 30,
+                                      stream=None),
     'smart_flow_duration_workspace_bytes': dict(n_reports=10, n_windows=2, with_objfn=1),
     'smart_sobol_workspace_bytes': dict(n_base=8, n_params=2, n_rows=3, n_resamples=4),
+    'smart_bootstrap_workspace_bytes': dict(n_samples=4, n_windows=2, n_resamples=4, with_replicates=0),
     'smart_quantiles_sort_capacity': {}, 'smart_objfn_max_windows': {}, 'smart_flow_duration_sort_capacity': {},
-    'smart_sobol_max_resamples': {}, 'smart_sobol_lds_capacity': {},
+    'smart_sobol_max_resamples': {}, 'smart_sobol_lds_capacity': {}, 'smart_bootstrap_max_windows': {},
+    'smart_bootstrap_max_resamples': {},
 }
 FDC_OBJFN = dict(objfn=FAKE, workspace=FAKE, workspace_bytes=1 << 20)      # the valid call with the curve's scores
 SOBOL_BOOT = dict(n_resamples=4, counts=FAKE, s1_std=FAKE, st_std=FAKE)    # ... with the bootstrap
@@ -226,6 +238,97 @@ CASES = [
     (S, dict(n_resamples=-1, ld=31), E_SIZE, 'smart_sobol_indices_hip: n_resamples -1 must be in 0 .. 512'),
     (S, dict(ld=31, workspace_bytes=-1), E_SIZE,
      'smart_sobol_indices_hip: ld 31 is less than n_base * (n_params + 2) = 32'),
+    # ---- smart_signatures_hip
+    (G, dict(sim=None), E_NULL, 'smart_signatures_hip: sim and sig are required (sim is NULL)'),
+    (G, dict(sig=None), E_NULL, 'smart_signatures_hip: sim and sig are required (sig is NULL)'),
+    (G, dict(sim=None, sig=None), E_NULL, 'smart_signatures_hip: sim and sig are required (sim is NULL)'),
+    (G, dict(sig=None, n_samples=0), E_NULL, 'smart_signatures_hip: sim and sig are required (sig is NULL)'),
+    (G, dict(n_samples=0), E_SIZE, 'smart_signatures_hip: need n_samples, n_reports, n_windows >= 1 (got 0, 3, 2)'),
+    (G, dict(n_samples=-2), E_SIZE, 'smart_signatures_hip: need n_samples, n_reports, n_windows >= 1 (got -2, 3, 2)'),
+    (G, dict(n_reports=0), E_SIZE, 'smart_signatures_hip: need n_samples, n_reports, n_windows >= 1 (got 4, 0, 2)'),
+    (G, dict(n_windows=0), E_SIZE, 'smart_signatures_hip: need n_samples, n_reports, n_windows >= 1 (got 4, 3, 0)'),
+    (G, dict(ld=3), E_SIZE, 'smart_signatures_hip: ld 3 is less than n_samples 4'),
+    (G, dict(n_reports=TWO31), E_SIZE,
+     'smart_signatures_hip: n_reports 2147483648 is more than one launch takes (2^31 - 1)'),
+    (G, dict(n_windows=1025), E_SIZE, 'smart_signatures_hip: n_windows 1025, at most 1024 per call'),
+    (G, dict(window=None), E_SIZE, 'smart_signatures_hip: n_windows 2 without a window array (NULL is one window)'),
+    (G, dict(alpha=0.0), E_SIZE, 'smart_signatures_hip: alpha 0 must lie inside (0, 1)'),
+    (G, dict(alpha=1.0), E_SIZE, 'smart_signatures_hip: alpha 1 must lie inside (0, 1)'),
+    (G, dict(alpha=NAN), E_SIZE, 'smart_signatures_hip: alpha nan must lie inside (0, 1)'),
+    (G, dict(alpha=INF), E_SIZE, 'smart_signatures_hip: alpha inf must lie inside (0, 1)'),
+    (G, dict(alpha=-0.5), E_SIZE, 'smart_signatures_hip: alpha -0.5 must lie inside (0, 1)'),
+    (G, dict(n_windows=0, ld=3), E_SIZE,
+     'smart_signatures_hip: need n_samples, n_reports, n_windows >= 1 (got 4, 3, 0)'),
+    (G, dict(ld=3, n_reports=TWO31), E_SIZE, 'smart_signatures_hip: ld 3 is less than n_samples 4'),
+    (G, dict(n_reports=TWO31, n_windows=1025), E_SIZE,
+     'smart_signatures_hip: n_reports 2147483648 is more than one launch takes (2^31 - 1)'),
+    (G, dict(n_windows=1025, window=None), E_SIZE, 'smart_signatures_hip: n_windows 1025, at most 1024 per call'),
+    (G, dict(window=None, alpha=2.0), E_SIZE,
+     'smart_signatures_hip: n_windows 2 without a window array (NULL is one window)'),
+    # ---- smart_objfn_bootstrap_hip (without replicates neither n_probs nor the probabilities are looked at)
+    (B, dict(sim=None), E_NULL, 'smart_objfn_bootstrap_hip: sim, obs, window and point are required (sim is NULL)'),
+    (B, dict(obs=None), E_NULL, 'smart_objfn_bootstrap_hip: sim, obs, window and point are required (obs is NULL)'),
+    (B, dict(window=None), E_NULL,
+     'smart_objfn_bootstrap_hip: sim, obs, window and point are required (window is NULL)'),
+    (B, dict(point=None), E_NULL, 'smart_objfn_bootstrap_hip: sim, obs, window and point are required (point is NULL)'),
+    (B, dict(counts=None), E_NULL,
+     'smart_objfn_bootstrap_hip: n_resamples 4 needs counts, probs and stats (counts is NULL)'),
+    (B, dict(probs=None), E_NULL,
+     'smart_objfn_bootstrap_hip: n_resamples 4 needs counts, probs and stats (probs is NULL)'),
+    (B, dict(stats=None), E_NULL,
+     'smart_objfn_bootstrap_hip: n_resamples 4 needs counts, probs and stats (stats is NULL)'),
+    (B, dict(obs=None, point=None), E_NULL,
+     'smart_objfn_bootstrap_hip: sim, obs, window and point are required (obs is NULL)'),
+    (B, dict(point=None, counts=None), E_NULL,
+     'smart_objfn_bootstrap_hip: sim, obs, window and point are required (point is NULL)'),
+    (B, dict(counts=None, stats=None), E_NULL,
+     'smart_objfn_bootstrap_hip: n_resamples 4 needs counts, probs and stats (counts is NULL)'),
+    (B, dict(stats=None, n_samples=0), E_NULL,
+     'smart_objfn_bootstrap_hip: n_resamples 4 needs counts, probs and stats (stats is NULL)'),
+    (B, dict(n_samples=0), E_SIZE, 'smart_objfn_bootstrap_hip: n_samples 0 must be in 1 .. 2^31 - 1'),
+    (B, dict(n_samples=TWO31, ld=TWO31), E_SIZE,
+     'smart_objfn_bootstrap_hip: n_samples 2147483648 must be in 1 .. 2^31 - 1'),
+    (B, dict(n_windows=0), E_SIZE, 'smart_objfn_bootstrap_hip: n_windows 0 must be in 1 .. 64'),
+    (B, dict(n_windows=65), E_SIZE, 'smart_objfn_bootstrap_hip: n_windows 65 must be in 1 .. 64'),
+    (B, dict(n_resamples=-1), E_SIZE, 'smart_objfn_bootstrap_hip: n_resamples -1 must be in 0 .. 4096'),
+    (B, dict(n_resamples=4097), E_SIZE, 'smart_objfn_bootstrap_hip: n_resamples 4097 must be in 0 .. 4096'),
+    (B, dict(n_reports=0), E_SIZE, 'smart_objfn_bootstrap_hip: need n_reports >= 1 (got 0)'),
+    (B, dict(n_reports=-5), E_SIZE, 'smart_objfn_bootstrap_hip: need n_reports >= 1 (got -5)'),
+    (B, dict(ld=3), E_SIZE, 'smart_objfn_bootstrap_hip: ld 3 is less than n_samples 4'),
+    (B, dict(n_reports=TWO31), E_SIZE,
+     'smart_objfn_bootstrap_hip: n_reports 2147483648 is more than one launch takes (2^31 - 1)'),
+    (B, dict(n_probs=0), E_SIZE, 'smart_objfn_bootstrap_hip: n_probs 0 must be in 1 .. 16'),
+    (B, dict(n_probs=17), E_SIZE, 'smart_objfn_bootstrap_hip: n_probs 17 must be in 1 .. 16'),
+    (B, dict(probs=(0.0, 0.5)), E_SIZE, 'smart_objfn_bootstrap_hip: probability 0 is 0, outside (0, 1]'),
+    (B, dict(probs=(0.5, 1.5)), E_SIZE, 'smart_objfn_bootstrap_hip: probability 1 is 1.5, outside (0, 1]'),
+    (B, dict(probs=(0.5, NAN)), E_SIZE, 'smart_objfn_bootstrap_hip: probability 1 is nan, outside (0, 1]'),
+    (B, dict(eps=-1.0), E_SIZE, 'smart_objfn_bootstrap_hip: eps -1 must be finite and >= 0'),
+    (B, dict(eps=NAN), E_SIZE, 'smart_objfn_bootstrap_hip: eps nan must be finite and >= 0'),
+    (B, dict(eps=INF), E_SIZE, 'smart_objfn_bootstrap_hip: eps inf must be finite and >= 0'),
+    (B, dict(transform=4), E_MODE, "smart_objfn_bootstrap_hip: transform '4' unknown."),
+    (B, dict(transform=-1), E_MODE, "smart_objfn_bootstrap_hip: transform '-1' unknown."),
+    (B, dict(workspace=None), E_NULL,
+     'smart_objfn_bootstrap_hip: a workspace of 5376 bytes is needed (workspace is NULL)'),
+    (B, dict(workspace_bytes=255), E_SIZE, 'smart_objfn_bootstrap_hip: workspace_bytes 255, need 5376'),
+    (B, dict(workspace=None, workspace_bytes=0), E_NULL,
+     'smart_objfn_bootstrap_hip: a workspace of 5376 bytes is needed (workspace is NULL)'),
+    (B, dict(replicates=FAKE, workspace_bytes=255), E_SIZE,
+     'smart_objfn_bootstrap_hip: workspace_bytes 255, need 5376'),
+    (B, dict(n_samples=0, n_windows=0), E_SIZE, 'smart_objfn_bootstrap_hip: n_samples 0 must be in 1 .. 2^31 - 1'),
+    (B, dict(n_windows=0, n_resamples=-1), E_SIZE, 'smart_objfn_bootstrap_hip: n_windows 0 must be in 1 .. 64'),
+    (B, dict(n_resamples=-1, n_reports=0), E_SIZE, 'smart_objfn_bootstrap_hip: n_resamples -1 must be in 0 .. 4096'),
+    (B, dict(n_reports=0, ld=3), E_SIZE, 'smart_objfn_bootstrap_hip: need n_reports >= 1 (got 0)'),
+    (B, dict(ld=3, n_reports=TWO31), E_SIZE, 'smart_objfn_bootstrap_hip: ld 3 is less than n_samples 4'),
+    (B, dict(n_reports=TWO31, n_probs=0), E_SIZE,
+     'smart_objfn_bootstrap_hip: n_reports 2147483648 is more than one launch takes (2^31 - 1)'),
+    (B, dict(n_probs=17, probs=(2.0, 0.5)), E_SIZE, 'smart_objfn_bootstrap_hip: n_probs 17 must be in 1 .. 16'),
+    (B, dict(probs=(2.0, 0.5), eps=-1.0), E_SIZE, 'smart_objfn_bootstrap_hip: probability 0 is 2, outside (0, 1]'),
+    (B, dict(eps=-1.0, transform=4), E_SIZE, 'smart_objfn_bootstrap_hip: eps -1 must be finite and >= 0'),
+    (B, dict(transform=4, workspace=None), E_MODE, "smart_objfn_bootstrap_hip: transform '4' unknown."),
+    (B, dict(n_resamples=0, counts=None, probs=None, stats=None, n_probs=0, eps=-1.0), E_SIZE,
+     'smart_objfn_bootstrap_hip: eps -1 must be finite and >= 0'),
+    (B, dict(n_resamples=0, n_probs=17, probs=(2.0, 0.5), transform=9), E_MODE,
+     "smart_objfn_bootstrap_hip: transform '9' unknown."),
     # ---- the capacity and workspace entries: a size, or SMART_E_SIZE where the sizes are refused
     ('smart_flow_duration_workspace_bytes', {}, 512, None),
     ('smart_flow_duration_workspace_bytes', dict(with_objfn=0), 0, None),
@@ -237,6 +340,17 @@ CASES = [
     ('smart_sobol_workspace_bytes', dict(n_params=17), E_SIZE, None),
     ('smart_sobol_workspace_bytes', dict(n_rows=TWO31), E_SIZE, None),
     ('smart_sobol_workspace_bytes', dict(n_resamples=513), E_SIZE, None),
+    ('smart_bootstrap_workspace_bytes', {}, 5376, None),
+    ('smart_bootstrap_workspace_bytes', dict(n_samples=0), E_SIZE, None),
+    ('smart_bootstrap_workspace_bytes', dict(n_samples=TWO31), E_SIZE, None),
+    ('smart_bootstrap_workspace_bytes', dict(n_windows=0), E_SIZE, None),
+    ('smart_bootstrap_workspace_bytes', dict(n_windows=65), E_SIZE, None),
+    ('smart_bootstrap_workspace_bytes', dict(n_resamples=-1), E_SIZE, None),
+    ('smart_bootstrap_workspace_bytes', dict(n_resamples=4097), E_SIZE, None),
+    ('smart_bootstrap_workspace_bytes', dict(n_resamples=0), 768, None),
+    ('smart_bootstrap_workspace_bytes', dict(with_replicates=1), 5376, None),
+    ('smart_bootstrap_max_windows', {}, 64, None),
+    ('smart_bootstrap_max_resamples', {}, 4096, None),
     ('smart_quantiles_sort_capacity', {}, 8192, None),
     ('smart_objfn_max_windows', {}, 1024, None),
     ('smart_flow_duration_sort_capacity', {}, 16384, None),

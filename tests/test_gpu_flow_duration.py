@@ -281,6 +281,19 @@ def test_engine_surface():
         engine.flow_duration(sim, probs, obs, bad, n_windows=3)
 
 
+def test_a_matrix_without_a_report_step_is_refused_in_the_entrys_own_words():
+    """smart_flow_duration_workspace_bytes refuses n_reports = 0, and so does the entry: the sentence is the entry's, not
+    whatever the thread's last failure left -- and it is about the size, though torch gives such a matrix no address."""
+    import torch
+    from smartpy_amd import _lib, engine
+    assert _lib.lib().smart_objfn_hip(1, 1, None, 1, None, None, 0.0, None, None) == -1      # leaves another entry's text
+    sim = torch.empty((0, 4), dtype=torch.float64, device='cuda')
+    with pytest.raises(engine.SmartEngineError) as e:
+        engine.flow_duration(sim, 0.5)
+    assert e.value.code == E_SIZE
+    assert str(e.value).startswith('smart_flow_duration_hip: need n_samples, n_reports'), str(e.value)
+
+
 def _settings(root, name, start, end, warm):
     with open(os.path.join(root, 'in', 'Catchment', name), 'w') as f:
         f.write('ARGUMENT,VALUE\ncatchment_area_km2,175.46\ngauged_area_km2,175.97\nstart_datetime,%s 09:00:00\n'
