@@ -753,6 +753,79 @@ int64_t smart_pawn_workspace_bytes(int64_t n_samples, int64_t n_rows, int32_t me
 int64_t smart_pawn_lds_capacity(void);
 
 /*
+ * One generation of DE-MCz -- differential evolution Markov chain with sampling from the past (ter Braak & Vrugt 2008,
+ * Stat. Comput. 18), with the subspace crossover of DREAM (Vrugt 2016) and a uniform prior on the box [lo, hi] -- AROUND
+ * the ensemble launch that scores the proposals: N chains in lockstep, d <= SMART_DEMCZ_MAX_DIMS varying parameters.  No
+ * snooker update, no crossover adaptation, no outlier handling.  One call runs the ACCEPT phase (score given), the PROPOSE
+ * phase (propose != 0) or both, in that order, as two small kernels on `stream`, one lane per chain; nothing is read
+ * back, nothing is allocated, no atomics.  The archive size M and the generation g are the caller's to keep.
+ *
+ * Chain i of the call has the number c = chain_offset + i (below 2^32); every per-chain array is indexed by i, the
+ * archive and the draws by c: a call over a part of the chains draws what the call over all of them draws.
+ *
+ * RANDOMNESS is Philox4x32-10 (Salmon et al. 2011), counter-based: the bits depend on (seed, chain, generation) only.
+ *   words(c, g, b) = Philox with counter (c, g, b, 0) and key (seed mod 2^32, seed div 2^32).
+ *   u53(w0, w1) = ((w0 >> 5) 2^26 + (w1 >> 6)) 2^-53.
+ *   mulhi(w, n) = (w n) >> 32 in 64-bit integers.
+ *   Block 0 = (r0, r1, r2, r3): a = mulhi(r0, M); b = mulhi(r1, M - 1), then b += (b >= a); jump = r2 < J; fallback
+ *     dimension = mulhi(r3, d).
+ *   Block 1 = (w0, w1, ., .): the acceptance uniform of generation g, u = u53(w0, w1).  The accept phase reads it for the
+ *     proposals that the propose phase of generation g made.
+ *   Block 2 + j, for dimension j: dimension j is updated iff w0 < C; eps_j = scale_j (2 u53(w1, w2) - 1).
+ *   If no dimension is selected, the fallback dimension alone is.
+ * The host passes J = floor(p_jump 2^32) and C = floor(CR 2^32) as 64-bit integers in [0, 2^32] (jump_threshold,
+ * cr_threshold), scale_j = b* (hi_j - lo_j), and a table gamma[d' - 1] = 2.38 / sqrt(2 d') for d' = 1 .. d; lo, hi, scale,
+ * gamma and columns are HOST arrays of n_dims values (they travel as kernel arguments).
+ *
+ * ACCEPT phase of a call with generation g: the decision on the proposals of generation g - 1.  Per chain: the score
+ * score[i * score_stride] gives the log-density l*:
+ *   SMART_DEMCZ_SCORE_LOGP        l* = score
+ *   SMART_DEMCZ_SCORE_RMSE        l* = -((n_eff / 2) ln(n_obs score^2))     the Gaussian likelihood with sigma integrated out;
+ *                                 the score is read in place, e.g. the RMSE column of the [N][8] objective table, stride 8
+ *   SMART_DEMCZ_SCORE_RMSE_SIGMA  l* = -(n_eff score^2) / (2 sigma^2)        for a fixed sigma
+ * With u of block 1 of generation g - 1: rejected if out[i] is set or l* is NaN, else accepted iff log(u) < l* - logp[i]
+ * (an IEEE compare: a NaN difference rejects).  On acceptance x[i][.] = proposal[i][.], logp[i] = l*, the payload
+ * carry[i][0 .. n_carry) = carry_new[i][.] (n_carry <= SMART_DEMCZ_MAX_CARRY doubles that travel with the chain: its
+ * objective functions, say) and accepted[i] += 1.  g = 1 is the INITIAL POPULATION taking its scores: x stays as the
+ * caller launched it, logp[i] = l* and the payload are taken unconditionally (a NaN too), accepted is not touched, nothing
+ * is drawn.  With append != 0 every chain's state, logp and payload as they are after the decision are written as archive
+ * row M + c (archive[capacity][d], archive_logp[capacity], archive_carry[capacity][n_carry]).
+ *
+ * PROPOSE phase of a call with generation g, from M' >= 2 archive rows -- M' = archive_size, or archive_size +
+ * chain_offset + n_chains where the accept phase of the same call appended (a call over a part of the chains that appends
+ * proposes in a call of its own, once every part has appended).  With gamma = 1 where jump is set, else gamma[d' - 1], d'
+ * the number of updated dimensions, an updated dimension j is
+ *     t = z_a,j - z_b,j;  t = gamma t;  t = t + eps_j;  y = x_j + t        (each operation rounded once, no contraction)
+ * then   if y < lo_j: y = 2 lo_j - y;   if y > hi_j: y = 2 hi_j - y;   y still outside [lo_j, hi_j] (or NaN): the
+ * proposal is `out`.  A dimension that is not updated keeps x_j.  Outputs: proposal[i][0 .. d), out[i] (uint8), and the
+ * launch matrix rows[i][columns[j]] = the proposal's j, or x_j for every j where the proposal is out (the lockstep launch
+ * stays valid); the other columns of rows[N][ld] are the caller's and are not touched.
+ *
+ * Errors (all found before the device is touched; the first offending argument wins): SMART_E_NULL x, logp, proposal, out
+ * or archive missing; SMART_E_SIZE n_chains < 1, a chain number >= 2^32, n_dims outside 1 .. 16, generation outside
+ * 1 .. 2^32 - 1, capacity outside 1 .. 2^31 - 1, archive_size outside 0 .. capacity, n_carry outside 0 .. 16; SMART_E_NULL
+ * neither phase asked for; accept phase: SMART_E_MODE unknown score_kind, SMART_E_SIZE score_stride < 1, n_obs < 1 (RMSE),
+ * n_eff or sigma not finite and > 0 (where read), SMART_E_NULL accepted, carry / carry_new (n_carry > 0), archive_logp /
+ * archive_carry (append) missing, SMART_E_SIZE an append past the capacity -- never a write past the end; SMART_E_NULL
+ * append without the accept phase; propose phase: SMART_E_NULL lo, hi, scale, gamma, rows or columns missing, SMART_E_SIZE
+ * M' < 2 or > capacity, a threshold outside 0 .. 2^32, ld < n_dims, a column outside 0 .. ld - 1 or named twice, bounds
+ * that are not finite or lo > hi; then SMART_E_NO_DEVICE without a HIP device.
+ */
+#define SMART_DEMCZ_MAX_DIMS 16
+#define SMART_DEMCZ_MAX_CARRY 16
+#define SMART_DEMCZ_SCORE_LOGP 0
+#define SMART_DEMCZ_SCORE_RMSE 1
+#define SMART_DEMCZ_SCORE_RMSE_SIGMA 2
+int smart_demcz_step_hip(int64_t n_chains, int64_t chain_offset, int32_t n_dims, uint64_t seed, int64_t generation,
+                         int64_t archive_size, int64_t capacity, double *x, double *logp, double *carry, int32_t *accepted,
+                         double *proposal, uint8_t *out, const double *score, int64_t score_stride, int32_t score_kind,
+                         int64_t n_obs, double n_eff, double sigma, const double *carry_new, int32_t n_carry,
+                         int32_t append, double *archive, double *archive_logp, double *archive_carry, int32_t propose,
+                         const double *lo, const double *hi, const double *scale, const double *gamma,
+                         int64_t jump_threshold, int64_t cr_threshold, double *rows, int64_t ld, const int32_t *columns,
+                         void *stream);
+
+/*
  * Sampling database, CSV flavour -- the rows MonteCarlo.save writes one by one (montecarlo.py:211-231): every value
  * cast to float32 and printed '%.6e', comma separated, one '\n'-terminated line per sample.  HOST pointers, no
  * device involved.  Appends n_rows lines of n_cols values (row-major float32 table: objective functions, parameters,

@@ -41,6 +41,8 @@ DYNIA_MAX_FACTORS, DYNIA_MAX_BINS = 16, 64
 DYNIA_SUPPORTS = {'equal': 0, 'linear': 1}                      # SMART_DYNIA_*
 PAWN_MAX_FACTORS, PAWN_MAX_BINS = 16, 64
 PAWN_METHODS = {'auto': 0, 'lds': 1, 'global': 2}               # SMART_PAWN_*
+DEMCZ_MAX_DIMS, DEMCZ_MAX_CARRY = 16, 16
+DEMCZ_SCORES = {'logp': 0, 'rmse': 1, 'rmse_sigma': 2}          # SMART_DEMCZ_SCORE_*
 
 _dp = ctypes.c_void_p   # device or host address, passed as an integer
 
@@ -125,6 +127,12 @@ SYMBOLS = {
                                          ctypes.c_int32, _dp, _dp, ctypes.c_int32, _dp, ctypes.c_int64, _dp]),
     'smart_pawn_workspace_bytes': (ctypes.c_int64, [ctypes.c_int64, ctypes.c_int64, ctypes.c_int32]),
     'smart_pawn_lds_capacity': (ctypes.c_int64, []),
+    'smart_demcz_step_hip': (ctypes.c_int, [ctypes.c_int64, ctypes.c_int64, ctypes.c_int32, ctypes.c_uint64, ctypes.c_int64,
+                                            ctypes.c_int64, ctypes.c_int64, _dp, _dp, _dp, _dp, _dp, _dp,
+                                            _dp, ctypes.c_int64, ctypes.c_int32, ctypes.c_int64, ctypes.c_double,
+                                            ctypes.c_double, _dp, ctypes.c_int32, ctypes.c_int32, _dp, _dp, _dp,
+                                            ctypes.c_int32, _dp, _dp, _dp, _dp, ctypes.c_int64, ctypes.c_int64, _dp,
+                                            ctypes.c_int64, _dp, _dp]),
     'smart_db_append_rows': (ctypes.c_int, [ctypes.c_char_p, ctypes.POINTER(ctypes.c_float), ctypes.c_int64,
                                             ctypes.c_int64, ctypes.c_int32]),
     'smart_db_parse_rows': (ctypes.c_int64, [ctypes.c_char_p, ctypes.c_int64, ctypes.c_int64,

@@ -59,6 +59,9 @@ UNITS = {
     # PAWN sensitivity (Kolmogorov-Smirnov distances across the samples, per row of a matrix): default flags, NaNs
     # honoured -- a value that is not finite is found by its key, and the integers held in doubles are exact either way
     'smart_pawn.hip': [],
+    # the step of the DE-MCz sampler (proposal, crossover, reflection, Metropolis decision, archive): every operation of
+    # the proposal rounded once -- the numpy statement of the tests is held to it bit for bit
+    'smart_demcz.hip': ['-ffp-contract=off'],
     'smart_capi.hip': [],
     # the C entries of the matrix analyses, and smart_objfn_matrix: the flags smart_capi.hip had it compiled with
     'smart_analysis_capi.hip': [],

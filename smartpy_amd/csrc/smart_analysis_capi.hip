@@ -694,5 +694,94 @@ int64_t smart_pawn_workspace_bytes(int64_t n_samples, int64_t n_rows, int32_t me
 
 int64_t smart_pawn_lds_capacity(void) { return pawn_lds_capacity(); }
 
+// (not an analysis of a matrix, but validated by the same Check: the step of the DE-MCz sampler, smart_demcz.hip)
+int smart_demcz_step_hip(int64_t n_chains, int64_t chain_offset, int32_t n_dims, uint64_t seed, int64_t generation,
+                         int64_t archive_size, int64_t capacity, double *x, double *logp, double *carry, int32_t *accepted,
+                         double *proposal, uint8_t *out, const double *score, int64_t score_stride, int32_t score_kind,
+                         int64_t n_obs, double n_eff, double sigma, const double *carry_new, int32_t n_carry,
+                         int32_t append, double *archive, double *archive_logp, double *archive_carry, int32_t propose,
+                         const double *lo, const double *hi, const double *scale, const double *gamma,
+                         int64_t jump_threshold, int64_t cr_threshold, double *rows, int64_t ld, const int32_t *columns,
+                         void *stream)
+{
+    constexpr long long kTwo32 = 1ll << 32;
+    Check c("smart_demcz_step_hip");
+    c.required({NAMED(x), NAMED(logp), NAMED(proposal), NAMED(out), NAMED(archive)});
+    c.at_least_one({COUNT(n_chains)});
+    c.in_range("chain_offset", chain_offset, 0, kTwo32 - 1);
+    if (c.ok() && n_chains > kTwo32 - chain_offset)
+        c.refuse(SMART_E_SIZE, "chains %lld .. %lld: a chain's number stays below 2^32", (long long)chain_offset,
+                 (long long)chain_offset + (long long)n_chains - 1);
+    c.in_range("n_dims", n_dims, 1, SMART_DEMCZ_MAX_DIMS);
+    c.in_range("generation", generation, 1, kTwo32 - 1);
+    c.in_range("capacity", capacity, 1, kInt32Max);
+    c.in_range("archive_size", archive_size, 0, capacity, " (the capacity)");
+    c.in_range("n_carry", n_carry, 0, SMART_DEMCZ_MAX_CARRY);
+    if (!score && !propose)
+        c.refuse(SMART_E_NULL, "neither phase is asked for (score is NULL and propose is 0)");
+    DemczCall call{};
+    call.n_chains = (long)n_chains, call.chain_offset = (long)chain_offset, call.n_dims = n_dims, call.seed = seed;
+    call.generation = (long)generation, call.archive_size = (long)archive_size, call.capacity = (long)capacity;
+    call.x = x, call.logp = logp, call.carry = carry, call.accepted = accepted, call.proposal = proposal, call.out = out;
+    call.score = score, call.score_stride = (long)score_stride, call.score_kind = score_kind, call.n_obs = (long)n_obs;
+    call.n_eff = n_eff, call.sigma = sigma, call.carry_new = carry_new, call.n_carry = n_carry, call.append = append != 0;
+    call.archive = archive, call.archive_logp = archive_logp, call.archive_carry = archive_carry, call.propose = propose != 0;
+    call.lo = lo, call.hi = hi, call.scale = scale, call.gamma = gamma, call.jump_threshold = (long)jump_threshold;
+    call.cr_threshold = (long)cr_threshold, call.rows = rows, call.ld = (long)ld, call.columns = columns;
+    if (score) { // ---- the accept phase
+        if (score_kind < SMART_DEMCZ_SCORE_LOGP || score_kind > SMART_DEMCZ_SCORE_RMSE_SIGMA)
+            c.refuse(SMART_E_MODE, "score_kind '%d' unknown.", (int)score_kind);
+        c.in_range("score_stride", score_stride, 1, kInt32Max);
+        if (score_kind == SMART_DEMCZ_SCORE_RMSE)
+            c.in_range("n_obs", n_obs, 1, kInt32Max);
+        if (score_kind != SMART_DEMCZ_SCORE_LOGP && !(n_eff > 0.0 && std::isfinite(n_eff)))
+            c.refuse(SMART_E_SIZE, "n_eff %g must be finite and > 0", n_eff);
+        if (score_kind == SMART_DEMCZ_SCORE_RMSE_SIGMA && !(sigma > 0.0 && std::isfinite(sigma)))
+            c.refuse(SMART_E_SIZE, "sigma %g must be finite and > 0", sigma);
+        if (!accepted)
+            c.refuse(SMART_E_NULL, "the accept phase needs accepted (accepted is NULL)");
+        c.needs("n_carry", n_carry, {NAMED(carry), NAMED(carry_new)});
+        if (append) {
+            if (!archive_logp)
+                c.refuse(SMART_E_NULL, "append needs archive_logp (archive_logp is NULL)");
+            c.needs("append with n_carry", n_carry, {NAMED(archive_carry)});
+            if (c.ok() && archive_size + chain_offset + n_chains > capacity)
+                c.refuse(SMART_E_SIZE, "append of archive rows %lld .. %lld passes the capacity %lld",
+                         (long long)(archive_size + chain_offset),
+                         (long long)(archive_size + chain_offset + n_chains - 1), (long long)capacity);
+        }
+    } else if (append) {
+        c.refuse(SMART_E_NULL, "append needs the accept phase (score is NULL)");
+    }
+    if (propose) { // ---- the propose phase
+        const Named needed[] = {NAMED(lo), NAMED(hi), NAMED(scale), NAMED(gamma), NAMED(rows), NAMED(columns)};
+        for (const Named &p : needed)
+            if (!p.ptr)
+                c.refuse(SMART_E_NULL, "the propose phase needs lo, hi, scale, gamma, rows and columns (%s is NULL)", p.name);
+        const long long after = c.ok() ? demcz_archive_after(call) : 0;
+        if (c.ok() && after < 2)
+            c.refuse(SMART_E_SIZE, "the propose phase draws two rows of the archive: its size is %lld, need at least 2", after);
+        if (c.ok() && after > capacity)
+            c.refuse(SMART_E_SIZE, "archive size %lld is more than the capacity %lld", after, (long long)capacity);
+        c.in_range("jump_threshold", jump_threshold, 0, kTwo32);
+        c.in_range("cr_threshold", cr_threshold, 0, kTwo32);
+        if (c.ok() && ld < n_dims)
+            c.refuse(SMART_E_SIZE, "ld %lld is less than n_dims %d", (long long)ld, (int)n_dims);
+        for (int j = 0; c.ok() && j < n_dims; ++j) {
+            if (columns[j] < 0 || columns[j] >= ld)
+                c.refuse(SMART_E_SIZE, "columns[%d] %d must be in 0 .. %lld", j, (int)columns[j], (long long)ld - 1);
+            for (int k = 0; c.ok() && k < j; ++k)
+                if (columns[k] == columns[j])
+                    c.refuse(SMART_E_SIZE, "columns[%d] and columns[%d] name the same column %d", k, j, (int)columns[j]);
+            if (c.ok() && !(std::isfinite(lo[j]) && std::isfinite(hi[j]) && lo[j] <= hi[j]))
+                c.refuse(SMART_E_SIZE, "lo[%d] %g and hi[%d] %g: need finite lo <= hi", j, lo[j], j, hi[j]);
+        }
+    }
+    if (int rc = c.ready())
+        return rc;
+    launch_demcz(call, (hipStream_t)stream);
+    return launched();
+}
+
 } // extern "C"
 

@@ -154,4 +154,36 @@ long pawn_step_bytes(long N);
 void launch_pawn(long N, long R, const double *y, long ld, const unsigned char *cat, int P, int B, double *ks, int *counts,
                  bool lds, void *workspace, long workspace_bytes, hipStream_t s);
 
+// ---- smart_demcz.hip: the arguments of smart_demcz_step_hip as the entry has checked them (score NULL: no accept phase)
+struct DemczCall {
+    long n_chains, chain_offset;
+    int n_dims;
+    unsigned long long seed;
+    long generation, archive_size, capacity;
+    double *x, *logp, *carry;
+    int *accepted;
+    double *proposal;
+    unsigned char *out;
+    const double *score;
+    long score_stride;
+    int score_kind;
+    long n_obs;
+    double n_eff, sigma;
+    const double *carry_new;
+    int n_carry, append;
+    double *archive, *archive_logp, *archive_carry;
+    int propose;
+    const double *lo, *hi, *scale, *gamma; // host, n_dims each
+    long jump_threshold, cr_threshold;
+    double *rows;
+    long ld;
+    const int *columns; // host, n_dims
+};
+// the archive rows the propose phase of a call draws from: what the accept phase of the same call has appended included
+inline long demcz_archive_after(const DemczCall &c)
+{
+    return c.archive_size + (c.score && c.append ? c.chain_offset + c.n_chains : 0);
+}
+void launch_demcz(const DemczCall &c, hipStream_t s);
+
 } // namespace smart

@@ -1,0 +1,198 @@
+"""DE-MCz posterior sampling of the SMART parameters (no counterpart in the reference, whose sampling tool ships DE-MCz
+and DREAM beside the plain Monte-Carlo loop the reference wraps).
+
+Every other workflow here works on a sample drawn once; this one MOVES its rows towards the posterior: N chains in
+lockstep, one ensemble launch per generation, and around it one call of smart_demcz_step_hip (smartpy_amd/demcz.py) that
+decides on the proposals the launch has just scored, appends to the archive every `thin`-th generation and proposes the
+next rows -- differential evolution with sampling from the past (ter Braak & Vrugt 2008), subspace crossover as in DREAM
+(Vrugt 2016), a uniform prior on the parameter ranges.  What is left is a MonteCarlo object like any other: the sample,
+device_obj_fns, device_gw and the database, for GLUE / Best / Pareto with `sampling=` and every analysis of the stored
+matrix.
+"""
+import math
+
+import numpy as np
+
+from .montecarlo import MonteCarlo, OBJ_FN_NAMES
+from .. import demcz as core
+from .. import distributed as sdist
+from ..engine import SmartEngineError
+from ..sampling import latin_hypercube
+
+RMSE_COLUMN, GW_FLAG_COLUMN = OBJ_FN_NAMES.index('RMSE'), len(OBJ_FN_NAMES)
+N_CARRY = len(OBJ_FN_NAMES) + 2      # the seven objective functions, the GW flag and the groundwater ratio
+
+
+class DEMCz(MonteCarlo):
+    """Sample the posterior of the parameters given the observed flow.
+
+    chains: N, the rows of every launch; generations: launches after the initial one; thin: every thin-th generation is
+    archived (the archive is what proposals are drawn from AND what the posterior sample is taken from); burn_in: the
+    share of the archived snapshots that is dropped from the sample; cr: the crossover probability of a dimension;
+    p_jump: the share of proposals with gamma = 1 (mode jumping); b_star: the width of the uniform jitter, as a share
+    of each range.  likelihood='gaussian': independent Gaussian errors on the report steps that carry an observation --
+    sigma=None integrates the error variance out (log-density -(n_eff / 2) ln(n RMSE^2)), a number fixes it
+    (-n_eff RMSE^2 / (2 sigma^2)); n_eff (default: n, the observed report steps) is the number of observations the
+    errors are worth, for autocorrelated residuals.  vary / fixed: as for Sobol (default: all ten vary; a parameter
+    that does not stays at fixed[name], or at the middle of its range).  gw_prior=True gives a row that fails the
+    groundwater constraint of the settings file the log-density -inf.  seed: of the initial Latin hypercube
+    (sampling.latin_hypercube over model.parameters.ranges) and of the counter-based draws of the chains: the same seed
+    gives the same bits.
+
+    run() leaves `posterior` (demcz.PosteriorSample), `log_density`, `acceptance_rate`, `rhat`, `diagnostics`, the sample
+    (the archived rows after the burn-in, full parameter width), obj_fns / device_obj_fns / device_gw of those rows as the
+    chains carried them, and the database `<catchment>.SMART.demcz`."""
+
+    def __init__(self, catchment, root_f, in_format, out_format,
+                 chains=1024, generations=500, thin=10, burn_in=0.5, cr=0.9, p_jump=0.1, b_star=1e-6,
+                 likelihood='gaussian', sigma=None, n_eff=None, vary=None, fixed=None, gw_prior=False, seed=0,
+                 settings_filename=None):
+        MonteCarlo.__init__(self, catchment, root_f, in_format, out_format,
+                            parallel='seq', save_sim=False, func='demcz', settings_filename=settings_filename)
+        self.chains, self.generations, self.thin = int(chains), int(generations), int(thin)
+        self.burn_in, self.cr, self.p_jump, self.b_star = float(burn_in), float(cr), float(p_jump), float(b_star)
+        self.likelihood, self.sigma, self.gw_prior, self.seed = likelihood, sigma, bool(gw_prior), seed
+        if self.chains < 2 or self.generations < 1 or self.thin < 1:
+            raise SmartEngineError(-2, "DEMCz: need chains >= 2, generations >= 1 and thin >= 1 (got {}, {}, {})."
+                                   .format(chains, generations, thin))
+        if not 0.0 <= self.burn_in < 1.0:
+            raise SmartEngineError(-2, "DEMCz: burn_in {} must be in [0, 1).".format(burn_in))
+        if likelihood != 'gaussian':
+            raise SmartEngineError(-7, "DEMCz: likelihood '{}' unknown.".format(likelihood))
+        if gw_prior and not self.constraints['gw']:
+            raise SmartEngineError(-2, "DEMCz: gw_prior needs the groundwater constraint of the settings file.")
+        core.thresholds(self.p_jump, self.cr)
+        self._check_observations()
+        self.n_obs = int(np.count_nonzero(~np.isnan(np.asarray(self.model.nd_flow, dtype=np.float64))))
+        self.n_eff = float(self.n_obs if n_eff is None else n_eff)
+        names, ranges = list(self.param_names), self.model.parameters.ranges
+        self.vary = list(names if vary is None else vary)
+        unknown = [p for p in self.vary if p not in names]
+        if unknown or len(set(self.vary)) != len(self.vary) or not self.vary:
+            raise Exception("DEMCz: `vary` must name at least one of {}, each once (got {}).".format(names, self.vary))
+        fixed = dict(fixed or {})
+        unknown = [p for p in fixed if p not in names or p in self.vary]
+        if unknown:
+            raise Exception("DEMCz: the fixed parameter(s) {} are unknown or also vary.".format(unknown))
+        self.columns = [names.index(p) for p in self.vary]
+        self.lo = np.asarray([ranges[p][0] for p in self.vary], dtype=np.float64)
+        self.hi = np.asarray([ranges[p][1] for p in self.vary], dtype=np.float64)
+        population = latin_hypercube(self.chains, ranges, names, seed=seed)
+        for j, p in enumerate(names):
+            if p not in self.vary:
+                population[:, j] = fixed.get(p, 0.5 * (float(ranges[p][0]) + float(ranges[p][1])))
+        self.initial_population = population
+        self._set_sample(population)
+        self.posterior = self.log_density = self.acceptance_rate = self.rhat = self.diagnostics = None
+
+    # ---- the log-density of a score ---------------------------------------------------------------------------
+    @property
+    def score_kind(self):
+        return 'rmse' if self.sigma is None else 'rmse_sigma'
+
+    def log_density_of(self, rmse):
+        """The log-density the chains are moved by, from the RMSE of a row (array or tensor; answered in kind)"""
+        log = np.log if isinstance(rmse, np.ndarray) else __import__('torch').log
+        if self.sigma is None:
+            return -((self.n_eff * 0.5) * log(self.n_obs * (rmse * rmse)))
+        return -(self.n_eff * (rmse * rmse)) / ((2.0 * float(self.sigma)) * float(self.sigma))
+
+    def _new_state(self, population, snapshots, device):
+        """The chains on the device: the launch matrix is the population at full width, the archive holds `snapshots` of
+        the chains"""
+        from ..engine import as_device
+        rows = as_device(population, device).clone()
+        return core.DemczState(rows[:, self.columns], self.lo, self.hi, capacity=int(snapshots) * self.chains,
+                               seed=0 if self.seed is None else self.seed, cr=self.cr, p_jump=self.p_jump,
+                               b_star=self.b_star, n_carry=N_CARRY, columns=self.columns, rows=rows,
+                               score_kind=self.score_kind, n_obs=self.n_obs, n_eff=self.n_eff,
+                               sigma=0.0 if self.sigma is None else float(self.sigma), device=device)
+
+    def _launch_chains(self, state):
+        """One launch over the launch matrix of the chains -> (scores [N] at a stride, payload [N, 9])"""
+        import torch
+        n = self.chains
+        # (a view of its own per launch: what the engine remembers about a tensor object is not asked about rows that the
+        # step kernel rewrites behind torch's back)
+        out = self.model.simulate_ensemble(state.rows.view(n, len(self.param_names)), objective_functions=True,
+                                           gw_constraint=self.constraints['gw'], save_discharge=False,
+                                           math_mode=self.math_mode)
+        table = out.objfn[:n]
+        payload = torch.cat([table, out.gw[:n].unsqueeze(1)], dim=1)
+        scores = table[:, RMSE_COLUMN]                      # read in place: stride 8
+        if self.gw_prior:
+            scores = torch.where(table[:, GW_FLAG_COLUMN] > 0.0, scores, torch.full_like(scores, float('inf')))
+        return scores, payload
+
+    # ---- run -----------------------------------------------------------------------------------------------------
+    def run(self, compression=None, write=False):
+        """The chains, then the database.  One step call and one launch per generation, nothing copied to the host in
+        between beyond what the engine's own preparation reads.  write=True also writes
+        `<catchment>.SMART.demcz.diagnostics` (generation, acceptance_rate, Rhat_<p> per archived generation).  Under
+        torch.distributed every rank computes everything itself and rank 0 alone writes."""
+        import torch
+        from ..engine import as_device, default_device
+        rank, world = sdist.rank_world()
+        population = self.initial_population
+        if world > 1:       # (seed=None draws from NumPy's global stream: rank 0's population is THE population)
+            population = sdist.broadcast_matrix(population, src=0)
+        N, G, thin, d = self.chains, self.generations, self.thin, len(self.vary)
+        S = 1 + G // thin
+        device = default_device()
+        state = self._new_state(population, S, device)
+        accepted_at = [torch.zeros((), dtype=torch.int64, device=device)]
+        scores, payload = self._launch_chains(state)
+        core.demcz_step(state, scores=scores, carry_new=payload, append=True, propose=True)     # the initial population
+        for g in range(1, G + 1):
+            scores, payload = self._launch_chains(state)
+            core.demcz_step(state, scores=scores, carry_new=payload, append=g % thin == 0, propose=g < G)
+            if g % thin == 0:
+                accepted_at.append(state.accepted.sum())
+        assert state.M == S * N
+        # ---- what the archive holds
+        history = state.archive.view(S, N, d)
+        history_logp = state.archive_logp.view(S, N)
+        first = min(S - 1, int(math.floor(self.burn_in * S)))
+        sample_d = state.archive[first * N:]
+        carry = state.archive_carry[first * N:]
+        base = as_device(population[:1], device)
+        full = base.repeat(sample_d.shape[0], 1)
+        full[:, self.columns] = sample_d
+        accepted = state.accepted.cpu().numpy()
+        gens = np.arange(S) * thin
+        counts = torch.stack(accepted_at).cpu().numpy().astype(np.float64)
+        rates = np.where(gens > 0, counts / np.maximum(gens * N, 1), np.nan)
+        rhats = np.stack([core.gelman_rubin(history[:s + 1]).cpu().numpy() for s in range(S)])
+        self.diagnostics = np.concatenate([gens[:, None].astype(np.float64), rates[:, None], rhats], axis=1)
+        self.rhat = rhats[-1]
+        self.acceptance_rate = float(accepted.sum()) / float(N * G)
+        self.log_density = history_logp.reshape(-1)[first * N:]
+        self.state = state
+        # ---- the MonteCarlo object every second stage and analysis takes
+        n_obj = len(self.obj_fn_names)
+        self._set_sample(full)
+        self.device_obj_fns, self.device_gw = carry[:, :n_obj].contiguous(), carry[:, N_CARRY - 1].contiguous()
+        host = carry.cpu().numpy()
+        self.obj_fns, self.gw_contributions = np.ascontiguousarray(host[:, :n_obj]), np.ascontiguousarray(host[:, -1])
+        self.posterior = core.PosteriorSample(self.vary, sample_d, self.log_density, carry, history, history_logp, accepted,
+                                              self.rhat, self.acceptance_rate, self.diagnostics, first)
+        failure = None
+        if rank == 0:
+            try:
+                db = self._open_database()
+                db.write_table(self.obj_fns, self._sample, None)
+                self._finish_database(db, compression)
+                if write:
+                    core.write_diagnostics(self.diagnostics_file, self.vary, self.diagnostics)
+                    self.posterior.file = self.diagnostics_file
+            except Exception as e:      # noqa: BLE001 -- a full disk on rank 0 ends the call on every rank
+                failure = e
+        if world > 1:
+            sdist.agree_or_raise(failure)
+        elif failure is not None:
+            raise failure
+
+    @property
+    def diagnostics_file(self):
+        """`<out>/<catchment>.SMART.demcz.diagnostics`: beside the sampling database, whatever its format."""
+        return self._side_file('.diagnostics')
