@@ -16,20 +16,34 @@
 // the value is a select: rising, falling, above or below a threshold, a new peak.  No divergent branch.
 //
 // Arithmetic.  One log per valid row; the previous row's logarithm is kept (a recession term is ln x_r - ln x_{r-1}, taken
-// only where 0 < x_r < x_{r-1}, where both logarithms are finite).  AC1 from one-pass moments of the pairs about a
-// per-sample shift, the sample's FIRST valid value, as smart_objfn_windows does.  A value that is not finite needs no test
-// of its own: the sum of x never becomes finite again, and ONE test of it at the end empties the (window, sample).
+// only where 0 < x_r < x_{r-1}, where both logarithms are finite).  AC1 from one-pass moments of the two pair lists, each
+// about a constant of its OWN, set at the window's first pair: the x_{r-1} about that pair's x_{r-1}, the x_r about that
+// pair's x_r.  Each constant is a member of the sums it centres, so the loss of digits in S2 - S1^2 / p is bounded by p
+// whatever the window opens on (a flood peak, a value before a gap), and a list that is constant has every term and so its
+// variance exactly 0: the NaN rule is exact.  A value that is not finite needs no test of its own: the sum of x never
+// becomes finite again, and ONE test of it at the end empties the (window, sample).
 //
-// State: sixteen doubles and eleven 32-bit counts and flags per lane, in registers for the whole walk.  With the loads in
-// flight and the logarithm's temporaries hipcc takes 113 VGPRs and no scratch under __launch_bounds__(256, 4): four
-// wavefronts per SIMD (left alone it takes 154, three wavefronts).  The pair is an `if` WITHOUT an else -- what a row
-// without a pair restarts is set before it: an if / else on the uniform flag makes hipcc keep the old and the new
-// state side by side (51 VGPRs spilled).
+// Counts.  A run above hi (below lo) and a rising limb are counted by what CONTINUES them: runs = rows above - pairs whose
+// x_{r-1} is above too, limbs = rising pairs - rising pairs whose row r - 1 rose as well.  What row r - 1 was is read off
+// values at hand (x_{r-1} against the threshold; the sign of its own difference, which a rounded subtraction keeps), so no
+// flag is carried from row to row: integers either way, and about ten instructions a row less than three carried flags.
+//
+// State: seventeen doubles and eight 32-bit counts per lane, in registers for the whole walk.  With the loads in flight and
+// the logarithm's temporaries hipcc takes 109 VGPRs and no scratch under __launch_bounds__(256, 4): four wavefronts per
+// SIMD.  The pair is an `if` WITHOUT an else -- what a row without a pair
+// restarts is set before it: an if / else on the uniform flag makes hipcc keep the old and the new state side by side
+// (51 VGPRs spilled).  Setting AC1's two constants at the first pair costs four selects and a scalar compare in every row if
+// the batches do it; so up to the window's first pair a copy of the step that has the selects walks one row at a time -- as
+// a rule two rows -- and the batches run the copy that has none (a second batched copy of the full step spills 120
+// bytes).  A window without a pair anywhere does not walk so to its end: eight rows none of which has a pair go through
+// `alone`, the step of such a row without its logarithm.
 //
 // Determinism.  No atomics; the association of every sum is the row order: two launches give the same bits.
 //
 // Not built: a split of the time axis across wavefronts.  The associative form of the clamped filter composes clamp-affine
 // maps, which changes the bits and needs two sweeps.
+#include <type_traits>
+
 #include "smart_capi_internal.h"
 #include "smart_window_rows.h"
 
@@ -62,54 +76,79 @@ __global__ __launch_bounds__(kSigThreads, kSigWavesPerSimd) void smart_signature
     auto valid = [&](long r) { return (!window || window[r] == w) && (!obs || !is_nan_bits(obs[r])); };
 
     int m = 0, p = 0;        // valid rows and pairs so far (the same in every thread)
-    bool have_shift = false; // (the same in every thread)
-    double shift = 0.0, prev = 0.0, prev_u = 0.0, prev_log = 0.0, quick = 0.0;
+    double shift_a = 0.0, shift_b = 0.0, prev = 0.0, prev_log = 0.0, quick = 0.0;
     double sum_x = 0.0, sum_base = 0.0, sum_abs = 0.0, sum_pair = 0.0, sum_rec = 0.0;
     double Sa = 0.0, Sb = 0.0, Saa = 0.0, Sbb = 0.0, Sab = 0.0;
     double peak = -__builtin_inf();
-    int peak_row = 0, n_rise = 0, n_limb = 0, n_rec = 0, hi_runs = 0, hi_rows = 0, lo_runs = 0, lo_rows = 0;
-    bool was_rising = false, was_above = false, was_below = false;
+    double last_d = 0.0; // x_{r-1} - x_{r-2} where row r - 1 has a pair, else 0
+    int peak_row = 0, n_rise = 0, n_rise_joins = 0, n_rec = 0, hi_rows = 0, hi_joins = 0, lo_rows = 0, lo_joins = 0;
 
-    auto step = [&](unsigned entry, double x) {
+    // `first`: the window's first pair may still lie ahead (std::true_type), or is behind (std::false_type)
+    auto step = [&](auto first, unsigned entry, double x) {
         const int r = (int)(entry >> 1);
         const bool pair = entry & 1u; // row r - 1 is valid, and it was the entry before this one (the same in every lane)
-        const double lx = log(x), u = x - shift;
+        const double lx = log(x);
         const bool above = x > hi, below = x < lo, top = x > peak;
-        const bool rising = pair && x > prev;
         sum_x += x;
         peak_row = top ? r : peak_row;
         peak = top ? x : peak;
-        // without a pair -- the window's first row, or the first after a gap -- the limbs and the runs start again ...
-        n_rise += rising ? 1 : 0;
-        n_limb += rising && !was_rising ? 1 : 0;
-        hi_runs += above && !(pair && was_above) ? 1 : 0;
-        lo_runs += below && !(pair && was_below) ? 1 : 0;
         hi_rows += above ? 1 : 0;
         lo_rows += below ? 1 : 0;
-        double q = 0.0; // ... and so does the filter
+        // without a pair -- the window's first row, or the first after a gap -- the limbs, the runs and the filter start again
+        double q = 0.0, d = 0.0;
         if (pair) {
-            const double d = x - prev;
-            const bool falling = x > 0.0 && x < prev;
+            d = x - prev;
+            const bool rising = x > prev, falling = x > 0.0 && x < prev;
+            // A row that continues what row r - 1 began joins it: runs = rows - joins, limbs = rising pairs - joins, in
+            // integers.  What row r - 1 was is read off the values at hand (x_{r-1} against the threshold, the sign of its own
+            // difference, which a rounded subtraction keeps), so no flag is carried from row to row.
+            hi_joins += above && prev > hi ? 1 : 0;
+            lo_joins += below && prev < lo ? 1 : 0;
+            n_rise += rising ? 1 : 0;
+            n_rise_joins += rising && last_d > 0.0 ? 1 : 0;
+            // The window's first pair gives the two lists their constants.  Only the walk that has not met it yet pays the
+            // four selects a row (p is the same in every lane).
+            if constexpr (decltype(first)::value) {
+                shift_a = p == 0 ? prev : shift_a;
+                shift_b = p == 0 ? x : shift_b;
+            }
+            const double ua = prev - shift_a, ub = x - shift_b;
             q = fmin(fmax(alpha * quick + gain * d, 0.0), x);
             sum_abs += fabs(d);
             sum_pair += x;
-            Sa += prev_u;
-            Sb += u;
-            Saa += prev_u * prev_u;
-            Sbb += u * u;
-            Sab += prev_u * u;
-            sum_rec += falling ? lx - prev_log : 0.0;
+            Sa += ua;
+            Sb += ub;
+            Saa += ua * ua;
+            Sbb += ub * ub;
+            Sab += ua * ub;
+            double before_log = prev_log;
+            if constexpr (decltype(first)::value)
+                before_log = log(prev); // (rows walked by `alone` keep no logarithm)
+            sum_rec += falling ? lx - before_log : 0.0;
             n_rec += falling ? 1 : 0;
             ++p;
         }
         quick = q;
         sum_base += x - q;
         prev = x;
-        prev_u = u;
         prev_log = lx;
-        was_rising = rising;
-        was_above = above;
-        was_below = below;
+        last_d = d;
+        ++m;
+    };
+
+    // a row without a pair, before the window's first pair: what `step` does to such a row, less the logarithm (the full
+    // step of a first pair takes ln x_{r-1} itself)
+    auto alone = [&](int r, double x) {
+        const bool top = x > peak;
+        sum_x += x;
+        peak_row = top ? r : peak_row;
+        peak = top ? x : peak;
+        hi_rows += x > hi ? 1 : 0;
+        lo_rows += x < lo ? 1 : 0;
+        quick = 0.0;
+        sum_base += x;
+        prev = x;
+        last_d = 0.0;
         ++m;
     };
 
@@ -125,13 +164,33 @@ __global__ __launch_bounds__(kSigThreads, kSigWavesPerSimd) void smart_signature
             },
             [&](int pos, long r, int k) { rows[pos] = ((unsigned)r << 1) | (pair[k] ? 1u : 0u); });
         int j = 0;
-        if (!have_shift && listed > 0) { // entry 0 of the first chunk that has one: the sample's shift
-            const unsigned e = __builtin_amdgcn_readfirstlane(rows[0]);
-            shift = col[(long)(e >> 1) * ld];
-            have_shift = true;
-            step(e, shift);
-            j = 1;
+        // Up to the window's first pair: batches of rows none of which has a pair take the short step; any other row the
+        // full step that sets AC1's constants, one at a time -- as a rule that is the chunk's first two entries ...
+        while (j < listed && p == 0) {
+            if (j + kSigUnroll <= listed) {
+                unsigned e[kSigUnroll], any = 0;
+                double x[kSigUnroll];
+#pragma unroll
+                for (int k = 0; k < kSigUnroll; ++k) {
+                    e[k] = __builtin_amdgcn_readfirstlane(rows[j + k]);
+                    any |= e[k];
+                }
+                if (!(any & 1u)) {
+#pragma unroll
+                    for (int k = 0; k < kSigUnroll; ++k)
+                        x[k] = col[(long)(e[k] >> 1) * ld];
+#pragma unroll
+                    for (int k = 0; k < kSigUnroll; ++k)
+                        alone((int)(e[k] >> 1), x[k]);
+                    j += kSigUnroll;
+                    continue;
+                }
+            }
+            const unsigned e = __builtin_amdgcn_readfirstlane(rows[j]);
+            step(std::true_type{}, e, col[(long)(e >> 1) * ld]);
+            ++j;
         }
+        // ... and from there in batches, the two constants of AC1 fixed
         for (; j + kSigUnroll <= listed; j += kSigUnroll) {
             unsigned e[kSigUnroll];
             double x[kSigUnroll];
@@ -142,15 +201,15 @@ __global__ __launch_bounds__(kSigThreads, kSigWavesPerSimd) void smart_signature
             }
 #pragma unroll
             for (int k = 0; k < kSigUnroll; ++k) {
-                step(e[k], x[k]);
-                // the rows are a chain (the filter, the flags): interleaving the logarithms of eight of them buys nothing
+                step(std::false_type{}, e[k], x[k]);
+                // the rows are a chain (the filter, the sums): interleaving the logarithms of eight of them buys nothing
                 // and costs the registers of eight
                 __builtin_amdgcn_sched_barrier(0);
             }
         }
         for (; j < listed; ++j) {
             const unsigned e = __builtin_amdgcn_readfirstlane(rows[j]);
-            step(e, col[(long)(e >> 1) * ld]);
+            step(std::false_type{}, e, col[(long)(e >> 1) * ld]);
         }
     }
     if (!live)
@@ -158,6 +217,7 @@ __global__ __launch_bounds__(kSigThreads, kSigWavesPerSimd) void smart_signature
 
     double o[SMART_SIGNATURE_COLS];
     const double nan = quiet_nan();
+    const int n_limb = n_rise - n_rise_joins; // (step: runs = rows - joins)
     o[SMART_SIG_MEAN] = sum_x / (double)m;
     o[SMART_SIG_BFI] = sum_x == 0.0 ? nan : sum_base / sum_x;
     o[SMART_SIG_FLASHINESS] = p == 0 || sum_pair == 0.0 ? nan : sum_abs / sum_pair;
@@ -171,6 +231,7 @@ __global__ __launch_bounds__(kSigThreads, kSigWavesPerSimd) void smart_signature
     o[SMART_SIG_PEAK] = peak;
     o[SMART_SIG_PEAK_ROW] = (double)peak_row;
     const bool with_hi = !is_nan_bits(hi), with_lo = !is_nan_bits(lo);
+    const int hi_runs = hi_rows - hi_joins, lo_runs = lo_rows - lo_joins;
     o[SMART_SIG_HIGH_COUNT] = with_hi ? (double)hi_runs : nan;
     o[SMART_SIG_HIGH_DURATION] = with_hi && hi_runs ? (double)hi_rows / (double)hi_runs : nan;
     o[SMART_SIG_LOW_COUNT] = with_lo ? (double)lo_runs : nan;

@@ -21,6 +21,14 @@ lists nothing and the first listed row (the shift of the one-pass moments) is fo
 
 Kept per output array: the bits of the sample columns 0, 1, 63 and N - 1, and a sha256 of the whole array -- the row list is
 shared by all samples of a workgroup, so a wrong list shows in every column.
+
+AC1 was later re-centred (its one-pass moments about a member of each pair list): the two `signatures` arrays keep the
+parent's bits in the eleven other columns only.  `--extend` adds, for those two arrays, the kept-column bits and the
+sha256 of the array WITHOUT its AC1 column under the name `<name>|but_ac1`, made by the library of the commit before
+that change -- after asserting that this library reproduces the full-array sha256 the fixture already holds -- and
+leaves every other key of the fixture as it is:
+
+    SMART_AMD_LIB=$PWD/tools/variants/libsmart_amd_parent.so python tests/golden/make_window_rows_parent.py --extend [out.npz]
 """
 import hashlib
 import os
@@ -39,6 +47,9 @@ WINDOW_KINDS = ('one', 'mod3', 'blocks', 'pair', 'minus')
 LOG_EPS = 0.05
 PROBS_BOOTSTRAP = (0.05, 0.5, 0.95)
 PROBS_CURVE = (0.1, 0.5, 1.0)
+SIGNATURE_ARRAYS = ('signatures', 'signatures_thresholds')      # [W, 12, N]
+AC1 = 3
+BUT_AC1 = '|but_ac1'
 
 
 def obs_kinds(R):
@@ -80,6 +91,19 @@ def counts(W):
     return c
 
 
+def run_signatures(eng, R, N, window_kind, obs_kind):
+    """the two signature launches of a case -> {name: (device array, the axis of it that runs over the samples)}"""
+    sim, obs, win, W = inputs(R, N, window_kind, obs_kind)
+    return {'signatures': (eng.signatures(sim, obs, win, n_windows=W), 2),
+            'signatures_thresholds': (eng.signatures(sim, obs, win, n_windows=W, thresholds=np.tile((1.5, 4.5), (W, 1))), 2)}
+
+
+def but_ac1(a):
+    """[W, 12, N] -> [W, 11, N]: the array without its AC1 column"""
+    assert a.shape[1] == 12
+    return np.ascontiguousarray(np.delete(a, AC1, axis=1))
+
+
 def run_case(eng, R, N, window_kind, obs_kind):
     """every entry on one case -> {name: (numpy array, the axis of it that runs over the samples)}"""
     sim, obs, win, W = inputs(R, N, window_kind, obs_kind)
@@ -89,8 +113,7 @@ def run_case(eng, R, N, window_kind, obs_kind):
                                                                        eps=eps), 1)
     b = eng.objective_functions_bootstrap(sim, obs, win, counts(W), probs=PROBS_BOOTSTRAP, n_windows=W, replicates=True)
     got.update(bootstrap_point=(b.point, 0), bootstrap_stats=(b.stats, 2), bootstrap_replicates=(b.replicates, 2))
-    got['signatures'] = (eng.signatures(sim, obs, win, n_windows=W), 2)
-    got['signatures_thresholds'] = (eng.signatures(sim, obs, win, n_windows=W, thresholds=np.tile((1.5, 4.5), (W, 1))), 2)
+    got.update(run_signatures(eng, R, N, window_kind, obs_kind))
     quant, scores = eng.flow_duration(sim, PROBS_CURVE, obs=obs, windows=win, n_windows=W, transform='sqrt', objfn=True,
                                       method='sort')
     got.update(curve_quant=(quant, 2), curve_objfn=(scores, 1))
@@ -139,5 +162,38 @@ def main(path):
     print('%d arrays, %d bytes -> %s' % (len(keys), os.path.getsize(path), path))
 
 
+def extend(path):
+    """add the `|but_ac1` entries of the two signature arrays, made by the selected (parent) library, to the fixture"""
+    import torch
+    from smartpy_amd import _lib, engine
+    assert torch.cuda.is_available(), 'the fixture is made on the GPU'
+    print('library:', _lib.LIB_PATH)
+    z = np.load(FIXTURE, allow_pickle=False)
+    old_ends = np.concatenate([[0], z['ends']])
+    keys, hashes, bits = [], [], []
+    for i, k in enumerate(z['keys']):
+        if not k.decode().endswith(BUT_AC1):
+            keys.append(k.decode())
+            hashes.append(z['sha256'][i].decode())
+            bits.append(z['bits'][old_ends[i]:old_ends[i + 1]])
+    held = dict(zip(keys, hashes))
+    n_old = len(keys)
+    for R, N in SHAPES:
+        for window_kind in WINDOW_KINDS:
+            for obs_kind in obs_kinds(R):
+                for name, (a, axis) in run_signatures(engine, R, N, window_kind, obs_kind).items():
+                    a = np.ascontiguousarray(a.cpu().numpy(), dtype=np.float64)
+                    k = key(R, N, window_kind, obs_kind, name)
+                    assert kept(a, axis, N)[1] == held[k], 'this library is not the one the fixture was made by: ' + k
+                    b, h = kept(but_ac1(a), axis, N)
+                    keys.append(k + BUT_AC1)
+                    hashes.append(h)
+                    bits.append(b.ravel())
+    np.savez_compressed(path, keys=np.array(keys, dtype='S'), sha256=np.array(hashes, dtype='S'), bits=np.concatenate(bits),
+                        ends=np.cumsum([len(b) for b in bits]))
+    print('%d arrays kept, %d added, %d bytes -> %s' % (n_old, len(keys) - n_old, os.path.getsize(path), path))
+
+
 if __name__ == '__main__':
-    main(sys.argv[1] if len(sys.argv) > 1 else FIXTURE)
+    args = [a for a in sys.argv[1:] if a != '--extend']
+    (extend if '--extend' in sys.argv[1:] else main)(args[0] if args else FIXTURE)

@@ -13,10 +13,21 @@ on 15 % of the rows; the observations are a perturbed column with 15 % missing. 
 and the 80th percentile of the window's simulated values, so that both kinds of run occur; window 0 gets two values of
 the matrix itself (strictness), the last of several windows a NaN pair.
 
-Gates.  PEAK, PEAK_ROW, HIGH_COUNT and LOW_COUNT are bit-equal to the statement (a zero compared by value); the pattern of
-NaN is equal in every column; AC1 is held to 1e-9 absolute; the other columns to the gate the suite holds the sibling
-kernels to: rel < 1e-9 with |want| floored at 1e-12, every compared |want| asserted to be 0 or above 1e-6 (a seed that
-fails this is changed, not the gate).  The largest margins of a run are printed at the end of the module (and written to
+Gates.  PEAK, PEAK_ROW, HIGH_COUNT, LOW_COUNT and the five columns that are plain additions in row order or one quotient of
+two counts -- MEAN, FLASHINESS, RLD, HIGH_DURATION, LOW_DURATION -- are bit-equal to the statement (a zero compared by
+value): a row that is dropped, doubled or added out of order shows however small its value.  The pattern of NaN is equal
+in every column; AC1 is held to 1e-9 absolute; BFI and RECESSION to the gate the suite holds the sibling kernels to:
+rel < 1e-9 with |want| floored at 1e-12, every compared |want| asserted to be 0 or above 1e-6 (a seed that fails this is
+changed, not the gate).
+
+The stress family.  tests/test_signatures_truth_host.py has the twelve columns in exact arithmetic (`truth`), what the
+kernel's documented form may differ from them by (`bounds`, derived there) and columns on which a badly centred AC1 shows:
+a window that opens on a flood peak (in a pair, and before a gap), series that barely move, a 1e6-fold flood, stretches of
+exact zeros, columns that are constant but for one row.  R = 9, 501, 1025 at N = 65, the family in the last columns (they
+straddle the two wavefronts), all twelve columns within `bounds` of `truth`, the pattern of NaN exact -- AC1 = NaN for both
+constant-but-for-one-row kinds, whose variance is exactly 0.
+
+The largest margins of a run are printed at the end of the module (and written to
 $SMART_MARGINS_DIR/signatures_margins.txt where that is set); profiles/signatures_margins.txt is that table."""
 import os
 import shutil
@@ -26,6 +37,8 @@ import pytest
 
 from conftest import GOLDEN
 from test_windows_host import rel
+from test_signatures_truth_host import (data, thresholds, stress_case, stress_reference, margins, KINDS, CONSTANT_KINDS,
+                                        STRESS_R)
 from test_signatures_host import (statement, NAMES, PAIR_COLUMNS, MEAN, BFI, FLASHINESS, AC1, RLD, RECESSION, PEAK, PEAK_ROW,
                                   HIGH_COUNT, HIGH_DURATION, LOW_COUNT, LOW_DURATION, E_SIZE)
 
@@ -35,12 +48,14 @@ EXTRA = {'aar': 1200, 'r-o_ratio': 0.45, 'r-o_split': (0.10, 0.15, 0.15, 0.30, 0
 GATE = 1e-9
 SENTINEL = -7.0
 GUARD = 64
-EXACT = [PEAK, PEAK_ROW, HIGH_COUNT, LOW_COUNT]
-CLOSE = [MEAN, BFI, FLASHINESS, RLD, RECESSION, HIGH_DURATION, LOW_DURATION]
+EXACT = [PEAK, PEAK_ROW, HIGH_COUNT, LOW_COUNT, MEAN, FLASHINESS, RLD, HIGH_DURATION, LOW_DURATION]
+CLOSE = [BFI, RECESSION]
 # R -> the N it is run with
 SHAPES = {1: (1, 65), 2: (1, 63, 257), 3: (65, 300), 7: (1, 257), 8: (63, 65), 9: (1, 300), 10: (65,), 501: (63, 300),
           1025: (1, 257), 4097: (65,)}
 MARGINS = {}            # column name -> (largest margin as a fraction of its gate, where it was seen)
+STRESS_MARGINS = {}     # column name -> (largest |got - truth| / bound on the stress family, where it was seen)
+FILLER = 65 - len(KINDS)
 
 
 def same_values(a, b):
@@ -55,39 +70,11 @@ def bits_equal(a, b):
     return a.shape == b.shape and np.array_equal(a.view(np.int64), b.view(np.int64))
 
 
-def data(seed, R, n):
-    """-> (rng, obs [R] with 15 % missing, sim [R, n])"""
-    rng = np.random.default_rng(seed)
-    k = rng.uniform(0.80, 0.98, n)
-    event = np.where(rng.random((R, n)) < 0.15, rng.exponential(2.0, (R, n)), 0.0)
-    sim = np.empty((R, n))
-    s = rng.exponential(1.0, n)
-    for r in range(R):
-        s = k * s + event[r]
-        sim[r] = 0.05 + s
-    obs = sim[:, 0] * rng.uniform(0.7, 1.3, R) + 0.01
-    obs[rng.random(R) < 0.15] = np.nan
-    return rng, obs, sim
-
-
 def window_arrays(rng, R):
     sixteen = (np.arange(R) * 16 // R).astype(np.int32)
     sixteen[rng.random(R) < 0.10] = -1
     return [(1, None), (2, (np.arange(R) >= R // 2).astype(np.int32)), (7, (np.arange(R) % 7).astype(np.int32)),
             (16, sixteen)]
-
-
-def thresholds(sim, obs, win, W):
-    """(lo, hi) per window: the 30th and the 80th percentile of the window's simulated values; window 0 takes two values
-    of the matrix itself; the last of several windows a NaN pair"""
-    pulse = np.full((W, 2), np.nan)
-    for w in range(W):
-        rows = np.ones(len(sim), dtype=bool) if win is None else (win == w)
-        if obs is not None:
-            rows = rows & ~np.isnan(obs)
-        if rows.any() and not (W > 1 and w == W - 1):
-            pulse[w] = np.quantile(sim[rows], [0.3, 0.8], method='inverted_cdf' if w == 0 else 'linear')
-    return pulse
 
 
 def launch(sim, obs=None, win=None, W=1, alpha=0.925, pulse=None, pad=0, expect=0):
@@ -125,7 +112,8 @@ def hold(got, want, what):
     """every gate of the module's docstring on one launch"""
     assert got.shape == want.shape
     assert np.array_equal(np.isnan(got), np.isnan(want)), what + ': the pattern of NaN'
-    assert same_values(got[:, EXACT], want[:, EXACT]), what + ': peak, its row and the counts'
+    assert same_values(got[:, EXACT], want[:, EXACT]), what + ': the columns that are bit-equal: ' + ', '.join(
+        NAMES[c] for c in EXACT if not same_values(got[:, c], want[:, c]))
     compared = want[:, CLOSE][~np.isnan(want[:, CLOSE])]
     assert compared.size == 0 or np.all((compared == 0.0) | (np.abs(compared) > 1e-6)), what      # (change the seed)
     for c in CLOSE + [AC1]:
@@ -142,12 +130,17 @@ def hold(got, want, what):
 @pytest.fixture(scope='module', autouse=True)
 def _print_the_margins():
     yield
-    if not MARGINS:
+    if not MARGINS and not STRESS_MARGINS:
         return
     text = ('largest error of this run against the statement, as a fraction of its gate (relative 1e-9 with |want| floored '
             'at 1e-12; AC1 absolute 1e-9): column, margin, the launch it was seen in\n' +
             '\n'.join('%-14s %-10.3g %s' % (name, MARGINS[name][0], MARGINS[name][1]) for name in NAMES if name in MARGINS) +
-            '\nPEAK, PEAK_ROW, HIGH_COUNT, LOW_COUNT: bit-equal\n')
+            '\n' + ', '.join(NAMES[c] for c in EXACT) + ': bit-equal\n'
+            '\nthe stress family (tests/test_signatures_truth_host.py) against exact truth: the largest |got - truth| / bound, '
+            'the bound derived there (0 = equal to the correctly rounded truth; a bound of 0 admits nothing else): column, '
+            'margin, the launch it was seen in\n' +
+            '\n'.join('%-14s %-10.3g %s' % (name, STRESS_MARGINS[name][0], STRESS_MARGINS[name][1])
+                      for name in NAMES if name in STRESS_MARGINS) + '\n')
     print('\n' + text)
     out = os.environ.get('SMART_MARGINS_DIR')
     if out and os.path.isdir(out):
@@ -177,6 +170,29 @@ def test_signatures_are_the_statement(R):
     # without thresholds the four pulse columns are NaN and the other eight are what they were
     bare = launch(sim, with_obs, win, W, alpha, None)
     assert np.isnan(bare[:, HIGH_COUNT:]).all() and bits_equal(bare[:, :HIGH_COUNT], got[:, :HIGH_COUNT])
+
+
+@pytest.mark.parametrize('R', STRESS_R)
+def test_the_stress_family_is_the_exact_truth_within_its_bounds(R):
+    sim, obs, _, kinds = stress_case(R)
+    _, _, filler = data(9000 + R, R, FILLER)
+    matrix = np.concatenate([filler, sim], axis=1)                      # N = 65: the family in columns 35 .. 64
+    assert matrix.shape == (R, 65)
+    for W, win, pulse, want, bnd in stress_reference(R):
+        what = 'stress R=%d W=%d' % (R, W)
+        got = launch(matrix, obs, win, W, 0.925, pulse, pad=3)
+        hold(got[:, :, :FILLER], statement(filler, obs, win, W, 0.925, pulse), what + ', the benign columns beside it')
+        got = got[:, :, FILLER:]
+        ratio = margins(got, want, bnd)
+        for c, name in enumerate(NAMES):
+            worst = np.unravel_index(np.argmax(ratio[:, c]), ratio[:, c].shape)
+            print('%s %-14s %.3g (window %d, %s)' % (what, name, ratio[:, c][worst], worst[0], kinds[worst[1]]))
+            if ratio[:, c][worst] > STRESS_MARGINS.get(name, (-1.0, ''))[0]:
+                STRESS_MARGINS[name] = (float(ratio[:, c][worst]), '%s window %d %s' % (what, worst[0], kinds[worst[1]]))
+        assert np.array_equal(np.isnan(got), np.isnan(want)), what + ': the pattern of NaN'
+        assert np.isnan(got[:, AC1][:, CONSTANT_KINDS]).all(), what + ': a constant list has a variance of exactly 0'
+        assert np.all(ratio <= 1.0), '%s: %s' % (what, {NAMES[c]: float(ratio[:, c].max()) for c in range(12)
+                                                        if ratio[:, c].max() > 1.0})
 
 
 def test_both_kinds_of_run_occur_and_thresholds_are_strict():

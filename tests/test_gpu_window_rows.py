@@ -7,7 +7,11 @@ Every case is held to two things:
       compaction were folded into one: the fold changed no arithmetic and no order of summation, so smart_objfn_windows,
       smart_bootstrap_*, smart_signatures and smart_fdc_observed / smart_fdc_sort have to reproduce every bit (compared as
       int64: a NaN only equals a NaN of the same payload, -0.0 is not 0.0) -- the kept sample columns element by element,
-      the whole array through its sha256;
+      the whole array through its sha256.  AC1 of smart_signatures was re-centred since (each pair list about a member of
+      its own): the two signature arrays are held to the pins `<name>|but_ac1` -- the eleven other columns, every bit of
+      every sample, made by the library of the commit before that change, which reproduced the full-array pins first --
+      and AC1 of the kept columns to the exact truth of tests/test_signatures_truth_host.py within the bounds derived
+      there;
   (b) for smart_objfn_windows_hip, the numpy statement of tests/test_windows_host.py at the gate of
       tests/test_gpu_objfn_windows.py (rel < 1e-9, |want| floored at 1e-12) on the kept columns: whatever the parent did at
       a chunk boundary, the list has to be the right one.
@@ -19,6 +23,7 @@ import numpy as np
 import pytest
 
 from test_windows_host import statement, rel
+from test_signatures_truth_host import exact, bounds, margins
 
 pytestmark = pytest.mark.gpu
 
@@ -85,7 +90,16 @@ def test_the_parent_commits_bits_and_the_statement(eng, parent, R, N):
                                                                                  int(np.isnan(want).sum())))
                 assert err < GATE, (tag, transform)
             # (a) the parent commit's bits
+            reference = exact(sim[:, cols], obs, win, W)
+            bound = bounds(sim[:, cols], obs, win, W, reference=reference)[:, cases.AC1]
             for name, (a, axis) in got.items():
+                if name in cases.SIGNATURE_ARRAYS:
+                    ac1 = a[:, cases.AC1][:, cols]
+                    ratio = margins(ac1, reference[0][:, cases.AC1], bound)
+                    print('%s %s: AC1 at %.3g of its bound, %d NaN entries' % (tag, name, ratio.max(),
+                                                                              int(np.isnan(ac1).sum())))
+                    assert np.all(ratio <= 1.0), (tag, name)
+                    a, name = cases.but_ac1(a), name + cases.BUT_AC1
                 bits, sha = cases.kept(a, axis, N)
                 want_bits, want_sha = parent[cases.key(R, N, window_kind, obs_kind, name)]
                 assert np.array_equal(bits.ravel(), want_bits), (tag, name)
