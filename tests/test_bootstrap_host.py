@@ -22,7 +22,7 @@ import pytest
 
 from conftest import GOLDEN
 from test_windows_host import transformed, E_NULL, E_SIZE, E_NO_DEVICE, E_MODE
-from test_gpu_signatures import data
+from test_signatures_truth_host import data
 
 LD = np.longdouble
 GATE = 1e-9
@@ -160,7 +160,6 @@ def make_counts(rng, W, B):
     for b, row in enumerate(special[:B]):
         counts[b] = row
     return counts.astype(np.uint16)
-
 
 
 def worst(got, want, floor=1e-12):

@@ -2,7 +2,6 @@
 bench.py and MonteCarlo.run() (on the GPU box the same code runs over RCCL with one rank per GPU), the rank-0-only
 collection of the saved series, empty shards, and a rank that fails."""
 import os
-import shutil
 import socket
 import sys
 from datetime import timedelta
@@ -13,7 +12,8 @@ import torch
 import torch.distributed as dist
 import torch.multiprocessing as mp
 
-from conftest import ROOT, GOLDEN
+from conftest import ROOT
+from support import example_root, settings_file
 
 
 def _free_port():
@@ -81,13 +81,8 @@ def _oracle_simulate_ensemble(self, parameters, report='summary', objective_func
 
 
 def _make_root(tmp, days=120):
-    root = os.path.join(tmp, 'data')
-    shutil.copytree(os.path.join(GOLDEN, 'data', 'in'), os.path.join(root, 'in'))
-    with open(os.path.join(root, 'in', 'Catchment', 'Catchment.sttngs'), 'w') as f:
-        f.write('ARGUMENT,VALUE\ncatchment_area_km2,175.46\ngauged_area_km2,175.97\n'
-                'start_datetime,01/01/2007 09:00:00\nend_datetime,%s 09:00:00\nsimu_timedelta_min,60\n'
-                'report_timedelta_min,1440\nwarm_up_days,30\ngw_constraint,0.12667\n'
-                % ('30/04/2007' if days == 120 else '31/12/2007'))
+    root = example_root(tmp)
+    settings_file(root, 'Catchment.sttngs', '01/01/2007', '30/04/2007' if days == 120 else '31/12/2007', 30)
     return root
 
 

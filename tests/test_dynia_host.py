@@ -9,6 +9,7 @@ from fractions import Fraction
 import numpy as np
 import pytest
 
+from support import same
 from smartpy_amd import _lib, identifiability as ident
 
 EQUAL, LINEAR = 0, 1
@@ -107,12 +108,6 @@ def exact_shares(E_row, cat, n_bins, fraction, support):
         s, S = {n: Fraction(1) for n in rows}, Fraction(len(rows))
     return c, rows, [[sum((s[n] for n in rows if cat[p][n] == b), Fraction(0)) / S for b in range(n_bins)]
                      for p in range(len(cat))]
-
-
-def same(a, b):
-    """`==` everywhere, NaN where NaN."""
-    a, b = np.asarray(a), np.asarray(b)
-    return a.shape == b.shape and np.array_equal(a, b, equal_nan=True)
 
 
 # ---- a record worked by hand ------------------------------------------------------------------------------------------

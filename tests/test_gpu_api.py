@@ -1,26 +1,22 @@
 """The reference's Python surface on top of the HIP engine, end to end on the GPU: SMART from the example
 files, the Monte-Carlo classes and their database, the smartcpp-compatible module."""
 import os
-import shutil
 from datetime import datetime, timedelta
 
 import numpy as np
 import pytest
 
 from conftest import load_golden, GOLDEN
+from support import EXTRA, bits_equal, example_root, settings_file
 from oracle import smart_oracle as so
 from oracle import objfn_oracle
 
 pytestmark = pytest.mark.gpu
 
-EXTRA = {'aar': 1200, 'r-o_ratio': 0.45, 'r-o_split': (0.10, 0.15, 0.15, 0.30, 0.30)}
-
 
 @pytest.fixture()
 def root(tmp_path):
-    r = str(tmp_path / 'data')
-    shutil.copytree(os.path.join(GOLDEN, 'data', 'in'), os.path.join(r, 'in'))
-    return r
+    return example_root(tmp_path)
 
 
 def test_smart_from_files_reproduces_the_reference_unit_test(root):
@@ -120,23 +116,11 @@ def test_a_repeated_simulate_uploads_its_ten_parameters_and_nothing_else(example
     assert bits_equal(sm.simulate(dict(zip(names, base)))[0], first[0])
 
 
-def bits_equal(a, b):
-    a, b = np.ascontiguousarray(a, dtype=np.float64), np.ascontiguousarray(b, dtype=np.float64)
-    return a.shape == b.shape and np.array_equal(a.view(np.int64), b.view(np.int64))
-
-
-def _settings(root, name, start, end, warm):
-    with open(os.path.join(root, 'in', 'Catchment', name), 'w') as f:
-        f.write('ARGUMENT,VALUE\ncatchment_area_km2,175.46\ngauged_area_km2,175.97\nstart_datetime,%s 09:00:00\n'
-                'end_datetime,%s 09:00:00\nsimu_timedelta_min,60\nreport_timedelta_min,1440\nwarm_up_days,%d\n'
-                'gw_constraint,0.12667\n' % (start, end, warm))
-
-
 def test_monte_carlo_pipeline_lhs_glue_best_total(root, example):
     """LHS sampling on one period, then GLUE / Best / Total on another: files, formats and numbers."""
     from smartpy_amd.montecarlo import LHS, GLUE, Best, Total
-    _settings(root, 'Catchment.sampling.sttngs', '01/01/2007', '31/12/2008', 365)
-    _settings(root, 'Catchment.evaluating.sttngs', '01/01/2009', '31/12/2009', 365)
+    settings_file(root, 'Catchment.sampling.sttngs', '01/01/2007', '31/12/2008', 365)
+    settings_file(root, 'Catchment.evaluating.sttngs', '01/01/2009', '31/12/2009', 365)
     np.random.seed(7)
     lhs = LHS('Catchment', root, 'csv', 'csv', 300, save_sim=True, settings_filename='Catchment.sampling.sttngs')
     lhs.model.extra = EXTRA
@@ -206,7 +190,7 @@ def test_second_stages_on_the_device_pick_the_references_rows(root):
     with open(os.path.join(GOLDEN, 'kat12_selection.json')) as fh:
         cases = json.load(fh)
     params, fns = z['params'], z['obj_fns']
-    _settings(root, 'Catchment.sampling.sttngs', '01/01/2007', '31/12/2007', 180)
+    settings_file(root, 'Catchment.sampling.sttngs', '01/01/2007', '31/12/2007', 180)
     lhs = LHS('Catchment', root, 'csv', 'csv', 48, settings_filename='Catchment.sampling.sttngs')
     assert lhs.obj_fn_names[-1] == 'GW'
     lhs._set_sample(params.astype(np.float64))
@@ -245,8 +229,8 @@ def test_second_stages_from_the_device_and_device_sampling(root, example):
     (f3) LHS(device_sampling=True): the Latin hypercube is drawn on the GPU and stays there for the launch."""
     import torch
     from smartpy_amd.montecarlo import LHS, GLUE, Best, Total
-    _settings(root, 'Catchment.sampling.sttngs', '01/01/2007', '31/12/2007', 180)
-    _settings(root, 'Catchment.evaluating.sttngs', '01/01/2008', '30/06/2008', 90)
+    settings_file(root, 'Catchment.sampling.sttngs', '01/01/2007', '31/12/2007', 180)
+    settings_file(root, 'Catchment.evaluating.sttngs', '01/01/2008', '30/06/2008', 90)
     np.random.seed(11)
     lhs = LHS('Catchment', root, 'csv', 'csv', 1000, settings_filename='Catchment.sampling.sttngs')
     lhs.model.extra = EXTRA
@@ -371,7 +355,7 @@ def test_netcdf_in_and_out_through_the_dataset_double(root, monkeypatch):
             nc.createVariable(kind, np.float64, ('DateTime',))
             nc.variables['DateTime'][0:len(rows)] = stamps
             nc.variables[kind][0:len(rows)] = values
-    _settings(root, 'Catchment.short.sttngs', '01/01/2007', '31/12/2007', 100)
+    settings_file(root, 'Catchment.short.sttngs', '01/01/2007', '31/12/2007', 100)
     np.random.seed(3)
     a = LHS('Catchment', root, 'csv', 'csv', 40, save_sim=True, settings_filename='Catchment.short.sttngs')
     a.model.extra = EXTRA

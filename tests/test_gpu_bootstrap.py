@@ -15,7 +15,7 @@ zeros (NaN for every sample), row 2 a single window W times, row 3 with 65,535 s
 for.  With R = 1 every replicate has fewer than two rows or repeats one row, whose scores are 0 / 0: the case keeps to
 B = 2 (ones, zeros), all NaN.
 
-Data: the generator of tests/test_gpu_signatures.py; windows arange(R) * W // R with 10 % of the rows in no window.
+Data: the generator of tests/test_signatures_truth_host.py; windows arange(R) * W // R with 10 % of the rows in no window.
 
 Gates.  The pattern of NaN (and of infinities) is equal everywhere; point, replicates, MEAN and STD are held to `truth` at
 relative 1e-9 with |want| floored at 1e-12, every compared |want| asserted to be 0 or above 1e-6 (a seed that fails this
@@ -25,22 +25,20 @@ the order keys hold to be one value); point against smart_objfn_windows_hip with
 same gate.  The largest margin per column is printed at the end of the module (and written to
 $SMART_MARGINS_DIR/bootstrap_margins.txt where that is set); profiles/bootstrap_margins.txt is that table."""
 import os
-import shutil
 
 import numpy as np
 import pytest
 
-from conftest import GOLDEN
+from support import (EXTRA, Guarded, Margins, bits_equal, example_root, margins_dir, padded, same_values, settings_file,
+                     to_device, workspace)
 from test_windows_host import E_NULL, E_SIZE
-from test_gpu_signatures import data, same_values, bits_equal, _settings, EXTRA
+from test_signatures_truth_host import data
 from test_bootstrap_host import truth, inverted_cdf, windows_of, make_counts, worst, assert_comparable, NAMES, GATE
 
 pytestmark = pytest.mark.gpu
 
-SENTINEL = -7.0
-GUARD = 64
 PROBS = (0.05, 0.5, 0.95)
-MARGINS = {}            # column name -> (largest margin as a fraction of the gate, where it was seen)
+MARGINS = Margins()     # column name -> (largest margin as a fraction of the gate, where it was seen)
 CAP_W, CAP_B = 64, 4096
 # (R, N, W, B, transform)
 CASES = [(1, 65, 1, 2, 'none'), (2, 63, 1, 63, 'none'), (2, 257, 2, 1, 'none'), (9, 1, 2, 0, 'none'),
@@ -49,14 +47,10 @@ CASES = [(1, 65, 1, 2, 'none'), (2, 63, 1, 63, 'none'), (2, 257, 2, 1, 'none'), 
          (4097, 65, 11, 65, 'none'), (501, 300, 16, 257, 'none')]
 
 
-def guarded(torch, own):
-    return torch.full((2 * GUARD + max(own, 1),), SENTINEL, dtype=torch.float64, device='cuda')
-
-
 def launch(sim, obs, win, W, counts, transform='none', eps=0.0, probs=PROBS, pad=3, with_reps=True, expect=0, **over):
     """The C entry on a [R, N] host matrix laid out with ld = N + pad (the padding holds NaN) -> (point [N, 7], stats
-    [7, 2 + K, N] or None, replicates [B, 7, N] or None) as numpy.  Every output lies GUARD doubles inside a buffer of
-    SENTINEL; everything around what the call owns is checked to be as it was.  over: arguments of the entry to replace."""
+    [7, 2 + K, N] or None, replicates [B, 7, N] or None) as numpy.  Every output lies support.GUARD doubles inside a buffer of
+    support.SENTINEL; everything around what the call owns is checked to be as it was.  over: arguments of the entry to replace."""
     import ctypes
     import torch
     from smartpy_amd import _lib
@@ -64,43 +58,34 @@ def launch(sim, obs, win, W, counts, transform='none', eps=0.0, probs=PROBS, pad
     R, N = sim.shape
     counts = np.ascontiguousarray(counts, dtype=np.uint16).reshape(-1, W)
     B, K = counts.shape[0], len(probs)
-    host = np.full((R, N + pad), np.nan)
-    host[:, :N] = sim
-    d_sim = torch.from_numpy(host).cuda()
-    d_obs = torch.from_numpy(np.ascontiguousarray(obs, dtype=np.float64)).cuda()
-    d_win = torch.from_numpy(np.ascontiguousarray(win, dtype=np.int32)).cuda()
+    d_sim, ld = padded(sim, pad)
+    d_obs, d_win = to_device(obs), to_device(win, np.int32)
     d_counts = torch.from_numpy(counts.view(np.int16).copy()).cuda() if B else None
     q = (ctypes.c_double * max(K, 1))(*probs)
     sizes = [N * 7, 7 * (2 + K) * N if B else 0, B * 7 * N if with_reps else 0]
-    bufs = [guarded(torch, s) for s in sizes]
+    bufs = [Guarded(s) for s in sizes]
     need = int(L.smart_bootstrap_workspace_bytes(N, min(W, CAP_W), min(B, CAP_B), 1 if with_reps else 0))
-    work = torch.empty(max(need, 256), dtype=torch.uint8, device='cuda')
-    a = dict(n=N, r=R, ld=N + pad, w=W, b=B, k=K, transform=_lib.TRANSFORMS.get(transform, transform), eps=float(eps),
+    work = workspace(need, least=256)
+    a = dict(n=N, r=R, ld=ld, w=W, b=B, k=K, transform=_lib.TRANSFORMS.get(transform, transform), eps=float(eps),
              ws_bytes=need)
     a.update(over)
     rc = L.smart_objfn_bootstrap_hip(a['n'], a['r'], d_sim.data_ptr(), a['ld'], d_obs.data_ptr(), d_win.data_ptr(), a['w'],
                                      a['transform'], a['eps'], d_counts.data_ptr() if B else None, a['b'], q, a['k'],
-                                     bufs[0].data_ptr() + 8 * GUARD, bufs[1].data_ptr() + 8 * GUARD if B else None,
-                                     bufs[2].data_ptr() + 8 * GUARD if with_reps and B else None, work.data_ptr(),
-                                     a['ws_bytes'], torch.cuda.current_stream().cuda_stream)
+                                     bufs[0].ptr(), bufs[1].ptr(null=not B), bufs[2].ptr(null=not (with_reps and B)),
+                                     work.data_ptr(), a['ws_bytes'], torch.cuda.current_stream().cuda_stream)
     torch.cuda.synchronize()
     if expect:
         assert rc == expect, (rc, L.smart_last_error().decode())
-        assert all(bool((b == SENTINEL).all()) for b in bufs)
+        assert all(b.untouched() for b in bufs)
         return L.smart_last_error().decode()
     _lib.check(rc)
     out = []
-    for buf, own in zip(bufs, sizes):
-        h = buf.cpu().numpy()
-        assert np.all(h[:GUARD] == SENTINEL) and np.all(h[GUARD + own:] == SENTINEL)
-        out.append(h[GUARD:GUARD + own])
+    for buf in bufs:
+        own, intact = buf.read()
+        assert intact
+        out.append(own)
     return (out[0].reshape(N, 7), out[1].reshape(7, 2 + K, N) if B else None,
             out[2].reshape(B, 7, N) if with_reps and B else None)
-
-
-def note(column, err, what):
-    if err / GATE > MARGINS.get(column, (-1.0, ''))[0]:
-        MARGINS[column] = (err / GATE, what)
 
 
 def hold(got, want, what, probs=PROBS):
@@ -121,15 +106,15 @@ def hold(got, want, what, probs=PROBS):
         for kind, g, w in pairs:
             err = worst(g, w)
             print('%s %s %s %.3e' % (what, name, kind, err))
-            note(name, err, what + ' ' + kind)
+            MARGINS.note(name, err / GATE, what + ' ' + kind)
             assert err < GATE, '%s: %s of %s off by %.3e' % (what, kind, name, err)
     if stats is not None and reps is not None:
         got_q = np.transpose(stats[:, 2:], (1, 0, 2))                   # [K, 7, N]
-        assert same_values(got_q, inverted_cdf(reps, probs)), what + ': the quantiles'
+        assert same_values(got_q, inverted_cdf(reps, probs), any_nan=True), what + ': the quantiles'
         clean = ~np.isnan(reps).any(axis=0)                             # (numpy gives NaN for a column that holds one)
         if clean.any():
             numpy_says = np.quantile(reps, probs, axis=0, method='inverted_cdf')
-            assert same_values(got_q[:, clean], numpy_says[:, clean]), what + ': np.quantile'
+            assert same_values(got_q[:, clean], numpy_says[:, clean], any_nan=True), what + ': np.quantile'
 
 
 @pytest.fixture(scope='module', autouse=True)
@@ -141,11 +126,7 @@ def _print_the_margins():
             '1e-9 with |want| floored at 1e-12), over point, replicates, MEAN and STD: column, margin, where it was seen\n' +
             '\n'.join('%-6s %-10.3g %s' % (name, MARGINS[name][0], MARGINS[name][1]) for name in NAMES if name in MARGINS) +
             '\nquantiles: the elements np.quantile(method=inverted_cdf) names on the replicates, bit for bit\n')
-    print('\n' + text)
-    out = os.environ.get('SMART_MARGINS_DIR')
-    if out and os.path.isdir(out):
-        with open(os.path.join(out, 'bootstrap_margins.txt'), 'w') as fh:
-            fh.write(text)
+    MARGINS.publish(text, margins_dir(), 'bootstrap_margins.txt')
 
 
 def case_inputs(R, n, W, B):
@@ -191,7 +172,7 @@ def test_bootstrap_is_the_truth(case):
     one = engine.objective_functions_windows(sim, obs, np.where(win >= 0, 0, -1).astype(np.int32), n_windows=1,
                                              transform=transform, eps=eps).cpu().numpy()[0]
     err = worst(point, one)
-    note('point', err, what + ' against smart_objfn_windows_hip')
+    MARGINS.note('point', err / GATE, what + ' against smart_objfn_windows_hip')
     assert err < GATE, what
 
 
@@ -264,9 +245,9 @@ def test_engine_surface():
     ids = np.minimum(np.arange(R) * 3 // R, 2).astype(np.int32)         # 0, 1, 2 occur; window 3 never does
     counts = engine.bootstrap_counts(W, B, seed=5, eligible=[1, 1, 1, 0])
     want = truth(sim, obs, ids, W, counts, 'sqrt', 0.0, (0.1, 0.9))
-    padded = torch.full((R, n + 63), float('nan'), dtype=torch.float64, device='cuda')
-    padded[:, :n] = torch.from_numpy(sim).cuda()
-    res = engine.objective_functions_bootstrap(padded[:, :n], torch.from_numpy(obs).cuda(), torch.from_numpy(ids).cuda(),
+    wide = torch.full((R, n + 63), float('nan'), dtype=torch.float64, device='cuda')
+    wide[:, :n] = torch.from_numpy(sim).cuda()
+    res = engine.objective_functions_bootstrap(wide[:, :n], torch.from_numpy(obs).cuda(), torch.from_numpy(ids).cuda(),
                                                counts, probs=(0.1, 0.9), n_windows=W, transform='sqrt', replicates=True)
     assert res.point.is_cuda and tuple(res.point.shape) == (n, 7) and tuple(res.stats.shape) == (7, 4, n)
     assert tuple(res.replicates.shape) == (B, 7, n) and res.stats[1, 2].is_contiguous()
@@ -296,9 +277,8 @@ def test_through_the_model(tmp_path):
     from smartpy_amd import engine, windows as swin
     from smartpy_amd.montecarlo import LHS
     from smartpy_amd.montecarlo.selection import as_stored
-    root = str(tmp_path / 'data')
-    shutil.copytree(os.path.join(GOLDEN, 'data', 'in'), os.path.join(root, 'in'))
-    _settings(root, 'Catchment.sampling.sttngs', '01/01/2007', '31/12/2010', 180)
+    root = example_root(tmp_path)
+    settings_file(root, 'Catchment.sampling.sttngs', '01/01/2007', '31/12/2010', 180)
     np.random.seed(2025)
     n = 70
     lhs = LHS('Catchment', root, 'csv', 'csv', sample_size=n, settings_filename='Catchment.sampling.sttngs')

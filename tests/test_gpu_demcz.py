@@ -8,15 +8,12 @@ The test plays the density: it copies the launch rows to the host, evaluates a q
 scores; the statement gets the same numbers.  The one device operation that is not correctly rounded by definition is
 log(u), so every comparison first asserts that the statement's smallest decision margin is far above what a last-bit
 difference of a logarithm can move."""
-import os
-import shutil
 
 import numpy as np
 import pytest
 
-from conftest import GOLDEN
+from support import EXTRA, Guarded, example_root, same_bits, settings_file
 from test_demcz_host import Chains, demcz_statement, log_density, LOGP, RMSE, RMSE_SIGMA
-from test_gpu_quantiles import EXTRA
 
 pytestmark = pytest.mark.gpu
 
@@ -26,34 +23,18 @@ ARRAYS = ('x', 'logp', 'carry', 'accepted', 'proposal', 'out', 'archive', 'archi
 MARGIN = 1e-12
 
 
-def same_bits(a, b):
-    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
-    return a.shape == b.shape and a.dtype == b.dtype and a.tobytes() == b.tobytes()
-
-
 def into_guards(state):
     """Every array of the state moved into the middle of a buffer of its own with GUARD sentinels on either side -> the
     buffers, by name."""
-    import torch
     buffers = {}
     for name in ARRAYS:
         t = getattr(state, name)
-        sentinel = SENTINEL[str(t.dtype).split('.')[-1]]
-        flat = torch.full((t.numel() + 2 * GUARD,), sentinel, dtype=t.dtype, device=t.device)
-        inner = flat[GUARD:GUARD + t.numel()].view(t.shape)
+        dtype = str(t.dtype).split('.')[-1]
+        buffers[name] = Guarded(t.numel(), dtype=dtype, guard=GUARD, sentinel=SENTINEL[dtype])
+        inner = buffers[name].inner().view(t.shape)
         inner.copy_(t)
         setattr(state, name, inner)
-        buffers[name] = flat
     return buffers
-
-
-def guards_intact(buffers):
-    for name, flat in buffers.items():
-        host = flat.cpu().numpy()
-        sentinel = SENTINEL[str(host.dtype)]
-        if not ((host[:GUARD] == sentinel).all() and (host[-GUARD:] == sentinel).all()):
-            return False
-    return True
 
 
 def quadratic(lo, hi, width=0.2):
@@ -162,7 +143,7 @@ def test_the_step_is_the_statement_bit_for_bit(name):
     smallest, _ = run_both(s, t, quadratic(s.lo, s.hi))
     assert smallest > MARGIN, 'a decision of this seed hangs on the last bits of log(u): take another seed'
     compare(s, t)
-    assert guards_intact(buffers)
+    assert all(b.intact() for b in buffers.values())
     assert s.M == len(s.archive) == t.capacity              # the appends filled the capacity exactly
     assert (s.accepted < 40).all() and (N == 1 or s.accepted.sum() > 0)      # (NaN and -inf scores were rejected)
     if name == 'above-a-wave-d16-fallback':
@@ -205,7 +186,7 @@ def test_a_box_as_narrow_as_the_archive_makes_out_proposals():
         seen += int(out.sum())
     assert seen > 0
     compare(s, t)
-    assert s.M == len(s.archive) and guards_intact(buffers)
+    assert s.M == len(s.archive) and all(b.intact() for b in buffers.values())
 
 
 def test_nan_and_minus_infinity_reject_and_plus_infinity_accepts():
@@ -325,13 +306,6 @@ def test_the_score_kinds_that_compute_on_the_device(kind):
 
 
 # ---- montecarlo.DEMCz end to end --------------------------------------------------------------------------------------
-def _daily_settings(root, name, start, end, warm):
-    with open(os.path.join(root, 'in', 'Catchment', name), 'w') as f:
-        f.write('ARGUMENT,VALUE\ncatchment_area_km2,175.46\ngauged_area_km2,175.97\nstart_datetime,%s 09:00:00\n'
-                'end_datetime,%s 09:00:00\nsimu_timedelta_min,1440\nreport_timedelta_min,1440\nwarm_up_days,%d\n'
-                'gw_constraint,0.12667\n' % (start, end, warm))
-
-
 def _sampler(root, **kw):
     from smartpy_amd.montecarlo import DEMCz
     args = dict(chains=256, generations=60, thin=5, seed=3, settings_filename='Catchment.demcz.sttngs')
@@ -344,9 +318,8 @@ def _sampler(root, **kw):
 def test_demcz_end_to_end(tmp_path):
     import torch
     from smartpy_amd.montecarlo import GLUE
-    root = str(tmp_path / 'data')
-    shutil.copytree(os.path.join(GOLDEN, 'data', 'in'), os.path.join(root, 'in'))
-    _daily_settings(root, 'Catchment.demcz.sttngs', '01/01/2007', '31/12/2009', 180)
+    root = example_root(tmp_path)
+    settings_file(root, 'Catchment.demcz.sttngs', '01/01/2007', '31/12/2009', 180, simu_minutes=1440)
     runs = []
     for _ in range(2):
         obj = _sampler(root)
@@ -399,9 +372,8 @@ def test_demcz_end_to_end(tmp_path):
 def test_demcz_accepted_counts_are_the_changes_of_the_archive(tmp_path):
     """thin = 1: every generation is a snapshot, so the proposals accepted are the state changes between consecutive
     snapshots; with a part of the parameters fixed and the groundwater constraint as a prior."""
-    root = str(tmp_path / 'data')
-    shutil.copytree(os.path.join(GOLDEN, 'data', 'in'), os.path.join(root, 'in'))
-    _daily_settings(root, 'Catchment.demcz.sttngs', '01/01/2007', '31/12/2007', 90)
+    root = example_root(tmp_path)
+    settings_file(root, 'Catchment.demcz.sttngs', '01/01/2007', '31/12/2007', 90, simu_minutes=1440)
     vary = ['T', 'SK', 'FK', 'GK']
     obj = _sampler(root, chains=64, generations=12, thin=1, burn_in=0.0, vary=vary, fixed={'C': 0.5}, gw_prior=True, seed=4)
     obj.run()

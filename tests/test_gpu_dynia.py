@@ -20,19 +20,18 @@ retained compare with `==`, and the shares within 2 (K + 2) 2**-53 relative, K =
 non-negative terms in another order).  The largest share of each tolerance that was used is printed at the end of the
 module (and written to $SMART_MARGINS_DIR/dynia_margins.txt where that is set); profiles/dynia_margins.txt is that table."""
 import os
-import shutil
 from fractions import Fraction
 
 import numpy as np
 import pytest
 
-from conftest import GOLDEN
-from test_dynia_host import dynia_statement, exact_sums, same, EQUAL, LINEAR, U
-from test_gpu_quantiles import EXTRA, _settings
+from support import (EXTRA, SENTINEL, Margins, example_root, filled, margins_dir, padded, same, same_bits, settings_file, to_device,
+                     workspace)
+from test_dynia_host import dynia_statement, exact_sums, EQUAL, LINEAR, U
 
 pytestmark = pytest.mark.gpu
 
-MARGINS = {}            # what -> (largest share of its tolerance, where it was seen)
+MARGINS = Margins()     # what -> (largest share of its tolerance, where it was seen)
 SMALL = 2048            # the largest N of the small instance of smart_dynia_shares (smart_dynia.hip: kDyniaSmallCapacity)
 
 
@@ -44,30 +43,24 @@ def capacity():
 def launch(sim, obs, cat, B, h, min_valid, fraction, support, pad=0, junk=np.nan, spare=0, ws_steps=None, keep=True,
            pad_err=0):
     """The C entry on a [R, N] host matrix laid out with ld = N + pad (the padding holds `junk`) -> dict of numpy arrays:
-    shares [R + spare, P, B], cut, retained, count [R + spare] (the spare rows as they were before the call: -7), err
+    shares [R + spare, P, B], cut, retained, count [R + spare] (the spare rows as they were before the call: SENTINEL), err
     [R + spare, N + pad_err] or None.  The workspace is what the helper entry asks for, or exactly `ws_steps` steps."""
     import torch
     from smartpy_amd import _lib
     L = _lib.lib()
-    sim = np.asarray(sim, dtype=np.float64)
-    R, N = sim.shape
+    R, N = np.shape(sim)
     P = len(cat)
-    host = np.full((R, N + pad), junk)
-    host[:, :N] = sim
-    d_sim = torch.from_numpy(host).cuda()
-    d_obs = torch.from_numpy(np.ascontiguousarray(obs, dtype=np.float64)).cuda()
-    d_cat = torch.from_numpy(np.ascontiguousarray(cat, dtype=np.uint8)).cuda()
-    shares = torch.full((R + spare, P, B), -7.0, dtype=torch.float64, device='cuda')
-    cut = torch.full((R + spare,), -7.0, dtype=torch.float64, device='cuda')
-    retained = torch.full((R + spare,), -7, dtype=torch.int32, device='cuda')
-    count = torch.full((R + spare,), -7, dtype=torch.int32, device='cuda')
-    err = torch.full((R + spare, N + pad_err), -7.0, dtype=torch.float64, device='cuda') if keep else None
+    d_sim, ld = padded(sim, pad, junk)
+    d_obs, d_cat = to_device(obs), to_device(cat, np.uint8)
+    shares, cut = filled((R + spare, P, B)), filled((R + spare,))
+    retained, count = filled((R + spare,), 'int32'), filled((R + spare,), 'int32')
+    err = filled((R + spare, N + pad_err)) if keep else None
     need = int(L.smart_dynia_workspace_bytes(N, R, h, P, B))
     if ws_steps is not None:
         need = ws_steps * int(L.smart_dynia_workspace_bytes(N, 1, h, P, B))
     assert need >= 0
-    work = torch.empty(max(need, 1), dtype=torch.uint8, device='cuda')
-    _lib.check(L.smart_dynia_hip(N, R, d_sim.data_ptr(), N + pad, d_obs.data_ptr(), h, min_valid, float(fraction),
+    work = workspace(need, least=1)
+    _lib.check(L.smart_dynia_hip(N, R, d_sim.data_ptr(), ld, d_obs.data_ptr(), h, min_valid, float(fraction),
                                  d_cat.data_ptr(), P, B, support, shares.data_ptr(), cut.data_ptr(), retained.data_ptr(),
                                  count.data_ptr(), None if err is None else err.data_ptr(), N + pad_err, work.data_ptr(),
                                  need, torch.cuda.current_stream().cuda_stream))
@@ -75,17 +68,8 @@ def launch(sim, obs, cat, B, h, min_valid, fraction, support, pad=0, junk=np.nan
                 count=count.cpu().numpy(), err=None if err is None else err.cpu().numpy())
 
 
-def same_bits(a, b):
-    return a.shape == b.shape and a.dtype == b.dtype and a.tobytes() == b.tobytes()
-
-
 def all_same_bits(a, b, keys=('shares', 'cut', 'retained', 'count')):
     return all(same_bits(a[k], b[k]) for k in keys)
-
-
-def note(what, share, where):
-    if share > MARGINS.get(what, (-1.0, ''))[0]:
-        MARGINS[what] = (share, where)
 
 
 @pytest.fixture(scope='module', autouse=True)
@@ -99,11 +83,7 @@ def _print_the_margins():
             '\n'.join('%-9s %-10.3g %s' % (name, MARGINS[name][0], MARGINS[name][1]) for name in sorted(MARGINS)) +
             '\ncut and retained of the general data: equal to the statement on the returned err\n'
             'exact cases (integers 0 .. 15): bit for bit\n')
-    print('\n' + text)
-    out = os.environ.get('SMART_MARGINS_DIR')
-    if out and os.path.isdir(out):
-        with open(os.path.join(out, 'dynia_margins.txt'), 'w') as fh:
-            fh.write(text)
+    MARGINS.publish(text, margins_dir(), 'dynia_margins.txt')
 
 
 # ---- exact cases ------------------------------------------------------------------------------------------------------
@@ -159,8 +139,8 @@ def test_exact_cases(size):
                 assert same(got['shares'][:R], want['shares']), where
                 assert (want['retained'] >= want['k']).all()
                 # the spare rows and the padding of err are untouched
-                assert (got['shares'][R:] == -7).all() and got['cut'][R] == -7 and got['retained'][R] == -7
-                assert got['count'][R] == -7 and (got['err'][R:] == -7).all() and (got['err'][:, N:] == -7).all()
+                assert (got['shares'][R:] == SENTINEL).all() and got['cut'][R] == SENTINEL and got['retained'][R] == SENTINEL
+                assert got['count'][R] == SENTINEL and (got['err'][R:] == SENTINEL).all() and (got['err'][:, N:] == SENTINEL).all()
                 if support == LINEAR and R in (3 * w + 1, 100):
                     # the same bits from a second launch, without err (the sums in the workspace), and whatever the
                     # batches: a workspace of one step, of two, of all
@@ -227,7 +207,7 @@ def test_general_data(h, N):
                     continue
                 share = float(abs(Fraction(float(got['err'][r, n])) - exact[r][j]) / ((w + 2) * U * exact[r][j]))
                 print('err', where, r, n, share) if share > 0.5 else None
-                note('err', share, where)
+                MARGINS.note('err', share, where)
                 assert share <= 1.0, (where, r, n, share)
         with np.errstate(invalid='ignore', divide='ignore'):
             falls = got['err'][:-1] / got['err'][1:]
@@ -245,7 +225,7 @@ def test_general_data(h, N):
             a, b = got['shares'][r], want['shares'][r]
             assert ((b == 0) == (a == 0)).all(), (where, r)
             share = float((np.abs(a - b)[b > 0] / (tol * b[b > 0])).max())
-            note('shares', share, where)
+            MARGINS.note('shares', share, where)
             assert share <= 1.0, (where, r, share)
         assert np.allclose(got['shares'][assessed][:, 0].sum(axis=1), 1.0, rtol=1e-12, atol=0)
         # the same bits without err, and from the batches of a small workspace
@@ -314,9 +294,8 @@ def test_a_planted_parameter_is_the_one_identified():
 def test_lhs_dynamic_identifiability_end_to_end(tmp_path):
     from smartpy_amd.montecarlo import LHS
     from smartpy_amd import engine, identifiability as ident
-    root = str(tmp_path / 'data')
-    shutil.copytree(os.path.join(GOLDEN, 'data', 'in'), os.path.join(root, 'in'))
-    _settings(root, 'Catchment.sampling.sttngs', '01/01/2007', '31/12/2007', 180)
+    root = example_root(tmp_path)
+    settings_file(root, 'Catchment.sampling.sttngs', '01/01/2007', '31/12/2007', 180)
     np.random.seed(2024)
     lhs = LHS('Catchment', root, 'csv', 'csv', sample_size=300, settings_filename='Catchment.sampling.sttngs')
     lhs.model.extra = EXTRA

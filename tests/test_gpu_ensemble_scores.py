@@ -19,21 +19,20 @@ The exact cases compare with `same`: `==` everywhere, NaN for NaN.  The cases wi
 of each tolerance that was used is printed at the end of the module (and written to
 $SMART_MARGINS_DIR/ensemble_scores_margins.txt where that is set); profiles/ensemble_scores_margins.txt is that table."""
 import os
-import shutil
 
 import numpy as np
 import pytest
 
-from conftest import GOLDEN
+from support import (EXTRA, NSE_MIN, SENTINEL, Margins, example_root, filled, margins_dir, padded, ptr, same, same_bits,
+                     settings_file, to_device, workspace)
 from test_ensemble_scores_host import (yardstick, yardstick_rows, assert_all_exact, as_floats, statement, shares,
                                        CRPS, SPREAD, PIT_LOW, PIT_HIGH, MEAN)
-from test_gpu_quantiles import EXTRA, NSE_MIN, _settings
 
 pytestmark = pytest.mark.gpu
 
 AUTO, LDS, GLOBAL = 0, 1, 2
 NAMES = ('CRPS', 'SPREAD', 'PIT_LOW', 'PIT_HIGH', 'MEAN')
-MARGINS = {}            # column name -> (largest share of its tolerance, where it was seen)
+MARGINS = Margins()     # column name -> (largest share of its tolerance, where it was seen)
 
 
 def capacity():
@@ -43,39 +42,24 @@ def capacity():
 
 def launch(matrix, weights, obs, method, pad=0, junk=np.nan, spare=0, ws_steps=None):
     """The C entry on a [R, N] host matrix laid out with ld = N + pad (the padding holds `junk`) -> numpy [5, R] (with
-    `spare` more rows below, as they were before the call: -7.0).  The workspace is what the helper entry asks for, or
+    `spare` more rows below, as they were before the call: SENTINEL).  The workspace is what the helper entry asks for, or
     exactly `ws_steps` steps."""
     import torch
     from smartpy_amd import _lib
     L = _lib.lib()
-    matrix = np.asarray(matrix, dtype=np.float64)
-    R, N = matrix.shape
-    host = np.full((R, N + pad), junk)
-    host[:, :N] = matrix
-    sim = torch.from_numpy(host).cuda()
-    w = None if weights is None else torch.from_numpy(np.ascontiguousarray(weights, dtype=np.float64)).cuda()
-    y = None if obs is None else torch.from_numpy(np.ascontiguousarray(obs, dtype=np.float64)).cuda()
-    out = torch.full((5 + spare, R), -7.0, dtype=torch.float64, device='cuda')
+    R, N = np.shape(matrix)
+    sim, ld = padded(matrix, pad, junk)
+    w, y = to_device(weights), to_device(obs)
+    out = filled((5 + spare, R))
     weighted = 0 if w is None else 1
     need = int(L.smart_ensemble_scores_workspace_bytes(N, R, weighted, method))
     if ws_steps is not None:
         need = ws_steps * int(L.smart_ensemble_scores_workspace_bytes(N, 1, weighted, method))
     assert need >= 0
-    work = torch.empty(need, dtype=torch.uint8, device='cuda') if need else None
-    _lib.check(L.smart_ensemble_scores_hip(N, R, sim.data_ptr(), N + pad, None if w is None else w.data_ptr(),
-                                           None if y is None else y.data_ptr(), out.data_ptr(), method,
-                                           None if work is None else work.data_ptr(), need,
-                                           torch.cuda.current_stream().cuda_stream))
+    work = workspace(need)
+    _lib.check(L.smart_ensemble_scores_hip(N, R, sim.data_ptr(), ld, ptr(w), ptr(y), out.data_ptr(), method, ptr(work),
+                                           need, torch.cuda.current_stream().cuda_stream))
     return out.cpu().numpy()
-
-
-def same(a, b):
-    """`==` everywhere (so -0.0 is 0.0), NaN where NaN."""
-    return a.shape == b.shape and np.array_equal(a, b, equal_nan=True)
-
-
-def same_bits(a, b):
-    return a.shape == b.shape and np.array_equal(a.view(np.int64), b.view(np.int64))
 
 
 def forms(N):
@@ -87,8 +71,7 @@ def record(got, exact_rows, x, w, what):
     for r, exact in enumerate(exact_rows):
         used = shares(got[:, r], exact, x[r], w)
         for name, share in used.items():
-            if share > MARGINS.get(name, (-1.0, ''))[0]:
-                MARGINS[name] = (share, what)
+            MARGINS.note(name, share, what)
         assert all(v <= 1.0 for v in used.values()), (what, r, used)
 
 
@@ -102,11 +85,7 @@ def _print_the_margins():
             'N 2**-53 sum w |x| / W: column, share, where it was seen\n' +
             '\n'.join('%-9s %-10.3g %s' % (name, MARGINS[name][0], MARGINS[name][1]) for name in NAMES if name in MARGINS) +
             '\nexact cases (small-integer members, weights whose sum is a power of two): bit for bit\n')
-    print('\n' + text)
-    out = os.environ.get('SMART_MARGINS_DIR')
-    if out and os.path.isdir(out):
-        with open(os.path.join(out, 'ensemble_scores_margins.txt'), 'w') as fh:
-            fh.write(text)
+    MARGINS.publish(text, margins_dir(), 'ensemble_scores_margins.txt')
 
 
 # ---- exact cases ------------------------------------------------------------------------------------------------------
@@ -280,8 +259,8 @@ def test_leading_dimension_spare_rows_and_two_launches(size):
     for m in forms(N):
         plain = launch(x, w, obs, m)
         assert not np.isnan(plain).any()
-        padded = launch(x, w, obs, m, pad=5, junk=np.nan, spare=2)
-        assert padded.shape == (7, 5) and same_bits(padded[:5], plain) and (padded[5:] == -7.0).all()
+        roomy = launch(x, w, obs, m, pad=5, junk=np.nan, spare=2)
+        assert roomy.shape == (7, 5) and same_bits(roomy[:5], plain) and (roomy[5:] == SENTINEL).all()
         assert same_bits(launch(x, w, obs, m, pad=1, junk=1e300), plain)
         assert same_bits(launch(x, w, obs, m), plain)               # two launches give the same bits
         assert same_bits(launch(x, None, obs, m), launch(x, None, obs, m, pad=3))
@@ -340,10 +319,9 @@ def test_engine_against_the_c_entry():
 def test_glue_ensemble_verification_end_to_end(tmp_path):
     from smartpy_amd.montecarlo import LHS, GLUE
     from smartpy_amd import verification
-    root = str(tmp_path / 'data')
-    shutil.copytree(os.path.join(GOLDEN, 'data', 'in'), os.path.join(root, 'in'))
-    _settings(root, 'Catchment.sampling.sttngs', '01/01/2007', '31/12/2007', 180)
-    _settings(root, 'Catchment.evaluating.sttngs', '01/01/2008', '30/06/2008', 90)
+    root = example_root(tmp_path)
+    settings_file(root, 'Catchment.sampling.sttngs', '01/01/2007', '31/12/2007', 180)
+    settings_file(root, 'Catchment.evaluating.sttngs', '01/01/2008', '30/06/2008', 90)
     np.random.seed(2024)
     lhs = LHS('Catchment', root, 'csv', 'csv', sample_size=256, settings_filename='Catchment.sampling.sttngs')
     lhs.model.extra = EXTRA

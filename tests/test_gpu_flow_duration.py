@@ -11,52 +11,23 @@ functions are held to the gate the suite holds smart_objfn_hip and the windows k
 < 1e-9 with |want| floored at 1e-12, every compared |want| asserted above 1e-6 (a seed that fails this is changed, not the
 gate)."""
 import os
-import shutil
 
 import numpy as np
 import pytest
 
-from conftest import GOLDEN
-from test_windows_host import rel, TRANSFORMS
+from support import (EXTRA, Guarded, bits_equal, columns, data, example_root, padded, ptr, rel_to_want, same_values,
+                     settings_file, to_device, window_arrays, workspace)
+from test_windows_host import TRANSFORMS
 from test_flow_duration_host import statement, rank_of, CAPACITY, E_SIZE
 
 pytestmark = pytest.mark.gpu
 
-EXTRA = {'aar': 1200, 'r-o_ratio': 0.45, 'r-o_split': (0.10, 0.15, 0.15, 0.30, 0.30)}
 EPS = {'none': 0.0, 'sqrt': 0.0, 'log': 0.05, 'inverse': 0.05}
 METHODS = {'auto': 0, 'sort': 1, 'select': 2}
 GATE = 1e-9
-SENTINEL = -7.0
-GUARD = 64
 # R -> the N it is run with (COLS of the instance: 16, 16, 16, 16, 8, 4, 2, 1; select beyond)
 SHAPES = {1: (1, 17, 65), 2: (1, 15, 65), 501: (1, 15, 17, 1000), 1024: (5, 63), 1025: (3, 15, 17, 65), 4096: (3, 4, 5, 63),
           4097: (1, 3, 5, 65), 16384: (1, 3, 17), 16385: (5, 65)}
-
-
-def same_values(a, b):
-    """bit-equal, a zero against a zero of either sign included"""
-    a, b = np.ascontiguousarray(a, dtype=np.float64), np.ascontiguousarray(b, dtype=np.float64)
-    return a.shape == b.shape and bool(np.all((a.view(np.int64) == b.view(np.int64)) | ((a == 0.0) & (b == 0.0))))
-
-
-def bits_equal(a, b):
-    a, b = np.ascontiguousarray(a, dtype=np.float64), np.ascontiguousarray(b, dtype=np.float64)
-    return a.shape == b.shape and np.array_equal(a.view(np.int64), b.view(np.int64))
-
-
-def data(seed, R, n):
-    rng = np.random.default_rng(seed)
-    obs = np.abs(rng.normal(3.0, 1.5, R)) + 0.05
-    obs[rng.random(R) < 0.15] = np.nan
-    sim = rng.random((R, n)) * 6 + 0.01
-    return rng, obs, sim
-
-
-def window_arrays(rng, R):
-    sixteen = (np.arange(R) * 16 // R).astype(np.int32)
-    sixteen[rng.random(R) < 0.10] = -1
-    return [(1, np.zeros(R, dtype=np.int32)), (2, (np.arange(R) >= R // 2).astype(np.int32)),
-            (7, (np.arange(R) % 7).astype(np.int32)), (16, sixteen)]
 
 
 def probabilities(obs, win, W):
@@ -74,7 +45,7 @@ def probabilities(obs, win, W):
 def launch(sim, probs, obs=None, win=None, W=1, transform='none', eps=0.0, segment=(0.0, 1.0), objfn=False, method='auto',
            pad=0, expect=0):
     """The C entry on a [R, N] host matrix laid out with ld = N + pad (the padding holds NaN) -> (quant [W, K, N], objfn
-    [W, N, 7] or None) as numpy.  Both outputs lie GUARD doubles inside a buffer of SENTINEL with a spare window behind
+    [W, N, 7] or None) as numpy.  Both outputs lie support.GUARD doubles inside a buffer of support.SENTINEL with a spare window behind
     them; everything around what the call owns is checked to be as it was."""
     import ctypes
     import torch
@@ -82,41 +53,35 @@ def launch(sim, probs, obs=None, win=None, W=1, transform='none', eps=0.0, segme
     L = _lib.lib()
     R, N = sim.shape
     K = len(probs)
-    host = np.full((R, N + pad), np.nan)
-    host[:, :N] = sim
-    d_sim = torch.from_numpy(host).cuda()
-    d_obs = None if obs is None else torch.from_numpy(np.ascontiguousarray(obs, dtype=np.float64)).cuda()
-    d_win = None if win is None else torch.from_numpy(np.ascontiguousarray(win, dtype=np.int32)).cuda()
+    d_sim, ld = padded(sim, pad)
+    d_obs, d_win = to_device(obs), to_device(win, np.int32)
     q = np.ascontiguousarray(probs, dtype=np.float64)
-    quant = torch.full((2 * GUARD + (W + 1) * K * N,), SENTINEL, dtype=torch.float64, device='cuda')
-    scores = torch.full((2 * GUARD + (W + 1) * N * 7,), SENTINEL, dtype=torch.float64, device='cuda')
+    quant = Guarded(W * K * N, tail=K * N)
+    own = W * N * 7 if objfn else 0                                     # (not asked for: the whole buffer stays as it was)
+    scores = Guarded(own, tail=(W + 1) * N * 7 - own)
     need = L.smart_flow_duration_workspace_bytes(R, W, 1 if objfn else 0)
-    work = torch.zeros(max(need, 8), dtype=torch.uint8, device='cuda') if objfn else None
-    rc = L.smart_flow_duration_hip(N, R, d_sim.data_ptr(), N + pad, None if d_obs is None else d_obs.data_ptr(),
-                                   None if d_win is None else d_win.data_ptr(), W,
-                                   q.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), K, quant.data_ptr() + 8 * GUARD,
+    work = workspace(need, least=8, fill=0) if objfn else None
+    rc = L.smart_flow_duration_hip(N, R, d_sim.data_ptr(), ld, ptr(d_obs), ptr(d_win), W,
+                                   q.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), K, quant.ptr(),
                                    TRANSFORMS[transform], float(eps), float(segment[0]), float(segment[1]),
-                                   scores.data_ptr() + 8 * GUARD if objfn else None,
-                                   None if work is None else work.data_ptr(), need if objfn else 0, METHODS[method],
+                                   scores.ptr(null=not objfn), ptr(work), need if objfn else 0, METHODS[method],
                                    torch.cuda.current_stream().cuda_stream)
     torch.cuda.synchronize()
     if expect:
         assert rc == expect, (rc, L.smart_last_error().decode())
-        assert bool((quant == SENTINEL).all()) and bool((scores == SENTINEL).all())
+        assert quant.untouched() and scores.untouched()
         return L.smart_last_error().decode()
     _lib.check(rc)
-    quant, scores = quant.cpu().numpy(), scores.cpu().numpy()
-    for buf, own in ((quant, W * K * N), (scores, W * N * 7 if objfn else 0)):
-        assert np.all(buf[:GUARD] == SENTINEL) and np.all(buf[GUARD + own:] == SENTINEL)
-    return (quant[GUARD:GUARD + W * K * N].reshape(W, K, N),
-            scores[GUARD:GUARD + W * N * 7].reshape(W, N, 7) if objfn else None)
+    (quant, ok_q), (scores, ok_s) = quant.read(), scores.read()
+    assert ok_q and ok_s
+    return quant.reshape(W, K, N), scores.reshape(W, N, 7) if objfn else None
 
 
 @pytest.mark.parametrize('R', sorted(SHAPES))
 def test_order_statistics_are_the_statement_bit_for_bit(R):
     for n in SHAPES[R]:
-        rng, obs, sim = data(100 * R + n, R, n)
-        variants = window_arrays(rng, R)
+        rng, obs, sim = data(100 * R + n, R, n, obs_plus=0.05)
+        variants = window_arrays(rng, R, 'zeros')
         for W, win in variants:
             for with_obs in (obs, None):
                 if R > CAPACITY and with_obs is None and W != 16:
@@ -141,7 +106,7 @@ def test_order_statistics_are_the_statement_bit_for_bit(R):
 
 def test_empty_windows_ties_zeros_and_values_that_are_not_finite():
     R, n, W = 501, 37, 5
-    rng, obs, sim = data(9, R, n)
+    rng, obs, sim = data(9, R, n, obs_plus=0.05)
     win = (np.arange(R) * 4 // R).astype(np.int32)                      # 0 .. 3 occur, window 4 never does
     obs[win == 1] = np.nan                                              # every observation missing: empty as well
     sim[:, 0] = 2.5                                                     # an all-equal column
@@ -165,13 +130,9 @@ def test_empty_windows_ties_zeros_and_values_that_are_not_finite():
     assert same_values(launch(sim, probs, None, win, W)[0], free)
 
 
-def columns(rng, n):
-    return np.unique(np.concatenate([[0, n - 1], rng.integers(0, n, 10)]))
-
-
 def compare(got, want, what):
     finite = want[~np.isnan(want)]
-    err = rel(got, want)
+    err = rel_to_want(got, want)
     print('%s: rel %.3e, smallest |want| %.3e, NaN entries %d' % (what, err, np.min(np.abs(finite)) if finite.size else -1,
                                                                   int(np.isnan(want).sum())))
     assert finite.size == 0 or np.min(np.abs(finite)) > 1e-6, what      # (change the seed, not the gate)
@@ -180,10 +141,10 @@ def compare(got, want, what):
 
 @pytest.mark.parametrize('R,n', [(501, 17), (1025, 15), (4097, 5), (16384, 3)])
 def test_objective_functions_of_the_curve(R, n):
-    rng, obs, sim = data(7000 + R, R, n)
-    cols = columns(rng, n)
+    rng, obs, sim = data(7000 + R, R, n, obs_plus=0.05)
+    cols = columns(rng, n, 10)
     probs = [0.05, 0.5, 0.95]
-    for W, win in window_arrays(rng, R)[:3] if R > 501 else window_arrays(rng, R):
+    for W, win in window_arrays(rng, R, 'zeros')[:3] if R > 501 else window_arrays(rng, R, 'zeros'):
         for transform in ('none', 'sqrt', 'log', 'inverse'):
             for segment in ((0.0, 1.0), (0.98, 1.0), (0.0, 0.3)):
                 if R * (segment[1] - segment[0]) / W < 4:
@@ -199,7 +160,7 @@ def test_objective_functions_of_the_curve(R, n):
 
 def test_the_two_rules_of_the_curve():
     R, n, W = 501, 20, 4
-    rng, obs, sim = data(31, R, n)
+    rng, obs, sim = data(31, R, n, obs_plus=0.05)
     win = (np.arange(R) * 3 // R).astype(np.int32)                      # 0 .. 2 occur, window 3 never does
     one = np.flatnonzero(win == 1)
     obs[one] = np.nan
@@ -241,7 +202,7 @@ def test_the_two_rules_of_the_curve():
 
 def test_beyond_the_capacity_is_refused_not_rerouted():
     R, n = CAPACITY + 1, 3
-    rng, obs, sim = data(5, R, n)
+    rng, obs, sim = data(5, R, n, obs_plus=0.05)
     win = (np.arange(R) % 16).astype(np.int32)
     text = launch(sim, [0.5], obs, win, 16, objfn=True, expect=E_SIZE)
     assert str(CAPACITY) in text and 'objective functions' in text
@@ -257,13 +218,13 @@ def test_engine_surface():
     import torch
     from smartpy_amd import engine
     R, n = 501, 130
-    rng, obs, sim = data(41, R, n)
+    rng, obs, sim = data(41, R, n, obs_plus=0.05)
     ids = (np.arange(R) % 3).astype(np.int32)
     probs = [0.1, 0.5, 0.9]
     want_q, want = statement(sim, probs, obs, ids, 4, 'sqrt', 0.0, (0.0, 0.3), objfn=True)
-    padded = torch.full((R, n + 63), float('nan'), dtype=torch.float64, device='cuda')
-    padded[:, :n] = torch.from_numpy(sim).cuda()
-    quant, scores = engine.flow_duration(padded[:, :n], probs, torch.from_numpy(obs).cuda(), torch.from_numpy(ids).cuda(),
+    wide = torch.full((R, n + 63), float('nan'), dtype=torch.float64, device='cuda')
+    wide[:, :n] = torch.from_numpy(sim).cuda()
+    quant, scores = engine.flow_duration(wide[:, :n], probs, torch.from_numpy(obs).cuda(), torch.from_numpy(ids).cuda(),
                                          n_windows=4, transform='sqrt', segment=(0.0, 0.3), objfn=True)
     assert quant.is_cuda and quant.dtype == torch.float64 and tuple(quant.shape) == (4, 3, n)
     assert scores.is_cuda and tuple(scores.shape) == (4, n, 7)
@@ -294,20 +255,12 @@ def test_a_matrix_without_a_report_step_is_refused_in_the_entrys_own_words():
     assert str(e.value).startswith('smart_flow_duration_hip: need n_samples, n_reports'), str(e.value)
 
 
-def _settings(root, name, start, end, warm):
-    with open(os.path.join(root, 'in', 'Catchment', name), 'w') as f:
-        f.write('ARGUMENT,VALUE\ncatchment_area_km2,175.46\ngauged_area_km2,175.97\nstart_datetime,%s 09:00:00\n'
-                'end_datetime,%s 09:00:00\nsimu_timedelta_min,60\nreport_timedelta_min,1440\nwarm_up_days,%d\n'
-                'gw_constraint,0.12667\n' % (start, end, warm))
-
-
 def test_through_the_model(tmp_path):
     from smartpy_amd.montecarlo import LHS
     from smartpy_amd.montecarlo.selection import condition_mask
     from smartpy_amd.windows import evaluation_windows, fdc_header_line, non_exceedance, observed_duration
-    root = str(tmp_path / 'data')
-    shutil.copytree(os.path.join(GOLDEN, 'data', 'in'), os.path.join(root, 'in'))
-    _settings(root, 'Catchment.sampling.sttngs', '01/01/2007', '31/12/2007', 180)
+    root = example_root(tmp_path)
+    settings_file(root, 'Catchment.sampling.sttngs', '01/01/2007', '31/12/2007', 180)
     np.random.seed(2025)
     n = 256
     lhs = LHS('Catchment', root, 'csv', 'csv', sample_size=n, settings_filename='Catchment.sampling.sttngs')
@@ -344,7 +297,7 @@ def test_through_the_model(tmp_path):
                            res.values.astype(np.float32).transpose(1, 0, 2).reshape(n, 14)], axis=1)
     assert [line.split(',') for line in lines[1:-1]] == [['%.6e' % v for v in row] for row in kept]
     back = np.array([[float(v) for v in line.split(',')] for line in lines[1:-1]])
-    assert back.shape == (n, 32) and rel(back, kept.astype(np.float64)) <= 5.0e-7
+    assert back.shape == (n, 32) and rel_to_want(back, kept.astype(np.float64)) <= 5.0e-7
     # a low-flow score: ln(Q + eps) over the bottom 30 % of the ranks, eps from the observations
     low = lhs.flow_duration_curves(exceedance=(0.7, 0.95), windows='all', transform='log', segment=(0.0, 0.3))
     assert low.file is None and low.labels == ['all'] and low.eps == float(np.mean(obs[~np.isnan(obs)])) / 100.0

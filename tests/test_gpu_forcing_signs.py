@@ -30,6 +30,7 @@ import os
 import numpy as np
 import pytest
 
+from support import Margins, bits_equal, excess, rel, eng      # noqa: F401 (eng is a fixture)
 from oracle import smart_oracle as so
 from oracle import objfn_oracle
 
@@ -41,35 +42,9 @@ cases = importlib.util.module_from_spec(_spec)
 _spec.loader.exec_module(cases)
 
 REL_FAST = 1e-9
-EXCESS_GATE, FUZZ_GATE = 0.1, 0.5       # the two gates of tests/test_gpu_parity.py on an excess()
+EXCESS_GATE, FUZZ_GATE = 0.1, 0.5       # the two gates of tests/test_gpu_parity.py on a support.excess()
 GATE = EXCESS_GATE                      # (the module docstring has the measurement behind the choice)
-MARGINS = {}        # (quantity, kernel) -> (largest margin seen in this run, the launch it was seen in)
-
-
-def excess(got, want, rtol, top=None, top_frac=1e-13, tiny=1e-40):
-    """Largest |got - want| / (rtol * |want| + top_frac * top + tiny): tests/test_gpu_parity.py has the story"""
-    got, want = np.asarray(got, float), np.asarray(want, float)
-    assert got.shape == want.shape and want.size
-    if top is None:
-        top = np.abs(want).max(axis=-1, keepdims=True) if want.ndim > 1 else np.abs(want).max()
-    with np.errstate(invalid='ignore', divide='ignore'):
-        r = np.abs(got - want) / (rtol * np.abs(want) + top_frac * top + tiny)
-    return float(np.nanmax(np.where(np.abs(got - want) == 0, 0.0, r)))
-
-
-def rel(a, b):
-    """max |a - b| / max(|a|, |b|) (tests/test_gpu_parity.py)"""
-    a, b = np.asarray(a, float), np.asarray(b, float)
-    m = np.maximum(np.abs(a), np.abs(b))
-    with np.errstate(invalid='ignore', divide='ignore'):
-        r = np.where(m > 0, np.abs(a - b) / m, 0.0)
-    return float(np.max(r)) if r.size else 0.0
-
-
-def bits_equal(a, b):
-    a = np.ascontiguousarray(a, dtype=np.float64)
-    b = np.ascontiguousarray(b, dtype=np.float64)
-    return a.shape == b.shape and np.array_equal(a.view(np.int64), b.view(np.int64))
+MARGINS = Margins()  # (quantity, kernel) -> (largest margin seen in this run, the launch it was seen in)
 
 
 def hold(quantity, kernel, tag, margin, gate=None):
@@ -109,15 +84,7 @@ def _print_the_margins():
     text = ('margins of this run against the reference-exact oracle (1.0 = the tolerance; discharge, gw and final are held to '
             '%.2g, the scores to 1): quantity, kernel, largest margin, the launch it was seen in\n' % GATE + '\n'.join(lines) +
             '\nlargest by quantity: ' + ', '.join('%s %.3g' % kv for kv in sorted(worst.items())) + '\n')
-    print('\n' + text)
-
-
-@pytest.fixture(scope='module')
-def eng():
-    import torch
-    assert torch.cuda.is_available(), 'these tests need the GPU'
-    from smartpy_amd import engine
-    return engine
+    MARGINS.publish(text)
 
 
 @functools.lru_cache(maxsize=None)

@@ -22,6 +22,7 @@ import os
 import numpy as np
 import pytest
 
+from support import Margins, margins_dir, padded, eng      # noqa: F401 (eng is a fixture)
 from test_objfn_truth_host import (BIG_CASE, LOG_EPS, MATRIX_CASES, SPECIAL_CASES, WINDOW_CASES, big_columns, bootstrap_case,
                                    bootstrap_reference, bounds, first_observed, matrix_case, truth, window_case,
                                    window_reference)
@@ -29,18 +30,14 @@ from test_objfn_truth_host import (BIG_CASE, LOG_EPS, MATRIX_CASES, SPECIAL_CASE
 pytestmark = pytest.mark.gpu
 
 PAD = 3             # ld = N + 3, the padding holds NaN
-MARGINS = {}
+MARGINS = Margins()
 PATHS = ['smart_objfn_hip', 'smart_objfn_hip, one lane per sample', 'smart_objfn_windows_hip none',
          'smart_objfn_windows_hip log', 'smart_objfn_bootstrap_hip point', 'smart_objfn_bootstrap_hip jackknife']
 
 
 def on_device(sim):
     """[R, N] host matrix -> the [R, N] view of a device matrix with ld = N + PAD whose padding holds NaN"""
-    import torch
-    R, N = sim.shape
-    host = np.full((R, N + PAD), np.nan)
-    host[:, :N] = sim
-    return torch.from_numpy(host).cuda()[:, :N]
+    return padded(sim, PAD)[0][:, :sim.shape[1]]
 
 
 def hold(path, what, got, want, bnd):
@@ -52,8 +49,7 @@ def hold(path, what, got, want, bnd):
     worst = float(np.max(used)) if used.size else 0.0
     where = np.unravel_index(int(np.argmax(used)), used.shape) if used.size else ()
     print('%s: %s: %.3g of the bound at %s' % (path, what, worst, where))
-    if worst > MARGINS.get(path, (-1.0, ''))[0]:
-        MARGINS[path] = (worst, what)
+    MARGINS.note(path, worst, what)
     assert np.array_equal(np.isnan(got), np.isnan(want)), '%s: %s: the pattern of NaN' % (path, what)
     assert np.array_equal(got[~finite & ~np.isnan(want)], want[~finite & ~np.isnan(want)]), '%s: %s: infinities' % (path, what)
     assert np.array_equal(np.isfinite(got), finite), '%s: %s: the pattern of infinities' % (path, what)
@@ -70,11 +66,7 @@ def _print_the_margins():
             'additions may differ by): path, fraction, where it was seen\n' +
             '\n'.join('%-38s %-10.3g %s' % (p, MARGINS[p][0], MARGINS[p][1])
                       for p in PATHS + sorted(set(MARGINS) - set(PATHS)) if p in MARGINS) + '\n')
-    print('\n' + text)
-    out = os.environ.get('SMART_MARGINS_DIR')
-    if out and os.path.isdir(out):
-        with open(os.path.join(out, 'objfn_conditioning_margins.txt'), 'w') as fh:
-            fh.write(text)
+    MARGINS.publish(text, margins_dir(), 'objfn_conditioning_margins.txt')
 
 
 # ---- smart_objfn_hip ---------------------------------------------------------------------------------------------------
@@ -272,12 +264,6 @@ def fused_launch(eng, name, days, setup, store, time_slices=0):
                              want_final=final, want_discharge=store, time_slices=time_slices)
     assert kernel in what and ' + ' not in what, what
     return got, obs, r1, kernel.rstrip('['), what
-
-
-@pytest.fixture(scope='module')
-def eng():
-    from smartpy_amd import engine
-    return engine
 
 
 @pytest.mark.parametrize('name', [l[0] for l in cases.LAUNCHES])

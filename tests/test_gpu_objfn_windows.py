@@ -7,40 +7,18 @@ full chunks.  The gate is the one the suite holds smart_objfn_hip to against the
 |want| floored at 1e-12; every compared |want| is asserted to be above 1e-6, so that no entry sits on a cancellation
 (a seed that fails this is changed, not the gate)."""
 import os
-import shutil
 
 import numpy as np
 import pytest
 
-from conftest import GOLDEN
-from test_windows_host import statement, rel, TRANSFORMS
+from support import (EXTRA, SENTINEL, bits_equal, columns, data, example_root, filled, padded, rel_to_want, settings_file,
+                     to_device, window_arrays)
+from test_windows_host import statement, TRANSFORMS
 
 pytestmark = pytest.mark.gpu
 
-EXTRA = {'aar': 1200, 'r-o_ratio': 0.45, 'r-o_split': (0.10, 0.15, 0.15, 0.30, 0.30)}
 EPS = {'none': 0.0, 'sqrt': 0.0, 'log': 0.05, 'inverse': 0.05}
 GATE = 1e-9
-SENTINEL = -7.0
-
-
-def bits_equal(a, b):
-    a, b = np.ascontiguousarray(a, dtype=np.float64), np.ascontiguousarray(b, dtype=np.float64)
-    return a.shape == b.shape and np.array_equal(a.view(np.int64), b.view(np.int64))
-
-
-def data(seed, R, n):
-    rng = np.random.default_rng(seed)
-    obs = np.abs(rng.normal(3.0, 1.5, R))
-    obs[rng.random(R) < 0.15] = np.nan
-    sim = rng.random((R, n)) * 6 + 0.01
-    return rng, obs, sim
-
-
-def window_arrays(rng, R):
-    sixteen = (np.arange(R) * 16 // R).astype(np.int32)
-    sixteen[rng.random(R) < 0.10] = -1
-    return [(1, np.zeros(R, dtype=np.int32)), (2, (np.arange(R) >= R // 2).astype(np.int32)),
-            (7, (np.arange(R) % 7).astype(np.int32)), (16, sixteen)]
 
 
 def launch(sim, obs, win, W, transform, eps, pad=0, junk=np.nan, spare=1):
@@ -50,27 +28,20 @@ def launch(sim, obs, win, W, transform, eps, pad=0, junk=np.nan, spare=1):
     from smartpy_amd import _lib
     L = _lib.lib()
     R, N = sim.shape
-    host = np.full((R, N + pad), junk)
-    host[:, :N] = sim
-    d_sim = torch.from_numpy(host).cuda()
-    d_obs = torch.from_numpy(np.ascontiguousarray(obs, dtype=np.float64)).cuda()
-    d_win = torch.from_numpy(np.ascontiguousarray(win, dtype=np.int32)).cuda()
-    out = torch.full((W + spare, N, 7), SENTINEL, dtype=torch.float64, device='cuda')
-    _lib.check(L.smart_objfn_windows_hip(N, R, d_sim.data_ptr(), N + pad, d_obs.data_ptr(), d_win.data_ptr(), W,
+    d_sim, ld = padded(sim, pad, junk)
+    d_obs, d_win = to_device(obs), to_device(win, np.int32)
+    out = filled((W + spare, N, 7))
+    _lib.check(L.smart_objfn_windows_hip(N, R, d_sim.data_ptr(), ld, d_obs.data_ptr(), d_win.data_ptr(), W,
                                          TRANSFORMS[transform], float(eps), out.data_ptr(),
                                          torch.cuda.current_stream().cuda_stream))
     torch.cuda.synchronize()
     return out.cpu().numpy()
 
 
-def columns(rng, n):
-    return np.unique(np.concatenate([[0, n - 1], rng.integers(0, n, 12)]))
-
-
 def compare(got, sim, obs, win, W, transform, eps, cols, what):
     want = statement(sim[:, cols], obs, win, W, transform, eps)
     finite = want[~np.isnan(want)]
-    err = rel(got[:W][:, cols], want)
+    err = rel_to_want(got[:W][:, cols], want)
     print('%s: rel %.3e, smallest |want| %.3e, NaN entries %d' % (what, err, np.min(np.abs(finite)) if finite.size else -1,
                                                                   int(np.isnan(want).sum())))
     assert finite.size == 0 or np.min(np.abs(finite)) > 1e-6, what      # (change the seed, not the gate)
@@ -81,9 +52,9 @@ def compare(got, sim, obs, win, W, transform, eps, cols, what):
 @pytest.mark.parametrize('n,ld', [(1, 1), (63, 64), (64, 64), (65, 128), (1000, 1000), (4097, 4160)])
 def test_geometries_windows_and_transforms(n, ld):
     R = 501
-    rng, obs, sim = data(1000 + n, R, n)
-    cols = columns(rng, n)
-    for W, win in window_arrays(rng, R):
+    rng, obs, sim = data(1000 + n, R, n, obs_plus=0.0)
+    cols = columns(rng, n, 12)
+    for W, win in window_arrays(rng, R, 'zeros'):
         for transform in ('none', 'sqrt', 'log', 'inverse'):
             got = launch(sim, obs, win, W, transform, EPS[transform], pad=ld - n)
             assert got.shape == (W + 1, n, 7) and np.all(got[W] == SENTINEL)
@@ -96,9 +67,9 @@ def test_as_many_windows_as_one_call_takes():
     from smartpy_amd import engine
     W = engine.objfn_max_windows()
     R, n = 2 * W, 65
-    rng, obs, sim = data(77, R, n)
+    rng, obs, sim = data(77, R, n, obs_plus=0.0)
     win = (np.arange(R) // 2).astype(np.int32)      # two report steps each: a window that misses one of them is NaN
-    cols = columns(rng, n)
+    cols = columns(rng, n, 12)
     for transform in ('none', 'log'):
         got = launch(sim, obs, win, W, transform, EPS[transform])
         want = compare(got, sim, obs, win, W, transform, EPS[transform], cols, 'W=%d %s' % (W, transform))
@@ -109,7 +80,7 @@ def test_as_many_windows_as_one_call_takes():
 
 def test_the_two_rules():
     R, n, W = 501, 130, 6
-    rng, obs, sim = data(5, R, n)
+    rng, obs, sim = data(5, R, n, obs_plus=0.0)
     win = (np.arange(R) * 5 // R).astype(np.int32)                     # 0 .. 4 occur, window 5 never does
     obs[win == 1] = np.nan                                              # every observation missing
     two = np.flatnonzero(win == 2)
@@ -151,19 +122,19 @@ def test_one_definition_two_kernels():
     import torch
     from smartpy_amd import engine
     R, n = 501, 4097
-    rng, obs, sim = data(11, R, n)
+    rng, obs, sim = data(11, R, n, obs_plus=0.0)
     d_sim = torch.from_numpy(sim).cuda()
     whole = engine.objective_functions(d_sim, obs).cpu().numpy()[:, :7]
     mine = engine.objective_functions_windows(d_sim, obs, np.zeros(R, dtype=np.int64))
     assert mine.shape == (1, n, 7) and mine.dtype == torch.float64 and mine.is_cuda
-    err = rel(mine.cpu().numpy()[0], whole)
+    err = rel_to_want(mine.cpu().numpy()[0], whole)
     print('windows kernel against smart_objfn_hip, %d columns: rel %.3e' % (n, err))
     assert err < GATE
     # the engine's other inputs: a device tensor of ids, a padded view, n_windows beyond the largest id
-    padded = torch.full((R, n + 63), float('nan'), dtype=torch.float64, device='cuda')
-    padded[:, :n] = d_sim
+    wide = torch.full((R, n + 63), float('nan'), dtype=torch.float64, device='cuda')
+    wide[:, :n] = d_sim
     ids = torch.from_numpy((np.arange(R) % 3).astype(np.int32)).cuda()
-    a = engine.objective_functions_windows(padded[:, :n], torch.from_numpy(obs).cuda(), ids, n_windows=4,
+    a = engine.objective_functions_windows(wide[:, :n], torch.from_numpy(obs).cuda(), ids, n_windows=4,
                                            transform='sqrt').cpu().numpy()
     b = launch(sim, obs, np.arange(R) % 3, 4, 'sqrt', 0.0, spare=0)
     assert a.shape == (4, n, 7) and bits_equal(a, b) and np.isnan(a[3]).all() and not np.isnan(a[:3]).any()
@@ -175,22 +146,15 @@ def test_one_definition_two_kernels():
 
 def test_determinism_and_bounds():
     R, n = 501, 1000
-    rng, obs, sim = data(23, R, n)
-    for W, win in window_arrays(rng, R):
+    rng, obs, sim = data(23, R, n, obs_plus=0.0)
+    for W, win in window_arrays(rng, R, 'zeros'):
         for transform in ('none', 'log'):
             first = launch(sim, obs, win, W, transform, EPS[transform])
             again = launch(sim, obs, win, W, transform, EPS[transform])
             assert bits_equal(first, again)
             assert np.all(first[W] == SENTINEL)                         # the spare window is untouched
-            padded = launch(sim, obs, win, W, transform, EPS[transform], pad=37, junk=np.nan)
-            assert bits_equal(first, padded)                            # NaN in the columns [n, ld) changes nothing
-
-
-def _settings(root, name, start, end, warm):
-    with open(os.path.join(root, 'in', 'Catchment', name), 'w') as f:
-        f.write('ARGUMENT,VALUE\ncatchment_area_km2,175.46\ngauged_area_km2,175.97\nstart_datetime,%s 09:00:00\n'
-                'end_datetime,%s 09:00:00\nsimu_timedelta_min,60\nreport_timedelta_min,1440\nwarm_up_days,%d\n'
-                'gw_constraint,0.12667\n' % (start, end, warm))
+            wide = launch(sim, obs, win, W, transform, EPS[transform], pad=37, junk=np.nan)
+            assert bits_equal(first, wide)                              # NaN in the columns [n, ld) changes nothing
 
 
 def test_through_the_model(tmp_path):
@@ -198,10 +162,9 @@ def test_through_the_model(tmp_path):
     from smartpy_amd.montecarlo import LHS, GLUE
     from smartpy_amd.montecarlo.selection import condition_mask
     from smartpy_amd.windows import evaluation_windows, header_line
-    root = str(tmp_path / 'data')
-    shutil.copytree(os.path.join(GOLDEN, 'data', 'in'), os.path.join(root, 'in'))
-    _settings(root, 'Catchment.sampling.sttngs', '01/01/2007', '31/12/2007', 180)
-    _settings(root, 'Catchment.evaluating.sttngs', '01/01/2008', '30/06/2008', 90)
+    root = example_root(tmp_path)
+    settings_file(root, 'Catchment.sampling.sttngs', '01/01/2007', '31/12/2007', 180)
+    settings_file(root, 'Catchment.evaluating.sttngs', '01/01/2008', '30/06/2008', 90)
     np.random.seed(2024)
     lhs = LHS('Catchment', root, 'csv', 'csv', sample_size=64, settings_filename='Catchment.sampling.sttngs')
     lhs.model.extra = EXTRA
@@ -215,17 +178,17 @@ def test_through_the_model(tmp_path):
     assert res.labels == labels and res.transform == 'none' and res.eps == 0.0 and res.file is None
     assert res.values.shape == (2, n, 7) and res.device_values.is_cuda and res.names[0] == 'NSE'
     assert bits_equal(res.values, res.device_values.cpu().numpy())
-    err = rel(res.values, statement(sim, obs, ids, 2))
+    err = rel_to_want(res.values, statement(sim, obs, ids, 2))
     print('hydrological years against the statement: rel %.3e' % err)
     assert err < GATE
     whole = lhs.window_objective_functions('all')
-    err = rel(whole.values[0], lhs.obj_fns[:, :7])
+    err = rel_to_want(whole.values[0], lhs.obj_fns[:, :7])
     print("'all' against the fused moments of run(): rel %.3e" % err)
     assert whole.labels == ['all'] and err < GATE
     # eps=None: one hundredth of the mean observation for 'log', and the value is reported
     logs = lhs.window_objective_functions((ids, labels), transform='log', write=True)
     assert logs.eps == float(np.mean(obs[~np.isnan(obs)])) / 100.0 and logs.eps > 0.0
-    err = rel(logs.values, statement(sim, obs, ids, 2, 'log', logs.eps))
+    err = rel_to_want(logs.values, statement(sim, obs, ids, 2, 'log', logs.eps))
     print('log flows against the statement: rel %.3e' % err)
     assert err < GATE
     assert logs.file == lhs.windows_file and os.path.normpath(logs.file) == os.path.join(root, 'out', 'Catchment', 'Catchment.SMART.lhs.windows')
@@ -236,7 +199,7 @@ def test_through_the_model(tmp_path):
     kept = logs.values.astype(np.float32).transpose(1, 0, 2).reshape(n, 14)
     assert [line.split(',') for line in lines[1:-1]] == [['%.6e' % v for v in row] for row in kept]
     back = np.array([[float(v) for v in line.split(',')] for line in lines[1:-1]])
-    assert back.shape == (n, 14) and rel(back, kept.astype(np.float64)) <= 5.0e-7
+    assert back.shape == (n, 14) and rel_to_want(back, kept.astype(np.float64)) <= 5.0e-7
     # GLUE from that run, conditioned per window of its own period
     threshold = float(np.median(lhs.obj_fns[:, 0]))
     glue = GLUE('Catchment', root, 'csv', 'csv', conditioning={'NSE': ('min', (threshold,))}, sampling=lhs,

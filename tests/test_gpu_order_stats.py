@@ -19,6 +19,8 @@ import os
 import numpy as np
 import pytest
 
+from support import eng        # noqa: F401 (a fixture)
+
 pytestmark = pytest.mark.gpu
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -26,14 +28,6 @@ _spec = importlib.util.spec_from_file_location('make_order_stats_parent',
                                                os.path.join(HERE, 'golden', 'make_order_stats_parent.py'))
 cases = importlib.util.module_from_spec(_spec)
 _spec.loader.exec_module(cases)
-
-
-@pytest.fixture(scope='module')
-def eng():
-    import torch
-    assert torch.cuda.is_available(), 'these tests need the GPU'
-    from smartpy_amd import engine
-    return engine
 
 
 @pytest.fixture(scope='module')

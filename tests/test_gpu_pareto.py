@@ -2,7 +2,7 @@
 integers: every comparison is exact equality of int32 arrays, no tolerance anywhere.
 
 Launch conditions (launch below): the score matrix has C = M + 2 columns of which M are selected, in an order that is not
-ascending, NaN in the two that are not, ld = C + 3 with NaN in the padding; dominated_by lies GUARD integers inside a
+ascending, NaN in the two that are not, ld = C + 3 with NaN in the padding; dominated_by lies support.GUARD integers inside a
 buffer of sentinels whose guards are checked; every launch is made twice and the two answers compared.
 
 Shapes stand on both sides of every switch the implementation has: the wavefront (63 / 64 / 65 rows), the workgroup of
@@ -12,22 +12,19 @@ their loop trips of 8, 4, 2, 1 challengers with a ragged end, and the slices of 
 last slice of 63 challengers; E = 1,025 (L = 72) has 17 challengers in slice 14 and NONE in slice 15.  E is the number of
 rows that take part: the cases that aim at a slice boundary run with eligible=None and without NaN, where E = N."""
 import os
-import shutil
 
 import numpy as np
 import pytest
 
-from conftest import GOLDEN
+from support import EXTRA, Guarded, example_root, padded, settings_file, to_device, ptr
 from test_pareto_host import pareto_statement, pareto_rank_statement, pareto_keys, dominance_counts
 
 pytestmark = pytest.mark.gpu
 
 SENTINEL = -77
-GUARD = 64            # int32 entries around dominated_by
 WGUARD = 256         # bytes around the workspace (its parts stay on the boundaries the kernels' wide loads like)
 WORDS = ['max', 'min', ('target', 0.5)]
 CODES = {'max': 0, 'min': 1, 'target': 2}
-EXTRA = {'aar': 1200, 'r-o_ratio': 0.45, 'r-o_split': (0.10, 0.15, 0.15, 0.30, 0.30)}
 
 
 def directions(M):
@@ -62,10 +59,8 @@ def launch(scores, words, cols, eligible=None, pad=3, twice=True):
     L = _lib.lib()
     N, C = scores.shape
     M = len(words)
-    host = np.full((N, C + pad), np.nan)
-    host[:, :C] = scores
-    d_s = torch.from_numpy(host).cuda()
-    d_e = None if eligible is None else torch.from_numpy(np.ascontiguousarray(eligible, dtype=np.uint8)).cuda()
+    d_s, ld = padded(scores, pad)
+    d_e = to_device(eligible, np.uint8)
     code = (ctypes.c_int32 * M)(*[CODES[w[0] if isinstance(w, tuple) else w] for w in words])
     target = (ctypes.c_double * M)(*[w[1] if isinstance(w, tuple) else float('nan') for w in words])
     col = (ctypes.c_int32 * M)(*cols)
@@ -73,17 +68,15 @@ def launch(scores, words, cols, eligible=None, pad=3, twice=True):
     assert need > 0
     answers = []
     for _ in range(2 if twice else 1):
-        work = torch.full((need + 2 * WGUARD,), 0x5a, dtype=torch.uint8, device='cuda')
-        buf = torch.full((N + 2 * GUARD,), SENTINEL, dtype=torch.int32, device='cuda')
-        rc = L.smart_pareto_counts_hip(N, d_s.data_ptr(), C + pad, col, code, target, M,
-                                       None if d_e is None else d_e.data_ptr(), buf.data_ptr() + 4 * GUARD,
-                                       work.data_ptr() + WGUARD, need, torch.cuda.current_stream().cuda_stream)
+        work = Guarded(need, dtype='uint8', guard=WGUARD, sentinel=0x5a)
+        buf = Guarded(N, dtype='int32', sentinel=SENTINEL)              # (GUARD int32 entries around dominated_by)
+        rc = L.smart_pareto_counts_hip(N, d_s.data_ptr(), ld, col, code, target, M, ptr(d_e), buf.ptr(), work.ptr(), need,
+                                       torch.cuda.current_stream().cuda_stream)
         torch.cuda.synchronize()
         _lib.check(rc)
-        flat, around = buf.cpu().numpy(), work.cpu().numpy()
-        assert np.all(flat[:GUARD] == SENTINEL) and np.all(flat[GUARD + N:] == SENTINEL)
-        assert np.all(around[:WGUARD] == 0x5a) and np.all(around[WGUARD + need:] == 0x5a)
-        answers.append(flat[GUARD:GUARD + N].copy())
+        (counts, around_counts), (_, around_work) = buf.read(), work.read()
+        assert around_counts and around_work
+        answers.append(counts.copy())
     if twice:
         assert np.array_equal(answers[0], answers[1])
     assert answers[0].dtype == np.int32
@@ -239,21 +232,13 @@ def test_pareto_rows_from_numpy_and_from_a_device_tensor():
     assert len(everything) == int((~np.isnan(fns).any(axis=1)).sum())
 
 
-def _settings(root, name, start, end, warm):
-    with open(os.path.join(root, 'in', 'Catchment', name), 'w') as f:
-        f.write('ARGUMENT,VALUE\ncatchment_area_km2,175.46\ngauged_area_km2,175.97\nstart_datetime,%s 09:00:00\n'
-                'end_datetime,%s 09:00:00\nsimu_timedelta_min,60\nreport_timedelta_min,1440\nwarm_up_days,%d\n'
-                'gw_constraint,0.12667\n' % (start, end, warm))
-
-
 def test_pareto_end_to_end(tmp_path):
     from datetime import datetime
     from smartpy_amd.montecarlo import LHS, Pareto
     from smartpy_amd.montecarlo.selection import as_stored
-    root = str(tmp_path / 'data')
-    shutil.copytree(os.path.join(GOLDEN, 'data', 'in'), os.path.join(root, 'in'))
-    _settings(root, 'Catchment.sampling.sttngs', '01/01/2007', '30/09/2007', 90)
-    _settings(root, 'Catchment.evaluating.sttngs', '01/01/2008', '31/03/2008', 30)
+    root = example_root(tmp_path)
+    settings_file(root, 'Catchment.sampling.sttngs', '01/01/2007', '30/09/2007', 90)
+    settings_file(root, 'Catchment.evaluating.sttngs', '01/01/2008', '31/03/2008', 30)
     np.random.seed(2025)
     lhs = LHS('Catchment', root, 'csv', 'csv', sample_size=256, settings_filename='Catchment.sampling.sttngs')
     lhs.model.extra = EXTRA

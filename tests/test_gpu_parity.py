@@ -6,6 +6,7 @@ Gates
                  fp64 bit patterns; and within 1e-11 of the reference-exact oracle / the reference's own values.
   fast mode    : relative difference <= 1e-9 on discharge (contract of BASELINE.json: 1e-6), 1e-10 on gw.
 """
+import functools
 import math
 import os
 
@@ -13,6 +14,7 @@ import numpy as np
 import pytest
 
 from conftest import load_golden
+from support import Margins, bits_equal, rel, eng     # noqa: F401 (eng is a fixture)
 from oracle import smart_oracle as so
 from oracle import objfn_oracle, lhs_oracle
 
@@ -20,16 +22,6 @@ pytestmark = pytest.mark.gpu
 
 REL_FAST = 1e-9
 REL_CONTRACT = 1e-6
-
-
-def rel(a, b, floor=0.0):
-    """max |a - b| / max(|a|, |b|); magnitudes below `floor` count as equal (subnormal reservoir volumes that
-    have been draining for ten years carry no relative precision)."""
-    a, b = np.asarray(a, float), np.asarray(b, float)
-    m = np.maximum(np.abs(a), np.abs(b))
-    with np.errstate(invalid='ignore', divide='ignore'):
-        r = np.where(m > floor, np.abs(a - b) / m, 0.0)
-    return float(np.max(r)) if r.size else 0.0
 
 
 #: what an excess() has to stay below.  1.0 is the tolerance itself; the call sites are held to a TENTH of it, which is
@@ -42,29 +34,9 @@ EXCESS_GATE = 0.1
 #: x 60 set-ups (profiles/r05_fuzz.txt) six comparisons came out between 0.10 and 0.25 of their tolerances -- the scores,
 #: the groundwater ratio and the final states of short runs, each once or twice -- and none above.
 FUZZ_GATE = 0.5
-MARGINS = {}        # call site (line of this file) -> largest excess() seen there in this run
-
-
-def excess(got, want, rtol, top=None, top_frac=1e-13, tiny=1e-40):
-    """Largest |got - want| / (rtol * |want| + top_frac * top + tiny); <= 1 is within the tolerance, and the call sites
-    ask for <= EXCESS_GATE.  `top` is the largest magnitude of
-    the row (default: of `want` along its last axis): a value that has drained to 1e-9 of its row's peak carries the
-    absolute rounding of the states it came from, not nine digits of its own.  `tiny`: a catchment that never held
-    water carries storages of 1e-59 m3, whose last digits the river's 95 % rule flips on rounding noise -- zero, to any
-    hydrologist, in any of the units compared here (m3, m3/s, mm).  Every call leaves its margin in MARGINS."""
-    import sys
-    got, want = np.asarray(got, float), np.asarray(want, float)
-    if want.size == 0:
-        return 0.0
-    if top is None:
-        top = np.abs(want).max(axis=-1, keepdims=True) if want.ndim > 1 else np.abs(want).max()
-    with np.errstate(invalid='ignore', divide='ignore'):
-        r = np.abs(got - want) / (rtol * np.abs(want) + top_frac * top + tiny)
-    worst = float(np.nanmax(np.where(np.abs(got - want) == 0, 0.0, r)))
-    frame = sys._getframe(1)
-    site = '%s:%d' % (frame.f_code.co_name, frame.f_lineno)
-    MARGINS[site] = max(MARGINS.get(site, 0.0), worst)
-    return worst
+MARGINS = Margins()     # call site (function:line of this file) -> largest excess() seen there in this run
+#: support.excess noted under the line of this file that calls it; a selection of rows that came out empty compares as 0
+excess = functools.partial(MARGINS.excess, empty_ok=True)
 
 
 @pytest.fixture(scope='module', autouse=True)
@@ -73,27 +45,10 @@ def _print_the_margins():
     yield
     if not MARGINS:
         return
-    lines = ['%-78s %.3g' % (site, m) for site, m in sorted(MARGINS.items(), key=lambda kv: -kv[1])]
+    lines = ['%-78s %.3g' % (site, m) for site, (m, _) in sorted(MARGINS.items(), key=lambda kv: -kv[1][0])]
     text = 'excess() margins of this run (1.0 = the tolerance, gate %.2g), largest first:\n' % EXCESS_GATE + '\n'.join(lines)
-    print('\n' + text)
     out = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'gpurun_out')
-    if os.path.isdir(out):
-        with open(os.path.join(out, 'parity_margins.txt'), 'w') as fh:
-            fh.write(text + '\n')
-
-
-def bits_equal(a, b):
-    a = np.ascontiguousarray(a, dtype=np.float64)
-    b = np.ascontiguousarray(b, dtype=np.float64)
-    return a.shape == b.shape and np.array_equal(a.view(np.int64), b.view(np.int64))
-
-
-@pytest.fixture(scope='module')
-def eng():
-    import torch
-    assert torch.cuda.is_available(), "these tests need the GPU"
-    from smartpy_amd import engine
-    return engine
+    MARGINS.publish(text, out, 'parity_margins.txt')
 
 
 def forcing_of(rain, peva):

@@ -24,14 +24,12 @@ one whose bins are the ranks of the first row's values (ks = (B - 1) / B in the 
 one with values beyond the bins."""
 import functools
 import os
-import shutil
 
 import numpy as np
 import pytest
 
-from conftest import GOLDEN
+from support import EXTRA, SENTINEL, example_root, filled, padded, same_bits, settings_file, workspace
 from test_pawn_host import pawn_statement
-from test_gpu_quantiles import EXTRA, _settings
 
 pytestmark = pytest.mark.gpu
 
@@ -46,34 +44,26 @@ def capacity():
 
 def launch(y, cat, B, method=AUTO, pad=3, spare=1, ws_steps=None):
     """The C entry on a [R, N] host matrix laid out with ld = N + pad (the padding holds NaN) -> (ks [R + spare, P, B],
-    counts [P + spare, B]); the spare rows as they were before the call: -7.  The workspace is what the helper entry asks
+    counts [P + spare, B]); the spare rows as they were before the call: SENTINEL.  The workspace is what the helper entry asks
     for, or exactly `ws_steps` steps."""
     import torch
     from smartpy_amd import _lib
     L = _lib.lib()
-    y = np.asarray(y, dtype=np.float64)
-    R, N = y.shape
+    R, N = np.shape(y)
     P = len(cat)
-    host = np.full((R, N + pad), np.nan)
-    host[:, :N] = y
-    d_y = torch.from_numpy(host).cuda()
+    d_y, ld = padded(y, pad)
     d_cat = torch.from_numpy(np.array(cat, dtype=np.uint8)).cuda()         # (a copy: the shared case is read-only)
-    ks = torch.full((R + spare, P, B), -7.0, dtype=torch.float64, device='cuda')
-    counts = torch.full((P + spare, B), -7, dtype=torch.int32, device='cuda')
+    ks, counts = filled((R + spare, P, B)), filled((P + spare, B), 'int32')
     need = int(L.smart_pawn_workspace_bytes(N, R, method))
     if ws_steps is not None:
         need = ws_steps * int(L.smart_pawn_workspace_bytes(N, 1, method))
     need = max(need, 0)         # (sizes the helper refuses: the entry refuses them too, with its text)
-    work = torch.empty(max(need, 1), dtype=torch.uint8, device='cuda')
-    _lib.check(L.smart_pawn_ks_hip(N, R, d_y.data_ptr(), N + pad, d_cat.data_ptr(), P, B, ks.data_ptr(), counts.data_ptr(),
+    work = workspace(need, least=1)
+    _lib.check(L.smart_pawn_ks_hip(N, R, d_y.data_ptr(), ld, d_cat.data_ptr(), P, B, ks.data_ptr(), counts.data_ptr(),
                                    method, work.data_ptr(), need,
                                    torch.cuda.current_stream().cuda_stream))
     torch.cuda.synchronize()
     return ks.cpu().numpy(), counts.cpu().numpy()
-
-
-def same_bits(a, b):
-    return a.shape == b.shape and a.dtype == b.dtype and a.tobytes() == b.tobytes()
 
 
 def nan_bits(a):
@@ -140,9 +130,9 @@ def check(N, method, table, which):
     R, P = len(y), len(cat)
     ks, counts = launch(y, cat, B, method)
     where = (N, method, TABLES[table], which)
-    assert (counts[:P] == want_counts).all() and (counts[P:] == -7).all(), where
+    assert (counts[:P] == want_counts).all() and (counts[P:] == SENTINEL).all(), where
     assert same_bits(nan_bits(ks[:R]), want_ks), (where, np.argwhere(~((ks[:R] == want_ks) | np.isnan(want_ks)))[:5])
-    assert (ks[R:] == -7).all(), where
+    assert (ks[R:] == SENTINEL).all(), where
     return ks[:R]
 
 
@@ -253,9 +243,8 @@ def test_a_planted_parameter_is_the_influential_one():
 def test_lhs_pawn_sensitivity_end_to_end(tmp_path):
     from smartpy_amd.montecarlo import LHS
     from smartpy_amd import identifiability as ident, pawn
-    root = str(tmp_path / 'data')
-    shutil.copytree(os.path.join(GOLDEN, 'data', 'in'), os.path.join(root, 'in'))
-    _settings(root, 'Catchment.sampling.sttngs', '01/01/2007', '31/12/2007', 180)
+    root = example_root(tmp_path)
+    settings_file(root, 'Catchment.sampling.sttngs', '01/01/2007', '31/12/2007', 180)
     np.random.seed(2024)
     lhs = LHS('Catchment', root, 'csv', 'csv', sample_size=300, settings_filename='Catchment.sampling.sttngs')
     lhs.model.extra = EXTRA

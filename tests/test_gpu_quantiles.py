@@ -24,12 +24,11 @@ AUTO takes the sort form up to the capacity: test_exact_cases launches it on bot
 `same`: bit for bit, NaN for NaN."""
 import ctypes
 import os
-import shutil
 
 import numpy as np
 import pytest
 
-from conftest import GOLDEN
+from support import EXTRA, NSE_MIN, SENTINEL, example_root, filled, padded, ptr, same, settings_file, to_device
 from test_quantiles_host import (statement, statement_rows, band_violations, DYADIC, power_of_two_weights, threshold_probs,
                                  distinct_rows, weightless_successor, many_nan_rows, mixed_nans, is_power_of_two,
                                  NAN_SHARE, SUBNORMAL, HUGE)
@@ -37,9 +36,6 @@ from test_quantiles_host import (statement, statement_rows, band_violations, DYA
 pytestmark = pytest.mark.gpu
 
 AUTO, SORT, SELECT = 0, 1, 2
-EXTRA = {'aar': 1200, 'r-o_ratio': 0.45, 'r-o_split': (0.10, 0.15, 0.15, 0.30, 0.30)}
-# the 'min' threshold on the sampling run's NSE in the GLUE test: between 10 and 200 of the 256 seeded rows pass
-NSE_MIN = 0.2
 SEVEN = (0.025, 0.05, 0.25, 0.5, 0.75, 0.95, 0.975)
 
 
@@ -50,27 +46,18 @@ def capacity():
 
 def launch(matrix, weights, probs, method, pad=0, junk=np.nan, spare=0):
     """The C entry on a [R, N] host matrix laid out with ld = N + pad (the padding holds `junk`) -> numpy [K, R]
-    (with `spare` more rows below, as they were before the call: -7.0)."""
+    (with `spare` more rows below, as they were before the call: SENTINEL)."""
     import torch
     from smartpy_amd import _lib
     L = _lib.lib()
-    matrix = np.asarray(matrix, dtype=np.float64)
-    R, N = matrix.shape
-    host = np.full((R, N + pad), junk)
-    host[:, :N] = matrix
-    sim = torch.from_numpy(host).cuda()
-    w = None if weights is None else torch.from_numpy(np.ascontiguousarray(weights, dtype=np.float64)).cuda()
+    R, N = np.shape(matrix)
+    sim, ld = padded(matrix, pad, junk)
+    w = to_device(weights)
     q = (ctypes.c_double * len(probs))(*probs)
-    out = torch.full((len(probs) + spare, R), -7.0, dtype=torch.float64, device='cuda')
-    _lib.check(L.smart_weighted_quantiles_hip(N, R, sim.data_ptr(), N + pad, None if w is None else w.data_ptr(), q,
-                                              len(probs), out.data_ptr(), method,
+    out = filled((len(probs) + spare, R))
+    _lib.check(L.smart_weighted_quantiles_hip(N, R, sim.data_ptr(), ld, ptr(w), q, len(probs), out.data_ptr(), method,
                                               torch.cuda.current_stream().cuda_stream))
     return out.cpu().numpy()
-
-
-def same(a, b):
-    """`==` everywhere (so -0.0 is 0.0), NaN where NaN."""
-    return a.shape == b.shape and np.array_equal(a, b, equal_nan=True)
 
 
 def exact_weights(rng, n):
@@ -179,7 +166,7 @@ def test_every_probability_count(K, size, kind):
         assert got.shape == (K + 1, 5)
         assert same(got[:K], want), (K, size, kind, m, got, want)
         assert same(got[1], got[K - 1]) or K == 1
-        assert (got[K] == -7.0).all(), (K, size, kind, m, got[K])
+        assert (got[K] == SENTINEL).all(), (K, size, kind, m, got[K])
 
 
 THRESHOLD_CASES = [('65', SORT), ('65', SELECT), ('1025', SORT), ('1025', SELECT), ('2049', SORT), ('2049', SELECT),
@@ -399,19 +386,11 @@ def test_engine_on_ensembles_of_a_few_thousand_rows(example, rows):
     assert same(equal.cpu().numpy(), statement(dis.T, None, SEVEN))
 
 
-def _settings(root, name, start, end, warm):
-    with open(os.path.join(root, 'in', 'Catchment', name), 'w') as f:
-        f.write('ARGUMENT,VALUE\ncatchment_area_km2,175.46\ngauged_area_km2,175.97\nstart_datetime,%s 09:00:00\n'
-                'end_datetime,%s 09:00:00\nsimu_timedelta_min,60\nreport_timedelta_min,1440\nwarm_up_days,%d\n'
-                'gw_constraint,0.12667\n' % (start, end, warm))
-
-
 def test_glue_prediction_bounds_end_to_end(tmp_path):
     from smartpy_amd.montecarlo import LHS, GLUE
-    root = str(tmp_path / 'data')
-    shutil.copytree(os.path.join(GOLDEN, 'data', 'in'), os.path.join(root, 'in'))
-    _settings(root, 'Catchment.sampling.sttngs', '01/01/2007', '31/12/2007', 180)
-    _settings(root, 'Catchment.evaluating.sttngs', '01/01/2008', '30/06/2008', 90)
+    root = example_root(tmp_path)
+    settings_file(root, 'Catchment.sampling.sttngs', '01/01/2007', '31/12/2007', 180)
+    settings_file(root, 'Catchment.evaluating.sttngs', '01/01/2008', '30/06/2008', 90)
     np.random.seed(2024)
     lhs = LHS('Catchment', root, 'csv', 'csv', sample_size=256, settings_filename='Catchment.sampling.sttngs')
     lhs.model.extra = EXTRA

@@ -30,13 +30,12 @@ constant-but-for-one-row kinds, whose variance is exactly 0.
 The largest margins of a run are printed at the end of the module (and written to
 $SMART_MARGINS_DIR/signatures_margins.txt where that is set); profiles/signatures_margins.txt is that table."""
 import os
-import shutil
 
 import numpy as np
 import pytest
 
-from conftest import GOLDEN
-from test_windows_host import rel
+from support import (EXTRA, Guarded, Margins, bits_equal, example_root, margins_dir, padded, ptr, same_values, settings_file,
+                     to_device, window_arrays)
 from test_signatures_truth_host import (data, thresholds, stress_case, stress_reference, margins, KINDS, CONSTANT_KINDS,
                                         STRESS_R)
 from test_signatures_host import (statement, NAMES, PAIR_COLUMNS, MEAN, BFI, FLASHINESS, AC1, RLD, RECESSION, PEAK, PEAK_ROW,
@@ -44,76 +43,47 @@ from test_signatures_host import (statement, NAMES, PAIR_COLUMNS, MEAN, BFI, FLA
 
 pytestmark = pytest.mark.gpu
 
-EXTRA = {'aar': 1200, 'r-o_ratio': 0.45, 'r-o_split': (0.10, 0.15, 0.15, 0.30, 0.30)}
 GATE = 1e-9
-SENTINEL = -7.0
-GUARD = 64
 EXACT = [PEAK, PEAK_ROW, HIGH_COUNT, LOW_COUNT, MEAN, FLASHINESS, RLD, HIGH_DURATION, LOW_DURATION]
 CLOSE = [BFI, RECESSION]
 # R -> the N it is run with
 SHAPES = {1: (1, 65), 2: (1, 63, 257), 3: (65, 300), 7: (1, 257), 8: (63, 65), 9: (1, 300), 10: (65,), 501: (63, 300),
           1025: (1, 257), 4097: (65,)}
-MARGINS = {}            # column name -> (largest margin as a fraction of its gate, where it was seen)
-STRESS_MARGINS = {}     # column name -> (largest |got - truth| / bound on the stress family, where it was seen)
+MARGINS = Margins()     # column name -> (largest margin as a fraction of its gate, where it was seen)
+STRESS_MARGINS = Margins()  # column name -> (largest |got - truth| / bound on the stress family, where it was seen)
 FILLER = 65 - len(KINDS)
-
-
-def same_values(a, b):
-    """bit-equal, a zero against a zero of either sign included; NaN against NaN of any payload"""
-    a, b = np.ascontiguousarray(a, dtype=np.float64), np.ascontiguousarray(b, dtype=np.float64)
-    return a.shape == b.shape and bool(np.all((a.view(np.int64) == b.view(np.int64)) | ((a == 0.0) & (b == 0.0))
-                                              | (np.isnan(a) & np.isnan(b))))
-
-
-def bits_equal(a, b):
-    a, b = np.ascontiguousarray(a, dtype=np.float64), np.ascontiguousarray(b, dtype=np.float64)
-    return a.shape == b.shape and np.array_equal(a.view(np.int64), b.view(np.int64))
-
-
-def window_arrays(rng, R):
-    sixteen = (np.arange(R) * 16 // R).astype(np.int32)
-    sixteen[rng.random(R) < 0.10] = -1
-    return [(1, None), (2, (np.arange(R) >= R // 2).astype(np.int32)), (7, (np.arange(R) % 7).astype(np.int32)),
-            (16, sixteen)]
 
 
 def launch(sim, obs=None, win=None, W=1, alpha=0.925, pulse=None, pad=0, expect=0):
     """The C entry on a [R, N] host matrix laid out with ld = N + pad (the padding holds NaN) -> sig [W, 12, N] as numpy.
-    The output lies GUARD doubles inside a buffer of SENTINEL with a spare window behind it; everything around what the
+    The output lies support.GUARD doubles inside a buffer of support.SENTINEL with a spare window behind it; everything around what the
     call owns is checked to be as it was."""
     import torch
     from smartpy_amd import _lib
     L = _lib.lib()
     R, N = sim.shape
-    host = np.full((R, N + pad), np.nan)
-    host[:, :N] = sim
-    d_sim = torch.from_numpy(host).cuda()
-    d_obs = None if obs is None else torch.from_numpy(np.ascontiguousarray(obs, dtype=np.float64)).cuda()
-    d_win = None if win is None else torch.from_numpy(np.ascontiguousarray(win, dtype=np.int32)).cuda()
-    d_pulse = None if pulse is None else torch.from_numpy(np.ascontiguousarray(pulse, dtype=np.float64)).cuda()
-    own = W * 12 * N
-    sig = torch.full((2 * GUARD + own + 12 * N,), SENTINEL, dtype=torch.float64, device='cuda')
-    rc = L.smart_signatures_hip(N, R, d_sim.data_ptr(), N + pad, None if d_obs is None else d_obs.data_ptr(),
-                                None if d_win is None else d_win.data_ptr(), W, float(alpha),
-                                None if d_pulse is None else d_pulse.data_ptr(), sig.data_ptr() + 8 * GUARD,
+    d_sim, ld = padded(sim, pad)
+    d_obs, d_win, d_pulse = to_device(obs), to_device(win, np.int32), to_device(pulse)
+    sig = Guarded(W * 12 * N, tail=12 * N)
+    rc = L.smart_signatures_hip(N, R, d_sim.data_ptr(), ld, ptr(d_obs), ptr(d_win), W, float(alpha), ptr(d_pulse), sig.ptr(),
                                 torch.cuda.current_stream().cuda_stream)
     torch.cuda.synchronize()
     if expect:
         assert rc == expect, (rc, L.smart_last_error().decode())
-        assert bool((sig == SENTINEL).all())
+        assert sig.untouched()
         return L.smart_last_error().decode()
     _lib.check(rc)
-    sig = sig.cpu().numpy()
-    assert np.all(sig[:GUARD] == SENTINEL) and np.all(sig[GUARD + own:] == SENTINEL)
-    return sig[GUARD:GUARD + own].reshape(W, 12, N)
+    sig, intact = sig.read()
+    assert intact
+    return sig.reshape(W, 12, N)
 
 
 def hold(got, want, what):
     """every gate of the module's docstring on one launch"""
     assert got.shape == want.shape
     assert np.array_equal(np.isnan(got), np.isnan(want)), what + ': the pattern of NaN'
-    assert same_values(got[:, EXACT], want[:, EXACT]), what + ': the columns that are bit-equal: ' + ', '.join(
-        NAMES[c] for c in EXACT if not same_values(got[:, c], want[:, c]))
+    assert same_values(got[:, EXACT], want[:, EXACT], any_nan=True), what + ': the columns that are bit-equal: ' + ', '.join(
+        NAMES[c] for c in EXACT if not same_values(got[:, c], want[:, c], any_nan=True))
     compared = want[:, CLOSE][~np.isnan(want[:, CLOSE])]
     assert compared.size == 0 or np.all((compared == 0.0) | (np.abs(compared) > 1e-6)), what      # (change the seed)
     for c in CLOSE + [AC1]:
@@ -122,8 +92,7 @@ def hold(got, want, what):
         if not ok.any():
             continue
         err = float(np.max(np.abs(g[ok] - w[ok]) / (1.0 if c == AC1 else np.maximum(np.abs(w[ok]), 1e-12))))
-        if err / GATE > MARGINS.get(NAMES[c], (-1.0, ''))[0]:
-            MARGINS[NAMES[c]] = (err / GATE, what)
+        MARGINS.note(NAMES[c], err / GATE, what)
         assert err < GATE, '%s: %s off by %.3e' % (what, NAMES[c], err)
 
 
@@ -141,18 +110,14 @@ def _print_the_margins():
             'margin, the launch it was seen in\n' +
             '\n'.join('%-14s %-10.3g %s' % (name, STRESS_MARGINS[name][0], STRESS_MARGINS[name][1])
                       for name in NAMES if name in STRESS_MARGINS) + '\n')
-    print('\n' + text)
-    out = os.environ.get('SMART_MARGINS_DIR')
-    if out and os.path.isdir(out):
-        with open(os.path.join(out, 'signatures_margins.txt'), 'w') as fh:
-            fh.write(text)
+    MARGINS.publish(text, margins_dir(), 'signatures_margins.txt')
 
 
 @pytest.mark.parametrize('R', sorted(SHAPES))
 def test_signatures_are_the_statement(R):
     for n in SHAPES[R]:
         rng, obs, sim = data(1000 * R + n, R, n)
-        for W, win in window_arrays(rng, R):
+        for W, win in window_arrays(rng, R, None):
             for with_obs in (obs, None):
                 pulse = thresholds(sim, with_obs, win, W)
                 for alpha in (0.925, 0.5):
@@ -187,8 +152,7 @@ def test_the_stress_family_is_the_exact_truth_within_its_bounds(R):
         for c, name in enumerate(NAMES):
             worst = np.unravel_index(np.argmax(ratio[:, c]), ratio[:, c].shape)
             print('%s %-14s %.3g (window %d, %s)' % (what, name, ratio[:, c][worst], worst[0], kinds[worst[1]]))
-            if ratio[:, c][worst] > STRESS_MARGINS.get(name, (-1.0, ''))[0]:
-                STRESS_MARGINS[name] = (float(ratio[:, c][worst]), '%s window %d %s' % (what, worst[0], kinds[worst[1]]))
+            STRESS_MARGINS.note(name, float(ratio[:, c][worst]), '%s window %d %s' % (what, worst[0], kinds[worst[1]]))
         assert np.array_equal(np.isnan(got), np.isnan(want)), what + ': the pattern of NaN'
         assert np.isnan(got[:, AC1][:, CONSTANT_KINDS]).all(), what + ': a constant list has a variance of exactly 0'
         assert np.all(ratio <= 1.0), '%s: %s' % (what, {NAMES[c]: float(ratio[:, c].max()) for c in range(12)
@@ -254,7 +218,7 @@ def test_planted_columns():
 def test_two_launches_give_the_same_bits():
     R, n = 1025, 300
     rng, obs, sim = data(11, R, n)
-    W, win = window_arrays(rng, R)[3]
+    W, win = window_arrays(rng, R, None)[3]
     pulse = thresholds(sim, obs, win, W)
     first = launch(sim, obs, win, W, 0.925, pulse, pad=1)
     assert bits_equal(first, launch(sim, obs, win, W, 0.925, pulse, pad=1))
@@ -264,7 +228,7 @@ def test_two_launches_give_the_same_bits():
 def test_the_observations_as_a_matrix_of_one_column():
     R = 1025
     rng, obs, sim = data(21, R, 1)
-    for W, win in window_arrays(rng, R):
+    for W, win in window_arrays(rng, R, None):
         pulse = thresholds(sim, obs, win, W)
         column = np.where(np.isnan(obs), -1.0, obs).reshape(R, 1)       # (a missing observation is never read as a flow)
         want = statement(column, obs, win, W, 0.925, pulse)
@@ -289,9 +253,9 @@ def test_engine_surface():
     ids = (np.arange(R) % 3 == 0).astype(np.int32) + (np.arange(R) >= 250)       # 0, 1, 2 in stretches; window 3 never
     pulse = thresholds(sim, obs, ids, 4)
     want = statement(sim, obs, ids, 4, 0.5, pulse)
-    padded = torch.full((R, n + 63), float('nan'), dtype=torch.float64, device='cuda')
-    padded[:, :n] = torch.from_numpy(sim).cuda()
-    got = engine.signatures(padded[:, :n], torch.from_numpy(obs).cuda(), torch.from_numpy(ids).cuda(), n_windows=4,
+    wide = torch.full((R, n + 63), float('nan'), dtype=torch.float64, device='cuda')
+    wide[:, :n] = torch.from_numpy(sim).cuda()
+    got = engine.signatures(wide[:, :n], torch.from_numpy(obs).cuda(), torch.from_numpy(ids).cuda(), n_windows=4,
                             alpha=0.5, thresholds=pulse)
     assert got.is_cuda and got.dtype == torch.float64 and tuple(got.shape) == (4, 12, n) and got[1, 3].is_contiguous()
     hold(got.cpu().numpy(), want, 'engine, strided view')
@@ -308,20 +272,12 @@ def test_engine_surface():
         engine.signatures(sim, obs, bad, n_windows=4)
 
 
-def _settings(root, name, start, end, warm):
-    with open(os.path.join(root, 'in', 'Catchment', name), 'w') as f:
-        f.write('ARGUMENT,VALUE\ncatchment_area_km2,175.46\ngauged_area_km2,175.97\nstart_datetime,%s 09:00:00\n'
-                'end_datetime,%s 09:00:00\nsimu_timedelta_min,60\nreport_timedelta_min,1440\nwarm_up_days,%d\n'
-                'gw_constraint,0.12667\n' % (start, end, warm))
-
-
 def test_through_the_model(tmp_path):
     from smartpy_amd.montecarlo import LHS
     from smartpy_amd.montecarlo.selection import as_stored, pareto_rows
     from smartpy_amd.windows import evaluation_windows, pulse_thresholds, signatures_header_line
-    root = str(tmp_path / 'data')
-    shutil.copytree(os.path.join(GOLDEN, 'data', 'in'), os.path.join(root, 'in'))
-    _settings(root, 'Catchment.sampling.sttngs', '01/01/2007', '31/12/2007', 180)
+    root = example_root(tmp_path)
+    settings_file(root, 'Catchment.sampling.sttngs', '01/01/2007', '31/12/2007', 180)
     np.random.seed(2025)
     n = 130
     lhs = LHS('Catchment', root, 'csv', 'csv', sample_size=n, settings_filename='Catchment.sampling.sttngs')

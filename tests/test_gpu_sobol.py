@@ -10,30 +10,21 @@ threads (n = 1,023 / 1,025), the wavefront (63 / 64 / 65), the bootstrap's tile 
 64 (B = 63 / 64 / 65 / 130 / the cap) and its three instances (k <= 4, 10, 16).  ld = N + 3 with NaN in the padding; the
 outputs lie inside buffers of sentinels with a spare row behind them."""
 import os
-import shutil
 
 import numpy as np
 import pytest
 
-from conftest import GOLDEN
+from support import EXTRA, Guarded, bits_equal, example_root, padded, ptr, settings_file
 from test_sobol_host import sobol_statement, design_values
 
 pytestmark = pytest.mark.gpu
 
 GATE = 1e-9
-SENTINEL = -7.0
-GUARD = 64
-EXTRA = {'aar': 1200, 'r-o_ratio': 0.45, 'r-o_split': (0.10, 0.15, 0.15, 0.30, 0.30)}
-
-
-def bits_equal(a, b):
-    a, b = np.ascontiguousarray(a, dtype=np.float64), np.ascontiguousarray(b, dtype=np.float64)
-    return a.shape == b.shape and np.array_equal(a.view(np.int64), b.view(np.int64))
 
 
 def launch(y, n, k, counts=None, pad=3):
     """The C entry on a host matrix laid out with ld = N + pad (NaN in the padding) -> dict of numpy arrays like
-    sobol_statement's.  Every output lies GUARD doubles inside a buffer of SENTINEL with a spare row behind it; what the
+    sobol_statement's.  Every output lies support.GUARD doubles inside a buffer of support.SENTINEL with a spare row behind it; what the
     call does not own is checked to be as it was (without counts: both buffers of standard deviations entirely)."""
     import torch
     from smartpy_amd import _lib
@@ -41,26 +32,22 @@ def launch(y, n, k, counts=None, pad=3):
     y = np.atleast_2d(y)
     M, N = y.shape
     assert N == n * (k + 2)
-    host = np.full((M, N + pad), np.nan)
-    host[:, :N] = y
-    d_y = torch.from_numpy(host).cuda()
+    d_y, ld = padded(y, pad)
     B = 0 if counts is None else counts.shape[1]
     d_c = None if not B else torch.from_numpy(np.ascontiguousarray(counts).view(np.int16)).cuda()
     sizes = {'S1': k, 'ST': k, 'moments': 2, 'S1_std': k, 'ST_std': k}
-    buf = {name: torch.full((2 * GUARD + (M + 1) * w,), SENTINEL, dtype=torch.float64, device='cuda')
-           for name, w in sizes.items()}
-    ptr = {name: t.data_ptr() + 8 * GUARD for name, t in buf.items()}
-    rc = L.smart_sobol_indices_hip(n, k, M, d_y.data_ptr(), N + pad, ptr['S1'], ptr['ST'], ptr['moments'],
-                                   None if d_c is None else d_c.data_ptr(), B, ptr['S1_std'] if B else None,
-                                   ptr['ST_std'] if B else None, None, 0, torch.cuda.current_stream().cuda_stream)
+    buf = {name: Guarded(M * w, tail=w) for name, w in sizes.items()}
+    rc = L.smart_sobol_indices_hip(n, k, M, d_y.data_ptr(), ld, buf['S1'].ptr(), buf['ST'].ptr(), buf['moments'].ptr(),
+                                   ptr(d_c), B, buf['S1_std'].ptr(null=not B), buf['ST_std'].ptr(null=not B), None, 0,
+                                   torch.cuda.current_stream().cuda_stream)
     torch.cuda.synchronize()
     _lib.check(rc)
     out = {}
     for name, w in sizes.items():
-        flat = buf[name].cpu().numpy()
         own = M * w if (B or not name.endswith('_std')) else 0
-        assert np.all(flat[:GUARD] == SENTINEL) and np.all(flat[GUARD + own:] == SENTINEL), name
-        out[name] = flat[GUARD:GUARD + M * w].reshape(M, w) if own else None
+        flat, intact = buf[name].read(own)
+        assert intact, name
+        out[name] = flat.reshape(M, w) if own else None
     out['mu'], out['V'] = out['moments'][:, 0], out['moments'][:, 1]
     return out
 
@@ -179,20 +166,12 @@ def test_engine_surface_honours_the_leading_dimension():
     assert host.S1_std is None and bits_equal(host.S1.cpu().numpy()[0], got['S1'][2])
 
 
-def _settings(root, name, start, end, warm):
-    with open(os.path.join(root, 'in', 'Catchment', name), 'w') as f:
-        f.write('ARGUMENT,VALUE\ncatchment_area_km2,175.46\ngauged_area_km2,175.97\nstart_datetime,%s 09:00:00\n'
-                'end_datetime,%s 09:00:00\nsimu_timedelta_min,60\nreport_timedelta_min,1440\nwarm_up_days,%d\n'
-                'gw_constraint,0.12667\n' % (start, end, warm))
-
-
 def test_through_the_model(tmp_path):
     from smartpy_amd import engine
     from smartpy_amd.montecarlo import Sobol
     from smartpy_amd.montecarlo.sobol import normal_quantile, series_header_line, INDICES_HEADER
-    root = str(tmp_path / 'data')
-    shutil.copytree(os.path.join(GOLDEN, 'data', 'in'), os.path.join(root, 'in'))
-    _settings(root, 'Catchment.sobol.sttngs', '01/01/2007', '19/07/2007', 60)       # two hundred report steps
+    root = example_root(tmp_path)
+    settings_file(root, 'Catchment.sobol.sttngs', '01/01/2007', '19/07/2007', 60)       # two hundred report steps
     n = 64
     sob = Sobol('Catchment', root, 'csv', 'csv', base_size=n, settings_filename='Catchment.sobol.sttngs', seed=4)
     sob.model.extra = EXTRA

@@ -22,7 +22,8 @@ import os
 import numpy as np
 import pytest
 
-from test_windows_host import statement, rel
+from support import rel_to_want, eng        # noqa: F401 (eng is a fixture)
+from test_windows_host import statement
 from test_signatures_truth_host import exact, bounds, margins
 
 pytestmark = pytest.mark.gpu
@@ -34,14 +35,6 @@ cases = importlib.util.module_from_spec(_spec)
 _spec.loader.exec_module(cases)
 
 GATE = 1e-9
-
-
-@pytest.fixture(scope='module')
-def eng():
-    import torch
-    assert torch.cuda.is_available(), 'these tests need the GPU'
-    from smartpy_amd import engine
-    return engine
 
 
 @pytest.fixture(scope='module')
@@ -85,7 +78,7 @@ def test_the_parent_commits_bits_and_the_statement(eng, parent, R, N):
             # (b) the statement
             for transform, eps in (('none', 0.0), ('log', cases.LOG_EPS)):
                 want = statement(sim[:, cols], obs, win, W, transform, eps)
-                err = rel(got['windows_' + transform][0][:, cols], want)
+                err = rel_to_want(got['windows_' + transform][0][:, cols], want)
                 print('%s %s: rel %.3e against the statement, %d NaN entries' % (tag, transform, err,
                                                                                  int(np.isnan(want).sum())))
                 assert err < GATE, (tag, transform)

@@ -18,6 +18,7 @@ import os
 import numpy as np
 import pytest
 
+from support import bits_equal, rel, eng      # noqa: F401 (eng is a fixture)
 from oracle import smart_oracle as so
 from oracle import objfn_oracle
 from test_objfn_truth_host import bounds, first_observed
@@ -31,29 +32,6 @@ cases = importlib.util.module_from_spec(_spec)
 _spec.loader.exec_module(cases)
 
 REL_FAST = 1e-9
-
-
-def rel(a, b, floor=0.0):
-    """max |a - b| / max(|a|, |b|), magnitudes below `floor` counting as equal (tests/test_gpu_parity.py)"""
-    a, b = np.asarray(a, float), np.asarray(b, float)
-    m = np.maximum(np.abs(a), np.abs(b))
-    with np.errstate(invalid='ignore', divide='ignore'):
-        r = np.where(m > floor, np.abs(a - b) / m, 0.0)
-    return float(np.max(r)) if r.size else 0.0
-
-
-def bits_equal(a, b):
-    a = np.ascontiguousarray(a, dtype=np.float64)
-    b = np.ascontiguousarray(b, dtype=np.float64)
-    return a.shape == b.shape and np.array_equal(a.view(np.int64), b.view(np.int64))
-
-
-@pytest.fixture(scope='module')
-def eng():
-    import torch
-    assert torch.cuda.is_available(), 'these tests need the GPU'
-    from smartpy_amd import engine
-    return engine
 
 
 @pytest.fixture(scope='module')

@@ -8,17 +8,9 @@ import numpy as np
 import pytest
 
 from conftest import load_golden
+from support import rel
 from oracle import smart_oracle as so
 from oracle import objfn_oracle, lhs_oracle
-
-
-def rel(a, b):
-    a, b = np.asarray(a, float), np.asarray(b, float)
-    d = np.abs(a - b)
-    m = np.maximum(np.abs(a), np.abs(b))
-    with np.errstate(invalid='ignore', divide='ignore'):
-        r = np.where(m > 0, d / m, 0.0)
-    return float(np.max(r)) if r.size else 0.0
 
 
 def test_kat6_single_steps_bit_exact():

@@ -10,12 +10,12 @@ take part.  Ranks by peeling: rank r = the rows with count 0 once the ranks belo
 max_rank; -1 = not taking part."""
 import ctypes
 import os
-import shutil
 
 import numpy as np
 import pytest
 
-from conftest import GOLDEN, load_golden
+from conftest import load_golden
+from support import example_root, settings_file
 
 E_NULL, E_SIZE, E_MODE = -1, -2, -7
 FAKE = 0x1000                       # a non-NULL address that no refusal path reads
@@ -270,12 +270,8 @@ OBJ = ['NSE', 'KGE', 'KGEc', 'KGEa', 'KGEb', 'PBias', 'RMSE', 'GW']
 def root(tmp_path):
     """the inputs of the golden catchment, a short period, and the database of a sampling run of 48 rows (KAT-12)"""
     from smartpy_amd.montecarlo.database import SamplingCsv
-    r = str(tmp_path / 'data')
-    shutil.copytree(os.path.join(GOLDEN, 'data', 'in'), os.path.join(r, 'in'))
-    with open(os.path.join(r, 'in', 'Catchment', 'Catchment.short.sttngs'), 'w') as f:
-        f.write('ARGUMENT,VALUE\ncatchment_area_km2,175.46\ngauged_area_km2,175.97\nstart_datetime,01/01/2007 09:00:00\n'
-                'end_datetime,01/03/2007 09:00:00\nsimu_timedelta_min,60\nreport_timedelta_min,1440\nwarm_up_days,10\n'
-                'gw_constraint,0.12667\n')
+    r = example_root(tmp_path)
+    settings_file(r, 'Catchment.short.sttngs', '01/01/2007', '01/03/2007', 10)
     z = load_golden('kat12_selection.npz')
     os.makedirs(os.path.join(r, 'out', 'Catchment'), exist_ok=True)
     db = SamplingCsv(os.path.join(r, 'out', 'Catchment', 'Catchment.SMART.lhs'), OBJ, NAMES).create(len(z['params']))

@@ -9,6 +9,7 @@ from fractions import Fraction
 import numpy as np
 import pytest
 
+from support import same
 from smartpy_amd import _lib, pawn
 
 U = 2.0 ** -53
@@ -69,12 +70,6 @@ def pawn_brute(y, cat, B):
                     best = max(best, abs(F - Fb))
                 ks[r, p, b] = float(best)
     return ks
-
-
-def same(a, b):
-    """`==` everywhere, NaN where NaN."""
-    a, b = np.asarray(a), np.asarray(b)
-    return a.shape == b.shape and np.array_equal(a, b, equal_nan=True)
 
 
 def random_case(rng, i):

@@ -6,12 +6,12 @@ import inspect
 import json
 import math
 import os
-import shutil
 
 import numpy as np
 import pytest
 
 from conftest import GOLDEN, load_golden
+from support import example_root, same_bits, settings_file
 
 E_NULL, E_SIZE, E_NO_DEVICE, E_MODE = -1, -2, -6, -7
 DYADIC = (0.0625, 0.5, 0.9375, 1.0)
@@ -192,10 +192,6 @@ def test_threshold_constructions_are_sound(n):
     assert np.array_equal(statement([x], w0 * HUGE, p0)[:, 0], v0)
 
 
-def same_bits(a, b):
-    return a.shape == b.shape and np.array_equal(a.view(np.int64), b.view(np.int64))
-
-
 def test_statement_on_rows_where_nans_decide():
     """numpy sorts every NaN last, whatever its sign and payload: with two fifths of a row NaN (and weights that give
     them between a sixteenth and a half of the total) the upper quantiles are NaN and the lower ones are not."""
@@ -329,12 +325,8 @@ OBJ = ['NSE', 'KGE', 'KGEc', 'KGEa', 'KGEb', 'PBias', 'RMSE', 'GW']
 
 @pytest.fixture()
 def root(tmp_path):
-    r = str(tmp_path / 'data')
-    shutil.copytree(os.path.join(GOLDEN, 'data', 'in'), os.path.join(r, 'in'))
-    with open(os.path.join(r, 'in', 'Catchment', 'Catchment.short.sttngs'), 'w') as f:
-        f.write('ARGUMENT,VALUE\ncatchment_area_km2,175.46\ngauged_area_km2,175.97\nstart_datetime,01/01/2007 09:00:00\n'
-                'end_datetime,01/03/2007 09:00:00\nsimu_timedelta_min,60\nreport_timedelta_min,1440\nwarm_up_days,10\n'
-                'gw_constraint,0.12667\n')
+    r = example_root(tmp_path)
+    settings_file(r, 'Catchment.short.sttngs', '01/01/2007', '01/03/2007', 10)
     return r
 
 

@@ -39,7 +39,8 @@ ORDERS = ('forward', 'reversed', 'pairwise')
 
 # ---- the benign generator and the thresholds (tests/test_gpu_signatures.py) --------------------------------------------
 def data(seed, R, n):
-    """-> (rng, obs [R] with 15 % missing, sim [R, n])"""
+    """-> (rng, obs [R] with 15 % missing, sim [R, n]): hydrographs, every column a recession fed by events, the
+    observations the first column times noise.  (Not the `data` of tests/support.py, whose columns are independent noise.)"""
     rng = np.random.default_rng(seed)
     k = rng.uniform(0.80, 0.98, n)
     event = np.where(rng.random((R, n)) < 0.15, rng.exponential(2.0, (R, n)), 0.0)

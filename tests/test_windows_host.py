@@ -41,17 +41,6 @@ def statement(sim, obs, win, n_windows, transform='none', eps=0.0):
     return out
 
 
-def rel(got, want, floor=1e-12):
-    """max |got - want| / max(|want|, floor); a NaN on one side only counts as infinitely far."""
-    got, want = np.asarray(got, float), np.asarray(want, float)
-    if got.shape != want.shape or not np.array_equal(np.isnan(got), np.isnan(want)):
-        return float('inf')
-    ok = ~np.isnan(want)
-    if not ok.any():
-        return 0.0
-    return float(np.max(np.abs(got[ok] - want[ok]) / np.maximum(np.abs(want[ok]), floor)))
-
-
 def test_statement_is_the_oracle_on_one_window_and_applies_the_two_rules():
     rng = np.random.default_rng(3)
     R = 60

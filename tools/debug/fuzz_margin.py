@@ -15,4 +15,4 @@ for seed in (int(a) for a in sys.argv[1:]):
     t.run_interval_cases(engine, setenv, seed, 10)
     t.run_interval_cases(engine, setenv, seed, 10, mode='raw')
     t.run_interval_cases(engine, setenv, seed, 5, mode='every')
-    print(seed, ['%s %.3f' % kv for kv in sorted(t.MARGINS.items(), key=lambda kv: -kv[1])[:3]])
+    print(seed, ['%s %.3f' % (site, m) for site, (m, _) in sorted(t.MARGINS.items(), key=lambda kv: -kv[1][0])[:3]])
