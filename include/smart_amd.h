@@ -826,6 +826,59 @@ int smart_demcz_step_hip(int64_t n_chains, int64_t chain_offset, int32_t n_dims,
                          void *stream);
 
 /*
+ * The residual error model of a stored discharge matrix sim[R][ld] (sample-minor): a standard deviation linear in the
+ * simulated flow, and standardised residuals that follow a first-order autoregression (Schoups & Vrugt 2010, Water
+ * Resour. Res. 46; the AR(1) on the STANDARDISED residuals: Evin et al. 2014, Water Resour. Res. 50).  Sample i has the
+ * error parameters (sigma0, sigma1, phi) = err[i * err_ld + 0 .. 2]: err_ld >= 3 is a row stride, so three columns of a
+ * wider matrix (the launch matrix of DE-MCz) are read where they lie.  With q = (1 - phi)(1 + phi), for a report step t:
+ *     sigma_t = sigma0 + sigma1 sim[t][i]          a_t = (obs[t] - sim[t][i]) / sigma_t
+ * each operation rounded once, no contraction.  Device pointers; stream-ordered; nothing is allocated, nothing is read
+ * back, no atomics.
+ *
+ * smart_error_model_loglik_hip: the log-likelihood of every sample -> loglik[3][N], row 0 LOGLIK, row 1 SSQ, row 2 LOGSIG.
+ * A step is OBSERVED where obs[t] is not a NaN; an observed step is a START if t = 0 or step t - 1 is not observed (a gap
+ * restarts the chain with its stationary density N(0, 1 / q)), else a CONTINUATION.  With n observed steps, S of them
+ * starts (both depend on obs alone):
+ *     SSQ    = sum over starts of q a_t^2  +  sum over continuations of (a_t - phi a_{t-1})^2       (no negative term)
+ *     LOGSIG = sum over observed steps of ln sigma_t                                                 (one log per step)
+ *     LOGLIK = ((-SSQ / 2 - LOGSIG) + (S / 2) ln q) - (n / 2) ln(2 pi)
+ * A sample is INVALID if |phi| >= 1, if one of its three parameters is not finite, or if at an observed step sim is not
+ * finite or sigma_t <= 0: LOGLIK = -inf, SSQ = LOGSIG = NaN.  What sim holds at a step that is not observed is never looked
+ * at.  n = 0: all three +0.0.
+ * THE ORDER OF THE SUMS is fixed, whatever the launch: the report steps are cut into segments of SMART_ERROR_MODEL_SEGMENT
+ * steps, segment s belongs to part s mod 4, a part adds the terms of its steps in ascending order, and the four parts are
+ * added as ((p0 + p1) + p2) + p3.  The first step of a segment takes a_{t-1} from row t - 1 itself.
+ * Errors (all found before the device is touched; the first offending argument wins): SMART_E_NULL sim, obs, err or
+ * loglik missing; SMART_E_SIZE n_samples or n_reports < 1, ld < n_samples, err_ld < 3, more than 2^31 - 1 samples or
+ * report steps; then SMART_E_NO_DEVICE without a HIP device.
+ *
+ * smart_error_model_draw_hip: realisations of the error model on top of the simulated flows -> out[R][out_ld], n_replicates
+ * = K columns per sample: column c = i K + k of the call is replicate k of its sample i, C = n_samples K columns in all.
+ * Along the report steps of a column, over EVERY step (observed or not):
+ *     a_0 = eps_0 / sqrt(q)      a_t = phi a_{t-1} + eps_t      y = sim[t][i] + sigma_t a_t      truncate != 0: y > 0 ? y : 0
+ * A sample that is invalid -- as above, judged over every report step -- gives columns of NaN.  RANDOMNESS is
+ * Philox4x32-10 with u53 as for smart_demcz_step_hip: for the pair of steps (2j, 2j + 1) the words w0 .. w3 of the counter
+ * (column_offset + c, j, 0, 0) under the key (seed mod 2^32, seed div 2^32) give
+ *     u1 = 1 - u53(w0, w1) in (0, 1]     u2 = u53(w2, w3)     r = sqrt(-2 ln u1)     ang = 6.283185307179586 u2
+ *     eps_{2j} = r cos(ang)              eps_{2j+1} = r sin(ang)
+ * so a call over a part of the samples (sim, err and out moved on by that many samples and columns, column_offset = the
+ * number of its first column) draws what the call over all of them draws.  Not correctly rounded by definition: ln, cos,
+ * sin.
+ * Errors, as above: SMART_E_NULL sim, err or out missing; SMART_E_SIZE n_samples, n_reports or n_replicates < 1, ld <
+ * n_samples, err_ld < 3, out_ld < C, a column number >= 2^32 (column_offset outside 0 .. 2^32 - 1 included), more than
+ * 2^31 - 1 report steps; then SMART_E_NO_DEVICE.
+ */
+#define SMART_ERROR_MODEL_SEGMENT 64
+#define SMART_ERROR_MODEL_LOGLIK 0
+#define SMART_ERROR_MODEL_SSQ 1
+#define SMART_ERROR_MODEL_LOGSIG 2
+int smart_error_model_loglik_hip(int64_t n_samples, int64_t n_reports, const double *sim, int64_t ld, const double *obs,
+                                 const double *err, int64_t err_ld, double *loglik, void *stream);
+int smart_error_model_draw_hip(int64_t n_samples, int64_t n_reports, int64_t n_replicates, const double *sim, int64_t ld,
+                               const double *err, int64_t err_ld, uint64_t seed, int64_t column_offset, int32_t truncate,
+                               double *out, int64_t out_ld, void *stream);
+
+/*
  * Sampling database, CSV flavour -- the rows MonteCarlo.save writes one by one (montecarlo.py:211-231): every value
  * cast to float32 and printed '%.6e', comma separated, one '\n'-terminated line per sample.  HOST pointers, no
  * device involved.  Appends n_rows lines of n_cols values (row-major float32 table: objective functions, parameters,

@@ -43,6 +43,8 @@ PAWN_MAX_FACTORS, PAWN_MAX_BINS = 16, 64
 PAWN_METHODS = {'auto': 0, 'lds': 1, 'global': 2}               # SMART_PAWN_*
 DEMCZ_MAX_DIMS, DEMCZ_MAX_CARRY = 16, 16
 DEMCZ_SCORES = {'logp': 0, 'rmse': 1, 'rmse_sigma': 2}          # SMART_DEMCZ_SCORE_*
+ERROR_MODEL_SEGMENT = 64                                        # SMART_ERROR_MODEL_SEGMENT
+ERROR_MODEL_ROWS = ['LOGLIK', 'SSQ', 'LOGSIG']                  # SMART_ERROR_MODEL_*, in row order
 
 _dp = ctypes.c_void_p   # device or host address, passed as an integer
 
@@ -133,6 +135,11 @@ SYMBOLS = {
                                             ctypes.c_double, _dp, ctypes.c_int32, ctypes.c_int32, _dp, _dp, _dp,
                                             ctypes.c_int32, _dp, _dp, _dp, _dp, ctypes.c_int64, ctypes.c_int64, _dp,
                                             ctypes.c_int64, _dp, _dp]),
+    'smart_error_model_loglik_hip': (ctypes.c_int, [ctypes.c_int64, ctypes.c_int64, _dp, ctypes.c_int64, _dp, _dp,
+                                                    ctypes.c_int64, _dp, _dp]),
+    'smart_error_model_draw_hip': (ctypes.c_int, [ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, _dp, ctypes.c_int64, _dp,
+                                                  ctypes.c_int64, ctypes.c_uint64, ctypes.c_int64, ctypes.c_int32, _dp,
+                                                  ctypes.c_int64, _dp]),
     'smart_db_append_rows': (ctypes.c_int, [ctypes.c_char_p, ctypes.POINTER(ctypes.c_float), ctypes.c_int64,
                                             ctypes.c_int64, ctypes.c_int32]),
     'smart_db_parse_rows': (ctypes.c_int64, [ctypes.c_char_p, ctypes.c_int64, ctypes.c_int64,

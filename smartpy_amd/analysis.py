@@ -1,7 +1,8 @@
 """The analyses of a stored [R, N] discharge matrix (row r = every sample's discharge of report step r), each one launch
 through the C ABI (csrc/smart_analysis_capi.hip): objective functions, weighted quantiles over the samples, objective
 functions per window of report steps, flow duration curves, hydrological signatures, Sobol indices, ensemble
-verification scores, the dynamic identifiability analysis, the PAWN sensitivity -- and the Pareto selection over the scores they leave, [N, C] with a row per sample.  torch tensors
+verification scores, the dynamic identifiability analysis, the PAWN sensitivity, the log-likelihood and the realisations
+of the residual error model -- and the Pareto selection over the scores they leave, [N, C] with a row per sample.  torch tensors
 in, torch tensors out, as in engine.py -- which imports this module and re-exports every public name of it
 (engine.flow_duration and the others are these functions); what they share on the way to the launch are the private
 helpers at the top.
@@ -730,3 +731,76 @@ def pawn_ks(values_row_major, categories, n_bins, method='auto'):
     _launch(dev, L.smart_pawn_ks_hip, N, R, y.data_ptr(), ld, cat.data_ptr(), P, B, ks.data_ptr(), counts.data_ptr(), code,
             _ptr(work), need)
     return PawnResult(ks, counts)
+
+
+ERROR_MODEL_ROWS = list(_lib.ERROR_MODEL_ROWS)
+
+
+def _error_parameters(who, error_parameters, device, n):
+    """The error_parameters= argument of a call: [n, 3] (sigma0, sigma1, phi per column of the matrix) or one triple for
+    all of them -> (float64 device tensor, its row stride).  Three columns of a wider device matrix -- rows[:, 10:13] of
+    the launch matrix of DE-MCz -- are read where they lie; anything else becomes a contiguous [n, 3]."""
+    t = error_parameters
+    if isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float64 and tuple(t.shape) == (n, 3) \
+            and t.device == device and t.stride(1) == 1 and (n == 1 or t.stride(0) >= 3):
+        return t, (t.stride(0) if n > 1 else 3)
+    shape = tuple(getattr(t, 'shape', np.shape(t)))
+    if shape == (3,):
+        t = _as_device(t, device, (1, 3)).repeat(n, 1)
+    elif shape == (n, 3):
+        t = _as_device(t, device, (n, 3))
+    else:
+        raise SmartEngineError(-2, "{}: error_parameters must be [{}, 3] (sigma0, sigma1, phi) or one triple, not shape {}."
+                               .format(who, n, shape))
+    return t, 3
+
+
+def residual_log_likelihood(discharge_report_major, obs, error_parameters):
+    """The log-likelihood of the observations under the residual error model, for every column of a stored [R, N]
+    discharge matrix -> device tensor [3, N] float64, the rows in the order of ERROR_MODEL_ROWS: LOGLIK, SSQ, LOGSIG.
+    With (sigma0, sigma1, phi) = error_parameters[i]: sigma_t = sigma0 + sigma1 sim[t, i], a_t = (obs[t] - sim[t, i]) /
+    sigma_t, and over the observed steps (obs not NaN) an AR(1) with coefficient phi on a_t that restarts, with its
+    stationary density, after every gap.  error_parameters: [N, 3], or one triple for all columns; a device tensor that
+    is three columns of a wider matrix is read in place.  A column with |phi| >= 1, a parameter that is not finite, or at
+    an observed step a flow that is not finite or sigma_t <= 0 is invalid: -inf, NaN, NaN.  No observed step: +0.0 in all
+    three.  Two calls give the same bits (include/smart_amd.h: smart_error_model_loglik_hip)."""
+    L = _lib.lib()
+    sim, R, N, ld = _matrix(discharge_report_major)
+    obs = _as_device(obs, sim.device, (R,))
+    out = torch.empty((len(ERROR_MODEL_ROWS), N), dtype=torch.float64, device=sim.device)
+    if N == 0:
+        return out
+    err, err_ld = _error_parameters('residual_log_likelihood', error_parameters, sim.device, N)
+    _launch(sim.device, L.smart_error_model_loglik_hip, N, R, sim.data_ptr(), ld, obs.data_ptr(), err.data_ptr(), err_ld,
+            out.data_ptr())
+    return out
+
+
+def predictive_draws(discharge_report_major, error_parameters, replicates=1, seed=0, truncate=True, out=None):
+    """Realisations of the residual error model on top of a stored [R, N] discharge matrix -> device tensor [R, N K]
+    float64 with K = replicates: column i K + k is replicate k of column i, sim[t, i] + sigma_t a_t with a_0 = eps_0 /
+    sqrt(1 - phi^2), a_t = phi a_{t-1} + eps_t over EVERY report step, eps standard normal (Philox4x32-10 counters
+    (column, t // 2) under `seed`, Box-Muller: the same bits from the same seed, whatever the launch).  truncate=True
+    replaces a negative flow by 0.  An invalid column (see residual_log_likelihood; judged over every step here) is NaN.
+    out: a float64 device matrix [R, N K] of the caller's to write into (its row stride is honoured), or None for a new
+    one.  The matrix goes into weighted_quantiles or ensemble_scores as any stored matrix does, with each column's
+    weight repeated over its replicates (include/smart_amd.h: smart_error_model_draw_hip)."""
+    who = 'predictive_draws'
+    L = _lib.lib()
+    K = int(replicates)
+    if K < 1:
+        raise SmartEngineError(-2, "{}: replicates must be at least 1 (got {}).".format(who, replicates))
+    sim, R, N, ld = _matrix(discharge_report_major)
+    C = N * K
+    if out is None:
+        out = torch.empty((R, C), dtype=torch.float64, device=sim.device)
+    elif not (isinstance(out, torch.Tensor) and out.is_cuda and out.device == sim.device and out.dtype == torch.float64
+              and tuple(out.shape) == (R, C) and (C == 0 or out.stride(1) == 1)):
+        raise SmartEngineError(-2, "{}: out must be a float64 matrix [{}, {}] on {} with unit stride along a row."
+                               .format(who, R, C, sim.device))
+    if N == 0 or R == 0:
+        return out
+    err, err_ld = _error_parameters(who, error_parameters, sim.device, N)
+    _launch(sim.device, L.smart_error_model_draw_hip, N, R, K, sim.data_ptr(), ld, err.data_ptr(), err_ld,
+            int(seed) & (2 ** 64 - 1), 0, 1 if truncate else 0, out.data_ptr(), out.stride(0) if R > 1 else C)
+    return out

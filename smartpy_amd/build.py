@@ -62,6 +62,10 @@ UNITS = {
     # the step of the DE-MCz sampler (proposal, crossover, reflection, Metropolis decision, archive): every operation of
     # the proposal rounded once -- the numpy statement of the tests is held to it bit for bit
     'smart_demcz.hip': ['-ffp-contract=off'],
+    # the residual error model (the AR(1) log-likelihood of a stored matrix, error realisations on top of it): every
+    # operation rounded once, as the numpy statement of the tests rounds it; NaNs honoured -- a NaN at a step without an
+    # observation is selected away, one at an observed step makes the sample invalid
+    'smart_error_model.hip': ['-ffp-contract=off'],
     'smart_capi.hip': [],
     # the C entries of the matrix analyses, and smart_objfn_matrix: the flags smart_capi.hip had it compiled with
     'smart_analysis_capi.hip': [],

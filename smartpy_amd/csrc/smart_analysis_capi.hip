@@ -1,6 +1,6 @@
 // smart_analysis_capi.hip -- the C ABI of the analyses of a stored discharge matrix sim[R][ld] (include/smart_amd.h):
 // objective functions, weighted quantiles, objective functions per window, flow duration curves, hydrological signatures, Sobol indices, the block bootstrap of the objective functions, and of
-// the Pareto selection over the scores they leave, the ensemble verification scores, the dynamic identifiability analysis and the PAWN sensitivity per report step, with their capacity and workspace entries -- validation and launch --
+// the Pareto selection over the scores they leave, the ensemble verification scores, the dynamic identifiability analysis and the PAWN sensitivity per report step, the residual error model (likelihood and draws), with their capacity and workspace entries -- validation and launch --
 // and the one kernel among them that has no unit of its own, smart_objfn_matrix.  Every refusal comes before the device is asked for; every rule is stated once, as a
 // method of the Check below, which carries the entry's name for the text.
 #include "smart_capi_internal.h"
@@ -780,6 +780,56 @@ int smart_demcz_step_hip(int64_t n_chains, int64_t chain_offset, int32_t n_dims,
     if (int rc = c.ready())
         return rc;
     launch_demcz(call, (hipStream_t)stream);
+    return launched();
+}
+
+// ---- the residual error model (smart_error_model.hip): the rules the two entries share, in the entries' order
+static void error_model_sizes(Check &c, std::initializer_list<Count> counts, int64_t n_samples, int64_t ld, int64_t err_ld)
+{
+    c.at_least_one(counts);
+    c.ld_holds("ld", ld, n_samples);
+    if (err_ld < 3)
+        c.refuse(SMART_E_SIZE, "err_ld %lld is less than the 3 parameters of a row", (long long)err_ld);
+}
+
+int smart_error_model_loglik_hip(int64_t n_samples, int64_t n_reports, const double *sim, int64_t ld, const double *obs,
+                                 const double *err, int64_t err_ld, double *loglik, void *stream)
+{
+    Check c("smart_error_model_loglik_hip");
+    c.required({NAMED(sim), NAMED(obs), NAMED(err), NAMED(loglik)});
+    error_model_sizes(c, {COUNT(n_samples), COUNT(n_reports)}, n_samples, ld, err_ld);
+    c.one_launch("n_samples", n_samples);
+    c.one_launch("n_reports", n_reports);
+    if (int rc = c.ready())
+        return rc;
+    launch_error_model_loglik((long)n_samples, (long)n_reports, sim, (long)ld, obs, err, (long)err_ld, loglik,
+                              (hipStream_t)stream);
+    return launched();
+}
+
+int smart_error_model_draw_hip(int64_t n_samples, int64_t n_reports, int64_t n_replicates, const double *sim, int64_t ld,
+                               const double *err, int64_t err_ld, uint64_t seed, int64_t column_offset, int32_t truncate,
+                               double *out, int64_t out_ld, void *stream)
+{
+    constexpr long long kTwo32 = 1ll << 32;
+    Check c("smart_error_model_draw_hip");
+    c.required({NAMED(sim), NAMED(err), NAMED(out)});
+    error_model_sizes(c, {COUNT(n_samples), COUNT(n_reports), COUNT(n_replicates)}, n_samples, ld, err_ld);
+    // the columns of the call: more than 2^32 of them are refused whatever their count is (it is not formed then)
+    const bool countable = c.ok() && n_samples <= kTwo32 / n_replicates;
+    const long long columns = countable ? (long long)n_samples * (long long)n_replicates : kTwo32 + 1;
+    if (c.ok() && countable && out_ld < columns)
+        c.refuse(SMART_E_SIZE, "out_ld %lld is less than the n_samples * n_replicates = %lld columns", (long long)out_ld,
+                 columns);
+    c.in_range("column_offset", column_offset, 0, kTwo32 - 1);
+    if (c.ok() && columns > kTwo32 - column_offset)
+        c.refuse(SMART_E_SIZE, "columns %lld ..: a column's number stays below 2^32 (%lld samples, %lld replicates)",
+                 (long long)column_offset, (long long)n_samples, (long long)n_replicates);
+    c.one_launch("n_reports", n_reports);
+    if (int rc = c.ready())
+        return rc;
+    launch_error_model_draw((long)n_samples, (long)n_reports, (long)n_replicates, sim, (long)ld, err, (long)err_ld, seed,
+                            (long)column_offset, truncate != 0, out, (long)out_ld, (hipStream_t)stream);
     return launched();
 }
 

@@ -186,4 +186,11 @@ inline long demcz_archive_after(const DemczCall &c)
 }
 void launch_demcz(const DemczCall &c, hipStream_t s);
 
+// ---- smart_error_model.hip
+void launch_error_model_loglik(long N, long R, const double *sim, long ld, const double *obs, const double *err, long err_ld,
+                               double *out, hipStream_t s);
+void launch_error_model_draw(long N, long R, long K, const double *sim, long ld, const double *err, long err_ld,
+                             unsigned long long seed, long column_offset, int truncate, double *out, long out_ld,
+                             hipStream_t s);
+
 } // namespace smart

@@ -190,13 +190,14 @@ class PosteriorSample(object):
     `history_log_density` [S, N] (every archived snapshot, the burn-in included -- what rhat was computed from); numpy:
     `accepted` [N] (int32, per chain), `rhat` [d], `acceptance_rate` (a float: accepted proposals over proposals made),
     `diagnostics` [S, 2 + d] (generation, acceptance rate up to it, R-hat over the second half of the snapshots up to
-    it); `burn_in` (snapshots dropped) and `file` (the diagnostics file, or None)."""
+    it); `burn_in` (snapshots dropped) and `file` (the diagnostics file, or None); `error_parameters` (device tensor [n, 3]:
+    sigma0, sigma1, phi of every row of the sample, where the run inferred a residual error model; else None)."""
 
     def __init__(self, names, sample, log_density, carry, history, history_log_density, accepted, rhat, acceptance_rate,
-                 diagnostics, burn_in, file=None):
+                 diagnostics, burn_in, file=None, error_parameters=None):
         self.names = list(names)
         self.sample, self.log_density, self.carry, self.history = sample, log_density, carry, history
         self.history_log_density, self.accepted = history_log_density, np.asarray(accepted)
         self.rhat, self.acceptance_rate = np.asarray(rhat, dtype=np.float64), float(acceptance_rate)
         self.diagnostics = np.asarray(diagnostics, dtype=np.float64)
-        self.burn_in, self.file = int(burn_in), file
+        self.burn_in, self.file, self.error_parameters = int(burn_in), file, error_parameters

@@ -570,7 +570,8 @@ from .analysis import (objective_functions, quantiles_sort_capacity, weighted_qu
                        pareto_max_objectives, pareto_counts, pareto_ranks,
                        ENSEMBLE_SCORE_NAMES, ensemble_scores_lds_capacity, ensemble_scores,
                        dynia_max_half_width, dynia_lds_capacity, DyniaResult, dynamic_identifiability,
-                       pawn_lds_capacity, PawnResult, pawn_ks)
+                       pawn_lds_capacity, PawnResult, pawn_ks,
+                       ERROR_MODEL_ROWS, residual_log_likelihood, predictive_draws)
 
 
 def allsteps(area_m2, delta_sec, length_simu, nd_rain, nd_peva, nd_parameters, nd_initial, report_type, report_gap):

@@ -16,6 +16,7 @@ import numpy as np
 from .montecarlo import MonteCarlo, OBJ_FN_NAMES
 from .. import demcz as core
 from .. import distributed as sdist
+from .. import errormodel
 from ..engine import SmartEngineError
 from ..sampling import latin_hypercube
 
@@ -33,20 +34,30 @@ class DEMCz(MonteCarlo):
     of each range.  likelihood='gaussian': independent Gaussian errors on the report steps that carry an observation --
     sigma=None integrates the error variance out (log-density -(n_eff / 2) ln(n RMSE^2)), a number fixes it
     (-n_eff RMSE^2 / (2 sigma^2)); n_eff (default: n, the observed report steps) is the number of observations the
-    errors are worth, for autocorrelated residuals.  vary / fixed: as for Sobol (default: all ten vary; a parameter
+    errors are worth, for autocorrelated residuals.  likelihood='ar1': the residual error model of smartpy_amd.errormodel
+    -- a standard deviation sigma0 + sigma1 sim_t and an AR(1) with coefficient phi on the standardised residuals -- whose
+    parameters are inferred with the model's: error_model maps 'sigma0' / 'sigma1' / 'phi' to a (lo, hi) range (the
+    parameter is a further dimension of the chains, initialised by the same Latin hypercube call over the widened ranges)
+    or to a number (it is fixed); a name that is missing takes errormodel.default_ranges.  The launch matrix is then 13
+    columns wide: the step kernel writes the error parameters like any other, the model launch sees a copy of the ten
+    model columns, and a generation is the launch with the discharge matrix kept, engine.residual_log_likelihood on the
+    matrix where it lies (the error parameters read in place from the launch matrix) and the step with a ready
+    log-density.  sigma= and n_eff= do not go with 'ar1'.  vary / fixed: as for Sobol (default: all ten vary; a parameter
     that does not stays at fixed[name], or at the middle of its range).  gw_prior=True gives a row that fails the
     groundwater constraint of the settings file the log-density -inf.  seed: of the initial Latin hypercube
     (sampling.latin_hypercube over model.parameters.ranges) and of the counter-based draws of the chains: the same seed
     gives the same bits.
 
-    run() leaves `posterior` (demcz.PosteriorSample), `log_density`, `acceptance_rate`, `rhat`, `diagnostics`, the sample
+    run() leaves `posterior` (demcz.PosteriorSample; with 'ar1' its `error_parameters` [n, 3] hold sigma0, sigma1, phi of
+    every archived row, fixed ones filled in, and `names`, `rhat` and `diagnostics` cover the sampled error parameters
+    after the model's), `log_density`, `acceptance_rate`, `rhat`, `diagnostics`, the sample
     (the archived rows after the burn-in, full parameter width), obj_fns / device_obj_fns / device_gw of those rows as the
     chains carried them, and the database `<catchment>.SMART.demcz`."""
 
     def __init__(self, catchment, root_f, in_format, out_format,
                  chains=1024, generations=500, thin=10, burn_in=0.5, cr=0.9, p_jump=0.1, b_star=1e-6,
                  likelihood='gaussian', sigma=None, n_eff=None, vary=None, fixed=None, gw_prior=False, seed=0,
-                 settings_filename=None):
+                 settings_filename=None, error_model=None):
         MonteCarlo.__init__(self, catchment, root_f, in_format, out_format,
                             parallel='seq', save_sim=False, func='demcz', settings_filename=settings_filename)
         self.chains, self.generations, self.thin = int(chains), int(generations), int(thin)
@@ -57,8 +68,13 @@ class DEMCz(MonteCarlo):
                                    .format(chains, generations, thin))
         if not 0.0 <= self.burn_in < 1.0:
             raise SmartEngineError(-2, "DEMCz: burn_in {} must be in [0, 1).".format(burn_in))
-        if likelihood != 'gaussian':
+        if likelihood not in ('gaussian', 'ar1'):
             raise SmartEngineError(-7, "DEMCz: likelihood '{}' unknown.".format(likelihood))
+        if likelihood == 'ar1' and (sigma is not None or n_eff is not None):
+            raise SmartEngineError(-2, "DEMCz: sigma= and n_eff= belong to likelihood='gaussian'; 'ar1' infers its error "
+                                       "parameters (error_model=).")
+        if likelihood != 'ar1' and error_model is not None:
+            raise SmartEngineError(-2, "DEMCz: error_model= belongs to likelihood='ar1'.")
         if gw_prior and not self.constraints['gw']:
             raise SmartEngineError(-2, "DEMCz: gw_prior needs the groundwater constraint of the settings file.")
         core.thresholds(self.p_jump, self.cr)
@@ -77,18 +93,44 @@ class DEMCz(MonteCarlo):
         self.columns = [names.index(p) for p in self.vary]
         self.lo = np.asarray([ranges[p][0] for p in self.vary], dtype=np.float64)
         self.hi = np.asarray([ranges[p][1] for p in self.vary], dtype=np.float64)
-        population = latin_hypercube(self.chains, ranges, names, seed=seed)
+        self.error_sampled, self.error_fixed = [], {}
+        if likelihood == 'ar1':
+            # the sampled error parameters: further dimensions of the chains, further columns of the launch matrix
+            self.error_sampled, error_ranges, self.error_fixed = errormodel.resolve(error_model, self.model.nd_flow)
+            if len(self.vary) + len(self.error_sampled) > core._lib.DEMCZ_MAX_DIMS:
+                raise SmartEngineError(-2, "DEMCz: {} dimensions, at most {}.".format(
+                    len(self.vary) + len(self.error_sampled), core._lib.DEMCZ_MAX_DIMS))
+            widened = dict((p, ranges[p]) for p in names)
+            widened.update(error_ranges)
+            drawn = latin_hypercube(self.chains, widened, names + self.error_sampled, seed=seed)
+            population = np.empty((self.chains, len(names) + len(errormodel.PARAMETER_NAMES)), dtype=np.float64)
+            population[:, :len(names)] = drawn[:, :len(names)]
+            for k, p in enumerate(errormodel.PARAMETER_NAMES):
+                population[:, len(names) + k] = drawn[:, len(names) + self.error_sampled.index(p)] \
+                    if p in self.error_sampled else self.error_fixed[p]
+            self.columns += [len(names) + errormodel.PARAMETER_NAMES.index(p) for p in self.error_sampled]
+            self.lo = np.concatenate([self.lo, [error_ranges[p][0] for p in self.error_sampled]])
+            self.hi = np.concatenate([self.hi, [error_ranges[p][1] for p in self.error_sampled]])
+        else:
+            population = latin_hypercube(self.chains, ranges, names, seed=seed)
         for j, p in enumerate(names):
             if p not in self.vary:
                 population[:, j] = fixed.get(p, 0.5 * (float(ranges[p][0]) + float(ranges[p][1])))
         self.initial_population = population
-        self._set_sample(population)
+        self._set_sample(population[:, :len(names)])
         self.posterior = self.log_density = self.acceptance_rate = self.rhat = self.diagnostics = None
 
     # ---- the log-density of a score ---------------------------------------------------------------------------
     @property
     def score_kind(self):
+        if self.likelihood == 'ar1':
+            return 'logp'
         return 'rmse' if self.sigma is None else 'rmse_sigma'
+
+    @property
+    def dimension_names(self):
+        """The dimensions of the chains: the model parameters that vary, then the error parameters that are sampled"""
+        return self.vary + self.error_sampled
 
     def log_density_of(self, rmse):
         """The log-density the chains are moved by, from the RMSE of a row (array or tensor; answered in kind)"""
@@ -112,6 +154,8 @@ class DEMCz(MonteCarlo):
         """One launch over the launch matrix of the chains -> (scores [N] at a stride, payload [N, 9])"""
         import torch
         n = self.chains
+        if self.likelihood == 'ar1':
+            return self._launch_chains_ar1(state)
         # (a view of its own per launch: what the engine remembers about a tensor object is not asked about rows that the
         # step kernel rewrites behind torch's back)
         out = self.model.simulate_ensemble(state.rows.view(n, len(self.param_names)), objective_functions=True,
@@ -123,6 +167,37 @@ class DEMCz(MonteCarlo):
         if self.gw_prior:
             scores = torch.where(table[:, GW_FLAG_COLUMN] > 0.0, scores, torch.full_like(scores, float('inf')))
         return scores, payload
+
+    def _launch_chains_ar1(self, state):
+        """The launch of a generation with likelihood='ar1' -> (log-likelihoods [N], payload [N, 9]): the model runs on a
+        contiguous copy of the ten model columns of the launch matrix (the engine takes a dense [N, 10]), keeps the [R, N]
+        matrix, and the likelihood kernel reads it where it lies, with the three error columns of the launch matrix at
+        the stride of its rows"""
+        import torch
+        from .. import engine
+        n, w = self.chains, len(self.param_names)
+        out = self.model.simulate_ensemble(state.rows[:, :w].contiguous(), objective_functions=True,
+                                           gw_constraint=self.constraints['gw'], save_discharge=True,
+                                           math_mode=self.math_mode)
+        table = out.objfn[:n]
+        payload = torch.cat([table, out.gw[:n].unsqueeze(1)], dim=1)
+        theta = state.rows[:, w:w + len(errormodel.PARAMETER_NAMES)]
+        scores = engine.residual_log_likelihood(out.discharge_report_major, self.model._device_cache[2], theta)[0]
+        if self.gw_prior:
+            scores = torch.where(table[:, GW_FLAG_COLUMN] > 0.0, scores, torch.full_like(scores, float('-inf')))
+        return scores, payload
+
+    def _check_memory(self, device):
+        """likelihood='ar1' keeps the [R, N] discharge matrix of a launch on the device: a chain count whose matrix does
+        not fit what is free there is refused before the first launch"""
+        import torch
+        R = len(self.model.timeseries_report) - 1
+        need = 8 * R * self.chains
+        free = torch.cuda.mem_get_info(device)[0]
+        if need > free:
+            raise SmartEngineError(-2, "DEMCz: likelihood='ar1' stores the [{}, {}] discharge matrix of a launch, {} bytes, "
+                                       "and the device has {} free: fewer chains, or a shorter period."
+                                   .format(R, self.chains, need, free))
 
     # ---- run -----------------------------------------------------------------------------------------------------
     def run(self, compression=None, write=False):
@@ -136,9 +211,11 @@ class DEMCz(MonteCarlo):
         population = self.initial_population
         if world > 1:       # (seed=None draws from NumPy's global stream: rank 0's population is THE population)
             population = sdist.broadcast_matrix(population, src=0)
-        N, G, thin, d = self.chains, self.generations, self.thin, len(self.vary)
+        N, G, thin, d = self.chains, self.generations, self.thin, len(self.dimension_names)
         S = 1 + G // thin
         device = default_device()
+        if self.likelihood == 'ar1':
+            self._check_memory(device)
         state = self._new_state(population, S, device)
         accepted_at = [torch.zeros((), dtype=torch.int64, device=device)]
         scores, payload = self._launch_chains(state)
@@ -158,6 +235,10 @@ class DEMCz(MonteCarlo):
         base = as_device(population[:1], device)
         full = base.repeat(sample_d.shape[0], 1)
         full[:, self.columns] = sample_d
+        # (with 'ar1' the rows are 13 wide: the ten model columns are the sample, the last three the error parameters)
+        width = len(self.param_names)
+        error_parameters = full[:, width:].contiguous() if self.likelihood == 'ar1' else None
+        full = full[:, :width].contiguous()
         accepted = state.accepted.cpu().numpy()
         gens = np.arange(S) * thin
         counts = torch.stack(accepted_at).cpu().numpy().astype(np.float64)
@@ -174,8 +255,9 @@ class DEMCz(MonteCarlo):
         self.device_obj_fns, self.device_gw = carry[:, :n_obj].contiguous(), carry[:, N_CARRY - 1].contiguous()
         host = carry.cpu().numpy()
         self.obj_fns, self.gw_contributions = np.ascontiguousarray(host[:, :n_obj]), np.ascontiguousarray(host[:, -1])
-        self.posterior = core.PosteriorSample(self.vary, sample_d, self.log_density, carry, history, history_logp, accepted,
-                                              self.rhat, self.acceptance_rate, self.diagnostics, first)
+        self.posterior = core.PosteriorSample(self.dimension_names, sample_d, self.log_density, carry, history,
+                                              history_logp, accepted, self.rhat, self.acceptance_rate, self.diagnostics,
+                                              first, error_parameters=error_parameters)
         failure = None
         if rank == 0:
             try:
@@ -183,7 +265,7 @@ class DEMCz(MonteCarlo):
                 db.write_table(self.obj_fns, self._sample, None)
                 self._finish_database(db, compression)
                 if write:
-                    core.write_diagnostics(self.diagnostics_file, self.vary, self.diagnostics)
+                    core.write_diagnostics(self.diagnostics_file, self.dimension_names, self.diagnostics)
                     self.posterior.file = self.diagnostics_file
             except Exception as e:      # noqa: BLE001 -- a full disk on rank 0 ends the call on every rank
                 failure = e
@@ -191,6 +273,12 @@ class DEMCz(MonteCarlo):
             sdist.agree_or_raise(failure)
         elif failure is not None:
             raise failure
+
+    def _default_error_parameters(self):
+        """what residual_likelihood and predictive_bounds take where none are given: the archived ones of an 'ar1' run"""
+        if self.posterior is None or self.posterior.error_parameters is None:
+            return None
+        return self.posterior.error_parameters.cpu().numpy()
 
     @property
     def diagnostics_file(self):

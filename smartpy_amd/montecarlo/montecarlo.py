@@ -562,6 +562,130 @@ class MonteCarlo(object):
         """`<out>/<catchment>.SMART.<func>.pawn`: beside the sampling database, whatever its format."""
         return self._side_file('.pawn')
 
+    # ---- the residual error model: likelihood and total predictive bounds -----------------------------------
+    def _default_error_parameters(self):
+        """[N, 3] where the object has inferred error parameters of its own (DEMCz with likelihood='ar1'), else None"""
+        return None
+
+    def _error_parameters(self, who, error_parameters):
+        """error_parameters of a call -> numpy [N, 3]: one (sigma0, sigma1, phi) per row of the sample, or one triple for
+        all of them; None takes the object's own"""
+        from .. import errormodel
+        if error_parameters is None:
+            error_parameters = self._default_error_parameters()
+            if error_parameters is None:
+                raise SmartEngineError(-1, "{}: error_parameters are needed ([N, 3] or one triple of sigma0, sigma1, phi; "
+                                           "a DEMCz run with likelihood='ar1' brings its own).".format(who))
+        if type(error_parameters).__module__.startswith('torch'):
+            error_parameters = error_parameters.cpu().numpy()
+        return errormodel.parameter_table(error_parameters, self._sample.shape[0])
+
+    def _row_weights(self, who, likelihood):
+        """None (equal weights) | the name of an objective function (its values in the last run()) | an array [N]
+        -> float64 [N] or None; negative or non-finite weights raise, nothing is clipped"""
+        n = self._sample.shape[0]
+        if likelihood is None:
+            return None
+        if isinstance(likelihood, str):
+            if likelihood not in self.obj_fn_names or self.obj_fns is None or self.obj_fns.shape[0] != n:
+                raise Exception("{}: the likelihood '{}' is not one of the objective functions of a finished run() of "
+                                "this object ({}).".format(who, likelihood, ', '.join(self.obj_fn_names)))
+            weights = np.asarray(self.obj_fns[:, self.obj_fn_names.index(likelihood)], dtype=np.float64)
+        else:
+            weights = np.asarray(likelihood, dtype=np.float64)
+            if weights.shape != (n,):
+                raise Exception("{}: the likelihood array has shape {} where one value per row of the sample ({}) is "
+                                "expected.".format(who, weights.shape, n))
+        bad = int(np.count_nonzero(~(np.isfinite(weights) & (weights >= 0.0))))
+        if bad:
+            raise Exception("{}: {} of the {} likelihood values are negative or not finite: they cannot be used as "
+                            "weights.".format(who, bad, n))
+        return weights
+
+    def residual_likelihood(self, error_parameters=None, write=False):
+        """The log-likelihood of the observed flow under the residual error model of smartpy_amd.errormodel, for every
+        row of the sample: sigma_t = sigma0 + sigma1 sim_t, an AR(1) with coefficient phi on the standardised residuals
+        that restarts after every gap of the observations.  error_parameters: [N, 3] (sigma0, sigma1, phi per row) or one
+        triple for all rows; None: those a DEMCz run with likelihood='ar1' archived.  One launch of its own over the
+        sample; the [R, N] matrix stays on the device and only [3, N] comes back (engine.residual_log_likelihood).
+        write=True also writes `<out>/<catchment>.SMART.<func>.errormodel` (header sigma0,sigma1,phi,LOGLIK,SSQ,LOGSIG;
+        one line per row of the sample, '%.6e').  Under torch.distributed every rank that calls this computes all rows
+        itself (no collective); rank 0 alone writes.  -> errormodel.ResidualLikelihood"""
+        from .. import engine, errormodel
+        self._check_observations()
+        theta = self._error_parameters('residual_likelihood', error_parameters)
+        on_device = None
+        if self._sample.shape[0] == 0:      # e.g. GLUE with no behavioural set: nothing to launch
+            values = np.empty((len(errormodel.LIKELIHOOD_NAMES), 0))
+        else:
+            out, obs = self._launch_stored()
+            on_device = engine.residual_log_likelihood(out.discharge_report_major, obs, theta)
+            values = on_device.cpu().numpy()
+        path = None
+        if self._writes(write):
+            path = self._side_file('.errormodel')
+            errormodel.write_likelihood_file(path, theta, values)
+        return errormodel.ResidualLikelihood(theta, values, on_device, path)
+
+    def predictive_bounds(self, error_parameters=None, quantiles=(0.05, 0.5, 0.95), replicates=1, likelihood=None, seed=0,
+                          truncate=True, verify=False, write=False):
+        """The TOTAL prediction bounds of the sample: at every report step the weighted quantiles of `replicates` error
+        realisations on top of every row's simulation (engine.predictive_draws: the residual error model with the row's
+        sigma0, sigma1, phi), each row's weight repeated over its replicates -- where GLUE.prediction_bounds describes
+        the spread of the parameter ensemble alone.  error_parameters: as for residual_likelihood.  likelihood: None =
+        equal weights (a posterior sample), the name of an objective function of this object's finished run(), or an
+        array [N]; negative or non-finite weights raise.  seed: of the draws (the same seed, the same bits); truncate:
+        negative flows become 0.  One launch of its own over the sample; the [R, N] matrix and the [R, N replicates]
+        draws stay on the device, and the draws matrix goes into engine.weighted_quantiles as any stored matrix does --
+        with verify=True into engine.ensemble_scores too (verification.EnsembleVerification of the total predictive
+        distribution: CRPS, PIT histogram, reliability).  The result also carries the parametric-only bounds of the same
+        rows and the containment of both.  write=True also writes `<out>/<catchment>.SMART.<func>.predictive` (CSV:
+        DateTime,q<p>,...,param_q<p>,...).  Under torch.distributed every rank that calls this computes all rows itself
+        (no collective); rank 0 alone writes.  -> errormodel.PredictiveBounds"""
+        import torch
+        from .. import engine, errormodel
+        from ..verification import EnsembleVerification
+        who = 'predictive_bounds'
+        q = np.atleast_1d(np.asarray(quantiles, dtype=np.float64))
+        K = int(replicates)
+        if K < 1:
+            raise SmartEngineError(-2, "{}: replicates must be at least 1 (got {}).".format(who, replicates))
+        stamps = self.model.timeseries_report[1:]
+        theta = self._error_parameters(who, error_parameters)
+        weights = self._row_weights(who, likelihood)
+        nan = float('nan')
+        verification = None
+        if self._sample.shape[0] == 0:      # e.g. GLUE with no behavioural set: nothing to launch
+            bounds = parametric = np.full((q.size, len(stamps)), nan)
+            containment = alone = nan
+        else:
+            out, obs = self._launch_stored()
+            sim = out.discharge_report_major
+            draws = engine.predictive_draws(sim, theta, replicates=K, seed=seed, truncate=truncate)
+            repeated = None if weights is None else np.repeat(weights, K)
+            total = engine.weighted_quantiles(draws, q, repeated)
+            spread = engine.weighted_quantiles(sim, q, weights)
+
+            def inside(band):
+                if obs is None:
+                    return nan
+                there = ~torch.isnan(obs)
+                hit = there & (band[0] <= obs) & (obs <= band[-1])
+                return float(hit.sum()) / float(there.sum()) if int(there.sum()) > 0 else nan
+            containment, alone = inside(total), inside(spread)
+            bounds, parametric = total.cpu().numpy(), spread.cpu().numpy()
+            if verify:
+                flow = self.model.nd_flow
+                scores = engine.ensemble_scores(draws, obs, repeated).cpu().numpy()
+                verification = EnsembleVerification(scores, None if flow is None else np.asarray(flow, dtype=np.float64),
+                                                    stamps)
+        path = None
+        if self._writes(write):
+            path = self._side_file('.predictive')
+            errormodel.write_predictive_file(path, stamps, q, bounds, parametric)
+        return errormodel.PredictiveBounds(q, bounds, parametric, containment, alone, stamps, K, seed, truncate,
+                                           verification, path)
+
     # ---- the per-sample protocol of the reference (spotpy setup class) ------------------------------------
     def parameters(self):
         return np.array([p() for p in self.params])
