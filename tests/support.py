@@ -128,6 +128,24 @@ def margins_dir():
     return os.environ.get('SMART_MARGINS_DIR')
 
 
+def hold(margins, path, what, got, want, bnd):
+    """scores against their exact truth and the bound derived for them: the pattern of NaN and of infinities equal, every
+    finite entry within its bound; the largest used fraction is noted in `margins` under `path`.  (Plain asserts with
+    their own messages: this module is not rewritten by pytest.)"""
+    assert got.shape == want.shape == bnd.shape, what
+    finite = np.isfinite(want)
+    with np.errstate(all='ignore'):
+        used = np.where(finite & np.isfinite(got), np.abs(got - want) / bnd, np.where(finite, np.inf, 0.0))
+    worst = float(np.max(used)) if used.size else 0.0
+    where = np.unravel_index(int(np.argmax(used)), used.shape) if used.size else ()
+    print('%s: %s: %.3g of the bound at %s' % (path, what, worst, where))
+    margins.note(path, worst, what)
+    assert np.array_equal(np.isnan(got), np.isnan(want)), '%s: %s: the pattern of NaN' % (path, what)
+    assert np.array_equal(got[~finite & ~np.isnan(want)], want[~finite & ~np.isnan(want)]), '%s: %s: infinities' % (path, what)
+    assert np.array_equal(np.isfinite(got), finite), '%s: %s: the pattern of infinities' % (path, what)
+    assert worst <= 1.0, '%s: %s: %.3g times the bound at %s' % (path, what, worst, where)
+
+
 # ---- the example catchment ---------------------------------------------------------------------------------------------
 def example_root(tmp_path):
     """a copy of the example catchment's input files (tests/golden/data/in) under tmp_path -> the root to run from"""

@@ -139,14 +139,14 @@ def compare(got, want, what):
     assert err < GATE, what
 
 
-@pytest.mark.parametrize('R,n', [(501, 17), (1025, 15), (4097, 5), (16384, 3)])
+@pytest.mark.parametrize('R,n', [(501, 17), (1025, 15), (2049, 5), (4097, 5), (16384, 3)])
 def test_objective_functions_of_the_curve(R, n):
     rng, obs, sim = data(7000 + R, R, n, obs_plus=0.05)
     cols = columns(rng, n, 10)
     probs = [0.05, 0.5, 0.95]
     for W, win in window_arrays(rng, R, 'zeros')[:3] if R > 501 else window_arrays(rng, R, 'zeros'):
         for transform in ('none', 'sqrt', 'log', 'inverse'):
-            for segment in ((0.0, 1.0), (0.98, 1.0), (0.0, 0.3)):
+            for segment in ((0.0, 1.0), (0.98, 1.0), (0.0, 0.3), (0.3, 0.7)):
                 if R * (segment[1] - segment[0]) / W < 4:
                     continue                                            # (the rule for short segments has its own test)
                 want_q, want = statement(sim[:, cols], probs, obs, win, W, transform, EPS[transform], segment, objfn=True)

@@ -11,8 +11,8 @@ about row 0 some entry of every case with r1 > 0 misses its bound a hundredfold 
 an unobserved report 0 (a flood before the gauge begins, a start-up value, a NaN) fails here.
 
 The fused moments of every time-loop kernel are held the same way, against truth on the discharge the same launch
-stored (second half of the module).  The flow-duration scores are not here: their constant is the first in-segment
-rank, inside the sums by construction.
+stored (second half of the module).  The flow-duration scores are held to the same truth in
+tests/test_gpu_flow_duration_truth.py: their constant is the first in-segment rank, and a constant from elsewhere fails there.
 
 The largest used fraction of the bound per path is printed at the end of the module (and written to
 $SMART_MARGINS_DIR/objfn_conditioning_margins.txt where that is set); profiles/objfn_conditioning_margins.txt is that
@@ -22,8 +22,9 @@ import os
 import numpy as np
 import pytest
 
+import support
 from support import Margins, margins_dir, padded, eng      # noqa: F401 (eng is a fixture)
-from test_objfn_truth_host import (BIG_CASE, LOG_EPS, MATRIX_CASES, SPECIAL_CASES, WINDOW_CASES, big_columns, bootstrap_case,
+from test_objfn_truth_host import (BIG_CASE, EPS, MATRIX_CASES, SPECIAL_CASES, WINDOW_CASES, big_columns, bootstrap_case,
                                    bootstrap_reference, bounds, first_observed, matrix_case, truth, window_case,
                                    window_reference)
 
@@ -32,7 +33,8 @@ pytestmark = pytest.mark.gpu
 PAD = 3             # ld = N + 3, the padding holds NaN
 MARGINS = Margins()
 PATHS = ['smart_objfn_hip', 'smart_objfn_hip, one lane per sample', 'smart_objfn_windows_hip none',
-         'smart_objfn_windows_hip log', 'smart_objfn_bootstrap_hip point', 'smart_objfn_bootstrap_hip jackknife']
+         'smart_objfn_windows_hip sqrt', 'smart_objfn_windows_hip log', 'smart_objfn_windows_hip inverse',
+         'smart_objfn_bootstrap_hip point', 'smart_objfn_bootstrap_hip jackknife']
 
 
 def on_device(sim):
@@ -42,18 +44,7 @@ def on_device(sim):
 
 def hold(path, what, got, want, bnd):
     """the pattern of NaN and infinities equal, every finite entry within its bound; the used fraction is kept"""
-    assert got.shape == want.shape == bnd.shape, what
-    finite = np.isfinite(want)
-    with np.errstate(all='ignore'):
-        used = np.where(finite & np.isfinite(got), np.abs(got - want) / bnd, np.where(finite, np.inf, 0.0))
-    worst = float(np.max(used)) if used.size else 0.0
-    where = np.unravel_index(int(np.argmax(used)), used.shape) if used.size else ()
-    print('%s: %s: %.3g of the bound at %s' % (path, what, worst, where))
-    MARGINS.note(path, worst, what)
-    assert np.array_equal(np.isnan(got), np.isnan(want)), '%s: %s: the pattern of NaN' % (path, what)
-    assert np.array_equal(got[~finite & ~np.isnan(want)], want[~finite & ~np.isnan(want)]), '%s: %s: infinities' % (path, what)
-    assert np.array_equal(np.isfinite(got), finite), '%s: %s: the pattern of infinities' % (path, what)
-    assert worst <= 1.0, '%s: %s: %.3g times the bound at %s' % (path, what, worst, where)
+    support.hold(MARGINS, path, what, got, want, bnd)
 
 
 @pytest.fixture(scope='module', autouse=True)
@@ -125,9 +116,9 @@ def test_matrix_kernel_with_one_lane_per_sample():
 @pytest.mark.parametrize('name,transform', WINDOW_CASES)
 def test_windows_kernel_about_each_windows_first_observed_report(name, transform):
     from smartpy_amd import engine
-    sim, obs, win, W = window_case(name)
+    sim, obs, win, W = window_case(name, transform)
     got = engine.objective_functions_windows(on_device(sim), obs, win, n_windows=W, transform=transform,
-                                             eps=LOG_EPS if transform == 'log' else 0.0).cpu().numpy()
+                                             eps=EPS[transform]).cpu().numpy()
     want, bnd = window_reference(sim, obs, win, W, transform)
     assert np.isfinite(want).all()
     hold('smart_objfn_windows_hip ' + transform, '%s, W=%d' % (name, W), got, want, bnd)
