@@ -350,6 +350,18 @@ def agree_or_raise(failure, device=None):
         raise SmartEngineError(-6, "smartpy_amd: another rank's launch failed; the gathered results would not be complete")
 
 
+def on_rank_zero(write):
+    """`write()` on rank 0 alone, then its outcome agreed over the ranks: a full disk on rank 0 ends the call on every
+    rank (every rank gets here: the barrier of the call, with an outcome)."""
+    failure = None
+    if rank_world()[0] == 0:
+        try:
+            write()
+        except Exception as e:      # noqa: BLE001 -- re-raised by agree_or_raise, on this rank as it is
+            failure = e
+    agree_or_raise(failure)
+
+
 def broadcast_matrix(matrix, src=0):
     """Every rank gets rank `src`'s copy of a numpy matrix (shape and dtype included).  The Monte-Carlo classes call
     this on their sample before sharding it: the reference's sampler draws from NumPy's unseeded global stream

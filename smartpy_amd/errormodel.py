@@ -5,8 +5,6 @@ ranges, how an `error_model=` argument is read, the result objects of MonteCarlo
 MonteCarlo.predictive_bounds, and the writers of their side files.  numpy only, nothing hot: the two kernels are behind
 engine.residual_log_likelihood and engine.predictive_draws (include/smart_amd.h: smart_error_model_loglik_hip).
 """
-from csv import writer
-
 import numpy as np
 
 from ._lib import SmartEngineError, ERROR_MODEL_ROWS
@@ -101,18 +99,15 @@ class PredictiveBounds(object):
 def write_likelihood_file(path, error_parameters, values):
     """`<catchment>.SMART.<func>.errormodel`: header sigma0,sigma1,phi,LOGLIK,SSQ,LOGSIG, one line per row of the sample in
     the sample's order, '%.6e'."""
+    from .montecarlo.selection import write_text_table
     table = np.concatenate([np.asarray(error_parameters, dtype=np.float64), np.asarray(values, dtype=np.float64).T], axis=1)
-    with open(path, 'w', newline='', encoding='utf8') as f:
-        w = writer(f, delimiter=',')
-        w.writerow(PARAMETER_NAMES + LIKELIHOOD_NAMES)
-        w.writerows(['%.6e' % v for v in row] for row in table)
+    write_text_table(path, ','.join(PARAMETER_NAMES + LIKELIHOOD_NAMES), table, '%.6e', '\r\n')
 
 
 def write_predictive_file(path, stamps, quantiles, bounds, parametric):
     """`<catchment>.SMART.<func>.predictive`: header DateTime,q<p>,...,param_q<p>,...; one line per report step with the
     dates and the '%e' of the modelled flow file."""
-    with open(path, 'w', newline='', encoding='utf8') as f:
-        w = writer(f, delimiter=',')
-        w.writerow(['DateTime'] + ['q%g' % p for p in quantiles] + ['param_q%g' % p for p in quantiles])
-        w.writerows([dt] + ['%e' % v for v in total] + ['%e' % v for v in alone]
-                    for dt, total, alone in zip(stamps, np.asarray(bounds).T, np.asarray(parametric).T))
+    from .montecarlo.selection import write_text_table
+    header = ','.join(['DateTime'] + ['q%g' % p for p in quantiles] + ['param_q%g' % p for p in quantiles])
+    write_text_table(path, header, np.concatenate([np.asarray(bounds).T, np.asarray(parametric).T], axis=1), '%e', '\r\n',
+                     labels=stamps)

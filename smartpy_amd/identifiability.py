@@ -124,13 +124,10 @@ def header_line(names):
 
 def write_file(path, stamps, names, information, limits):
     """header_line, then one line per report step: its stamp and '%.6e' of IC, LO, HI per parameter."""
-    with open(path, 'w', newline='', encoding='utf8') as f:
-        f.write(header_line(names))
-        for r, stamp in enumerate(stamps):
-            cells = [str(stamp)]
-            for p in range(len(names)):
-                cells += ['%.6e' % information[r, p], '%.6e' % limits[r, p, 0], '%.6e' % limits[r, p, 1]]
-            f.write(','.join(cells) + '\n')
+    from .montecarlo.selection import write_text_table
+    R, P = len(stamps), len(names)
+    table = np.concatenate([np.asarray(information)[:R, :P, None], np.asarray(limits)[:R, :P]], axis=2).reshape(R, 3 * P)
+    write_text_table(path, header_line(names)[:-1], table, '%.6e', '\n', labels=stamps)
 
 
 class DynamicIdentifiability(object):

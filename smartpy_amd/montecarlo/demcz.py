@@ -207,7 +207,7 @@ class DEMCz(MonteCarlo):
         torch.distributed every rank computes everything itself and rank 0 alone writes."""
         import torch
         from ..engine import as_device, default_device
-        rank, world = sdist.rank_world()
+        world = sdist.rank_world()[1]
         population = self.initial_population
         if world > 1:       # (seed=None draws from NumPy's global stream: rank 0's population is THE population)
             population = sdist.broadcast_matrix(population, src=0)
@@ -258,21 +258,12 @@ class DEMCz(MonteCarlo):
         self.posterior = core.PosteriorSample(self.dimension_names, sample_d, self.log_density, carry, history,
                                               history_logp, accepted, self.rhat, self.acceptance_rate, self.diagnostics,
                                               first, error_parameters=error_parameters)
-        failure = None
-        if rank == 0:
-            try:
-                db = self._open_database()
-                db.write_table(self.obj_fns, self._sample, None)
-                self._finish_database(db, compression)
-                if write:
-                    core.write_diagnostics(self.diagnostics_file, self.dimension_names, self.diagnostics)
-                    self.posterior.file = self.diagnostics_file
-            except Exception as e:      # noqa: BLE001 -- a full disk on rank 0 ends the call on every rank
-                failure = e
-        if world > 1:
-            sdist.agree_or_raise(failure)
-        elif failure is not None:
-            raise failure
+
+        def write_files():
+            self._write_database(None, compression)
+            self.posterior.file = self._write_side(write, '.diagnostics', lambda path: core.write_diagnostics(
+                path, self.dimension_names, self.diagnostics))
+        sdist.on_rank_zero(write_files)
 
     def _default_error_parameters(self):
         """what residual_likelihood and predictive_bounds take where none are given: the archived ones of an 'ar1' run"""

@@ -2,13 +2,20 @@
 LHS sampling, re-simulate them (typically on another period) -- and, beyond the reference, hand out what a GLUE
 analysis is run for: the likelihood-weighted prediction bounds of the behavioural ensemble (prediction_bounds), and
 how good that predictive distribution is against the observations (ensemble_verification)."""
-from csv import writer
-
 import numpy as np
 
+from .analyses import containment, likelihood_weights
 from .montecarlo import MonteCarlo
-from .selection import condition_mask, check_shapes, SecondStage
+from .selection import condition_mask, check_shapes, write_text_table, SecondStage
 from ..verification import EnsembleVerification
+
+#: the refusals of analyses.likelihood_weights as GLUE words them
+LIKELIHOOD_TEXTS = {
+    'name': "The likelihood '{name}' is not one of the objective functions of the sampling run ({names}).",
+    'shape': "The likelihood array has shape {shape} where one value per behavioural set ({n}) is expected.",
+    'values': "{bad} of the {n} likelihood values are negative or not finite: they cannot be used as weights (shift or "
+              "select them first, nothing is clipped here).",
+}
 
 
 class PredictionBounds(object):
@@ -65,24 +72,8 @@ class GLUE(SecondStage, MonteCarlo):
     def _likelihood_weights(self, likelihood):
         """None (equal weights) | the name of an objective function (its values in the sampling run, for the
         behavioural rows) | an array [N_behavioural] -> float64 [N_behavioural] or None.  Nothing is clipped."""
-        n = self._sample.shape[0]
-        if likelihood is None:
-            return None
-        if isinstance(likelihood, str):
-            if likelihood not in self.obj_fn_names:
-                raise Exception("The likelihood '{}' is not one of the objective functions of the sampling run "
-                                "({}).".format(likelihood, ', '.join(self.obj_fn_names)))
-            weights = self.behavioural_obj_fns[:, self.obj_fn_names.index(likelihood)].astype(np.float64)
-        else:
-            weights = np.asarray(likelihood, dtype=np.float64)
-            if weights.shape != (n,):
-                raise Exception("The likelihood array has shape {} where one value per behavioural set ({}) is "
-                                "expected.".format(weights.shape, n))
-        bad = int(np.count_nonzero(~(np.isfinite(weights) & (weights >= 0.0))))
-        if bad:
-            raise Exception("{} of the {} likelihood values are negative or not finite: they cannot be used as "
-                            "weights (shift or select them first, nothing is clipped here).".format(bad, n))
-        return weights
+        return likelihood_weights(likelihood, self._sample.shape[0], self.obj_fn_names, self.behavioural_obj_fns,
+                                  LIKELIHOOD_TEXTS)
 
     def prediction_bounds(self, quantiles=(0.05, 0.5, 0.95), likelihood=None, write=False):
         """The GLUE prediction bounds: at every report step the likelihood-weighted quantiles of the behavioural
@@ -93,32 +84,21 @@ class GLUE(SecondStage, MonteCarlo):
         negative or non-finite weights raise.  write=True also writes `<out>/<catchment>.SMART.glue.bounds` (CSV:
         DateTime,q<p>,... with the dates and the '%e' of the modelled flow file).  Under torch.distributed every rank
         that calls this computes all rows itself (no collective); rank 0 alone writes.  -> PredictionBounds"""
-        import torch
         from .. import engine
         q = np.atleast_1d(np.asarray(quantiles, dtype=np.float64))
         stamps = self.model.timeseries_report[1:]
         weights = self._likelihood_weights(likelihood)
-        n = self._sample.shape[0]
-        if n == 0:      # no behavioural set: nothing to launch
-            bounds, containment = np.full((q.size, len(stamps)), np.nan), float('nan')
+        if self._sample.shape[0] == 0:      # no behavioural set: nothing to launch
+            bounds, inside = np.full((q.size, len(stamps)), np.nan), float('nan')
         else:
             out, obs = self._launch_stored()
             on_device = engine.weighted_quantiles(out.discharge_report_major, q, weights)
-            containment = float('nan')
-            if obs is not None:
-                there = ~torch.isnan(obs)
-                inside = there & (on_device[0] <= obs) & (obs <= on_device[-1])
-                if int(there.sum()) > 0:
-                    containment = float(inside.sum()) / float(there.sum())
+            inside = containment(on_device, obs)
             bounds = on_device.cpu().numpy()
-        path = None
-        if self._writes(write):
-            path = self._side_file('.bounds')
-            with open(path, 'w', newline='', encoding='utf8') as f:
-                w = writer(f, delimiter=',')
-                w.writerow(['DateTime'] + ['q%g' % p for p in q])
-                w.writerows([dt] + ['%e' % v for v in column] for dt, column in zip(stamps, bounds.T))
-        return PredictionBounds(q, bounds, stamps, containment, path)
+        header = ','.join(['DateTime'] + ['q%g' % p for p in q])
+        path = self._write_side(write, '.bounds',
+                                lambda path: write_text_table(path, header, bounds.T, '%e', '\r\n', labels=stamps))
+        return PredictionBounds(q, bounds, stamps, inside, path)
 
     # ---- ensemble verification --------------------------------------------------------------------------
     def ensemble_verification(self, likelihood=None, bins=10, write=False):
@@ -140,12 +120,8 @@ class GLUE(SecondStage, MonteCarlo):
         else:
             out, obs = self._launch_stored()
             scores = engine.ensemble_scores(out.discharge_report_major, obs, weights).cpu().numpy()
-        path = None
-        if self._writes(write):
-            path = self._side_file('.verification')
-            with open(path, 'w', newline='', encoding='utf8') as f:
-                w = writer(f, delimiter=',')
-                w.writerow(['DateTime', 'crps', 'spread', 'pit_low', 'pit_high', 'mean'])
-                w.writerows([dt] + ['%e' % v for v in column] for dt, column in zip(stamps, scores.T))
+        path = self._write_side(write, '.verification',
+                                lambda path: write_text_table(path, 'DateTime,crps,spread,pit_low,pit_high,mean', scores.T,
+                                                              '%e', '\r\n', labels=stamps))
         return EnsembleVerification(scores, None if flow is None else np.asarray(flow, dtype=np.float64), stamps, bins,
                                     path)

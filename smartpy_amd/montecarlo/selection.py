@@ -147,6 +147,21 @@ def write_float32_table(path, header, table, labels=None):
             f.write(label + ',' + line + '\n')
 
 
+def write_text_table(path, header, table, fmt, end, labels=None):
+    """The side file of an analysis whose cells Python formats: `header` (the header line without its terminator), then one
+    line per row of the [n, k] table, every cell `fmt` % its float64 ('%e': the modelled flow file's; '%.6e'), behind
+    str(label) where `labels` holds one per row (report stamps, names of outputs: nothing in them is quoted).  Every line,
+    the header's too, ends with `end`: '\r\n' in the files that began as csv.writer output (.errormodel, .predictive,
+    .bounds, .verification), '\n' in the others (.dynia, .pawn) -- each file keeps the terminator it was first written
+    with."""
+    table = np.asarray(table, dtype=np.float64)
+    with open(path, 'w', newline='', encoding='utf8') as f:
+        f.write(header + end)
+        for r, row in enumerate(table):
+            cells = [fmt % v for v in row]
+            f.write(','.join(cells if labels is None else [str(labels[r])] + cells) + end)
+
+
 def as_stored(matrix):
     """What a float64 matrix becomes on its way through a sampling database: cast to float32, printed '%.6e', parsed
     back to float32 (montecarlo.py:225-231, :262) -- 7 significant digits, not a float32 round trip.  Done with the

@@ -124,10 +124,8 @@ class Sobol(MonteCarlo):
         '%.6e' of the sampling database; rank 0 alone writes).  -> SobolIndices"""
         names, values = self._target_rows(targets)
         res, S1, ST, S1_conf, ST_conf, mean, variance = self._analyse(values, resamples, conf_level, seed)
-        path = None
-        if self._writes(write):
-            path = self.indices_file
-            _write_indices_file(path, names, self.vary, S1, S1_conf, ST, ST_conf)
+        path = self._write_side(write, '.indices',
+                                lambda path: _write_indices_file(path, names, self.vary, S1, S1_conf, ST, ST_conf))
         return SobolIndices(self.vary, names, S1, ST, S1_conf, ST_conf, mean, variance, float(conf_level), int(resamples),
                             res, path)
 
@@ -142,10 +140,7 @@ class Sobol(MonteCarlo):
         res, S1, ST, S1_conf, ST_conf, mean, variance = self._analyse(out.discharge_report_major, resamples, conf_level,
                                                                       seed)
         stamps = self.model.timeseries_report[1:]
-        path = None
-        if self._writes(write):
-            path = self.series_file
-            _write_series_file(path, stamps, self.vary, S1, ST)
+        path = self._write_side(write, '.series', lambda path: _write_series_file(path, stamps, self.vary, S1, ST))
         return SobolSeries(self.vary, stamps, S1, ST, S1_conf, ST_conf, mean, variance, float(conf_level), int(resamples),
                            res, path)
 

@@ -86,11 +86,10 @@ def header_line(names):
 def write_file(path, stamps, names, index, dummy):
     """header_line, then one line per output: its stamp (or label), '%.6e' of the index of every parameter and of the
     dummy."""
-    with open(path, 'w', newline='', encoding='utf8') as f:
-        f.write(header_line(names))
-        for r, stamp in enumerate(stamps):
-            f.write(','.join([str(stamp)] + ['%.6e' % index[r, p] for p in range(len(names))] + ['%.6e' % dummy[r]])
-                    + '\n')
+    from .montecarlo.selection import write_text_table
+    R = len(stamps)
+    table = np.concatenate([np.asarray(index)[:R, :len(names)], np.asarray(dummy)[:R, None]], axis=1)
+    write_text_table(path, header_line(names)[:-1], table, '%.6e', '\n', labels=stamps)
 
 
 class PawnSensitivity(object):

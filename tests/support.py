@@ -163,6 +163,15 @@ def settings_file(root, name, start, end, warm, simu_minutes=60):
                 'gw_constraint,0.12667\n' % (start, end, simu_minutes, warm))
 
 
+def golden_script(name):
+    """tests/golden/<name>.py as a module: the script that made a fixture holds the cases, and the test runs them"""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location(name, os.path.join(GOLDEN, name + '.py'))
+    module = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(module)
+    return module
+
+
 # ---- seeded inputs of the windowed matrix analyses ---------------------------------------------------------------------
 def data(seed, R, n, obs_plus):
     """(rng, obs [R] with 15 % missing, sim [R, n]) of one seed; the observations are |normal(3, 1.5)| + obs_plus.  (The

@@ -417,7 +417,7 @@ def test_every_workflow_has_score_uncertainty():
 
 def test_eligible_windows_and_the_uncertainty_file(tmp_path):
     from smartpy_amd import windows
-    from smartpy_amd.montecarlo.montecarlo import _write_uncertainty_file
+    from smartpy_amd.montecarlo.analyses import _write_uncertainty_file
     obs = np.ones(1230)
     ids = np.repeat(np.arange(5), [100, 365, 366, 330, 69]).astype(np.int32)
     obs[120:140] = np.nan                                               # window 1 keeps 345 of 365

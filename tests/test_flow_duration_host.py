@@ -277,7 +277,7 @@ def test_exceedance_becomes_non_exceedance_on_the_host():
 
 def test_the_fdc_file(tmp_path):
     from smartpy_amd import windows
-    from smartpy_amd.montecarlo.montecarlo import _write_fdc_file
+    from smartpy_amd.montecarlo.analyses import _write_fdc_file
     names = ['NSE', 'KGE', 'KGEc', 'KGEa', 'KGEb', 'PBias', 'RMSE']
     assert windows.fdc_header_line((0.01, 0.5), ['2007', '2008'], 'log') == \
         ','.join(['Q0.01@2007', 'Q0.5@2007', 'Q0.01@2008', 'Q0.5@2008'] + ['%s:log@2007' % f for f in names]

@@ -278,7 +278,7 @@ def test_default_alpha_and_thresholds():
 
 def test_the_signatures_file_and_the_result(tmp_path):
     from smartpy_amd import windows
-    from smartpy_amd.montecarlo.montecarlo import _write_signatures_file
+    from smartpy_amd.montecarlo.analyses import _write_signatures_file
     from smartpy_amd.montecarlo.selection import as_stored
     assert windows.signatures_header_line(['2007', '2008']) == \
         ','.join(['%s@2007' % f for f in NAMES] + ['%s@2008' % f for f in NAMES]) + '\n'

@@ -243,7 +243,7 @@ def test_every_workflow_has_window_objective_functions():
 
 def test_header_line_of_the_windows_file_and_default_eps(tmp_path):
     from smartpy_amd import windows
-    from smartpy_amd.montecarlo.montecarlo import _write_windows_file
+    from smartpy_amd.montecarlo.analyses import _write_windows_file
     names = ['NSE', 'KGE', 'KGEc', 'KGEa', 'KGEb', 'PBias', 'RMSE']
     assert windows.OBJ_FN_NAMES == names
     assert windows.header_line(['1994', '1995'], 'log') == \
