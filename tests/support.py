@@ -4,12 +4,13 @@ the C-entry tests.  A plain module: pytest does not collect it, and it imports t
 that need them.  Its checks return a bool for the test to assert on (pytest rewrites `assert` only in test modules)."""
 import os
 import shutil
+import subprocess
 import sys
 
 import numpy as np
 import pytest
 
-from conftest import GOLDEN
+from conftest import GOLDEN, ROOT
 
 EXTRA = {'aar': 1200, 'r-o_ratio': 0.45, 'r-o_split': (0.10, 0.15, 0.15, 0.30, 0.30)}
 SENTINEL = -7.0         # what an output buffer holds before a call
@@ -17,6 +18,10 @@ GUARD = 64              # elements of SENTINEL on either side of a guarded outpu
 #: the 'min' threshold on the sampling run's NSE in the GLUE tests (256 rows from np.random.seed(2024) on the example
 #: catchment): between 10 and 200 of the rows pass
 NSE_MIN = 0.2
+GATE = 1e-9             # the relative gate the analysis tests of the suite hold a kernel's results to
+SMALL = 1e-6            # a finite |truth| below this is left out of relative comparisons
+E_NULL, E_SIZE, E_NO_DEVICE, E_MODE = -1, -2, -6, -7
+FAKE = 0x1000           # a non-NULL address that no refusal path reads
 
 
 # ---- comparisons -------------------------------------------------------------------------------------------------------
@@ -175,7 +180,7 @@ def golden_script(name):
 # ---- seeded inputs of the windowed matrix analyses ---------------------------------------------------------------------
 def data(seed, R, n, obs_plus):
     """(rng, obs [R] with 15 % missing, sim [R, n]) of one seed; the observations are |normal(3, 1.5)| + obs_plus.  (The
-    signatures and the bootstrap draw theirs from tests/test_signatures_truth_host.py: a hydrograph, not noise.)"""
+    signatures and the bootstrap draw theirs from cases_signatures.data: a hydrograph, not noise.)"""
     rng = np.random.default_rng(seed)
     obs = np.abs(rng.normal(3.0, 1.5, R)) + obs_plus           # (+ 0.0 leaves every bit of a magnitude as it is)
     obs[rng.random(R) < 0.15] = np.nan
@@ -195,6 +200,25 @@ def window_arrays(rng, R, whole):
 def columns(rng, n, draws):
     """the first and the last of n columns and `draws` random ones, sorted, each once"""
     return np.unique(np.concatenate([[0, n - 1], rng.integers(0, n, draws)]))
+
+
+# ---- the C entries without a device: the refusal tables ----------------------------------------------------------------
+def binding():
+    """-> (smartpy_amd._lib, the loaded library)"""
+    from smartpy_amd import _lib
+    return _lib, _lib.lib()
+
+
+def refusal(valid, entry, changes):
+    """valid[entry] (name -> value of a call that breaks no rule) with `changes` -> (what the entry returned, the text it
+    left; None for the entries that leave none).  A tuple becomes an array of doubles."""
+    import ctypes
+    args = dict(valid[entry], **changes)
+    assert list(args) == list(valid[entry]), 'a change names no parameter of %s' % entry
+    keep = [(ctypes.c_double * len(v))(*v) if isinstance(v, tuple) else v for v in args.values()]
+    L = binding()[1]
+    rc = getattr(L, entry)(*keep)
+    return rc, (L.smart_last_error().decode() if entry.endswith('_hip') else None)
 
 
 # ---- device plumbing of the C-entry tests ------------------------------------------------------------------------------
@@ -271,3 +295,15 @@ class Guarded:
 
     def intact(self):
         return self.read()[1]
+
+
+def build_c_example(tmp_path):
+    """examples/ensemble_from_c.c with plain gcc (C, not C++): the header is C, the only link dependencies are the
+    library and the HIP runtime."""
+    exe = str(tmp_path / 'ensemble_from_c')
+    csrc = os.path.join(ROOT, 'smartpy_amd', 'csrc')
+    subprocess.check_call(['gcc', '-O2', '-Wall', '-Werror', '-D__HIP_PLATFORM_AMD__', '-I/opt/rocm/include',
+                           '-I', os.path.join(ROOT, 'include'), os.path.join(ROOT, 'examples', 'ensemble_from_c.c'),
+                           '-L', csrc, '-lsmart_amd', '-L/opt/rocm/lib', '-lamdhip64', '-lm',
+                           '-Wl,-rpath,' + csrc, '-Wl,-rpath,/opt/rocm/lib', '-o', exe])
+    return exe

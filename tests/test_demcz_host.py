@@ -8,30 +8,10 @@ import math
 import numpy as np
 import pytest
 
+from oracle.analyses.demcz import (LOGP, RMSE, RMSE_SIGMA, Chains, demcz_statement, log_density, mulhi, run_statement)
+from oracle.philox import philox4x32, u53
 from smartpy_amd import _lib, demcz
-
-M32 = np.uint64(0xFFFFFFFF)
-LOGP, RMSE, RMSE_SIGMA = 0, 1, 2
-
-
-# ---- Philox4x32-10 (Salmon et al. 2011) ---------------------------------------------------------------------------------
-def philox4x32(counter, key):
-    """counter: four words (numbers or arrays), key: two -> the four output words, uint64 arrays holding 32-bit values"""
-    c0, c1, c2, c3 = np.broadcast_arrays(*[np.asarray(c, dtype=np.uint64) for c in counter])
-    k0, k1 = np.uint64(key[0]), np.uint64(key[1])
-    for _ in range(10):
-        p0, p1 = np.uint64(0xD2511F53) * c0, np.uint64(0xCD9E8D57) * c2
-        c0, c1, c2, c3 = (p1 >> np.uint64(32)) ^ c1 ^ k0, p1 & M32, (p0 >> np.uint64(32)) ^ c3 ^ k1, p0 & M32
-        k0, k1 = (k0 + np.uint64(0x9E3779B9)) & M32, (k1 + np.uint64(0xBB67AE85)) & M32
-    return c0, c1, c2, c3
-
-
-def u53(w0, w1):
-    return (((w0 >> np.uint64(5)) << np.uint64(26)) + (w1 >> np.uint64(6))).astype(np.float64) * 2.0 ** -53
-
-
-def mulhi(w, n):
-    return (w * np.uint64(n)) >> np.uint64(32)
+from support import E_MODE, E_NO_DEVICE, E_NULL, E_SIZE, FAKE, refusal
 
 
 def test_philox_known_answers():
@@ -48,142 +28,6 @@ def test_philox_known_answers():
         assert [int(w[i]) for w in got] == [int(w) for w in philox4x32((i, 7, 1, 0), (3, 9))]
     assert u53(np.uint64(ones), np.uint64(ones)) == 1.0 - 2.0 ** -53 and u53(np.uint64(31), np.uint64(63)) == 0.0
     assert int(mulhi(np.uint64(ones), 10)) == 9 and int(mulhi(np.uint64(0), 10)) == 0
-
-
-# ---- the statement ----------------------------------------------------------------------------------------------------
-class Chains(object):
-    """The state of the statement, in numpy: what demcz.DemczState keeps on the device."""
-
-    def __init__(self, x, lo, hi, capacity, seed=0, cr=0.9, p_jump=0.1, b_star=1e-6, n_carry=0, columns=None, ld=None,
-                 fill=np.nan, score_kind=LOGP, n_obs=0, n_eff=0.0, sigma=0.0):
-        self.x = np.array(x, dtype=np.float64)
-        N, d = self.x.shape
-        self.lo, self.hi = np.asarray(lo, dtype=np.float64), np.asarray(hi, dtype=np.float64)
-        self.scale = float(b_star) * (self.hi - self.lo)
-        self.gamma = demcz.gamma_table(d)
-        self.J, self.C = demcz.thresholds(p_jump, cr)
-        self.key = (int(seed) & 0xFFFFFFFF, (int(seed) >> 32) & 0xFFFFFFFF)
-        self.columns = np.arange(d) if columns is None else np.asarray(columns)
-        self.score_kind, self.n_obs, self.n_eff, self.sigma = score_kind, n_obs, n_eff, sigma
-        self.logp = np.full(N, -np.inf)
-        self.carry = np.zeros((N, n_carry))
-        self.accepted = np.zeros(N, dtype=np.int32)
-        self.proposal = self.x.copy()
-        self.out = np.zeros(N, dtype=np.uint8)
-        self.archive = np.zeros((capacity, d))
-        self.archive_logp = np.zeros(capacity)
-        self.archive_carry = np.zeros((capacity, n_carry))
-        self.rows = np.full((N, d if ld is None else ld), fill)
-        self.rows[:, self.columns] = self.x
-        self.M, self.g = 0, 1
-        self.fallbacks = self.jumps = 0         # how often the fallback dimension was taken, gamma = 1 was drawn
-
-
-def log_density(score, kind, n_obs, n_eff, sigma):
-    score = np.asarray(score, dtype=np.float64)
-    with np.errstate(divide='ignore', invalid='ignore'):
-        if kind == RMSE:
-            return -((n_eff * 0.5) * np.log(np.float64(n_obs) * (score * score)))
-        if kind == RMSE_SIGMA:
-            return -(n_eff * (score * score)) / ((2.0 * sigma) * sigma)
-    return score.copy()
-
-
-class Decisions(object):
-    """What the accept phase of the statement decided: take [n] bool, log_u, delta (l* - l) and margin = |log u - delta|
-    per chain (NaN where nothing was compared: an `out` proposal, a NaN l*, the initial population); `smallest` is the
-    smallest margin among the finite comparisons, relative to max(1, |delta|, |log u|) (inf where there was none)."""
-
-    def __init__(self, take, log_u, delta, compared):
-        self.take, self.log_u, self.delta = take, log_u, delta
-        with np.errstate(invalid='ignore'):
-            self.margin = np.where(compared, np.abs(log_u - delta), np.nan)
-            finite = compared & np.isfinite(log_u) & np.isfinite(delta)
-            rel = self.margin / np.maximum(1.0, np.maximum(np.abs(delta), np.abs(log_u)))
-        self.finite = finite
-        self.smallest = float(rel[finite].min()) if finite.any() else np.inf
-        self.absolute = float(self.margin[finite].min()) if finite.any() else np.inf
-
-
-def demcz_statement(s, scores=None, carry_new=None, propose=True, append=False, chains=None):
-    """One call of smart_demcz_step_hip, as include/smart_amd.h words it, on a Chains object -> Decisions of the accept
-    phase (None without one).  chains=(first, count): that part of the chains only; s.M and s.g are then left alone."""
-    N, d = s.x.shape
-    first, count = (0, N) if chains is None else chains
-    sl = slice(first, first + count)
-    c = np.arange(first, first + count, dtype=np.uint64)
-    decisions = None
-    M = s.M
-    if scores is not None:
-        lstar = log_density(np.asarray(scores, dtype=np.float64)[sl], s.score_kind, s.n_obs, s.n_eff, s.sigma)
-        if s.g - 1 == 0:
-            take = np.ones(count, dtype=bool)
-            decisions = Decisions(take, np.full(count, np.nan), np.full(count, np.nan), np.zeros(count, dtype=bool))
-        else:
-            w = philox4x32((c, s.g - 1, 1, 0), s.key)
-            with np.errstate(divide='ignore', invalid='ignore'):
-                log_u = np.log(u53(w[0], w[1]))
-                delta = lstar - s.logp[sl]
-                compared = (s.out[sl] == 0) & ~np.isnan(lstar)
-                take = compared & (log_u < delta)
-            decisions = Decisions(take, log_u, delta, compared)
-            s.x[sl][take] = s.proposal[sl][take]
-            s.accepted[sl][take] += 1
-        s.logp[sl][take] = lstar[take]
-        if s.carry.shape[1]:
-            s.carry[sl][take] = np.asarray(carry_new)[sl][take]
-        if append:
-            assert M + first + count <= len(s.archive)
-            at = slice(M + first, M + first + count)
-            s.archive[at], s.archive_logp[at], s.archive_carry[at] = s.x[sl], s.logp[sl], s.carry[sl]
-            M = M + first + count
-    if propose:
-        assert M >= 2
-        r = philox4x32((c, s.g, 0, 0), s.key)
-        a = mulhi(r[0], M)
-        b = mulhi(r[1], M - 1)
-        b = b + (b >= a).astype(np.uint64)
-        jump = r[2] < np.uint64(s.J)
-        fallback = mulhi(r[3], d).astype(np.int64)
-        W = [philox4x32((c, s.g, 2 + j, 0), s.key) for j in range(d)]
-        moved = np.stack([W[j][0] < np.uint64(s.C) for j in range(d)], axis=1)
-        none = ~moved.any(axis=1)
-        moved[none, fallback[none]] = True
-        s.fallbacks += int(none.sum())
-        s.jumps += int(jump.sum())
-        gamma = np.where(jump, 1.0, s.gamma[moved.sum(axis=1) - 1])
-        eps = np.stack([s.scale[j] * (2.0 * u53(W[j][1], W[j][2]) - 1.0) for j in range(d)], axis=1)
-        x = s.x[sl]
-        lo, hi = s.lo[None, :], s.hi[None, :]
-        with np.errstate(invalid='ignore', over='ignore'):
-            t = s.archive[a.astype(np.int64)] - s.archive[b.astype(np.int64)]
-            t = gamma[:, None] * t
-            t = t + eps
-            y = x + t
-            y = np.where(y < lo, 2.0 * lo - y, y)
-            y = np.where(y > hi, 2.0 * hi - y, y)
-            inside = (y >= lo) & (y <= hi)
-        out = (moved & ~inside).any(axis=1)
-        s.proposal[sl] = np.where(moved, y, x)
-        s.out[sl] = out
-        s.rows[sl, s.columns] = np.where(out[:, None], x, s.proposal[sl])
-    if chains is None:
-        s.M = M
-        s.g += 1 if propose else 0
-    return decisions
-
-
-def run_statement(s, density, generations, thin, keep=None):
-    """The loop of montecarlo.DEMCz on a Chains object and a density of the test's -> the smallest relative margin.
-    keep: a list that takes a copy of the states after every generation."""
-    smallest = np.inf
-    demcz_statement(s, scores=density(s.rows[:, s.columns]), append=True, propose=True)
-    for g in range(1, generations + 1):
-        dec = demcz_statement(s, scores=density(s.rows[:, s.columns]), append=g % thin == 0, propose=g < generations)
-        smallest = min(smallest, dec.smallest)
-        if keep is not None:
-            keep.append(s.x.copy())
-    return smallest
 
 
 def test_the_statement_by_hand():
@@ -295,8 +139,6 @@ def test_the_diagnostics_file(tmp_path):
 
 
 # ---- the refusals of the C entry ------------------------------------------------------------------------------------------
-E_NULL, E_SIZE, E_NO_DEVICE, E_MODE = -1, -2, -6, -7
-FAKE = 0x1000                       # a non-NULL address that no refusal path reads
 TWO31, TWO32 = 2 ** 31, 2 ** 32
 K_ = 'smart_demcz_step_hip'
 _LO = (ctypes.c_double * 16)(*([0.0] * 16))
@@ -395,14 +237,6 @@ CASES = [
 ]
 
 
-def call(changes):
-    args = dict(VALID, **changes)
-    assert list(args) == list(VALID), 'a change names no parameter of the entry'
-    L = _lib.lib()
-    rc = getattr(L, K_)(*args.values())
-    return rc, L.smart_last_error().decode()
-
-
 def _case_id(i, changes):
     return '%02d-' % i + '-'.join('%s=%s' % (k, 'table' if k in ('lo', 'hi', 'columns') and v else v)
                                   for k, v in changes.items())
@@ -410,7 +244,7 @@ def _case_id(i, changes):
 
 @pytest.mark.parametrize('changes,code,text', CASES, ids=[_case_id(i, c[0]) for i, c in enumerate(CASES)])
 def test_refusals(changes, code, text):
-    assert call(changes) == (code, text)
+    assert refusal({K_: VALID}, K_, changes) == (code, text)
 
 
 def test_a_well_formed_call_gets_as_far_as_the_device():
@@ -425,12 +259,12 @@ def test_a_well_formed_call_gets_as_far_as_the_device():
                         dict(score_kind=RMSE_SIGMA, n_eff=10.0, sigma=0.5),
                         dict(jump_threshold=0, cr_threshold=0), dict(jump_threshold=TWO32),
                         dict(generation=TWO32 - 1, chain_offset=TWO32 - 8, append=0, capacity=TWO31 - 1)):
-            rc, text = call(changes)
+            rc, text = refusal({K_: VALID}, K_, changes)
             assert rc == E_NO_DEVICE and 'device' in text, changes
     else:
         # with a device the refusals leave the error text as they set it, and the entry is run for real by
         # tests/test_gpu_demcz.py
-        assert call(dict(x=None))[0] == E_NULL
+        assert refusal({K_: VALID}, K_, dict(x=None))[0] == E_NULL
 
 
 def test_the_new_name_is_bound():

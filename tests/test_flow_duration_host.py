@@ -1,12 +1,7 @@
 """Flow duration curves, host side: the numpy statement of smart_flow_duration_hip (the truth of
 tests/test_gpu_flow_duration.py as well), that statement against numpy's own 'inverted_cdf', the C entry's validation
 without a device, the capacity and workspace functions, the engine's refusals, the Monte-Carlo surface, the exceedance ->
-non-exceedance conversion and the `.fdc` file.
-
-`statement`: per window sort the rows that belong to it (and carry an observation), take rank max(1, ceil(q * m)); for the
-objective functions pair the sorted simulation with the sorted observations by rank, keep the ranks of the segment, apply f,
-oracle.objfn_oracle.objective_functions(...)[:7], and the two rules (fewer than two pairs -> NaN; a transformed value of
-the segment that is not finite -> NaN)."""
+non-exceedance conversion and the `.fdc` file."""
 import ctypes
 import inspect
 import os
@@ -14,49 +9,12 @@ import os
 import numpy as np
 import pytest
 
+import support
+from cases_flow_duration import CAPACITY
 from conftest import GOLDEN
 from oracle import objfn_oracle
-from test_windows_host import transformed, TRANSFORMS
-
-E_NULL, E_SIZE, E_NO_DEVICE, E_MODE = -1, -2, -6, -7
-CAPACITY = 16384
-
-
-def rank_of(q, m):
-    """1-based rank of the order statistic: max(1, ceil(q * m)), the product formed in double."""
-    return max(1, int(np.ceil(float(q) * float(m))))
-
-
-def statement(sim, probs, obs=None, win=None, n_windows=1, transform='none', eps=0.0, segment=(0.0, 1.0), objfn=False):
-    """sim [R, n], probs [K], obs [R] or None (NaN = missing), win [R] or None -> (quant [W, K, n], objfn [W, n, 7] or
-    None)."""
-    R, n = sim.shape
-    quant = np.full((n_windows, len(probs), n), np.nan)
-    scores = np.full((n_windows, n, 7), np.nan) if objfn else None
-    lo, hi = float(segment[0]), float(segment[1])
-    for w in range(n_windows):
-        rows = np.ones(R, dtype=bool) if win is None else (np.asarray(win) == w)
-        if obs is not None:
-            rows = rows & ~np.isnan(obs)
-        m = int(rows.sum())
-        if m == 0:
-            continue
-        x = np.sort(sim[rows], axis=0)                       # NaN sorts last, above +inf
-        for k, q in enumerate(probs):
-            quant[w, k] = x[rank_of(q, m) - 1]
-        if not objfn:
-            continue
-        i = np.arange(m, dtype=np.float64)
-        keep = (lo * float(m) <= i) & (i < hi * float(m))
-        e = transformed(transform, np.sort(obs[rows])[keep], eps)
-        if keep.sum() < 2 or not np.isfinite(e).all():
-            continue
-        for c in range(n):
-            s = transformed(transform, x[keep, c], eps)
-            if np.isfinite(s).all():
-                with np.errstate(all='ignore'):
-                    scores[w, c] = objfn_oracle.objective_functions(s, e)[:7]
-    return quant, scores
+from oracle.analyses.flow_duration import rank_of, statement
+from support import E_MODE, E_NO_DEVICE, E_NULL, E_SIZE, FAKE
 
 
 # ---- the statement ---------------------------------------------------------------------------------------------------
@@ -131,13 +89,8 @@ def test_statement_objective_functions_segments_and_rules():
 
 
 # ---- the C entry -----------------------------------------------------------------------------------------------------
-def _lib():
-    from smartpy_amd import _lib as binding
-    return binding, binding.lib()
-
-
 def test_symbols_capacity_and_workspace():
-    binding, L = _lib()
+    binding, L = support.binding()
     for name in ('smart_flow_duration_hip', 'smart_flow_duration_workspace_bytes', 'smart_flow_duration_sort_capacity'):
         assert name in binding.SYMBOLS
     assert L.smart_abi_version() == 7
@@ -158,12 +111,11 @@ def test_symbols_capacity_and_workspace():
 
 
 def test_validation_comes_before_the_device():
-    binding, L = _lib()
+    binding, L = support.binding()
     max_windows = L.smart_objfn_max_windows()
-    fake = 4096                         # a non-NULL address that is never followed: every call below is refused first
     half = (ctypes.c_double * 16)(*([0.5] * 16))
 
-    def call(n=100, r=50, sim=fake, ld=None, obs=fake, window=fake, w=3, probs=half, k=3, quant=fake, transform=0, eps=0.0,
+    def call(n=100, r=50, sim=FAKE, ld=None, obs=FAKE, window=FAKE, w=3, probs=half, k=3, quant=FAKE, transform=0, eps=0.0,
              lo=0.0, hi=1.0, objfn=None, work=None, work_bytes=0, method=0):
         rc = L.smart_flow_duration_hip(n, r, sim, n if ld is None else ld, obs, window, w, probs, k, quant, transform, eps,
                                        lo, hi, objfn, work, work_bytes, method, None)
@@ -175,9 +127,9 @@ def test_validation_comes_before_the_device():
     for name in ('sim', 'probs', 'quant'):
         rc, text = call(**{name: None})
         assert rc == E_NULL and 'smart_flow_duration_hip' in text and '(%s is NULL)' % name in text, name
-    rc, text = call(objfn=fake, obs=None, work=fake, work_bytes=1 << 20)
+    rc, text = call(objfn=FAKE, obs=None, work=FAKE, work_bytes=1 << 20)
     assert rc == E_NULL and 'objfn needs obs' in text
-    rc, text = call(objfn=fake, work=None)
+    rc, text = call(objfn=FAKE, work=None)
     assert rc == E_NULL and 'workspace is NULL' in text
     need = L.smart_flow_duration_workspace_bytes(50, 3, 1)
     for kw, word in ((dict(n=0), 'n_samples'), (dict(n=-2), 'n_samples'), (dict(r=0), 'n_reports'), (dict(w=0), 'n_windows'),
@@ -188,10 +140,10 @@ def test_validation_comes_before_the_device():
                      (dict(eps=-1e-300), 'eps'), (dict(eps=float('inf')), 'eps'), (dict(eps=float('nan')), 'eps'),
                      (dict(lo=-0.1), 'segment'), (dict(lo=0.5, hi=0.5), 'segment'), (dict(lo=0.6, hi=0.5), 'segment'),
                      (dict(hi=1.5), 'segment'), (dict(lo=float('nan')), 'segment'), (dict(hi=float('nan')), 'segment'),
-                     (dict(objfn=fake, work=fake, work_bytes=need - 1), 'workspace_bytes'),
+                     (dict(objfn=FAKE, work=FAKE, work_bytes=need - 1), 'workspace_bytes'),
                      (dict(r=CAPACITY + 1, method=1), 'sort form takes at most %d' % CAPACITY),
-                     (dict(r=CAPACITY + 1, objfn=fake, work=fake, work_bytes=1 << 30), 'take at most %d' % CAPACITY),
-                     (dict(r=CAPACITY + 1, objfn=fake, work=fake, work_bytes=1 << 30, method=1), 'at most %d' % CAPACITY)):
+                     (dict(r=CAPACITY + 1, objfn=FAKE, work=FAKE, work_bytes=1 << 30), 'take at most %d' % CAPACITY),
+                     (dict(r=CAPACITY + 1, objfn=FAKE, work=FAKE, work_bytes=1 << 30, method=1), 'at most %d' % CAPACITY)):
         rc, text = call(**kw)
         assert rc == E_SIZE and 'smart_flow_duration_hip' in text and word in text, (kw, text)
     for t in (-1, 4, 99):
@@ -200,7 +152,7 @@ def test_validation_comes_before_the_device():
     for how in (-1, 3, 99):
         rc, text = call(method=how)
         assert rc == E_MODE and 'method' in text, how
-    rc, text = call(objfn=fake, work=fake, work_bytes=need, method=2)
+    rc, text = call(objfn=FAKE, work=FAKE, work_bytes=need, method=2)
     assert rc == E_MODE and 'select form' in text
     # the order: NULL before SIZE before MODE
     assert call(sim=None, n=0, transform=9)[0] == E_NULL
@@ -209,7 +161,7 @@ def test_validation_comes_before_the_device():
     if L.smart_device_count() == 0:
         # a well-formed call gets as far as the device, and no further: there is no CPU fallback
         for kw in (dict(), dict(probs=probs_of(0.0, 1.0, 0.5)), dict(window=None, w=1, obs=None), dict(k=16),
-                   dict(objfn=fake, work=fake, work_bytes=need, transform=2, eps=0.5, lo=0.98), dict(r=CAPACITY + 1),
+                   dict(objfn=FAKE, work=FAKE, work_bytes=need, transform=2, eps=0.5, lo=0.98), dict(r=CAPACITY + 1),
                    dict(r=CAPACITY + 1, method=2), dict(r=CAPACITY, method=1, w=max_windows)):
             assert call(**kw)[0] == E_NO_DEVICE, kw
 

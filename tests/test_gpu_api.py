@@ -388,7 +388,7 @@ def test_the_c_abi_from_a_c_program(tmp_path, example):
     """examples/ensemble_from_c.c -- plain C, no Python, no torch in the process -- plans, launches (time-sliced: 70,000
     samples) and reads back through include/smart_amd.h; its numbers are those of the Python binding, bit for bit."""
     import subprocess
-    from test_capi_symbols import build_c_example
+    from support import build_c_example
     from smartpy_amd import engine
     from oracle import lhs_oracle
     exe = build_c_example(tmp_path)

@@ -1,4 +1,4 @@
-"""smart_objfn_bootstrap_hip on the GPU against the yardstick of tests/test_bootstrap_host.py (`truth`: direct resampling
+"""smart_objfn_bootstrap_hip on the GPU against the yardstick of oracle/analyses/bootstrap.py (`truth`: direct resampling
 in np.longdouble).
 
 Shapes are the smallest at which the kernels can go wrong.  R: 1, 2 (fewer than two rows, and exactly two), 9, 501, 1025
@@ -10,12 +10,12 @@ is a full chunk and a partial one -- the host test of the workspace entry shows 
 'none' runs at every shape, the other three transforms at one shape each (eps = 0.01).  ld = N + pad with NaN in the
 padding; every output lies 64 doubles inside a buffer of sentinels.
 
-Counts (test_bootstrap_host.make_counts): random draws; row 0 all ones (bit-equal to `point` in `replicates`), row 1 all
+Counts (oracle.analyses.bootstrap.make_counts): random draws; row 0 all ones (bit-equal to `point` in `replicates`), row 1 all
 zeros (NaN for every sample), row 2 a single window W times, row 3 with 65,535 somewhere -- as many of them as B has room
 for.  With R = 1 every replicate has fewer than two rows or repeats one row, whose scores are 0 / 0: the case keeps to
 B = 2 (ones, zeros), all NaN.
 
-Data: the generator of tests/test_signatures_truth_host.py; windows arange(R) * W // R with 10 % of the rows in no window.
+Data: the generator of tests/cases_signatures.py; windows arange(R) * W // R with 10 % of the rows in no window.
 
 Gates.  The pattern of NaN (and of infinities) is equal everywhere; point, replicates, MEAN and STD are held to `truth` at
 relative 1e-9 with |want| floored at 1e-12, every compared |want| asserted to be 0 or above 1e-6 (a seed that fails this
@@ -29,11 +29,10 @@ import os
 import numpy as np
 import pytest
 
-from support import (EXTRA, Guarded, Margins, bits_equal, example_root, margins_dir, padded, same_values, settings_file,
-                     to_device, workspace)
-from test_windows_host import E_NULL, E_SIZE
-from test_signatures_truth_host import data
-from test_bootstrap_host import truth, inverted_cdf, windows_of, make_counts, worst, assert_comparable, NAMES, GATE
+from cases_signatures import data
+from oracle.analyses.bootstrap import truth, inverted_cdf, windows_of, make_counts, worst, assert_comparable, NAMES
+from support import (EXTRA, E_SIZE, GATE, Guarded, Margins, bits_equal, example_root, margins_dir, padded, same_values,
+                     settings_file, to_device, workspace)
 
 pytestmark = pytest.mark.gpu
 

@@ -1,4 +1,4 @@
-"""DE-MCz on the device: smart_demcz_step_hip against the numpy statement of tests/test_demcz_host.py BIT FOR BIT -- chain
+"""DE-MCz on the device: smart_demcz_step_hip against the numpy statement of oracle/analyses/demcz.py BIT FOR BIT -- chain
 states, log-densities, payload, acceptance counts, `out` flags, proposals, launch rows and the whole archive after 40
 generations, on both sides of every switch, inside buffers with guards; the score kinds that take a logarithm or a
 quotient on the device; the same bits from one seed however the call is cut (phases, parts of the chains); and
@@ -12,8 +12,8 @@ difference of a logarithm can move."""
 import numpy as np
 import pytest
 
+from oracle.analyses.demcz import Chains, demcz_statement, log_density, LOGP, RMSE, RMSE_SIGMA
 from support import EXTRA, Guarded, example_root, same_bits, settings_file
-from test_demcz_host import Chains, demcz_statement, log_density, LOGP, RMSE, RMSE_SIGMA
 
 pytestmark = pytest.mark.gpu
 

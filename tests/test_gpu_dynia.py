@@ -1,5 +1,5 @@
 """Dynamic identifiability analysis on the GPU (smartpy_amd/csrc/smart_dynia.hip) against the statement and the exact
-yardsticks of tests/test_dynia_host.py: the C entry with its own leading dimensions and its batches, the engine and
+yardsticks of oracle/analyses/dynia.py: the C entry with its own leading dimensions and its batches, the engine and
 MonteCarlo.dynamic_identifiability on top.  launch_dynia runs five kernel instances; each is reached here by (instance,
 chosen when, the cases that reach it)
 
@@ -25,9 +25,10 @@ from fractions import Fraction
 import numpy as np
 import pytest
 
+from oracle.analyses.dynia import dynia_statement, exact_sums, EQUAL, LINEAR
+from oracle.exact import U
 from support import (EXTRA, SENTINEL, Margins, example_root, filled, margins_dir, padded, same, same_bits, settings_file, to_device,
                      workspace)
-from test_dynia_host import dynia_statement, exact_sums, EQUAL, LINEAR, U
 
 pytestmark = pytest.mark.gpu
 

@@ -1,5 +1,5 @@
 """Ensemble verification scores on the GPU (smartpy_amd/csrc/smart_ensemble_scores.hip) against the exact yardstick and
-the numpy statement of tests/test_ensemble_scores_host.py: both forms, the C entry with its own leading dimension and its
+the numpy statement of oracle/analyses/ensemble_scores.py: both forms, the C entry with its own leading dimension and its
 batches, the engine and GLUE.ensemble_verification on top.  launch_ensemble_scores chooses among ten kernel instances;
 each is reached here by (instance -- with and without weights --, chosen when, the N of test_exact_cases that reach it)
 
@@ -23,10 +23,10 @@ import os
 import numpy as np
 import pytest
 
+from oracle.analyses.ensemble_scores import (yardstick, yardstick_rows, assert_all_exact, as_floats, statement, shares,
+                                             CRPS, SPREAD, PIT_LOW, PIT_HIGH, MEAN)
 from support import (EXTRA, NSE_MIN, SENTINEL, Margins, example_root, filled, margins_dir, padded, ptr, same, same_bits,
                      settings_file, to_device, workspace)
-from test_ensemble_scores_host import (yardstick, yardstick_rows, assert_all_exact, as_floats, statement, shares,
-                                       CRPS, SPREAD, PIT_LOW, PIT_HIGH, MEAN)
 
 pytestmark = pytest.mark.gpu
 
@@ -148,7 +148,7 @@ def test_all_members_equal(size):
 # ---- general weights and values -----------------------------------------------------------------------------------------
 @pytest.mark.parametrize('size', ['1500', 'cap', 'cap+1', '3*cap+5', '100000'])
 def test_general_weights_and_values(size):
-    from test_ensemble_scores_host import float_scores
+    from oracle.analyses.ensemble_scores import float_scores
     cap = capacity()
     N = eval(size, {'cap': cap})
     rng = np.random.default_rng(900 + N)

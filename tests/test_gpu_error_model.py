@@ -1,5 +1,5 @@
 """The residual error model on the device: smart_error_model_loglik_hip against the 50-digit yardstick of
-tests/test_error_model_host.py within the bounds of the issue (every N and R at which the kernel takes another path, a
+oracle/analyses/error_model.py within the bounds of the issue (every N and R at which the kernel takes another path, a
 leading dimension with guarded padding, the error parameters at a row stride), an exactly representable case bit for bit,
 invalid rows among valid ones, observations that are all missing; smart_error_model_draw_hip against the numpy statement
 with a bound carried through the recurrence, and the same bits from a call in two halves; then through the API on the
@@ -11,8 +11,9 @@ profiles/error_model_margins.txt (SMART_MARGINS_DIR)."""
 import numpy as np
 import pytest
 
+from oracle.analyses.error_model import Draws, Truth, loglik_statement, shares
+from oracle.exact import U
 from support import EXTRA, Guarded, Margins, eng, example_root, margins_dir, padded, same_bits, settings_file, to_device  # noqa: F401
-from test_error_model_host import Draws, Truth, U, loglik_statement, shares
 
 pytestmark = pytest.mark.gpu
 
@@ -171,7 +172,7 @@ def draw(N, R, K, sim, ld, err, err_ld, seed, offset, truncate, out_ptr, out_ld)
 
 
 def draw_bound(d):
-    """The bound of the issue, carried through the recurrence of the statement `d` (tests/test_error_model_host.Draws):
+    """The bound of the issue, carried through the recurrence of the statement `d` (oracle.analyses.error_model.Draws):
     |d eps_t| <= 16 u r_t; d a_t <= |phi| d a_{t-1} + |d eps_t| + 4 u (|phi a_{t-1}| + |eps_t|) -- step 0, a quotient by
     a square root, takes |d eps_0| / sqrt(q) + 4 u |a_0| --; d y <= sigma_t d a_t + 4 u (|x| + sigma_t |a_t|)"""
     R, C = d.a.shape

@@ -1,4 +1,4 @@
-"""smart_flow_duration_hip on the GPU against the numpy statement of tests/test_flow_duration_host.py.
+"""smart_flow_duration_hip on the GPU against the numpy statement of oracle/analyses/flow_duration.py.
 
 Shapes straddle every switch: the sort form has five instances chosen from R (1,024 x 16 columns, 2,048 x 8, 4,096 x 4,
 8,192 x 2, 16,384 x 1), so R in {1, 2, 501, 1024 | 1025 | 4096 | 4097 | 16384} runs each at its first and its full size
@@ -15,16 +15,13 @@ import os
 import numpy as np
 import pytest
 
-from support import (EXTRA, Guarded, bits_equal, columns, data, example_root, padded, ptr, rel_to_want, same_values,
-                     settings_file, to_device, window_arrays, workspace)
-from test_windows_host import TRANSFORMS
-from test_flow_duration_host import statement, rank_of, CAPACITY, E_SIZE
+from cases_flow_duration import CAPACITY, EPS, launch
+from oracle.analyses.flow_duration import rank_of, statement
+from support import (EXTRA, E_SIZE, GATE, bits_equal, columns, data, example_root, rel_to_want, same_values, settings_file,
+                     window_arrays)
 
 pytestmark = pytest.mark.gpu
 
-EPS = {'none': 0.0, 'sqrt': 0.0, 'log': 0.05, 'inverse': 0.05}
-METHODS = {'auto': 0, 'sort': 1, 'select': 2}
-GATE = 1e-9
 # R -> the N it is run with (COLS of the instance: 16, 16, 16, 16, 8, 4, 2, 1; select beyond)
 SHAPES = {1: (1, 17, 65), 2: (1, 15, 65), 501: (1, 15, 17, 1000), 1024: (5, 63), 1025: (3, 15, 17, 65), 4096: (3, 4, 5, 63),
           4097: (1, 3, 5, 65), 16384: (1, 3, 17), 16385: (5, 65)}
@@ -40,41 +37,6 @@ def probabilities(obs, win, W):
             probs += [1.0 / m, (m - 1.0) / m, (m // 2) / float(m)]
             break
     return probs
-
-
-def launch(sim, probs, obs=None, win=None, W=1, transform='none', eps=0.0, segment=(0.0, 1.0), objfn=False, method='auto',
-           pad=0, expect=0):
-    """The C entry on a [R, N] host matrix laid out with ld = N + pad (the padding holds NaN) -> (quant [W, K, N], objfn
-    [W, N, 7] or None) as numpy.  Both outputs lie support.GUARD doubles inside a buffer of support.SENTINEL with a spare window behind
-    them; everything around what the call owns is checked to be as it was."""
-    import ctypes
-    import torch
-    from smartpy_amd import _lib
-    L = _lib.lib()
-    R, N = sim.shape
-    K = len(probs)
-    d_sim, ld = padded(sim, pad)
-    d_obs, d_win = to_device(obs), to_device(win, np.int32)
-    q = np.ascontiguousarray(probs, dtype=np.float64)
-    quant = Guarded(W * K * N, tail=K * N)
-    own = W * N * 7 if objfn else 0                                     # (not asked for: the whole buffer stays as it was)
-    scores = Guarded(own, tail=(W + 1) * N * 7 - own)
-    need = L.smart_flow_duration_workspace_bytes(R, W, 1 if objfn else 0)
-    work = workspace(need, least=8, fill=0) if objfn else None
-    rc = L.smart_flow_duration_hip(N, R, d_sim.data_ptr(), ld, ptr(d_obs), ptr(d_win), W,
-                                   q.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), K, quant.ptr(),
-                                   TRANSFORMS[transform], float(eps), float(segment[0]), float(segment[1]),
-                                   scores.ptr(null=not objfn), ptr(work), need if objfn else 0, METHODS[method],
-                                   torch.cuda.current_stream().cuda_stream)
-    torch.cuda.synchronize()
-    if expect:
-        assert rc == expect, (rc, L.smart_last_error().decode())
-        assert quant.untouched() and scores.untouched()
-        return L.smart_last_error().decode()
-    _lib.check(rc)
-    (quant, ok_q), (scores, ok_s) = quant.read(), scores.read()
-    assert ok_q and ok_s
-    return quant.reshape(W, K, N), scores.reshape(W, N, 7) if objfn else None
 
 
 @pytest.mark.parametrize('R', sorted(SHAPES))

@@ -1,4 +1,4 @@
-"""The scores of smart_flow_duration_hip against the exact scores of tests/test_flow_duration_truth_host.py.
+"""The scores of smart_flow_duration_hip against the exact scores of oracle/analyses/flow_duration.py.
 
 Every case of that module's list -- one R per instance of the sort form (1,024 x 16, 2,048 x 8, 4,096 x 4, 8,192 x 2,
 16,384 x 1), an N that leaves the instance's last workgroup partial, the four transforms, the whole curve, its top 2 %,
@@ -18,11 +18,11 @@ import numpy as np
 import pytest
 
 import support
+from cases_flow_duration import (CASES, EMPTY, INSTANCES, SEGMENTS, TRANSFORMS, case_data, case_id, case_reference, launch,
+                                 plateau, window_array)
+from cases_objfn import EPS
+from oracle.analyses.flow_duration import curve_reference, statement
 from support import Margins, bits_equal, margins_dir, same_values
-from test_flow_duration_host import statement
-from test_flow_duration_truth_host import (CASES, EMPTY, EPS, INSTANCES, SEGMENTS, TRANSFORMS, case_data, case_id, case_reference,
-                                           curve_reference, plateau, window_array)
-from test_gpu_flow_duration import launch
 
 pytestmark = pytest.mark.gpu
 
@@ -45,7 +45,7 @@ def _print_the_margins():
     if not MARGINS:
         return
     paths = [path_of(R, t) for R in sorted(INSTANCES) for t in TRANSFORMS]
-    text = ('largest |result - truth| of this run as a fraction of bounds(S, E, 0) of tests/test_flow_duration_truth_host.py '
+    text = ('largest |result - truth| of this run as a fraction of bounds(S, E, 0) of oracle/analyses/flow_duration.py '
             '(truth in fractions.Fraction on the pairs of the segment; the bound is what any order of the float64 additions '
             'about the first in-segment rank may differ by): instance of the sort form (rows x columns) and transform, '
             'fraction, where it was seen\n' +

@@ -1,6 +1,6 @@
 """The objective functions where the first report is unobserved: smart_objfn_hip, smart_objfn_windows_hip,
 smart_objfn_bootstrap_hip and the fused moments of the time-loop kernels against the exact scores of
-tests/test_objfn_truth_host.py.
+oracle/analyses/objfn.py.
 
 Every result is held to `truth` (fractions.Fraction over the observed rows) within `bounds(..., the first observed row)`:
 what any order of the kernel's float64 additions may differ by when the one-pass moments are taken about the sample's
@@ -24,9 +24,9 @@ import pytest
 
 import support
 from support import Margins, margins_dir, padded, eng      # noqa: F401 (eng is a fixture)
-from test_objfn_truth_host import (BIG_CASE, EPS, MATRIX_CASES, SPECIAL_CASES, WINDOW_CASES, big_columns, bootstrap_case,
-                                   bootstrap_reference, bounds, first_observed, matrix_case, truth, window_case,
-                                   window_reference)
+from cases_objfn import (BIG_CASE, EPS, MATRIX_CASES, SPECIAL_CASES, WINDOW_CASES, big_columns, bootstrap_case, compared,
+                         inside_and_below_the_gate, matrix_case, window_case)
+from oracle.analyses.objfn import bootstrap_reference, bounds, emulate, first_observed, kappa, truth, window_reference
 
 pytestmark = pytest.mark.gpu
 
@@ -53,7 +53,7 @@ def _print_the_margins():
     if not MARGINS:
         return
     text = ('largest |result - truth| of this run as a fraction of bounds(..., first observed row) of '
-            'tests/test_objfn_truth_host.py (truth in fractions.Fraction; the bound is what any order of the float64 '
+            'oracle/analyses/objfn.py (truth in fractions.Fraction; the bound is what any order of the float64 '
             'additions may differ by): path, fraction, where it was seen\n' +
             '\n'.join('%-38s %-10.3g %s' % (p, MARGINS[p][0], MARGINS[p][1])
                       for p in PATHS + sorted(set(MARGINS) - set(PATHS)) if p in MARGINS) + '\n')
@@ -163,7 +163,7 @@ def test_bootstrap_point_and_jackknife_about_the_launchs_first_valid_row():
 #     RIPPLE of its size: every six hours, every step still has a value of its own, which is what picks the kernel.
 # 'late' therefore sees a constant taken from report 0 in every kernel: kappa > 1e6 and a hundredfold miss of the
 # emulation about report 0 are asserted on the stored discharge of every such launch, with conditions (b) and (d) of
-# tests/test_objfn_truth_host.py.
+# oracle/analyses/objfn.py.
 # 'from_1' CANNOT see it and is here for the r1 = 1 control path alone -- the constant set twice, one report apart, whole
 # and across slices, bit for bit with and without the stored matrix.  The series that follows report 0 at once still holds
 # the flood's recession or the rise to the equilibrium: kappa about report 0 is 11 to 152 there and the emulation about it
@@ -171,8 +171,6 @@ def test_bootstrap_point_and_jackknife_about_the_launchs_first_valid_row():
 # reports that follow it under any forcing tried, so nothing is asserted of kappa there; it is printed.
 import functools                    # noqa: E402
 import importlib.util               # noqa: E402
-
-from test_objfn_truth_host import compared, emulate, inside_and_below_the_gate, kappa     # noqa: E402
 
 _spec = importlib.util.spec_from_file_location(
     'make_forcing_signs', os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden', 'make_forcing_signs.py'))

@@ -1,4 +1,4 @@
-"""smart_objfn_windows_hip on the GPU against the numpy statement of tests/test_windows_host.py (apply f, mask by window
+"""smart_objfn_windows_hip on the GPU against the numpy statement of oracle/analyses/windows.py (apply f, mask by window
 and missing observation, oracle.objfn_oracle.objective_functions(...)[:7], the entry's two rules).
 
 The kernel has ONE geometry (grid = 64-sample blocks x windows, eight wavefronts per workgroup; chunks of 1,024 report
@@ -11,14 +11,12 @@ import os
 import numpy as np
 import pytest
 
-from support import (EXTRA, SENTINEL, bits_equal, columns, data, example_root, filled, padded, rel_to_want, settings_file,
-                     to_device, window_arrays)
-from test_windows_host import statement, TRANSFORMS
+from cases_objfn import EPS
+from oracle.analyses.windows import statement, TRANSFORMS
+from support import (EXTRA, GATE, SENTINEL, bits_equal, columns, data, example_root, filled, padded, rel_to_want,
+                     settings_file, to_device, window_arrays)
 
 pytestmark = pytest.mark.gpu
-
-EPS = {'none': 0.0, 'sqrt': 0.0, 'log': 0.05, 'inverse': 0.05}
-GATE = 1e-9
 
 
 def launch(sim, obs, win, W, transform, eps, pad=0, junk=np.nan, spare=1):

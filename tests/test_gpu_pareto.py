@@ -1,4 +1,4 @@
-"""smart_pareto_counts_hip on the GPU against the numpy statement of tests/test_pareto_host.py.  The results are
+"""smart_pareto_counts_hip on the GPU against the numpy statement of oracle/analyses/pareto.py.  The results are
 integers: every comparison is exact equality of int32 arrays, no tolerance anywhere.
 
 Launch conditions (launch below): the score matrix has C = M + 2 columns of which M are selected, in an order that is not
@@ -16,8 +16,8 @@ import os
 import numpy as np
 import pytest
 
+from oracle.analyses.pareto import pareto_statement, pareto_rank_statement, pareto_keys, dominance_counts
 from support import EXTRA, Guarded, example_root, padded, settings_file, to_device, ptr
-from test_pareto_host import pareto_statement, pareto_rank_statement, pareto_keys, dominance_counts
 
 pytestmark = pytest.mark.gpu
 

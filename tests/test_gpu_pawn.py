@@ -1,4 +1,4 @@
-"""PAWN sensitivity on the GPU (smartpy_amd/csrc/smart_pawn.hip) against the numpy statement of tests/test_pawn_host.py: the
+"""PAWN sensitivity on the GPU (smartpy_amd/csrc/smart_pawn.hip) against the numpy statement of oracle/analyses/pawn.py: the
 C entry with a leading dimension of its own, spare output rows and its batches, the engine and MonteCarlo.pawn_sensitivity
 on top.  EVERY comparison is an equality of bytes (NaN for NaN): the result is a ratio of integers and there is no
 tolerance anywhere in this file.  launch_pawn runs six kernel instances; each is reached here by (instance, chosen when,
@@ -28,8 +28,8 @@ import os
 import numpy as np
 import pytest
 
+from oracle.analyses.pawn import pawn_statement
 from support import EXTRA, SENTINEL, example_root, filled, padded, same_bits, settings_file, workspace
-from test_pawn_host import pawn_statement
 
 pytestmark = pytest.mark.gpu
 

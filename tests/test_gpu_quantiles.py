@@ -1,5 +1,5 @@
 """Weighted ensemble quantiles on the GPU (smartpy_amd/csrc/smart_quantiles.hip) against the numpy statement of the
-definition in tests/test_quantiles_host.py: both forms, the C entry with its own leading dimension, the engine and
+definition in oracle/analyses/quantiles.py: both forms, the C entry with its own leading dimension, the engine and
 GLUE.prediction_bounds on top.  launch_quantiles chooses among seven kernel instances; each is reached here by
 (instance, chosen when, and below it the tests with the N or K that reach it)
 
@@ -28,10 +28,10 @@ import os
 import numpy as np
 import pytest
 
+from oracle.analyses.quantiles import (statement, statement_rows, band_violations, DYADIC, power_of_two_weights, threshold_probs,
+                                       distinct_rows, weightless_successor, many_nan_rows, mixed_nans, is_power_of_two,
+                                       NAN_SHARE, SUBNORMAL, HUGE)
 from support import EXTRA, NSE_MIN, SENTINEL, example_root, filled, padded, ptr, same, settings_file, to_device
-from test_quantiles_host import (statement, statement_rows, band_violations, DYADIC, power_of_two_weights, threshold_probs,
-                                 distinct_rows, weightless_successor, many_nan_rows, mixed_nans, is_power_of_two,
-                                 NAN_SHARE, SUBNORMAL, HUGE)
 
 pytestmark = pytest.mark.gpu
 

@@ -1,4 +1,4 @@
-"""smart_signatures_hip on the GPU against the statement of tests/test_signatures_host.py.
+"""smart_signatures_hip on the GPU against the statement of oracle/analyses/signatures.py.
 
 Shapes are the smallest at which the kernel can go wrong.  R: 1, 2, 3 (no pair, one pair, the first limb); 7, 8, 9 (the load
 batch of kSigUnroll = 8 rows: one short, full, one over -- the first listed row is walked ahead of the batches, so 9 and
@@ -20,7 +20,7 @@ in every column; AC1 is held to 1e-9 absolute; BFI and RECESSION to the gate the
 rel < 1e-9 with |want| floored at 1e-12, every compared |want| asserted to be 0 or above 1e-6 (a seed that fails this is
 changed, not the gate).
 
-The stress family.  tests/test_signatures_truth_host.py has the twelve columns in exact arithmetic (`truth`), what the
+The stress family.  oracle/analyses/signatures.py has the twelve columns in exact arithmetic (`truth`), what the
 kernel's documented form may differ from them by (`bounds`, derived there) and columns on which a badly centred AC1 shows:
 a window that opens on a flood peak (in a pair, and before a gap), series that barely move, a 1e6-fold flood, stretches of
 exact zeros, columns that are constant but for one row.  R = 9, 501, 1025 at N = 65, the family in the last columns (they
@@ -34,16 +34,14 @@ import os
 import numpy as np
 import pytest
 
-from support import (EXTRA, Guarded, Margins, bits_equal, example_root, margins_dir, padded, ptr, same_values, settings_file,
-                     to_device, window_arrays)
-from test_signatures_truth_host import (data, thresholds, stress_case, stress_reference, margins, KINDS, CONSTANT_KINDS,
-                                        STRESS_R)
-from test_signatures_host import (statement, NAMES, PAIR_COLUMNS, MEAN, BFI, FLASHINESS, AC1, RLD, RECESSION, PEAK, PEAK_ROW,
-                                  HIGH_COUNT, HIGH_DURATION, LOW_COUNT, LOW_DURATION, E_SIZE)
+from cases_signatures import data, thresholds, stress_case, stress_reference, KINDS, CONSTANT_KINDS, STRESS_R
+from oracle.analyses.signatures import (statement, margins, NAMES, PAIR_COLUMNS, MEAN, BFI, FLASHINESS, AC1, RLD, RECESSION,
+                                        PEAK, PEAK_ROW, HIGH_COUNT, HIGH_DURATION, LOW_COUNT, LOW_DURATION)
+from support import (EXTRA, E_SIZE, GATE, Guarded, Margins, bits_equal, example_root, margins_dir, padded, ptr, same_values,
+                     settings_file, to_device, window_arrays)
 
 pytestmark = pytest.mark.gpu
 
-GATE = 1e-9
 EXACT = [PEAK, PEAK_ROW, HIGH_COUNT, LOW_COUNT, MEAN, FLASHINESS, RLD, HIGH_DURATION, LOW_DURATION]
 CLOSE = [BFI, RECESSION]
 # R -> the N it is run with
@@ -105,7 +103,7 @@ def _print_the_margins():
             'at 1e-12; AC1 absolute 1e-9): column, margin, the launch it was seen in\n' +
             '\n'.join('%-14s %-10.3g %s' % (name, MARGINS[name][0], MARGINS[name][1]) for name in NAMES if name in MARGINS) +
             '\n' + ', '.join(NAMES[c] for c in EXACT) + ': bit-equal\n'
-            '\nthe stress family (tests/test_signatures_truth_host.py) against exact truth: the largest |got - truth| / bound, '
+            '\nthe stress family (tests/cases_signatures.py) against exact truth: the largest |got - truth| / bound, '
             'the bound derived there (0 = equal to the correctly rounded truth; a bound of 0 admits nothing else): column, '
             'margin, the launch it was seen in\n' +
             '\n'.join('%-14s %-10.3g %s' % (name, STRESS_MARGINS[name][0], STRESS_MARGINS[name][1])

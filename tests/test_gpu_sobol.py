@@ -1,4 +1,4 @@
-"""smart_sobol_indices_hip on the GPU against the numpy statement of tests/test_sobol_host.py (sums in math.fsum).
+"""smart_sobol_indices_hip on the GPU against the numpy statement of oracle/analyses/sobol.py (sums in math.fsum).
 
 The tolerance of every comparison is not a chosen number: sobol_statement(..., bounds=True) computes from the data what
 ANY order of additions may differ by -- (m - 1) 2^-53 sum|c t| per sum of m terms, carried through the quotients, plus 4
@@ -14,12 +14,10 @@ import os
 import numpy as np
 import pytest
 
-from support import EXTRA, Guarded, bits_equal, example_root, padded, ptr, settings_file
-from test_sobol_host import sobol_statement, design_values
+from oracle.analyses.sobol import sobol_statement, design_values
+from support import EXTRA, GATE, Guarded, bits_equal, example_root, padded, ptr, settings_file
 
 pytestmark = pytest.mark.gpu
-
-GATE = 1e-9
 
 
 def launch(y, n, k, counts=None, pad=3):

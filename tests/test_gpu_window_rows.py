@@ -10,9 +10,9 @@ Every case is held to two things:
       the whole array through its sha256.  AC1 of smart_signatures was re-centred since (each pair list about a member of
       its own): the two signature arrays are held to the pins `<name>|but_ac1` -- the eleven other columns, every bit of
       every sample, made by the library of the commit before that change, which reproduced the full-array pins first --
-      and AC1 of the kept columns to the exact truth of tests/test_signatures_truth_host.py within the bounds derived
+      and AC1 of the kept columns to the exact truth of oracle/analyses/signatures.py within the bounds derived
       there;
-  (b) for smart_objfn_windows_hip, the numpy statement of tests/test_windows_host.py at the gate of
+  (b) for smart_objfn_windows_hip, the numpy statement of oracle/analyses/windows.py at the gate of
       tests/test_gpu_objfn_windows.py (rel < 1e-9, |want| floored at 1e-12) on the kept columns: whatever the parent did at
       a chunk boundary, the list has to be the right one.
 """
@@ -22,9 +22,9 @@ import os
 import numpy as np
 import pytest
 
-from support import rel_to_want, eng        # noqa: F401 (eng is a fixture)
-from test_windows_host import statement
-from test_signatures_truth_host import exact, bounds, margins
+from oracle.analyses.signatures import exact, bounds, margins
+from oracle.analyses.windows import statement
+from support import GATE, rel_to_want, eng      # noqa: F401 (eng is a fixture)
 
 pytestmark = pytest.mark.gpu
 
@@ -33,8 +33,6 @@ _spec = importlib.util.spec_from_file_location('make_window_rows_parent',
                                                os.path.join(HERE, 'golden', 'make_window_rows_parent.py'))
 cases = importlib.util.module_from_spec(_spec)
 _spec.loader.exec_module(cases)
-
-GATE = 1e-9
 
 
 @pytest.fixture(scope='module')

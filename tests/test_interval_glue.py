@@ -21,7 +21,7 @@ import pytest
 from support import bits_equal, rel, eng      # noqa: F401 (eng is a fixture)
 from oracle import smart_oracle as so
 from oracle import objfn_oracle
-from test_objfn_truth_host import bounds, first_observed
+from oracle.analyses.objfn import bounds, first_observed
 
 pytestmark = pytest.mark.gpu
 
@@ -101,7 +101,7 @@ def test_every_mode_against_the_oracle_and_the_parent_commits_bits(eng, parent, 
         # (b) the parent commit's bits -- but for KGE, KGEc and KGEa where report 0 carries no observation: the constant of
         # their moments is now the sample's value at the first OBSERVED report, where that library took report 0.  There
         # both values lie within their own bound of the same exact scores of the same discharge (its bits are the
-        # parent's), so they differ by no more than the two bounds together (tests/test_objfn_truth_host.py: bounds about
+        # parent's), so they differ by no more than the two bounds together (oracle/analyses/objfn.py: bounds about
         # row r1 and about row 0); NSE, KGEb, PBias, RMSE and the constraint flag, sums that hold no constant, keep the bits
         moved = with_obs and obs_kind != 'all_nan' and bool(np.isnan(obs[0]))
         for field, a in got.items():

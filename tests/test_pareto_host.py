@@ -1,13 +1,6 @@
-"""Pareto selection without a device: the numpy statement of the dominance counts and ranks (the truth of
-tests/test_gpu_pareto.py) on hand-worked cases written as literals, every refusal of the two new C entries as (return
-code, text) literals, and the refusals of the Python layer that come before any device call.
-
-The statement.  key = x for 'max', -x for 'min', -|x - value| for ('target', value), in float64 exactly as written.  A row
-takes part iff it is eligible and none of its SELECTED scores is a NaN.  Row j dominates row i iff both take part, every
-key of j is >= that of i and at least one is > (all >= and not all <=): brute force over all pairs, chunked over the
-candidates so that no array passes about 256 MB.  dominated_by = the number of dominating rows, -1 where the row does not
-take part.  Ranks by peeling: rank r = the rows with count 0 once the ranks below r are left out; 0 = not ranked within
-max_rank; -1 = not taking part."""
+"""Pareto selection without a device: the numpy statement of the dominance counts and ranks (oracle/analyses/pareto.py, the
+truth of tests/test_gpu_pareto.py) on hand-worked cases written as literals, every refusal of the two new C entries as
+(return code, text) literals, and the refusals of the Python layer that come before any device call."""
 import ctypes
 import os
 
@@ -15,78 +8,10 @@ import numpy as np
 import pytest
 
 from conftest import load_golden
-from support import example_root, settings_file
+from oracle.analyses.pareto import pareto_keys, pareto_rank_statement, pareto_statement
+from support import E_MODE, E_NULL, E_SIZE, FAKE, example_root, refusal, settings_file
 
-E_NULL, E_SIZE, E_MODE = -1, -2, -7
-FAKE = 0x1000                       # a non-NULL address that no refusal path reads
 NAN, INF = float('nan'), float('inf')
-CHUNK_BYTES = 256 * 2 ** 20
-
-
-# ---- the statement ---------------------------------------------------------------------------------------------------
-def pareto_keys(scores, directions, targets=None, columns=None):
-    """-> float64 [N, M]; NaN exactly where the selected score is a NaN"""
-    scores = np.asarray(scores, dtype=np.float64)
-    if scores.ndim == 1:
-        scores = scores[:, None]
-    M = len(directions)
-    columns = list(range(M)) if columns is None else list(columns)
-    keys = np.empty((scores.shape[0], M), dtype=np.float64)
-    for m, (word, col) in enumerate(zip(directions, columns)):
-        x = scores[:, col]
-        value = None
-        if isinstance(word, tuple):
-            word, value = word
-        elif word == 'target':
-            value = targets[m]
-        if word == 'max':
-            keys[:, m] = x
-        elif word == 'min':
-            keys[:, m] = -x
-        else:
-            assert word == 'target'
-            keys[:, m] = -np.abs(x - np.float64(value))
-    return keys
-
-
-def dominance_counts(keys):
-    """brute force over all pairs of the rows of keys [E, M] (no NaN) -> int64 [E]"""
-    E, M = keys.shape
-    out = np.zeros(E, dtype=np.int64)
-    step = max(1, CHUNK_BYTES // max(1, E * M))
-    for lo in range(0, E, step):
-        mine = keys[lo:lo + step, None, :]
-        with np.errstate(invalid='ignore'):
-            ge = (keys[None, :, :] >= mine).all(axis=2)
-            le = (keys[None, :, :] <= mine).all(axis=2)
-        out[lo:lo + step] = (ge & ~le).sum(axis=1)
-    return out
-
-
-def pareto_statement(scores, directions, targets=None, columns=None, eligible=None):
-    keys = pareto_keys(scores, directions, targets, columns)
-    part = ~np.isnan(keys).any(axis=1)
-    if eligible is not None:
-        part &= np.asarray(eligible) != 0
-    out = np.full(keys.shape[0], -1, dtype=np.int32)
-    out[part] = dominance_counts(keys[part])
-    return out
-
-
-def pareto_rank_statement(scores, directions, targets=None, columns=None, eligible=None, max_rank=1):
-    keys = pareto_keys(scores, directions, targets, columns)
-    part = ~np.isnan(keys).any(axis=1)
-    if eligible is not None:
-        part &= np.asarray(eligible) != 0
-    ranks = np.where(part, 0, -1).astype(np.int32)
-    left, rank = part.copy(), 0
-    while left.any() and (max_rank is None or rank < max_rank):
-        rank += 1
-        idx = np.nonzero(left)[0]
-        front = idx[dominance_counts(keys[idx]) == 0]
-        ranks[front] = rank
-        left[front] = False
-    return ranks
 
 
 # ---- hand-worked cases -----------------------------------------------------------------------------------------------
@@ -153,15 +78,11 @@ SIXTEEN = tuple(range(16))
 
 
 def call(changes):
-    from smartpy_amd import _lib
-    args = dict(VALID, **changes)
-    assert list(args) == list(VALID), 'a change names no parameter of %s' % P
-    for name, kind in (('columns', ctypes.c_int32), ('direction', ctypes.c_int32), ('target', ctypes.c_double)):
-        if args[name] is not None:
-            args[name] = (kind * len(args[name]))(*args[name])
-    L = _lib.lib()
-    rc = L.smart_pareto_counts_hip(*args.values())
-    return rc, L.smart_last_error().decode()
+    """support.refusal on the one entry, its two lists of integers as int32 arrays (a tuple left to it becomes doubles)"""
+    def arrays(args):
+        return {k: (ctypes.c_int32 * len(v))(*v) if k in ('columns', 'direction') and v is not None else v
+                for k, v in args.items()}
+    return refusal({P: arrays(VALID)}, P, arrays(changes))
 
 
 CASES = [

@@ -4,88 +4,14 @@ two-sample statistic where scipy is there); the host functions of smartpy_amd/pa
 literals; the `.pawn` writer.  Nothing here needs a device."""
 import ctypes
 import math
-from fractions import Fraction
 
 import numpy as np
 import pytest
 
-from support import same
+from oracle.analyses.pawn import pawn_brute, pawn_statement, random_case
+from oracle.exact import U
 from smartpy_amd import _lib, pawn
-
-U = 2.0 ** -53
-
-
-# ---- the statement ----------------------------------------------------------------------------------------------------
-def pawn_counts(cat, B):
-    cat = np.asarray(cat)
-    return np.stack([np.bincount(row[row < B].astype(np.int64), minlength=B)[:B] for row in cat]).astype(np.int32)
-
-
-def pawn_statement(y, cat, B):
-    """The definition as written, in numpy -> (ks [R, P, B] float64, counts [P, B] int32): a stable argsort of the row, the
-    ends of the runs of ties, the cumulative one-hot counts of every bin at those ends, int64 until the one division."""
-    y, cat = np.asarray(y, dtype=np.float64), np.asarray(cat)
-    R, N = y.shape
-    P = len(cat)
-    counts = pawn_counts(cat, B)
-    ks = np.full((R, P, B), np.nan)
-    bins = np.arange(B)
-    for r in range(R):
-        if not np.isfinite(y[r]).all():
-            continue
-        order = np.argsort(y[r], kind='stable')
-        s = y[r][order]
-        ev = np.ones(N, dtype=bool)
-        ev[:-1] = s[:-1] != s[1:]                                   # (-0.0 == +0.0: one run)
-        at = np.arange(1, N + 1, dtype=np.int64)[ev]                # i + 1 at the evaluation points
-        for p in range(P):
-            n_b = counts[p].astype(np.int64)
-            c = np.cumsum(cat[p][order][:, None] == bins[None, :], axis=0, dtype=np.int64)[ev]
-            num = np.abs(at[:, None] * n_b[None, :] - c * np.int64(N)).max(axis=0)
-            assert num.max() < 2 ** 48
-            with np.errstate(invalid='ignore', divide='ignore'):
-                ks[r, p] = np.where(n_b > 0, num.astype(np.float64) / (np.float64(N) * n_b.astype(np.float64)), np.nan)
-    return ks, counts
-
-
-def pawn_brute(y, cat, B):
-    """sup over x of |F(x) - F_b(x)| by counting, in exact arithmetic, x running over every sample value -> ks [R, P, B],
-    the float of the exact rational (one correctly rounded division)"""
-    y, cat = np.asarray(y, dtype=np.float64), np.asarray(cat)
-    R, N = y.shape
-    P = len(cat)
-    ks = np.full((R, P, B), np.nan)
-    for r in range(R):
-        if not all(math.isfinite(v) for v in y[r]):
-            continue
-        for p in range(P):
-            for b in range(B):
-                inside = y[r][cat[p] == b]
-                if not len(inside):
-                    continue
-                best = Fraction(0)
-                for x in y[r]:
-                    F = Fraction(int((y[r] <= x).sum()), N)
-                    Fb = Fraction(int((inside <= x).sum()), len(inside))
-                    best = max(best, abs(F - Fb))
-                ks[r, p, b] = float(best)
-    return ks
-
-
-def random_case(rng, i):
-    N = int(rng.integers(1, 65))
-    R, P, B = 3, 2, int(rng.integers(1, 7))
-    if i % 2 == 0:
-        y = rng.integers(0, 8, size=(R, N)).astype(np.float64)      # ties everywhere
-        if N > 2:
-            y[0, :2] = (-0.0, 0.0)
-    else:
-        y = np.exp(rng.normal(0.0, 2.0, size=(R, N)))
-    cat = rng.integers(0, B + 1, size=(P, N)).astype(np.uint8)      # B: a value beyond the bins
-    cat[cat == B] = 255
-    if B > 1:
-        cat[1][cat[1] == B - 1] = 0                                  # an empty bin
-    return y, cat, B
+from support import E_MODE, E_NO_DEVICE, E_NULL, E_SIZE, FAKE, refusal, same
 
 
 def test_the_statement_is_the_supremum():
@@ -227,8 +153,6 @@ def test_the_result_object_and_the_pawn_writer(tmp_path):
 
 
 # ---- the refusals of the C entries --------------------------------------------------------------------------------------
-E_NULL, E_SIZE, E_NO_DEVICE, E_MODE = -1, -2, -6, -7
-FAKE = 0x1000                       # a non-NULL address that no refusal path reads
 TWO24, TWO31 = 2 ** 24, 2 ** 31
 AUTO, LDS, GLOBAL = 0, 1, 2
 K_, WS = 'smart_pawn_ks_hip', 'smart_pawn_workspace_bytes'
@@ -285,18 +209,10 @@ CASES = [
 ]
 
 
-def call(entry, changes):
-    args = dict(VALID[entry], **changes)
-    assert list(args) == list(VALID[entry]), 'a change names no parameter of %s' % entry
-    L = _lib.lib()
-    rc = getattr(L, entry)(*args.values())
-    return rc, (L.smart_last_error().decode() if entry.endswith('_hip') else None)
-
-
 @pytest.mark.parametrize('entry,changes,code,text', CASES,
                          ids=['%s-%s' % (c[0][6:], '-'.join('%s=%s' % kv for kv in c[1].items())) for c in CASES])
 def test_refusals(entry, changes, code, text):
-    assert call(entry, changes) == (code, text)
+    assert refusal(VALID, entry, changes) == (code, text)
 
 
 def test_a_well_formed_call_gets_as_far_as_the_device():
@@ -309,12 +225,12 @@ def test_a_well_formed_call_gets_as_far_as_the_device():
                         dict(method=AUTO, n_samples=8193, ld=8200, workspace_bytes=16384 * 12),
                         dict(n_samples=TWO24, ld=TWO24, n_rows=TWO31 - 1, n_factors=16, n_bins=64,
                              workspace_bytes=TWO24 * 12)):
-            rc, text = call(K_, changes)
+            rc, text = refusal(VALID, K_, changes)
             assert rc == E_NO_DEVICE and 'device' in text, changes
     else:
         # with a device the refusals leave the error text as they set it, and the entry is run for real by
         # tests/test_gpu_pawn.py
-        assert call(K_, dict(y=None))[0] == E_NULL
+        assert refusal(VALID, K_, dict(y=None))[0] == E_NULL
 
 
 def test_workspace_and_capacities():

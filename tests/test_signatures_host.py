@@ -1,118 +1,21 @@
-"""Hydrological signatures, host side: the statement of smart_signatures_hip in plain Python loops over the rows (the
-truth of tests/test_gpu_signatures.py as well), that statement against a series worked by hand, the C entry's validation
+"""Hydrological signatures, host side: the statement of smart_signatures_hip (oracle/analyses/signatures.py, the truth of
+tests/test_gpu_signatures.py as well) against a series worked by hand, the C entry's validation
 without a device, the engine's refusals, the Monte-Carlo surface, the default thresholds and alpha, and the `.signatures`
-file.
-
-`statement` restates the definition of include/smart_amd.h.  For window w a row r is VALID iff win[r] == w and, where obs
-is given, obs[r] is not NaN (m valid rows); there is a PAIR at r iff r >= 1 and rows r-1 and r are both valid (p pairs);
-rows are walked in ascending r.  The twelve columns, x_r = sim[r][c]:
-   MEAN sum x / m;  BFI sum (x_r - f_r) / sum x_r with f_r = 0 at a valid row without a pair, else
-   min(max(alpha f_{r-1} + (1 + alpha) / 2 (x_r - x_{r-1}), 0), x_r), NaN if sum x is 0;  FLASHINESS sum over the pairs
-   |x_r - x_{r-1}| / sum over the pairs x_r, NaN if p is 0 or the denominator is 0;  AC1 the Pearson correlation of
-   (x_{r-1}, x_r) over the pairs (two-pass here: the mean-centred sums of the pair lists), NaN if p < 2 or either variance
-   is <= 0;  RLD limbs / rising pairs (rising: x_r > x_{r-1}; a limb starts at a rising pair at r when there is no rising
-   pair at r-1), NaN without a rising pair;  RECESSION the mean of log(x_r / x_{r-1}) over the pairs with 0 < x_r <
-   x_{r-1}, NaN if there is none;  PEAK the maximum of x;  PEAK_ROW the smallest r attaining it;  HIGH_COUNT the runs above
-   hi (a run starts at a valid row with x_r > hi that has no pair, or whose x_{r-1} <= hi);  HIGH_DURATION rows with x_r
-   > hi / runs, NaN with no run;  LOW_COUNT, LOW_DURATION the same with x_r < lo.
-Rules: m == 0 -> twelve NaN; a valid row with a value that is not finite (or a sum of x that overflows) -> twelve NaN for
-that (window, column); no thresholds, or a NaN threshold -> NaN in the two columns it feeds."""
-import ctypes
+file."""
 import inspect
 import os
 
 import numpy as np
 import pytest
 
+import support
 from conftest import ROOT
-
-E_NULL, E_SIZE, E_NO_DEVICE = -1, -2, -6
-NAMES = ['MEAN', 'BFI', 'FLASHINESS', 'AC1', 'RLD', 'RECESSION', 'PEAK', 'PEAK_ROW', 'HIGH_COUNT', 'HIGH_DURATION',
-         'LOW_COUNT', 'LOW_DURATION']
-(MEAN, BFI, FLASHINESS, AC1, RLD, RECESSION, PEAK, PEAK_ROW, HIGH_COUNT, HIGH_DURATION, LOW_COUNT,
- LOW_DURATION) = range(12)
-PAIR_COLUMNS = [FLASHINESS, AC1, RLD, RECESSION]         # NaN wherever there is no pair
-
-
-def statement(sim, obs=None, win=None, n_windows=1, alpha=0.925, pulse=None):
-    """sim [R, n], obs [R] or None (NaN = missing), win [R] or None, pulse [W, 2] (lo, hi) or None -> [W, 12, n].  One
-    Python loop over the rows; the n columns of a row are carried side by side as numpy vectors."""
-    sim = np.asarray(sim, dtype=np.float64)
-    R, n = sim.shape
-    out = np.full((n_windows, 12, n), np.nan)
-    nan = np.full(n, np.nan)
-    for w in range(n_windows):
-        valid = [(win is None or win[r] == w) and (obs is None or not np.isnan(obs[r])) for r in range(R)]
-        lo, hi = (np.nan, np.nan) if pulse is None else (float(pulse[w][0]), float(pulse[w][1]))
-        m = p = 0
-        sum_x, sum_base, f = np.zeros(n), np.zeros(n), np.zeros(n)
-        num, den = np.zeros(n), np.zeros(n)
-        first, second = [], []                                  # the pair lists of AC1
-        rises, limbs, was_rising = np.zeros(n), np.zeros(n), np.zeros(n, dtype=bool)
-        rec_sum, rec_n = np.zeros(n), np.zeros(n)
-        peak, peak_row = np.full(n, -np.inf), np.zeros(n)
-        hi_runs, hi_rows, lo_runs, lo_rows = np.zeros(n), np.zeros(n), np.zeros(n), np.zeros(n)
-        with np.errstate(all='ignore'):
-            for r in range(R):
-                if not valid[r]:
-                    continue
-                x = sim[r]
-                m += 1
-                sum_x = sum_x + x
-                if r >= 1 and valid[r - 1]:
-                    before = sim[r - 1]
-                    p += 1
-                    f = np.minimum(np.maximum(alpha * f + (1.0 + alpha) / 2.0 * (x - before), 0.0), x)
-                    num = num + np.abs(x - before)
-                    den = den + x
-                    first.append(before)
-                    second.append(x)
-                    rising = x > before
-                    rises = rises + rising
-                    limbs = limbs + (rising & ~was_rising)
-                    was_rising = rising
-                    falling = (0.0 < x) & (x < before)
-                    rec_sum = rec_sum + np.where(falling, np.log(np.where(falling, x / before, 1.0)), 0.0)
-                    rec_n = rec_n + falling
-                    hi_runs = hi_runs + ((x > hi) & (before <= hi))
-                    lo_runs = lo_runs + ((x < lo) & (before >= lo))
-                else:
-                    f = np.zeros(n)
-                    was_rising = np.zeros(n, dtype=bool)
-                    hi_runs = hi_runs + (x > hi)
-                    lo_runs = lo_runs + (x < lo)
-                sum_base = sum_base + (x - f)
-                top = x > peak
-                peak_row = np.where(top, float(r), peak_row)
-                peak = np.where(top, x, peak)
-                hi_rows = hi_rows + (x > hi)
-                lo_rows = lo_rows + (x < lo)
-            if m == 0:
-                continue
-            o = out[w]
-            o[MEAN] = sum_x / m
-            o[BFI] = np.where(sum_x == 0.0, np.nan, sum_base / sum_x)
-            o[FLASHINESS] = nan if p == 0 else np.where(den == 0.0, np.nan, num / den)
-            if p >= 2:
-                a, b = np.array(first), np.array(second)
-                a, b = a - a.mean(axis=0), b - b.mean(axis=0)
-                va, vb, cov = (a * a).sum(axis=0), (b * b).sum(axis=0), (a * b).sum(axis=0)
-                o[AC1] = np.where((va > 0.0) & (vb > 0.0), cov / np.sqrt(va * vb), np.nan)
-            o[RLD] = np.where(rises > 0, limbs / rises, np.nan)
-            o[RECESSION] = np.where(rec_n > 0, rec_sum / rec_n, np.nan)
-            o[PEAK], o[PEAK_ROW] = peak, peak_row
-            if not np.isnan(hi):
-                o[HIGH_COUNT], o[HIGH_DURATION] = hi_runs, np.where(hi_runs > 0, hi_rows / hi_runs, np.nan)
-            if not np.isnan(lo):
-                o[LOW_COUNT], o[LOW_DURATION] = lo_runs, np.where(lo_runs > 0, lo_rows / lo_runs, np.nan)
-            o[:, ~np.isfinite(sum_x)] = np.nan
-    return out
+from oracle.analyses.signatures import (statement, X8, NAMES, PAIR_COLUMNS, MEAN, BFI, FLASHINESS, AC1, RLD, RECESSION, PEAK, PEAK_ROW,
+                                       HIGH_COUNT, HIGH_DURATION, LOW_COUNT, LOW_DURATION)
+from support import E_NO_DEVICE, E_NULL, E_SIZE, FAKE
 
 
 # ---- the statement ---------------------------------------------------------------------------------------------------
-X8 = [1.0, 3.0, 4.0, 2.0, 9.0, 4.0, 2.0, 3.0]
-
-
 def test_statement_on_a_series_worked_by_hand():
     """Eight rows, the observation of row 4 missing: valid rows 0 1 2 3 5 6 7 (m = 7), pairs at 1 2 3 6 7 (p = 5).
     alpha = 0.5, so the filter's gain (1 + alpha) / 2 is 0.75; lo = 3.5, hi = 2."""
@@ -164,13 +67,8 @@ def test_statement_windows_and_rules():
 
 
 # ---- the C entry -----------------------------------------------------------------------------------------------------
-def _lib():
-    from smartpy_amd import _lib as binding
-    return binding, binding.lib()
-
-
 def test_symbols_and_columns():
-    binding, L = _lib()
+    binding, L = support.binding()
     assert 'smart_signatures_hip' in binding.SYMBOLS and 'smart_signature_cols' in binding.SYMBOLS
     assert L.smart_signature_cols() == 12 == binding.SIGNATURE_COLS and L.smart_abi_version() == 7
     assert binding.SIGNATURE_NAMES == NAMES
@@ -187,11 +85,10 @@ def test_symbols_and_columns():
 
 
 def test_validation_comes_before_the_device():
-    binding, L = _lib()
+    binding, L = support.binding()
     max_windows = L.smart_objfn_max_windows()
-    fake = 4096                         # a non-NULL address that is never followed: every call below is refused first
 
-    def call(n=100, r=50, sim=fake, ld=None, obs=fake, window=fake, w=3, alpha=0.925, pulse=fake, sig=fake):
+    def call(n=100, r=50, sim=FAKE, ld=None, obs=FAKE, window=FAKE, w=3, alpha=0.925, pulse=FAKE, sig=FAKE):
         rc = L.smart_signatures_hip(n, r, sim, n if ld is None else ld, obs, window, w, alpha, pulse, sig, None)
         return rc, L.smart_last_error().decode()
 

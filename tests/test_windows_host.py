@@ -11,34 +11,11 @@ from datetime import datetime, timedelta
 import numpy as np
 import pytest
 
+import support
 from conftest import GOLDEN
 from oracle import objfn_oracle
-
-E_NULL, E_SIZE, E_NO_DEVICE, E_MODE = -1, -2, -6, -7
-TRANSFORMS = {'none': 0, 'sqrt': 1, 'log': 2, 'inverse': 3}
-
-
-def transformed(name, x, eps):
-    x = np.asarray(x, dtype=np.float64)
-    with np.errstate(all='ignore'):
-        return {'none': lambda: x + 0.0, 'sqrt': lambda: np.sqrt(x), 'log': lambda: np.log(x + eps),
-                'inverse': lambda: 1.0 / (x + eps)}[name]()
-
-
-def statement(sim, obs, win, n_windows, transform='none', eps=0.0):
-    """sim [R, n], obs [R] (NaN = missing), win [R] -> [n_windows, n, 7]."""
-    out = np.full((n_windows, sim.shape[1], 7), np.nan)
-    for w in range(n_windows):
-        rows = (win == w) & ~np.isnan(obs)
-        e = transformed(transform, obs[rows], eps)
-        if rows.sum() < 2 or not np.isfinite(e).all():
-            continue
-        for n in range(sim.shape[1]):
-            s = transformed(transform, sim[rows, n], eps)
-            if np.isfinite(s).all():
-                with np.errstate(all='ignore'):
-                    out[w, n] = objfn_oracle.objective_functions(s, e)[:7]
-    return out
+from oracle.analyses.windows import TRANSFORMS, statement
+from support import E_MODE, E_NO_DEVICE, E_NULL, E_SIZE, FAKE
 
 
 def test_statement_is_the_oracle_on_one_window_and_applies_the_two_rules():
@@ -160,13 +137,8 @@ def test_window_argument_errors():
 
 
 # ---- the C entry ----------------------------------------------------------------------------------------------------
-def _lib():
-    from smartpy_amd import _lib as binding
-    return binding, binding.lib()
-
-
 def test_symbols_are_bound_and_the_header_states_the_rules():
-    binding, L = _lib()
+    binding, L = support.binding()
     assert 'smart_objfn_windows_hip' in binding.SYMBOLS and 'smart_objfn_max_windows' in binding.SYMBOLS
     assert L.smart_objfn_max_windows() >= 1024 and L.smart_abi_version() == 7
     assert binding.TRANSFORMS == TRANSFORMS
@@ -180,11 +152,10 @@ def test_symbols_are_bound_and_the_header_states_the_rules():
 
 
 def test_validation_comes_before_the_device():
-    binding, L = _lib()
+    binding, L = support.binding()
     cap = L.smart_objfn_max_windows()
-    fake = 4096                         # a non-NULL address that is never followed: every call below is refused first
 
-    def call(n=100, r=50, sim=fake, ld=None, obs=fake, window=fake, w=3, transform=0, eps=0.0, out=fake):
+    def call(n=100, r=50, sim=FAKE, ld=None, obs=FAKE, window=FAKE, w=3, transform=0, eps=0.0, out=FAKE):
         rc = L.smart_objfn_windows_hip(n, r, sim, n if ld is None else ld, obs, window, w, transform, eps, out, None)
         return rc, L.smart_last_error().decode()
 
