@@ -23,7 +23,7 @@ sys.path.insert(0, os.path.dirname(HERE))
 
 import smartpy_amd                                   # noqa: E402
 from smartpy_amd import distributed                  # noqa: E402
-from smartpy_amd.montecarlo import LHS, GLUE, Best, Sobol   # noqa: E402
+from smartpy_amd.montecarlo import LHS, GLUE, Best, Sobol, NSGA2   # noqa: E402
 
 EXTRA = {'aar': 1200, 'r-o_ratio': 0.45, 'r-o_split': (0.10, 0.15, 0.15, 0.30, 0.30)}
 
@@ -104,7 +104,18 @@ def main():
     sob.run()
     sens = sob.sensitivity(targets=['NSE', 'KGE'], resamples=128, write=True)
     in_time = sob.sensitivity_series(write=True)
+    # a calibration that MOVES its rows: NSGA-II on the fit against the volume bias, 256 rows, one launch per generation and
+    # one step call around it (rank parents and offspring, keep the best by front and crowding, make the next offspring);
+    # the final population lies in tournament order, nsga.front_index are its rows of rank 1, and GLUE / Pareto take it
+    # with sampling=nsga like the LHS run above
+    nsga = NSGA2('Catchment', root, 'csv', 'csv', objectives=['NSE', 'PBias'], population=256, generations=30, seed=0)
+    nsga.model.extra = EXTRA
+    nsga.run(write=True)
     if rank == 0:
+        front = nsga.obj_fns[nsga.front_index]
+        print('NSGA-II: %d rows on the front after %d generations: NSE %.3f .. %.3f against PBias %.2f .. %.2f %% -> %s'
+              % (len(nsga.front_index), nsga.generations, front[:, 0].min(), front[:, 0].max(), front[:, 5].min(),
+                 front[:, 5].max(), nsga.db_file))
         print('DYNIA: mean information content over the record: %s -> %s'
               % (', '.join('%s %.2f' % (p, v) for p, v in zip(dynia.names, np.nanmean(dynia.information, axis=0))), dynia.file))
         print('GLUE: %d behavioural sets -> %s' % (len(glue.behavioural_params), glue.db_file))

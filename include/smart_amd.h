@@ -826,6 +826,102 @@ int smart_demcz_step_hip(int64_t n_chains, int64_t chain_offset, int32_t n_dims,
                          void *stream);
 
 /*
+ * One generation of NSGA-II (Deb et al. 2002, IEEE Trans. Evol. Comput. 6) -- non-dominated sorting, crowding distance and
+ * truncation over parents and offspring -- with the variation of differential evolution on that selection (NSDE, GDE3:
+ * Kukkonen & Lampinen 2005), AROUND the ensemble launch that scores the offspring: N rows in lockstep, d varying parameters,
+ * M objectives.  Simulated binary crossover and polynomial mutation are not built: both need pow, which is not correctly
+ * rounded, and every output of this entry is defined to the bit.  One call runs the SURVIVE phase (scores given), the VARY
+ * phase (vary != 0) or both, in that order, on `stream`; nothing is allocated: the workspace is the caller's.  The only
+ * atomics are integer counters whose final value does not depend on the order; every output has the same bits on every
+ * launch.  The generation g and which of its two population buffers is current are the caller's to keep.
+ *
+ * SIZES.  4 <= N = n_rows <= SMART_NSGA2_MAX_ROWS, 1 <= d = n_dims <= SMART_NSGA2_MAX_DIMS, 2 <= M = n_objectives <=
+ * SMART_NSGA2_MAX_OBJECTIVES, a payload of n_carry <= SMART_NSGA2_MAX_CARRY doubles per row.  CANDIDATES e in [0, E): with
+ * parents != 0, E = 2 N, e < N is parent e (row e of pop_x, pop_keys, pop_carry, pop_part) and e >= N is offspring e - N; with
+ * parents == 0 (the first call: the N launched rows are the candidates) E = N and e is offspring e.  Offspring c has the
+ * parameters offspring[c][0 .. d), the flag out[c], the scores scores[c * ld_scores + score_columns[m]] (read in place: the
+ * [N][8] objective table of smart_run_ensemble_hip with ld_scores = 8 is the main case), eligible[c] (eligible may be NULL) and
+ * the payload carry_new[c][0 .. n_carry).
+ *
+ * KEYS, as for smart_pareto_counts_hip: key_m = x for SMART_PARETO_MAX, -x for SMART_PARETO_MIN, -|x - target[m]| for
+ * SMART_PARETO_TARGET, of x = the score in column score_columns[m]; larger keys are better.
+ * TAKING PART.  An offspring takes part iff out[c] == 0, eligible is NULL or eligible[c] != 0, and none of its M selected
+ * scores is a NaN.  The M keys of an offspring that does not take part are stored as the quiet NaN 0x7ff8000000000000,
+ * whatever its scores are.  A parent takes part iff it did when it entered the population (pop_part).
+ * DOMINANCE, exactly as for smart_pareto_counts_hip: j dominates i iff both take part, key_m(j) >= key_m(i) for every m and
+ * not key_m(j) <= key_m(i) for every m (IEEE compares).  Candidates with equal keys do not dominate each other.
+ * RANK.  Fronts are peeled: rank 1 are the candidates that take part and that nobody dominates, rank r + 1 those that only
+ * candidates of ranks <= r dominate.  Peeling stops after the first front with which at least N candidates are ranked, or
+ * when none that takes part is left.  A candidate that takes part but lies beyond the last peeled front has rank
+ * SMART_NSGA2_RANK_BEYOND = 2^31 - 2, one that does not take part SMART_NSGA2_RANK_OUT = 2^31 - 1.
+ * CROWDING DISTANCE, by value (it does not depend on the order a sort would leave ties in).  For candidate i of a peeled
+ * front F, with min_m and max_m the smallest and largest key_m over F, dist = 0.0, then for m = 0 .. M - 1 in this order:
+ *     key_m(i) == min_m or key_m(i) == max_m:   dist = +inf
+ *     otherwise:   U = the smallest key_m(j) >= key_m(i), L = the largest key_m(j) <= key_m(i), over the j in F, j != i;
+ *                  t = U - L;  w = max_m - min_m;  t = t / w;  dist = dist + t      (each operation rounded once)
+ * Every duplicate of an extreme has +inf, a duplicate in the interior has U = L there, and on keys without ties this is
+ * Deb's sorted-neighbour sum.  A candidate outside the peeled fronts has the distance 0.0.
+ * SURVIVAL.  The total order is (rank ascending, distance descending, e ascending); pos(e) = the number of candidates that
+ * precede e.  e survives iff pos(e) < N and becomes row p = pos(e) of the NEXT population: next_x[p][.] = its d parameters,
+ * next_keys[p][0 .. M) its keys, next_carry[p][.] its payload, next_part[p] whether it takes part, rank[p], crowding[p],
+ * origin[p] = e.  The population therefore lies in tournament order: a smaller row number wins the binary tournament.
+ * counts[0] = the number of fronts peeled, counts[1] = the number of candidates of rank 1 (int32, left on the device).
+ * next_* must not overlap pop_*: the caller keeps two population buffers and swaps them.
+ *
+ * VARIATION of generation g, from the population the SURVIVE phase of the same call wrote (next_x), or from pop_x in a call
+ * without one (parents != 0 is required then); one lane per offspring c.  Philox4x32-10 with the counter (c, g, block, 0) and
+ * the key (seed mod 2^32, seed div 2^32); u53 and mulhi as for smart_demcz_step_hip.
+ *   Block 0 = (r0, r1, r2, r3): a = mulhi(r0, N); b = mulhi(r1, N - 1), then b += (b >= a); the base row t = min(a, b) --
+ *     the binary tournament by rank and then crowding; p1 = mulhi(r2, N); p2 = mulhi(r3, N - 1), then p2 += (p2 >= p1).
+ *   Block 1 = (w0, ., ., .): the fallback dimension mulhi(w0, d).
+ *   Block 2 + j, for dimension j: j is crossed iff w0 < C, C = cr_threshold = floor(CR 2^32) in [0, 2^32];
+ *     eps_j = scale_j (2 u53(w1, w2) - 1), scale_j = b* (hi_j - lo_j).  If no dimension is crossed, the fallback one alone is.
+ * A crossed dimension, each operation rounded once, no contraction, x the population:
+ *     s = x[p1][j] - x[p2][j];  s = f s;  s = s + eps_j;  y = x[t][j] + s
+ * then   if y < lo_j: y = 2 lo_j - y;   if y > hi_j: y = 2 hi_j - y;   y still outside [lo_j, hi_j] (or NaN): the offspring
+ * is `out`.  A dimension that is not crossed keeps x[t][j].  Outputs: offspring[c][0 .. d), out[c] (uint8) and the launch
+ * matrix rows[c][columns[j]] = the offspring's j, or x[t][j] for every j where the offspring is out (the lockstep launch
+ * stays valid); the other columns of rows[N][ld] are the caller's and are not touched.  lo, hi, scale, score_columns,
+ * direction, target and columns are HOST arrays (they travel as kernel arguments).
+ *
+ * The SURVIVE phase peels with one small launch per front, issued in batches, and reads ONE 4-byte flag back per batch to
+ * learn that the stop condition was met (16 passes in the first batch, twice as many in every further one, at most 1024): a
+ * pass that finds it met returns at once.  That is the entry's only wait on the stream; the caller reads nothing.
+ *
+ * Errors (all found before the device is touched; the first offending argument wins): SMART_E_NULL offspring or out
+ * missing; SMART_E_SIZE n_rows outside 4 .. 8192, n_dims outside 1 .. 16, n_objectives outside 2 .. 4, n_carry outside
+ * 0 .. 16, generation outside 1 .. 2^32 - 1; SMART_E_NULL neither phase asked for; survive phase: SMART_E_NULL next_x,
+ * next_keys, next_part, rank, crowding, origin, counts, score_columns or direction missing, pop_x, pop_keys or pop_part
+ * (parents != 0), next_carry, carry_new or -- with parents -- pop_carry (n_carry > 0) missing, SMART_E_SIZE ld_scores < 1, a
+ * score column outside 0 .. ld_scores - 1 or named twice, SMART_E_MODE an unknown direction, SMART_E_NULL / SMART_E_SIZE a
+ * TARGET without a finite target, SMART_E_NULL no workspace, SMART_E_SIZE one of fewer than smart_nsga2_workspace_bytes
+ * bytes; vary phase: SMART_E_NULL lo, hi, scale, rows or columns missing, a call without the survive phase that has no
+ * parents or no pop_x, SMART_E_SIZE f not finite, cr_threshold outside 0 .. 2^32, ld < n_dims, a column outside 0 .. ld - 1
+ * or named twice, bounds that are not finite or lo > hi; then SMART_E_NO_DEVICE without a HIP device.
+ */
+#define SMART_NSGA2_MAX_ROWS 8192
+#define SMART_NSGA2_MAX_DIMS 16
+#define SMART_NSGA2_MAX_OBJECTIVES 4
+#define SMART_NSGA2_MAX_CARRY 16
+#define SMART_NSGA2_RANK_BEYOND 2147483646
+#define SMART_NSGA2_RANK_OUT 2147483647
+int smart_nsga2_step_hip(int64_t n_rows, int32_t n_dims, int32_t n_objectives, int32_t n_carry, uint64_t seed,
+                         int64_t generation, int32_t parents, const double *pop_x, const double *pop_keys,
+                         const double *pop_carry, const uint8_t *pop_part, double *next_x, double *next_keys,
+                         double *next_carry, uint8_t *next_part, int32_t *rank, double *crowding, int32_t *origin,
+                         int32_t *counts, double *offspring, uint8_t *out, const double *scores, int64_t ld_scores,
+                         const int32_t *score_columns, const int32_t *direction, const double *target,
+                         const uint8_t *eligible, const double *carry_new, void *workspace, int64_t workspace_bytes,
+                         int32_t vary, const double *lo, const double *hi, const double *scale, double f,
+                         int64_t cr_threshold, double *rows, int64_t ld, const int32_t *columns, void *stream);
+
+/* The workspace smart_nsga2_step_hip asks for, in bytes, for 2 N candidates: their padded keys, counts, ranks and
+ * distances, the counters of the peel, and the bit matrix of who dominates whom, (2 N)^2 / 8 bytes (32 MiB at N = 8192; at
+ * least 128 bytes per candidate: the crowding pass keeps its partial results there once the fronts are peeled).
+ * SMART_E_SIZE (negative) for sizes the entry refuses.  Needs no device. */
+int64_t smart_nsga2_workspace_bytes(int64_t n_rows, int32_t n_objectives);
+
+/*
  * The residual error model of a stored discharge matrix sim[R][ld] (sample-minor): a standard deviation linear in the
  * simulated flow, and standardised residuals that follow a first-order autoregression (Schoups & Vrugt 2010, Water
  * Resour. Res. 46; the AR(1) on the STANDARDISED residuals: Evin et al. 2014, Water Resour. Res. 50).  Sample i has the

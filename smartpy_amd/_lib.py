@@ -43,7 +43,9 @@ PAWN_MAX_FACTORS, PAWN_MAX_BINS = 16, 64
 PAWN_METHODS = {'auto': 0, 'lds': 1, 'global': 2}               # SMART_PAWN_*
 DEMCZ_MAX_DIMS, DEMCZ_MAX_CARRY = 16, 16
 DEMCZ_SCORES = {'logp': 0, 'rmse': 1, 'rmse_sigma': 2}          # SMART_DEMCZ_SCORE_*
-ERROR_MODEL_SEGMENT = 64                                        # SMART_ERROR_MODEL_SEGMENT
+NSGA2_MAX_ROWS, NSGA2_MAX_DIMS, NSGA2_MAX_OBJECTIVES, NSGA2_MAX_CARRY = 8192, 16, 4, 16
+NSGA2_RANK_BEYOND, NSGA2_RANK_OUT = 2 ** 31 - 2, 2 ** 31 - 1     # SMART_NSGA2_RANK_*
+ERROR_MODEL_SEGMENT = 64                                       # SMART_ERROR_MODEL_SEGMENT
 ERROR_MODEL_ROWS = ['LOGLIK', 'SSQ', 'LOGSIG']                  # SMART_ERROR_MODEL_*, in row order
 
 _dp = ctypes.c_void_p   # device or host address, passed as an integer
@@ -135,6 +137,12 @@ SYMBOLS = {
                                             ctypes.c_double, _dp, ctypes.c_int32, ctypes.c_int32, _dp, _dp, _dp,
                                             ctypes.c_int32, _dp, _dp, _dp, _dp, ctypes.c_int64, ctypes.c_int64, _dp,
                                             ctypes.c_int64, _dp, _dp]),
+    'smart_nsga2_step_hip': (ctypes.c_int, [ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_uint64,
+                                            ctypes.c_int64, ctypes.c_int32, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp,
+                                            _dp, _dp, _dp, _dp, _dp, _dp, ctypes.c_int64, _dp, _dp, _dp, _dp, _dp, _dp,
+                                            ctypes.c_int64, ctypes.c_int32, _dp, _dp, _dp, ctypes.c_double,
+                                            ctypes.c_int64, _dp, ctypes.c_int64, _dp, _dp]),
+    'smart_nsga2_workspace_bytes': (ctypes.c_int64, [ctypes.c_int64, ctypes.c_int32]),
     'smart_error_model_loglik_hip': (ctypes.c_int, [ctypes.c_int64, ctypes.c_int64, _dp, ctypes.c_int64, _dp, _dp,
                                                     ctypes.c_int64, _dp, _dp]),
     'smart_error_model_draw_hip': (ctypes.c_int, [ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, _dp, ctypes.c_int64, _dp,

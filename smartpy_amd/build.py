@@ -62,6 +62,10 @@ UNITS = {
     # the step of the DE-MCz sampler (proposal, crossover, reflection, Metropolis decision, archive): every operation of
     # the proposal rounded once -- the numpy statement of the tests is held to it bit for bit
     'smart_demcz.hip': ['-ffp-contract=off'],
+    # the step of the NSGA-II sampler (dominance bit matrix, peeled fronts, crowding distance, truncation, differential
+    # variation): every operation of the distance and of the offspring rounded once -- the numpy statement of the tests is
+    # held to it bit for bit; NaNs honoured -- a NaN key loses every compare, which is how a row that takes no part is kept out
+    'smart_nsga2.hip': ['-ffp-contract=off'],
     # the residual error model (the AR(1) log-likelihood of a stored matrix, error realisations on top of it): every
     # operation rounded once, as the numpy statement of the tests rounds it; NaNs honoured -- a NaN at a step without an
     # observation is selected away, one at an observed step makes the sample invalid

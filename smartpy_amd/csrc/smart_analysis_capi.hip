@@ -783,6 +783,125 @@ int smart_demcz_step_hip(int64_t n_chains, int64_t chain_offset, int32_t n_dims,
     return launched();
 }
 
+// (the step of the NSGA-II sampler, smart_nsga2.hip: the sizes the entry shares with its workspace query)
+static void nsga2_sizes(Check &c, int64_t n_rows, int32_t n_objectives)
+{
+    c.in_range("n_rows", n_rows, 4, SMART_NSGA2_MAX_ROWS);
+    c.in_range("n_objectives", n_objectives, 2, SMART_NSGA2_MAX_OBJECTIVES);
+}
+
+int smart_nsga2_step_hip(int64_t n_rows, int32_t n_dims, int32_t n_objectives, int32_t n_carry, uint64_t seed,
+                         int64_t generation, int32_t parents, const double *pop_x, const double *pop_keys,
+                         const double *pop_carry, const uint8_t *pop_part, double *next_x, double *next_keys,
+                         double *next_carry, uint8_t *next_part, int32_t *rank, double *crowding, int32_t *origin,
+                         int32_t *counts, double *offspring, uint8_t *out, const double *scores, int64_t ld_scores,
+                         const int32_t *score_columns, const int32_t *direction, const double *target,
+                         const uint8_t *eligible, const double *carry_new, void *workspace, int64_t workspace_bytes,
+                         int32_t vary, const double *lo, const double *hi, const double *scale, double f,
+                         int64_t cr_threshold, double *rows, int64_t ld, const int32_t *columns, void *stream)
+{
+    constexpr long long kTwo32 = 1ll << 32;
+    Check c("smart_nsga2_step_hip");
+    c.required({NAMED(offspring), NAMED(out)});
+    c.in_range("n_rows", n_rows, 4, SMART_NSGA2_MAX_ROWS);
+    c.in_range("n_dims", n_dims, 1, SMART_NSGA2_MAX_DIMS);
+    c.in_range("n_objectives", n_objectives, 2, SMART_NSGA2_MAX_OBJECTIVES);
+    c.in_range("n_carry", n_carry, 0, SMART_NSGA2_MAX_CARRY);
+    c.in_range("generation", generation, 1, kTwo32 - 1);
+    if (!scores && !vary)
+        c.refuse(SMART_E_NULL, "neither phase is asked for (scores is NULL and vary is 0)");
+    if (scores) { // ---- the survive phase
+        const Named needed[] = {NAMED(next_x), NAMED(next_keys), NAMED(next_part), NAMED(rank),         NAMED(crowding),
+                                NAMED(origin), NAMED(counts),    NAMED(score_columns), NAMED(direction)};
+        for (const Named &p : needed)
+            if (!p.ptr)
+                c.refuse(SMART_E_NULL,
+                         "the survive phase needs next_x, next_keys, next_part, rank, crowding, origin, counts, "
+                         "score_columns and direction (%s is NULL)",
+                         p.name);
+        if (parents) {
+            const Named old[] = {NAMED(pop_x), NAMED(pop_keys), NAMED(pop_part)};
+            for (const Named &p : old)
+                if (!p.ptr)
+                    c.refuse(SMART_E_NULL, "parents need pop_x, pop_keys and pop_part (%s is NULL)", p.name);
+        }
+        c.needs("n_carry", n_carry, {NAMED(next_carry), NAMED(carry_new)});
+        if (parents)
+            c.needs("parents with n_carry", n_carry, {NAMED(pop_carry)});
+        c.in_range("ld_scores", ld_scores, 1, kInt32Max);
+        // (the loops below read the arrays: they are walked only while no rule is broken, one objective after the other)
+        for (int32_t m = 0; c.ok() && m < n_objectives; ++m) {
+            if (score_columns[m] < 0 || score_columns[m] >= ld_scores)
+                c.refuse(SMART_E_SIZE, "score column %d of objective %d is outside 0 .. ld_scores - 1 = %lld",
+                         (int)score_columns[m], (int)m, (long long)ld_scores - 1);
+            for (int32_t k = 0; k < m; ++k)
+                if (score_columns[k] == score_columns[m])
+                    c.refuse(SMART_E_SIZE, "score column %d is named twice (objectives %d and %d)", (int)score_columns[m],
+                             (int)k, (int)m);
+        }
+        for (int32_t m = 0; c.ok() && m < n_objectives; ++m)
+            if (direction[m] != SMART_PARETO_MAX && direction[m] != SMART_PARETO_MIN && direction[m] != SMART_PARETO_TARGET)
+                c.refuse(SMART_E_MODE, "direction '%d' of objective %d unknown.", (int)direction[m], (int)m);
+        for (int32_t m = 0; c.ok() && m < n_objectives; ++m) {
+            if (direction[m] != SMART_PARETO_TARGET)
+                continue;
+            if (!target)
+                c.refuse(SMART_E_NULL, "objective %d is a TARGET (target is NULL)", (int)m);
+            else if (!std::isfinite(target[m]))
+                c.refuse(SMART_E_SIZE, "target %g of objective %d must be finite", target[m], (int)m);
+        }
+        if (c.ok())
+            c.workspace_fits(/*for_objfn=*/false, workspace, workspace_bytes, nsga2_workspace_bytes((long)n_rows));
+    }
+    if (vary) { // ---- the vary phase
+        const Named needed[] = {NAMED(lo), NAMED(hi), NAMED(scale), NAMED(rows), NAMED(columns)};
+        for (const Named &p : needed)
+            if (!p.ptr)
+                c.refuse(SMART_E_NULL, "the vary phase needs lo, hi, scale, rows and columns (%s is NULL)", p.name);
+        if (!scores && !parents)
+            c.refuse(SMART_E_NULL, "the vary phase needs a population: the survive phase, or parents (scores is NULL)");
+        if (!scores && !pop_x)
+            c.refuse(SMART_E_NULL, "the vary phase without the survive phase reads pop_x (pop_x is NULL)");
+        if (!std::isfinite(f))
+            c.refuse(SMART_E_SIZE, "f %g must be finite", f);
+        c.in_range("cr_threshold", cr_threshold, 0, kTwo32);
+        if (c.ok() && ld < n_dims)
+            c.refuse(SMART_E_SIZE, "ld %lld is less than n_dims %d", (long long)ld, (int)n_dims);
+        for (int j = 0; c.ok() && j < n_dims; ++j) {
+            if (columns[j] < 0 || columns[j] >= ld)
+                c.refuse(SMART_E_SIZE, "columns[%d] %d must be in 0 .. %lld", j, (int)columns[j], (long long)ld - 1);
+            for (int k = 0; c.ok() && k < j; ++k)
+                if (columns[k] == columns[j])
+                    c.refuse(SMART_E_SIZE, "columns[%d] and columns[%d] name the same column %d", k, j, (int)columns[j]);
+            if (c.ok() && !(std::isfinite(lo[j]) && std::isfinite(hi[j]) && lo[j] <= hi[j]))
+                c.refuse(SMART_E_SIZE, "lo[%d] %g and hi[%d] %g: need finite lo <= hi", j, lo[j], j, hi[j]);
+        }
+    }
+    if (int rc = c.ready())
+        return rc;
+    Nsga2Call call{};
+    call.n_rows = (long)n_rows, call.n_dims = n_dims, call.n_objectives = n_objectives, call.n_carry = n_carry;
+    call.seed = seed, call.generation = (long)generation, call.parents = parents != 0;
+    call.pop_x = pop_x, call.pop_keys = pop_keys, call.pop_carry = pop_carry, call.pop_part = pop_part;
+    call.next_x = next_x, call.next_keys = next_keys, call.next_carry = next_carry, call.next_part = next_part;
+    call.rank = rank, call.crowding = crowding, call.origin = origin, call.counts = counts;
+    call.offspring = offspring, call.out = out, call.scores = scores, call.ld_scores = (long)ld_scores;
+    call.score_columns = score_columns, call.direction = direction, call.target = target, call.eligible = eligible;
+    call.carry_new = carry_new, call.workspace = workspace, call.vary = vary != 0;
+    call.lo = lo, call.hi = hi, call.scale = scale, call.f = f, call.cr_threshold = (long)cr_threshold;
+    call.rows = rows, call.ld = (long)ld, call.columns = columns;
+    if (int rc = launch_nsga2(call, (hipStream_t)stream))
+        return rc;
+    return launched();
+}
+
+int64_t smart_nsga2_workspace_bytes(int64_t n_rows, int32_t n_objectives)
+{
+    Check c(nullptr);
+    nsga2_sizes(c, n_rows, n_objectives);
+    return c.ok() ? nsga2_workspace_bytes((long)n_rows) : c.rc;
+}
+
 // ---- the residual error model (smart_error_model.hip): the rules the two entries share, in the entries' order
 static void error_model_sizes(Check &c, std::initializer_list<Count> counts, int64_t n_samples, int64_t ld, int64_t err_ld)
 {

@@ -186,6 +186,40 @@ inline long demcz_archive_after(const DemczCall &c)
 }
 void launch_demcz(const DemczCall &c, hipStream_t s);
 
+// ---- smart_nsga2.hip: the arguments of smart_nsga2_step_hip as the entry has checked them (scores NULL: no survive phase)
+struct Nsga2Call {
+    long n_rows;
+    int n_dims, n_objectives, n_carry;
+    unsigned long long seed;
+    long generation;
+    int parents;
+    const double *pop_x, *pop_keys, *pop_carry;
+    const unsigned char *pop_part;
+    double *next_x, *next_keys, *next_carry;
+    unsigned char *next_part;
+    int *rank;
+    double *crowding;
+    int *origin, *counts;
+    double *offspring;
+    unsigned char *out;
+    const double *scores;
+    long ld_scores;
+    const int *score_columns, *direction; // host, n_objectives
+    const double *target;                 // host, n_objectives (read where the direction is TARGET)
+    const unsigned char *eligible;
+    const double *carry_new;
+    void *workspace;
+    int vary;
+    const double *lo, *hi, *scale; // host, n_dims each
+    double f;
+    long cr_threshold;
+    double *rows;
+    long ld;
+    const int *columns; // host, n_dims
+};
+long nsga2_workspace_bytes(long N);
+int launch_nsga2(const Nsga2Call &c, hipStream_t s); // SMART_OK, or the code of hip_fail (the flag of a peel batch is read)
+
 // ---- smart_error_model.hip
 void launch_error_model_loglik(long N, long R, const double *sim, long ld, const double *obs, const double *err, long err_ld,
                                double *out, hipStream_t s);

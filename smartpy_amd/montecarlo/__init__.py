@@ -1,6 +1,6 @@
 """Monte-Carlo workflows on the GPU engine (counterpart of smartpy/montecarlo): LHS, GLUE, Best, Total, the Sobol
-sensitivity analysis on a Saltelli design, the Pareto selection over several objective functions, and DE-MCz posterior
-sampling."""
+sensitivity analysis on a Saltelli design, the Pareto selection over several objective functions, DE-MCz posterior
+sampling, and multi-objective calibration by NSGA-II."""
 from .lhs import LHS
 from .glue import GLUE
 from .best import Best
@@ -8,5 +8,6 @@ from .total import Total
 from .sobol import Sobol
 from .pareto import Pareto
 from .demcz import DEMCz
+from .nsga2 import NSGA2
 
-__all__ = ['LHS', 'GLUE', 'Best', 'Total', 'Sobol', 'Pareto', 'DEMCz']
+__all__ = ['LHS', 'GLUE', 'Best', 'Total', 'Sobol', 'Pareto', 'DEMCz', 'NSGA2']
