@@ -4,13 +4,10 @@ import math
 
 import numpy as np
 
+from oracle.analyses.de_move import crossover, launch_rows, move, mulhi
 from oracle.philox import philox4x32, u53
 
 LOGP, RMSE, RMSE_SIGMA = 0, 1, 2
-
-
-def mulhi(w, n):
-    return (w * np.uint64(n)) >> np.uint64(32)
 
 
 # ---- the statement ----------------------------------------------------------------------------------------------------
@@ -107,29 +104,15 @@ def demcz_statement(s, scores=None, carry_new=None, propose=True, append=False, 
         b = mulhi(r[1], M - 1)
         b = b + (b >= a).astype(np.uint64)
         jump = r[2] < np.uint64(s.J)
-        fallback = mulhi(r[3], d).astype(np.int64)
-        W = [philox4x32((c, s.g, 2 + j, 0), s.key) for j in range(d)]
-        moved = np.stack([W[j][0] < np.uint64(s.C) for j in range(d)], axis=1)
-        none = ~moved.any(axis=1)
-        moved[none, fallback[none]] = True
-        s.fallbacks += int(none.sum())
+        W, moved, fallbacks = crossover(c, s.g, s.key, d, s.C, mulhi(r[3], d).astype(np.int64))
+        s.fallbacks += fallbacks
         s.jumps += int(jump.sum())
         gamma = np.where(jump, 1.0, s.gamma[moved.sum(axis=1) - 1])
-        eps = np.stack([s.scale[j] * (2.0 * u53(W[j][1], W[j][2]) - 1.0) for j in range(d)], axis=1)
         x = s.x[sl]
-        lo, hi = s.lo[None, :], s.hi[None, :]
-        with np.errstate(invalid='ignore', over='ignore'):
-            t = s.archive[a.astype(np.int64)] - s.archive[b.astype(np.int64)]
-            t = gamma[:, None] * t
-            t = t + eps
-            y = x + t
-            y = np.where(y < lo, 2.0 * lo - y, y)
-            y = np.where(y > hi, 2.0 * hi - y, y)
-            inside = (y >= lo) & (y <= hi)
-        out = (moved & ~inside).any(axis=1)
-        s.proposal[sl] = np.where(moved, y, x)
+        s.proposal[sl], out = move(W, moved, s.scale, s.lo, s.hi, x, s.archive[a.astype(np.int64)],
+                                   s.archive[b.astype(np.int64)], gamma[:, None])
         s.out[sl] = out
-        s.rows[sl, s.columns] = np.where(out[:, None], x, s.proposal[sl])
+        s.rows[sl, s.columns] = launch_rows(out, x, s.proposal[sl])
     if chains is None:
         s.M = M
         s.g += 1 if propose else 0

@@ -1,17 +1,14 @@
 """NSGA-II: the numpy statement of include/smart_amd.h (smart_nsga2_step_hip), which the kernels are held to BIT FOR BIT.
-TEST INFRASTRUCTURE ONLY: a plain module that tests/test_nsga2_host.py and tests/test_gpu_nsga2.py both import."""
+TEST INFRASTRUCTURE ONLY."""
 import math
 
 import numpy as np
 
-from oracle.philox import philox4x32, u53
+from oracle.analyses.de_move import crossover, launch_rows, move, mulhi
+from oracle.philox import philox4x32
 
 MAX, MIN, TARGET = 0, 1, 2
 RANK_BEYOND, RANK_OUT = 2 ** 31 - 2, 2 ** 31 - 1
-
-
-def mulhi(w, n):
-    return (w * np.uint64(n)) >> np.uint64(32)
 
 
 class Population(object):
@@ -161,68 +158,11 @@ def nsga2_statement(s, scores=None, carry_new=None, eligible=None, vary=True):
         p2 = mulhi(r[3], N - 1)
         p2 = p2 + (p2 >= p1).astype(np.uint64)
         fallback = mulhi(philox4x32((c, s.g, 1, 0), s.key)[0], d).astype(np.int64)
-        W = [philox4x32((c, s.g, 2 + j, 0), s.key) for j in range(d)]
-        crossed = np.stack([W[j][0] < np.uint64(s.C) for j in range(d)], axis=1)
-        none = ~crossed.any(axis=1)
-        crossed[none, fallback[none]] = True
-        s.fallbacks += int(none.sum())
-        eps = np.stack([s.scale[j] * (2.0 * u53(W[j][1], W[j][2]) - 1.0) for j in range(d)], axis=1)
+        W, crossed, fallbacks = crossover(c, s.g, s.key, d, s.C, fallback)
+        s.fallbacks += fallbacks
         base = s.x[t]
-        lo, hi = s.lo[None, :], s.hi[None, :]
-        with np.errstate(invalid='ignore', over='ignore'):
-            step = s.x[p1.astype(np.int64)] - s.x[p2.astype(np.int64)]
-            step = s.f * step
-            step = step + eps
-            y = base + step
-            y = np.where(y < lo, 2.0 * lo - y, y)
-            y = np.where(y > hi, 2.0 * hi - y, y)
-            inside = (y >= lo) & (y <= hi)
-        out = (crossed & ~inside).any(axis=1)
-        s.offspring = np.where(crossed, y, base)
+        s.offspring, out = move(W, crossed, s.scale, s.lo, s.hi, base, s.x[p1.astype(np.int64)], s.x[p2.astype(np.int64)],
+                                s.f)
         s.out = out.astype(np.uint8)
-        s.rows[:, s.columns] = np.where(out[:, None], base, s.offspring)
+        s.rows[:, s.columns] = launch_rows(out, base, s.offspring)
         s.g += 1
-
-
-# ---- the convergence problem of tests/test_nsga2_host.py and profiles/nsga2_statement.txt ---------------------------------
-POINT_A = np.array([0.2, 0.3, 0.7, 0.6, 0.25, 0.8])
-POINT_B = np.array([0.8, 0.6, 0.2, 0.4, 0.75, 0.3])
-CONVERGENCE = dict(N=128, d=6, generations=60, seeds=range(6))
-
-
-def two_point_scores(x):
-    """Two objectives to maximise: the negated squared distances to POINT_A and POINT_B.  The Pareto set is the segment
-    between the two points."""
-    return np.stack([-((x - POINT_A) ** 2).sum(axis=1), -((x - POINT_B) ** 2).sum(axis=1)], axis=1)
-
-
-def segment_figures(x):
-    """-> (the mean distance of the rows of x to the segment A B, the largest gap between neighbouring projections along
-    it, how far the outermost projections are from its two ends -- the larger of the two); projections in [0, 1]"""
-    ab = POINT_B - POINT_A
-    t = np.clip((x - POINT_A) @ ab / (ab @ ab), 0.0, 1.0)
-    foot = POINT_A + t[:, None] * ab
-    along = np.sort(t)
-    return (float(np.sqrt(((x - foot) ** 2).sum(axis=1)).mean()), float(np.diff(along).max()),
-            float(max(along[0], 1.0 - along[-1])))
-
-
-def convergence_run(seed):
-    """The statement on the two-point problem from a uniform population of the seed -> (figures before, figures after,
-    the best key per objective after every survive phase [generations + 1, 2])"""
-    N, d, G = CONVERGENCE['N'], CONVERGENCE['d'], CONVERGENCE['generations']
-    x0 = np.random.default_rng(seed).uniform(0.0, 1.0, size=(N, d))
-    s = Population(x0, [0.0] * d, [1.0] * d, [(0, MAX), (1, MAX)], seed=seed)
-    kept = []
-    run_statement(s, two_point_scores, G, keep=kept)
-    best = np.stack([np.nanmax(keys, axis=0) for keys, _ in kept])
-    return segment_figures(x0), segment_figures(s.x), best
-
-
-def run_statement(s, score_function, generations, keep=None):
-    """The loop of montecarlo.NSGA2 on a Population object and a score function of the test's (launch rows -> score
-    matrix).  keep: a list that takes (keys, x) of the population after every survive phase."""
-    for g in range(0, generations + 1):
-        nsga2_statement(s, scores=score_function(s.rows[:, s.columns]), vary=g < generations)
-        if keep is not None:
-            keep.append((s.keys.copy(), s.x.copy()))

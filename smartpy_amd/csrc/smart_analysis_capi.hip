@@ -113,6 +113,7 @@ struct Count {
 #define COUNT(n) Count{#n, (long long)(n)}
 
 constexpr long long kInt32Max = 0x7fffffffll;
+constexpr long long kTwo32 = 1ll << 32; // counter words and thresholds of the entries that draw
 
 class Check
 {
@@ -152,6 +153,12 @@ class Check
         const char *missing = count > 0 ? first_null(ptrs) : nullptr;
         if (missing)
             refuse(SMART_E_NULL, "%s %d needs %s (%s is NULL)", what, count, names(ptrs, " and ").s, missing);
+    }
+    // ... and those a phase of a step, or an option of it, cannot do without: "the propose phase needs", "parents need"
+    void wants(const char *who_needs, std::initializer_list<Named> ptrs)
+    {
+        if (const char *missing = first_null(ptrs))
+            refuse(SMART_E_NULL, "%s %s (%s is NULL)", who_needs, names(ptrs, " and ").s, missing);
     }
     void at_least_one(std::initializer_list<Count> counts)
     {
@@ -230,6 +237,49 @@ class Check
     {
         if (transform < SMART_TRANSFORM_NONE || transform > SMART_TRANSFORM_INVERSE)
             refuse(SMART_E_MODE, "transform '%d' unknown.", (int)transform);
+    }
+    // the objectives of a call: every column inside the matrix and named once, every direction known, a finite target
+    // where the direction is TARGET.  (The loops read the arrays: they are walked only while no rule is broken, one
+    // objective after the other.)  `column` and `ld_name` are the entry's words for the two.
+    void objectives_hold(int32_t n_objectives, const char *column, const int32_t *columns, const char *ld_name, long long ld,
+                         const int32_t *direction, const double *target)
+    {
+        for (int32_t m = 0; ok() && m < n_objectives; ++m) {
+            if (columns[m] < 0 || columns[m] >= ld)
+                refuse(SMART_E_SIZE, "%s %d of objective %d is outside 0 .. %s - 1 = %lld", column, (int)columns[m], (int)m,
+                       ld_name, ld - 1);
+            for (int32_t k = 0; k < m; ++k)
+                if (columns[k] == columns[m])
+                    refuse(SMART_E_SIZE, "%s %d is named twice (objectives %d and %d)", column, (int)columns[m], (int)k,
+                           (int)m);
+        }
+        for (int32_t m = 0; ok() && m < n_objectives; ++m)
+            if (direction[m] != SMART_PARETO_MAX && direction[m] != SMART_PARETO_MIN && direction[m] != SMART_PARETO_TARGET)
+                refuse(SMART_E_MODE, "direction '%d' of objective %d unknown.", (int)direction[m], (int)m);
+        for (int32_t m = 0; ok() && m < n_objectives; ++m) {
+            if (direction[m] != SMART_PARETO_TARGET)
+                continue;
+            if (!target)
+                refuse(SMART_E_NULL, "objective %d is a TARGET (target is NULL)", (int)m);
+            else if (!std::isfinite(target[m]))
+                refuse(SMART_E_SIZE, "target %g of objective %d must be finite", target[m], (int)m);
+        }
+    }
+    // the box of a generational sampler's call: the launch matrix wide enough, every varying column inside it and named
+    // once, finite lo <= hi per dimension
+    void box_holds(int32_t n_dims, long long ld, const int32_t *columns, const double *lo, const double *hi)
+    {
+        if (ok() && ld < n_dims)
+            refuse(SMART_E_SIZE, "ld %lld is less than n_dims %d", ld, (int)n_dims);
+        for (int j = 0; ok() && j < n_dims; ++j) {
+            if (columns[j] < 0 || columns[j] >= ld)
+                refuse(SMART_E_SIZE, "columns[%d] %d must be in 0 .. %lld", j, (int)columns[j], ld - 1);
+            for (int k = 0; ok() && k < j; ++k)
+                if (columns[k] == columns[j])
+                    refuse(SMART_E_SIZE, "columns[%d] and columns[%d] name the same column %d", k, j, (int)columns[j]);
+            if (ok() && !(std::isfinite(lo[j]) && std::isfinite(hi[j]) && lo[j] <= hi[j]))
+                refuse(SMART_E_SIZE, "lo[%d] %g and hi[%d] %g: need finite lo <= hi", j, lo[j], j, hi[j]);
+        }
     }
     // a workspace of `need` bytes: present where any are needed, and large enough
     void workspace_fits(bool for_objfn, const void *workspace, int64_t workspace_bytes, long need)
@@ -551,26 +601,7 @@ int smart_pareto_counts_hip(int64_t n_rows, const double *scores, int64_t ld, co
     Check c("smart_pareto_counts_hip");
     c.required({NAMED(scores), NAMED(columns), NAMED(direction), NAMED(dominated_by)});
     pareto_sizes(c, n_rows, n_objectives);
-    // (the loops below read the arrays: they are walked only while no rule is broken, one objective after the other)
-    for (int32_t m = 0; c.ok() && m < n_objectives; ++m) {
-        if (columns[m] < 0 || columns[m] >= ld)
-            c.refuse(SMART_E_SIZE, "column %d of objective %d is outside 0 .. ld - 1 = %lld", (int)columns[m], (int)m,
-                     (long long)ld - 1);
-        for (int32_t k = 0; k < m; ++k)
-            if (columns[k] == columns[m])
-                c.refuse(SMART_E_SIZE, "column %d is named twice (objectives %d and %d)", (int)columns[m], (int)k, (int)m);
-    }
-    for (int32_t m = 0; c.ok() && m < n_objectives; ++m)
-        if (direction[m] != SMART_PARETO_MAX && direction[m] != SMART_PARETO_MIN && direction[m] != SMART_PARETO_TARGET)
-            c.refuse(SMART_E_MODE, "direction '%d' of objective %d unknown.", (int)direction[m], (int)m);
-    for (int32_t m = 0; c.ok() && m < n_objectives; ++m) {
-        if (direction[m] != SMART_PARETO_TARGET)
-            continue;
-        if (!target)
-            c.refuse(SMART_E_NULL, "objective %d is a TARGET (target is NULL)", (int)m);
-        else if (!std::isfinite(target[m]))
-            c.refuse(SMART_E_SIZE, "target %g of objective %d must be finite", target[m], (int)m);
-    }
+    c.objectives_hold(n_objectives, "column", columns, "ld", (long long)ld, direction, target);
     if (c.ok())
         c.workspace_fits(/*for_objfn=*/false, workspace, workspace_bytes,
                          pareto_workspace_bytes((long)n_rows, (int)n_objectives));
@@ -704,7 +735,6 @@ int smart_demcz_step_hip(int64_t n_chains, int64_t chain_offset, int32_t n_dims,
                          int64_t jump_threshold, int64_t cr_threshold, double *rows, int64_t ld, const int32_t *columns,
                          void *stream)
 {
-    constexpr long long kTwo32 = 1ll << 32;
     Check c("smart_demcz_step_hip");
     c.required({NAMED(x), NAMED(logp), NAMED(proposal), NAMED(out), NAMED(archive)});
     c.at_least_one({COUNT(n_chains)});
@@ -754,10 +784,7 @@ int smart_demcz_step_hip(int64_t n_chains, int64_t chain_offset, int32_t n_dims,
         c.refuse(SMART_E_NULL, "append needs the accept phase (score is NULL)");
     }
     if (propose) { // ---- the propose phase
-        const Named needed[] = {NAMED(lo), NAMED(hi), NAMED(scale), NAMED(gamma), NAMED(rows), NAMED(columns)};
-        for (const Named &p : needed)
-            if (!p.ptr)
-                c.refuse(SMART_E_NULL, "the propose phase needs lo, hi, scale, gamma, rows and columns (%s is NULL)", p.name);
+        c.wants("the propose phase needs", {NAMED(lo), NAMED(hi), NAMED(scale), NAMED(gamma), NAMED(rows), NAMED(columns)});
         const long long after = c.ok() ? demcz_archive_after(call) : 0;
         if (c.ok() && after < 2)
             c.refuse(SMART_E_SIZE, "the propose phase draws two rows of the archive: its size is %lld, need at least 2", after);
@@ -765,17 +792,7 @@ int smart_demcz_step_hip(int64_t n_chains, int64_t chain_offset, int32_t n_dims,
             c.refuse(SMART_E_SIZE, "archive size %lld is more than the capacity %lld", after, (long long)capacity);
         c.in_range("jump_threshold", jump_threshold, 0, kTwo32);
         c.in_range("cr_threshold", cr_threshold, 0, kTwo32);
-        if (c.ok() && ld < n_dims)
-            c.refuse(SMART_E_SIZE, "ld %lld is less than n_dims %d", (long long)ld, (int)n_dims);
-        for (int j = 0; c.ok() && j < n_dims; ++j) {
-            if (columns[j] < 0 || columns[j] >= ld)
-                c.refuse(SMART_E_SIZE, "columns[%d] %d must be in 0 .. %lld", j, (int)columns[j], (long long)ld - 1);
-            for (int k = 0; c.ok() && k < j; ++k)
-                if (columns[k] == columns[j])
-                    c.refuse(SMART_E_SIZE, "columns[%d] and columns[%d] name the same column %d", k, j, (int)columns[j]);
-            if (c.ok() && !(std::isfinite(lo[j]) && std::isfinite(hi[j]) && lo[j] <= hi[j]))
-                c.refuse(SMART_E_SIZE, "lo[%d] %g and hi[%d] %g: need finite lo <= hi", j, lo[j], j, hi[j]);
-        }
+        c.box_holds(n_dims, (long long)ld, columns, lo, hi);
     }
     if (int rc = c.ready())
         return rc;
@@ -800,9 +817,10 @@ int smart_nsga2_step_hip(int64_t n_rows, int32_t n_dims, int32_t n_objectives, i
                          int32_t vary, const double *lo, const double *hi, const double *scale, double f,
                          int64_t cr_threshold, double *rows, int64_t ld, const int32_t *columns, void *stream)
 {
-    constexpr long long kTwo32 = 1ll << 32;
     Check c("smart_nsga2_step_hip");
     c.required({NAMED(offspring), NAMED(out)});
+    // (nsga2_sizes states the rules of n_rows and n_objectives for the workspace query; here n_dims is asked between the two,
+    // and the order of refusals is ABI, so the entry states the three in its own order)
     c.in_range("n_rows", n_rows, 4, SMART_NSGA2_MAX_ROWS);
     c.in_range("n_dims", n_dims, 1, SMART_NSGA2_MAX_DIMS);
     c.in_range("n_objectives", n_objectives, 2, SMART_NSGA2_MAX_OBJECTIVES);
@@ -811,53 +829,20 @@ int smart_nsga2_step_hip(int64_t n_rows, int32_t n_dims, int32_t n_objectives, i
     if (!scores && !vary)
         c.refuse(SMART_E_NULL, "neither phase is asked for (scores is NULL and vary is 0)");
     if (scores) { // ---- the survive phase
-        const Named needed[] = {NAMED(next_x), NAMED(next_keys), NAMED(next_part), NAMED(rank),         NAMED(crowding),
-                                NAMED(origin), NAMED(counts),    NAMED(score_columns), NAMED(direction)};
-        for (const Named &p : needed)
-            if (!p.ptr)
-                c.refuse(SMART_E_NULL,
-                         "the survive phase needs next_x, next_keys, next_part, rank, crowding, origin, counts, "
-                         "score_columns and direction (%s is NULL)",
-                         p.name);
-        if (parents) {
-            const Named old[] = {NAMED(pop_x), NAMED(pop_keys), NAMED(pop_part)};
-            for (const Named &p : old)
-                if (!p.ptr)
-                    c.refuse(SMART_E_NULL, "parents need pop_x, pop_keys and pop_part (%s is NULL)", p.name);
-        }
+        c.wants("the survive phase needs", {NAMED(next_x), NAMED(next_keys), NAMED(next_part), NAMED(rank), NAMED(crowding),
+                                            NAMED(origin), NAMED(counts), NAMED(score_columns), NAMED(direction)});
+        if (parents)
+            c.wants("parents need", {NAMED(pop_x), NAMED(pop_keys), NAMED(pop_part)});
         c.needs("n_carry", n_carry, {NAMED(next_carry), NAMED(carry_new)});
         if (parents)
             c.needs("parents with n_carry", n_carry, {NAMED(pop_carry)});
         c.in_range("ld_scores", ld_scores, 1, kInt32Max);
-        // (the loops below read the arrays: they are walked only while no rule is broken, one objective after the other)
-        for (int32_t m = 0; c.ok() && m < n_objectives; ++m) {
-            if (score_columns[m] < 0 || score_columns[m] >= ld_scores)
-                c.refuse(SMART_E_SIZE, "score column %d of objective %d is outside 0 .. ld_scores - 1 = %lld",
-                         (int)score_columns[m], (int)m, (long long)ld_scores - 1);
-            for (int32_t k = 0; k < m; ++k)
-                if (score_columns[k] == score_columns[m])
-                    c.refuse(SMART_E_SIZE, "score column %d is named twice (objectives %d and %d)", (int)score_columns[m],
-                             (int)k, (int)m);
-        }
-        for (int32_t m = 0; c.ok() && m < n_objectives; ++m)
-            if (direction[m] != SMART_PARETO_MAX && direction[m] != SMART_PARETO_MIN && direction[m] != SMART_PARETO_TARGET)
-                c.refuse(SMART_E_MODE, "direction '%d' of objective %d unknown.", (int)direction[m], (int)m);
-        for (int32_t m = 0; c.ok() && m < n_objectives; ++m) {
-            if (direction[m] != SMART_PARETO_TARGET)
-                continue;
-            if (!target)
-                c.refuse(SMART_E_NULL, "objective %d is a TARGET (target is NULL)", (int)m);
-            else if (!std::isfinite(target[m]))
-                c.refuse(SMART_E_SIZE, "target %g of objective %d must be finite", target[m], (int)m);
-        }
+        c.objectives_hold(n_objectives, "score column", score_columns, "ld_scores", (long long)ld_scores, direction, target);
         if (c.ok())
             c.workspace_fits(/*for_objfn=*/false, workspace, workspace_bytes, nsga2_workspace_bytes((long)n_rows));
     }
     if (vary) { // ---- the vary phase
-        const Named needed[] = {NAMED(lo), NAMED(hi), NAMED(scale), NAMED(rows), NAMED(columns)};
-        for (const Named &p : needed)
-            if (!p.ptr)
-                c.refuse(SMART_E_NULL, "the vary phase needs lo, hi, scale, rows and columns (%s is NULL)", p.name);
+        c.wants("the vary phase needs", {NAMED(lo), NAMED(hi), NAMED(scale), NAMED(rows), NAMED(columns)});
         if (!scores && !parents)
             c.refuse(SMART_E_NULL, "the vary phase needs a population: the survive phase, or parents (scores is NULL)");
         if (!scores && !pop_x)
@@ -865,17 +850,7 @@ int smart_nsga2_step_hip(int64_t n_rows, int32_t n_dims, int32_t n_objectives, i
         if (!std::isfinite(f))
             c.refuse(SMART_E_SIZE, "f %g must be finite", f);
         c.in_range("cr_threshold", cr_threshold, 0, kTwo32);
-        if (c.ok() && ld < n_dims)
-            c.refuse(SMART_E_SIZE, "ld %lld is less than n_dims %d", (long long)ld, (int)n_dims);
-        for (int j = 0; c.ok() && j < n_dims; ++j) {
-            if (columns[j] < 0 || columns[j] >= ld)
-                c.refuse(SMART_E_SIZE, "columns[%d] %d must be in 0 .. %lld", j, (int)columns[j], (long long)ld - 1);
-            for (int k = 0; c.ok() && k < j; ++k)
-                if (columns[k] == columns[j])
-                    c.refuse(SMART_E_SIZE, "columns[%d] and columns[%d] name the same column %d", k, j, (int)columns[j]);
-            if (c.ok() && !(std::isfinite(lo[j]) && std::isfinite(hi[j]) && lo[j] <= hi[j]))
-                c.refuse(SMART_E_SIZE, "lo[%d] %g and hi[%d] %g: need finite lo <= hi", j, lo[j], j, hi[j]);
-        }
+        c.box_holds(n_dims, (long long)ld, columns, lo, hi);
     }
     if (int rc = c.ready())
         return rc;
@@ -930,7 +905,6 @@ int smart_error_model_draw_hip(int64_t n_samples, int64_t n_reports, int64_t n_r
                                const double *err, int64_t err_ld, uint64_t seed, int64_t column_offset, int32_t truncate,
                                double *out, int64_t out_ld, void *stream)
 {
-    constexpr long long kTwo32 = 1ll << 32;
     Check c("smart_error_model_draw_hip");
     c.required({NAMED(sim), NAMED(err), NAMED(out)});
     error_model_sizes(c, {COUNT(n_samples), COUNT(n_reports), COUNT(n_replicates)}, n_samples, ld, err_ld);

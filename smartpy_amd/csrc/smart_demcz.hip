@@ -8,21 +8,20 @@
 //                        log-density, payload and count updated in place, and (append) every chain's state after the
 //                        decision written as archive row M + chain
 //   smart_demcz_propose  the proposals of generation g from two rows of the archive, into the proposal matrix, the `out`
-//                        flags and the varying columns of the launch matrix
+//                        flags and the varying columns of the launch matrix (the archive rows, the jump and gamma here,
+//                        the move itself in smart_de_move.h, shared with smart_nsga2_vary)
 // RANDOMNESS.  Philox4x32-10 (Salmon et al. 2011), counter (chain, generation, block, 0), key (seed lo, seed hi): the bits
 // of a chain depend on the seed, the chain's number and the generation, never on the launch -- a call over half of the
 // chains (chain_offset) draws what the call over all of them draws.
 // ARITHMETIC.  The unit is compiled with -ffp-contract=off: every operation of the proposal is rounded once, as the numpy
 // statement of the tests rounds it.  The one operation that is not correctly rounded by definition is log(u).
 #include "smart_capi_internal.h"
-#include "smart_philox.h"
+#include "smart_de_move.h"
 #include <cstdint>
 
 namespace smart {
 
 constexpr int kDemczThreads = 256;
-
-__device__ inline unsigned long long mulhi(unsigned w, unsigned long long n) { return ((unsigned long long)w * n) >> 32; }
 
 // the log-density of a score (include/smart_amd.h: SMART_DEMCZ_SCORE_*)
 __device__ inline double log_density(double score, int kind, double n_obs, double n_eff, double sigma)
@@ -42,8 +41,7 @@ struct DemczAccept {
     long N;             // chains of this call
     long offset;        // the number of its first chain
     int d, n_carry;
-    unsigned gen;       // the generation whose proposals are decided (0: the initial population takes its scores)
-    unsigned k0, k1;
+    DeKey key;          // gen: the generation whose proposals are decided (0: the initial population takes its scores)
     double *x, *logp, *carry;
     int *accepted;
     const double *proposal;
@@ -69,10 +67,10 @@ __global__ __launch_bounds__(kDemczThreads) void smart_demcz_accept(DemczAccept 
     const double lstar = log_density(a.score[i * a.score_stride], a.score_kind, a.n_obs, a.n_eff, a.sigma);
     double l = a.logp[i];
     bool take;
-    if (a.gen == 0) {
+    if (a.key.gen == 0) {
         take = true;        // the initial population: its state is what was launched
     } else {
-        const Philox4 r = philox4x32_10((unsigned)chain, a.gen, 1u, 0u, a.k0, a.k1);
+        const Philox4 r = philox4x32_10((unsigned)chain, a.key.gen, 1u, 0u, a.key.k0, a.key.k1);
         const double u = u53(r.w[0], r.w[1]);
         take = !a.out[i] && lstar == lstar && log(u) < lstar - l;      // (a NaN difference: false)
         if (take) {
@@ -104,13 +102,13 @@ __global__ __launch_bounds__(kDemczThreads) void smart_demcz_accept(DemczAccept 
 struct DemczPropose {
     long N, offset;
     int d;
-    unsigned gen, k0, k1;
+    DeKey key;
     const double *x;
     const double *archive;
     unsigned long long M;       // archive rows to draw from, >= 2
     unsigned long long J, C;    // thresholds of the jump and of the crossover, in [0, 2^32]
-    double lo[SMART_DEMCZ_MAX_DIMS], hi[SMART_DEMCZ_MAX_DIMS], scale[SMART_DEMCZ_MAX_DIMS], gamma[SMART_DEMCZ_MAX_DIMS];
-    int columns[SMART_DEMCZ_MAX_DIMS];
+    DeBox box;
+    double gamma[SMART_DEMCZ_MAX_DIMS];
     double *proposal;
     unsigned char *out;
     double *rows;
@@ -124,61 +122,28 @@ __global__ __launch_bounds__(kDemczThreads) void smart_demcz_propose(DemczPropos
         return;
     const unsigned chain = (unsigned)(p.offset + i);
     const int d = p.d;
-    const Philox4 r = philox4x32_10(chain, p.gen, 0u, 0u, p.k0, p.k1);
+    const Philox4 r = philox4x32_10(chain, p.key.gen, 0u, 0u, p.key.k0, p.key.k1);
     const unsigned long long za = mulhi(r.w[0], p.M);
     unsigned long long zb = mulhi(r.w[1], p.M - 1);
     zb += zb >= za;
     const bool jump = (unsigned long long)r.w[2] < p.J;
-    const int fallback = (int)mulhi(r.w[3], (unsigned long long)d);
-    // which dimensions move: the crossover draw of each, the fallback dimension where none was drawn
-    unsigned moved = 0;
-    for (int j = 0; j < d; ++j) {
-        const Philox4 w = philox4x32_10(chain, p.gen, 2u + j, 0u, p.k0, p.k1);
-        if ((unsigned long long)w.w[0] < p.C)
-            moved |= 1u << j;
-    }
-    if (moved == 0)
-        moved = 1u << fallback;
+    const unsigned moved = de_crossover(chain, p.key, d, p.C, (int)mulhi(r.w[3], (unsigned long long)d));
     const double gamma = jump ? 1.0 : p.gamma[__popc(moved) - 1];
     const double *x = p.x + i * d;
-    const double *a = p.archive + za * d, *b = p.archive + zb * d;
     double *y_out = p.proposal + i * d;
-    bool out = false;
-    for (int j = 0; j < d; ++j) {
-        double y = x[j];
-        if ((moved >> j) & 1u) {
-            const Philox4 w = philox4x32_10(chain, p.gen, 2u + j, 0u, p.k0, p.k1);
-            const double eps = p.scale[j] * (2.0 * u53(w.w[1], w.w[2]) - 1.0);
-            double t = a[j] - b[j];
-            t = gamma * t;
-            t = t + eps;
-            y = y + t;
-            const double lo = p.lo[j], hi = p.hi[j];
-            if (y < lo)
-                y = 2.0 * lo - y;
-            if (y > hi)
-                y = 2.0 * hi - y;
-            if (!(y >= lo && y <= hi))
-                out = true;
-        }
-        y_out[j] = y;
-    }
+    const bool out = de_move(chain, p.key, d, moved, p.box, x, p.archive + za * d, p.archive + zb * d, gamma, y_out);
     p.out[i] = out ? 1 : 0;
-    // the launch matrix: the proposal, or the chain's state where the proposal left the box (a row the model can run)
-    double *row = p.rows + i * p.ld;
-    for (int j = 0; j < d; ++j)
-        row[p.columns[j]] = out ? x[j] : y_out[j];
+    de_launch_row(d, p.box, out, x, y_out, p.rows + i * p.ld);
 }
 
 // ---- launch (validated by smart_analysis_capi.hip) -------------------------------------------------------------------
 void launch_demcz(const DemczCall &c, hipStream_t s)
 {
     const unsigned grid = (unsigned)((c.n_chains + kDemczThreads - 1) / kDemczThreads);
-    const unsigned k0 = (unsigned)(c.seed & 0xffffffffull), k1 = (unsigned)(c.seed >> 32);
     if (c.score) {
         DemczAccept a;
         a.N = c.n_chains, a.offset = c.chain_offset, a.d = c.n_dims, a.n_carry = c.n_carry;
-        a.gen = (unsigned)(c.generation - 1), a.k0 = k0, a.k1 = k1;
+        a.key = de_key(c.generation - 1, c.seed);
         a.x = c.x, a.logp = c.logp, a.carry = c.carry, a.accepted = c.accepted;
         a.proposal = c.proposal, a.out = c.out;
         a.score = c.score, a.score_stride = c.score_stride, a.score_kind = c.score_kind;
@@ -190,15 +155,12 @@ void launch_demcz(const DemczCall &c, hipStream_t s)
     if (c.propose) {
         DemczPropose p;
         p.N = c.n_chains, p.offset = c.chain_offset, p.d = c.n_dims;
-        p.gen = (unsigned)c.generation, p.k0 = k0, p.k1 = k1;
+        p.key = de_key(c.generation, c.seed);
         p.x = c.x, p.archive = c.archive, p.M = (unsigned long long)demcz_archive_after(c);
         p.J = (unsigned long long)c.jump_threshold, p.C = (unsigned long long)c.cr_threshold;
-        for (int j = 0; j < SMART_DEMCZ_MAX_DIMS; ++j) {
-            const bool live = j < c.n_dims;
-            p.lo[j] = live ? c.lo[j] : 0.0, p.hi[j] = live ? c.hi[j] : 0.0;
-            p.scale[j] = live ? c.scale[j] : 0.0, p.gamma[j] = live ? c.gamma[j] : 0.0;
-            p.columns[j] = live ? c.columns[j] : 0;
-        }
+        p.box = de_box(c.n_dims, c.lo, c.hi, c.scale, c.columns);
+        for (int j = 0; j < SMART_DEMCZ_MAX_DIMS; ++j)
+            p.gamma[j] = j < c.n_dims ? c.gamma[j] : 0.0;
         p.proposal = c.proposal, p.out = c.out, p.rows = c.rows, p.ld = c.ld;
         hipLaunchKernelGGL(smart_demcz_propose, dim3(grid), dim3(kDemczThreads), 0, s, p);
     }

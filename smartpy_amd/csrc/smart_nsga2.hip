@@ -27,12 +27,13 @@
 //   smart_nsga2_place      pos(e) = that number; the survivors scatter themselves (parameters, keys, payload, flags) into
 //                          the NEXT population
 // VARY:
-//   smart_nsga2_vary       one lane per offspring, shaped like smart_demcz_propose
+//   smart_nsga2_vary       one lane per offspring: the tournament and the partners here, the move itself in smart_de_move.h
+//                          (shared with smart_demcz_propose)
 // ARITHMETIC.  The unit is compiled with -ffp-contract=off: every operation is rounded once, as the numpy statement of the
 // tests rounds it; there is no operation here that is not correctly rounded (no pow, no log).
 #include "smart_capi_internal.h"
+#include "smart_de_move.h"
 #include "smart_matrix_common.h"
-#include "smart_philox.h"
 #include <cstdint>
 
 namespace smart {
@@ -47,11 +48,9 @@ constexpr long kNsAlign = 256;      // of the workspace's parts
 constexpr int kNsFirstBatch = 16, kNsMaxBatch = 1024;
 constexpr int kRankBeyond = SMART_NSGA2_RANK_BEYOND, kRankOut = SMART_NSGA2_RANK_OUT;
 static_assert(SMART_NSGA2_MAX_OBJECTIVES == kNsKeys, "the padded keys");
-static_assert(SMART_NSGA2_MAX_DIMS == 16 && SMART_NSGA2_MAX_CARRY == 16, "the arrays below");
+static_assert(SMART_NSGA2_MAX_CARRY == 16, "the arrays below");
 
 typedef unsigned long long u64;
-
-__device__ inline u64 ns_mulhi(unsigned w, u64 n) { return ((u64)w * n) >> 32; }
 
 // ---- the workspace: ctl[2] | cum[N + 8] | mask[2][W] | keys[Eld][4] | part[Eld] | count[Eld] | rank[Eld] | dist[Eld] |
 // D[max(W, 16)][Eld], for 2 N candidates: W = ceil(2 N / 64) mask words, Eld = 64 W
@@ -421,12 +420,11 @@ __global__ __launch_bounds__(kNsThreads) void smart_nsga2_place(Nsga2Place p)
 // ---- variation --------------------------------------------------------------------------------------------------------
 struct Nsga2Vary {
     int N, d;
-    unsigned gen, k0, k1;
+    DeKey key;
     const double *x; // the population, in tournament order
     u64 C;           // the threshold of the crossover, in [0, 2^32]
     double f;
-    double lo[SMART_NSGA2_MAX_DIMS], hi[SMART_NSGA2_MAX_DIMS], scale[SMART_NSGA2_MAX_DIMS];
-    int columns[SMART_NSGA2_MAX_DIMS];
+    DeBox box;
     double *offspring;
     unsigned char *out;
     double *rows;
@@ -440,51 +438,21 @@ __global__ __launch_bounds__(kNsThreads) void smart_nsga2_vary(Nsga2Vary p)
         return;
     const int d = p.d;
     const u64 N = (u64)p.N;
-    const Philox4 r = philox4x32_10((unsigned)c, p.gen, 0u, 0u, p.k0, p.k1);
-    const u64 a = ns_mulhi(r.w[0], N);
-    u64 b = ns_mulhi(r.w[1], N - 1);
+    const Philox4 r = philox4x32_10((unsigned)c, p.key.gen, 0u, 0u, p.key.k0, p.key.k1);
+    const u64 a = mulhi(r.w[0], N);
+    u64 b = mulhi(r.w[1], N - 1);
     b += b >= a;
     const u64 t = a < b ? a : b;    // the binary tournament: the population lies in (rank, -distance) order
-    const u64 p1 = ns_mulhi(r.w[2], N);
-    u64 p2 = ns_mulhi(r.w[3], N - 1);
+    const u64 p1 = mulhi(r.w[2], N);
+    u64 p2 = mulhi(r.w[3], N - 1);
     p2 += p2 >= p1;
-    const Philox4 fb = philox4x32_10((unsigned)c, p.gen, 1u, 0u, p.k0, p.k1);
-    const int fallback = (int)ns_mulhi(fb.w[0], (u64)d);
-    unsigned crossed = 0;
-    for (int j = 0; j < d; ++j) {
-        const Philox4 w = philox4x32_10((unsigned)c, p.gen, 2u + j, 0u, p.k0, p.k1);
-        if ((u64)w.w[0] < p.C)
-            crossed |= 1u << j;
-    }
-    if (crossed == 0)
-        crossed = 1u << fallback;
-    const double *const base = p.x + t * d, *const x1 = p.x + p1 * d, *const x2 = p.x + p2 * d;
+    const Philox4 fb = philox4x32_10((unsigned)c, p.key.gen, 1u, 0u, p.key.k0, p.key.k1);
+    const unsigned crossed = de_crossover((unsigned)c, p.key, d, p.C, (int)mulhi(fb.w[0], (u64)d));
+    const double *const base = p.x + t * d;
     double *const y_out = p.offspring + (long)c * d;
-    bool out = false;
-    for (int j = 0; j < d; ++j) {
-        double y = base[j];
-        if ((crossed >> j) & 1u) {
-            const Philox4 w = philox4x32_10((unsigned)c, p.gen, 2u + j, 0u, p.k0, p.k1);
-            const double eps = p.scale[j] * (2.0 * u53(w.w[1], w.w[2]) - 1.0);
-            double s = x1[j] - x2[j];
-            s = p.f * s;
-            s = s + eps;
-            y = y + s;
-            const double lo = p.lo[j], hi = p.hi[j];
-            if (y < lo)
-                y = 2.0 * lo - y;
-            if (y > hi)
-                y = 2.0 * hi - y;
-            if (!(y >= lo && y <= hi))
-                out = true;
-        }
-        y_out[j] = y;
-    }
+    const bool out = de_move((unsigned)c, p.key, d, crossed, p.box, base, p.x + p1 * d, p.x + p2 * d, p.f, y_out);
     p.out[c] = out ? 1 : 0;
-    // the launch matrix: the offspring, or its base row where it left the box (a row the model can run)
-    double *const row = p.rows + (long)c * p.ld;
-    for (int j = 0; j < d; ++j)
-        row[p.columns[j]] = out ? base[j] : y_out[j];
+    de_launch_row(d, p.box, out, base, y_out, p.rows + (long)c * p.ld);
 }
 
 // ---- launch (validated by smart_analysis_capi.hip) -------------------------------------------------------------------
@@ -586,15 +554,10 @@ int launch_nsga2(const Nsga2Call &c, hipStream_t s)
     if (c.vary) {
         Nsga2Vary p;
         p.N = (int)c.n_rows, p.d = c.n_dims;
-        p.gen = (unsigned)c.generation;
-        p.k0 = (unsigned)(c.seed & 0xffffffffull), p.k1 = (unsigned)(c.seed >> 32);
+        p.key = de_key(c.generation, c.seed);
         p.x = c.scores ? c.next_x : c.pop_x;
         p.C = (u64)c.cr_threshold, p.f = c.f;
-        for (int j = 0; j < SMART_NSGA2_MAX_DIMS; ++j) {
-            const bool live = j < c.n_dims;
-            p.lo[j] = live ? c.lo[j] : 0.0, p.hi[j] = live ? c.hi[j] : 0.0, p.scale[j] = live ? c.scale[j] : 0.0;
-            p.columns[j] = live ? c.columns[j] : 0;
-        }
+        p.box = de_box(c.n_dims, c.lo, c.hi, c.scale, c.columns);
         p.offspring = c.offspring, p.out = c.out, p.rows = c.rows, p.ld = c.ld;
         hipLaunchKernelGGL(smart_nsga2_vary, dim3((unsigned)((c.n_rows + kNsThreads - 1) / kNsThreads)), dim3(kNsThreads), 0,
                            s, p);

@@ -1,4 +1,4 @@
-// smart_philox.h -- the counter-based generator the units that draw share (smart_demcz.hip, smart_error_model.hip):
+// smart_philox.h -- the counter-based generator the units that draw share (smart_demcz.hip, smart_nsga2.hip, smart_error_model.hip):
 // Philox4x32-10 (Salmon et al. 2011) and the 53-bit uniform made of two of its words.  What a counter's four words mean is
 // the unit's own business (include/smart_amd.h says it per entry); the bits of a counter and key never depend on the
 // launch.
@@ -33,5 +33,8 @@ __device__ inline double u53(unsigned w0, unsigned w1)
 {
     return (double)(((unsigned long long)(w0 >> 5) << 26) + (unsigned long long)(w1 >> 6)) * 0x1p-53;
 }
+
+// a word -> 0 .. n - 1: floor(w n / 2^32), exact
+__device__ inline unsigned long long mulhi(unsigned w, unsigned long long n) { return ((unsigned long long)w * n) >> 32; }
 
 } // namespace smart

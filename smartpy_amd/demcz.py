@@ -7,22 +7,16 @@ snapshots (gelman_rubin) and the result object (PosteriorSample) with its diagno
 SMART ensemble launch between two steps; any other density can stand there (tests/test_gpu_demcz.py plays one).
 """
 import ctypes
-import math
 
 import numpy as np
 
-from . import _lib
+from . import _lib, generational
 from ._lib import SmartEngineError
-
-TWO32 = 1 << 32
 
 
 def thresholds(p_jump, cr):
     """-> (J, C) = (floor(p_jump 2^32), floor(CR 2^32)): what a 32-bit word is compared with"""
-    for name, v in (('p_jump', p_jump), ('cr', cr)):
-        if not 0.0 <= float(v) <= 1.0:
-            raise SmartEngineError(-2, "demcz: {} {} must be in [0, 1].".format(name, v))
-    return int(math.floor(float(p_jump) * TWO32)), int(math.floor(float(cr) * TWO32))
+    return generational.threshold('demcz', 'p_jump', p_jump), generational.threshold('demcz', 'cr', cr)
 
 
 def gamma_table(d):
@@ -34,7 +28,7 @@ def _dbl(a):
     return a.ctypes.data_as(ctypes.c_void_p)
 
 
-class DemczState(object):
+class DemczState(generational.BoxState):
     """N chains of d varying parameters on the device, and what the host keeps of them.
 
     Device tensors: x [N, d] (the chains), logp [N], carry [N, n_carry] (a payload that travels with a chain: the
@@ -50,24 +44,13 @@ class DemczState(object):
     def __init__(self, x, lo, hi, capacity, seed=0, cr=0.9, p_jump=0.1, b_star=1e-6, n_carry=0, columns=None, ld=None,
                  rows=None, fill=float('nan'), score_kind='logp', n_obs=0, n_eff=0.0, sigma=0.0, device=None):
         import torch
-        from .engine import as_device, default_device
-        device = torch.device(device) if device is not None else (
-            x.device if isinstance(x, torch.Tensor) and x.is_cuda else default_device())
-        self.device = device
-        self.x = as_device(x, device).clone().contiguous()
-        if self.x.dim() != 2:
-            raise SmartEngineError(-2, "demcz: the population must be [chains, dimensions], not {}.".format(tuple(self.x.shape)))
+        self.x = self._place('demcz', 'chains', x, device)
+        device = self.device
         N, d = self.x.shape
         self.n_chains, self.n_dims, self.n_carry, self.capacity = N, d, int(n_carry), int(capacity)
-        self.lo = np.ascontiguousarray(np.asarray(lo, dtype=np.float64).reshape(-1))
-        self.hi = np.ascontiguousarray(np.asarray(hi, dtype=np.float64).reshape(-1))
-        if self.lo.shape != (d,) or self.hi.shape != (d,):
-            raise SmartEngineError(-2, "demcz: lo and hi must hold {} values.".format(d))
-        self.scale = np.ascontiguousarray(float(b_star) * (self.hi - self.lo))
+        self._set_box('demcz', self.x, lo, hi, b_star, seed, columns, ld, rows, fill)
         self.gamma = np.ascontiguousarray(gamma_table(d))
         self.J, self.C = thresholds(p_jump, cr)
-        self.seed = int(seed) & (2 ** 64 - 1)
-        self.columns = np.ascontiguousarray(np.arange(d) if columns is None else columns, dtype=np.int32)
         self.score_kind = score_kind
         self.n_obs, self.n_eff, self.sigma = int(n_obs), float(n_eff), float(sigma)
         f64 = dict(dtype=torch.float64, device=device)
@@ -79,12 +62,6 @@ class DemczState(object):
         self.archive = torch.zeros((self.capacity, d), **f64)
         self.archive_logp = torch.zeros((self.capacity,), **f64)
         self.archive_carry = torch.zeros((self.capacity, self.n_carry), **f64)
-        if rows is None:
-            ld = d if ld is None else int(ld)
-            rows = torch.full((N, ld), float(fill), **f64)
-            if ld >= d and int(self.columns.max()) < ld:
-                rows[:, torch.from_numpy(self.columns.astype(np.int64)).to(device)] = self.x
-        self.rows = rows
         self.M, self.g = 0, 1
 
 
@@ -116,17 +93,13 @@ def demcz_step(state, scores=None, carry_new=None, propose=True, append=False, c
             raise SmartEngineError(-2, "demcz_step: scores must be a float64 device tensor [{}].".format(s.n_chains))
         stride = scores.stride(0) if s.n_chains > 1 else 1
         score_ptr = scores.data_ptr() + 8 * stride * first
-    if carry_new is not None:
-        if not (isinstance(carry_new, torch.Tensor) and carry_new.is_cuda and carry_new.dtype == torch.float64
-                and tuple(carry_new.shape) == (s.n_chains, s.n_carry) and carry_new.is_contiguous()):
-            raise SmartEngineError(-2, "demcz_step: carry_new must be a contiguous float64 device tensor [{}, {}]."
-                                   .format(s.n_chains, s.n_carry))
+    generational.check_carry_new('demcz_step', carry_new, s.n_chains, s.n_carry)
     d, nc = s.n_dims, s.n_carry
 
     def at(t, width, size=8):       # the address of row `first` of a per-chain array
         return None if t is None else t.data_ptr() + size * width * first
 
-    ld = s.rows.stride(0) if s.rows.dim() == 2 and s.rows.shape[0] > 1 else s.rows.shape[-1]
+    ld = s.ld
     with torch.cuda.device(s.device):
         _lib.check(L.smart_demcz_step_hip(
             count, first, d, s.seed, s.g, s.M, s.capacity,
@@ -178,10 +151,7 @@ def diagnostics_header(names):
 def write_diagnostics(path, names, diagnostics):
     """diagnostics: rows of (generation, acceptance rate so far, R-hat per parameter) -- one per archived generation; the
     generation as an integer, the others '%.6e'."""
-    with open(path, 'w', newline='', encoding='utf8') as f:
-        f.write(diagnostics_header(names))
-        for row in np.asarray(diagnostics, dtype=np.float64).reshape(-1, 2 + len(names)):
-            f.write(','.join(['%d' % int(row[0])] + ['%.6e' % v for v in row[1:]]) + '\n')
+    generational.write_diagnostics(path, diagnostics_header(names), 1, diagnostics)
 
 
 class PosteriorSample(object):

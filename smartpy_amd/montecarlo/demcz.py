@@ -13,18 +13,17 @@ import math
 
 import numpy as np
 
+from .generational import GW_FLAG_COLUMN, N_CARRY, Generational
 from .montecarlo import MonteCarlo, OBJ_FN_NAMES
 from .. import demcz as core
-from .. import distributed as sdist
 from .. import errormodel
 from ..engine import SmartEngineError
 from ..sampling import latin_hypercube
 
-RMSE_COLUMN, GW_FLAG_COLUMN = OBJ_FN_NAMES.index('RMSE'), len(OBJ_FN_NAMES)
-N_CARRY = len(OBJ_FN_NAMES) + 2      # the seven objective functions, the GW flag and the groundwater ratio
+RMSE_COLUMN = OBJ_FN_NAMES.index('RMSE')
 
 
-class DEMCz(MonteCarlo):
+class DEMCz(Generational):
     """Sample the posterior of the parameters given the observed flow.
 
     chains: N, the rows of every launch; generations: launches after the initial one; thin: every thin-th generation is
@@ -81,18 +80,9 @@ class DEMCz(MonteCarlo):
         self._check_observations()
         self.n_obs = int(np.count_nonzero(~np.isnan(np.asarray(self.model.nd_flow, dtype=np.float64))))
         self.n_eff = float(self.n_obs if n_eff is None else n_eff)
+        fixed = self._resolve_box(vary, fixed)
         names, ranges = list(self.param_names), self.model.parameters.ranges
-        self.vary = list(names if vary is None else vary)
-        unknown = [p for p in self.vary if p not in names]
-        if unknown or len(set(self.vary)) != len(self.vary) or not self.vary:
-            raise Exception("DEMCz: `vary` must name at least one of {}, each once (got {}).".format(names, self.vary))
-        fixed = dict(fixed or {})
-        unknown = [p for p in fixed if p not in names or p in self.vary]
-        if unknown:
-            raise Exception("DEMCz: the fixed parameter(s) {} are unknown or also vary.".format(unknown))
-        self.columns = [names.index(p) for p in self.vary]
-        self.lo = np.asarray([ranges[p][0] for p in self.vary], dtype=np.float64)
-        self.hi = np.asarray([ranges[p][1] for p in self.vary], dtype=np.float64)
+        population = None
         self.error_sampled, self.error_fixed = [], {}
         if likelihood == 'ar1':
             # the sampled error parameters: further dimensions of the chains, further columns of the launch matrix
@@ -111,13 +101,7 @@ class DEMCz(MonteCarlo):
             self.columns += [len(names) + errormodel.PARAMETER_NAMES.index(p) for p in self.error_sampled]
             self.lo = np.concatenate([self.lo, [error_ranges[p][0] for p in self.error_sampled]])
             self.hi = np.concatenate([self.hi, [error_ranges[p][1] for p in self.error_sampled]])
-        else:
-            population = latin_hypercube(self.chains, ranges, names, seed=seed)
-        for j, p in enumerate(names):
-            if p not in self.vary:
-                population[:, j] = fixed.get(p, 0.5 * (float(ranges[p][0]) + float(ranges[p][1])))
-        self.initial_population = population
-        self._set_sample(population[:, :len(names)])
+        self._start_from(self.chains, fixed, population)
         self.posterior = self.log_density = self.acceptance_rate = self.rhat = self.diagnostics = None
 
     # ---- the log-density of a score ---------------------------------------------------------------------------
@@ -142,8 +126,7 @@ class DEMCz(MonteCarlo):
     def _new_state(self, population, snapshots, device):
         """The chains on the device: the launch matrix is the population at full width, the archive holds `snapshots` of
         the chains"""
-        from ..engine import as_device
-        rows = as_device(population, device).clone()
+        rows = self._device_rows(population, device)
         return core.DemczState(rows[:, self.columns], self.lo, self.hi, capacity=int(snapshots) * self.chains,
                                seed=0 if self.seed is None else self.seed, cr=self.cr, p_jump=self.p_jump,
                                b_star=self.b_star, n_carry=N_CARRY, columns=self.columns, rows=rows,
@@ -153,16 +136,11 @@ class DEMCz(MonteCarlo):
     def _launch_chains(self, state):
         """One launch over the launch matrix of the chains -> (scores [N] at a stride, payload [N, 9])"""
         import torch
-        n = self.chains
         if self.likelihood == 'ar1':
             return self._launch_chains_ar1(state)
         # (a view of its own per launch: what the engine remembers about a tensor object is not asked about rows that the
         # step kernel rewrites behind torch's back)
-        out = self.model.simulate_ensemble(state.rows.view(n, len(self.param_names)), objective_functions=True,
-                                           gw_constraint=self.constraints['gw'], save_discharge=False,
-                                           math_mode=self.math_mode)
-        table = out.objfn[:n]
-        payload = torch.cat([table, out.gw[:n].unsqueeze(1)], dim=1)
+        _, table, payload = self._launch(state.rows.view(self.chains, len(self.param_names)))
         scores = table[:, RMSE_COLUMN]                      # read in place: stride 8
         if self.gw_prior:
             scores = torch.where(table[:, GW_FLAG_COLUMN] > 0.0, scores, torch.full_like(scores, float('inf')))
@@ -175,12 +153,8 @@ class DEMCz(MonteCarlo):
         the stride of its rows"""
         import torch
         from .. import engine
-        n, w = self.chains, len(self.param_names)
-        out = self.model.simulate_ensemble(state.rows[:, :w].contiguous(), objective_functions=True,
-                                           gw_constraint=self.constraints['gw'], save_discharge=True,
-                                           math_mode=self.math_mode)
-        table = out.objfn[:n]
-        payload = torch.cat([table, out.gw[:n].unsqueeze(1)], dim=1)
+        w = len(self.param_names)
+        out, table, payload = self._launch(state.rows[:, :w].contiguous(), save_discharge=True)
         theta = state.rows[:, w:w + len(errormodel.PARAMETER_NAMES)]
         scores = engine.residual_log_likelihood(out.discharge_report_major, self.model._device_cache[2], theta)[0]
         if self.gw_prior:
@@ -206,11 +180,8 @@ class DEMCz(MonteCarlo):
         `<catchment>.SMART.demcz.diagnostics` (generation, acceptance_rate, Rhat_<p> per archived generation).  Under
         torch.distributed every rank computes everything itself and rank 0 alone writes."""
         import torch
-        from ..engine import as_device, default_device
-        world = sdist.rank_world()[1]
-        population = self.initial_population
-        if world > 1:       # (seed=None draws from NumPy's global stream: rank 0's population is THE population)
-            population = sdist.broadcast_matrix(population, src=0)
+        from ..engine import default_device
+        population = self._population_of_all_ranks()
         N, G, thin, d = self.chains, self.generations, self.thin, len(self.dimension_names)
         S = 1 + G // thin
         device = default_device()
@@ -232,9 +203,7 @@ class DEMCz(MonteCarlo):
         first = min(S - 1, int(math.floor(self.burn_in * S)))
         sample_d = state.archive[first * N:]
         carry = state.archive_carry[first * N:]
-        base = as_device(population[:1], device)
-        full = base.repeat(sample_d.shape[0], 1)
-        full[:, self.columns] = sample_d
+        full = self._full_rows(population, sample_d)
         # (with 'ar1' the rows are 13 wide: the ten model columns are the sample, the last three the error parameters)
         width = len(self.param_names)
         error_parameters = full[:, width:].contiguous() if self.likelihood == 'ar1' else None
@@ -249,29 +218,15 @@ class DEMCz(MonteCarlo):
         self.acceptance_rate = float(accepted.sum()) / float(N * G)
         self.log_density = history_logp.reshape(-1)[first * N:]
         self.state = state
-        # ---- the MonteCarlo object every second stage and analysis takes
-        n_obj = len(self.obj_fn_names)
-        self._set_sample(full)
-        self.device_obj_fns, self.device_gw = carry[:, :n_obj].contiguous(), carry[:, N_CARRY - 1].contiguous()
-        host = carry.cpu().numpy()
-        self.obj_fns, self.gw_contributions = np.ascontiguousarray(host[:, :n_obj]), np.ascontiguousarray(host[:, -1])
+        self._adopt(full, carry)
         self.posterior = core.PosteriorSample(self.dimension_names, sample_d, self.log_density, carry, history,
                                               history_logp, accepted, self.rhat, self.acceptance_rate, self.diagnostics,
                                               first, error_parameters=error_parameters)
-
-        def write_files():
-            self._write_database(None, compression)
-            self.posterior.file = self._write_side(write, '.diagnostics', lambda path: core.write_diagnostics(
-                path, self.dimension_names, self.diagnostics))
-        sdist.on_rank_zero(write_files)
+        self.posterior.file = self._write_files(compression, write, lambda path: core.write_diagnostics(
+            path, self.dimension_names, self.diagnostics))
 
     def _default_error_parameters(self):
         """what residual_likelihood and predictive_bounds take where none are given: the archived ones of an 'ar1' run"""
         if self.posterior is None or self.posterior.error_parameters is None:
             return None
         return self.posterior.error_parameters.cpu().numpy()
-
-    @property
-    def diagnostics_file(self):
-        """`<out>/<catchment>.SMART.demcz.diagnostics`: beside the sampling database, whatever its format."""
-        return self._side_file('.diagnostics')

@@ -11,18 +11,14 @@ stored matrix.
 """
 import numpy as np
 
-from .montecarlo import MonteCarlo, OBJ_FN_NAMES
+from .generational import GW_FLAG_COLUMN, N_CARRY, Generational
+from .montecarlo import MonteCarlo
 from .pareto import Pareto
-from .. import distributed as sdist
 from .. import nsga2 as core
 from ..engine import SmartEngineError
-from ..sampling import latin_hypercube
-
-GW_FLAG_COLUMN = len(OBJ_FN_NAMES)
-N_CARRY = len(OBJ_FN_NAMES) + 2      # the seven objective functions, the GW flag and the groundwater ratio
 
 
-class NSGA2(MonteCarlo):
+class NSGA2(Generational):
     """Move a population towards the Pareto front of several objective functions.
 
     objectives: as for Pareto -- a dict {name of an objective function: direction} or a list of names taking
@@ -72,32 +68,13 @@ class NSGA2(MonteCarlo):
         self.directions = [objectives[name] for name in objectives]
         self.objectives = [(self.obj_fn_names.index(name), objectives[name]) for name in objectives]
         core.directions_of(self.objectives)
-        names, ranges = list(self.param_names), self.model.parameters.ranges
-        self.vary = list(names if vary is None else vary)
-        if len(self.vary) > core._lib.NSGA2_MAX_DIMS:
-            raise SmartEngineError(-2, "NSGA2: {} dimensions, at most {}.".format(len(self.vary), core._lib.NSGA2_MAX_DIMS))
-        unknown = [p for p in self.vary if p not in names]
-        if unknown or len(set(self.vary)) != len(self.vary) or not self.vary:
-            raise Exception("NSGA2: `vary` must name at least one of {}, each once (got {}).".format(names, self.vary))
-        fixed = dict(fixed or {})
-        unknown = [p for p in fixed if p not in names or p in self.vary]
-        if unknown:
-            raise Exception("NSGA2: the fixed parameter(s) {} are unknown or also vary.".format(unknown))
-        self.columns = [names.index(p) for p in self.vary]
-        self.lo = np.asarray([ranges[p][0] for p in self.vary], dtype=np.float64)
-        self.hi = np.asarray([ranges[p][1] for p in self.vary], dtype=np.float64)
-        initial = latin_hypercube(self.population, ranges, names, seed=seed)
-        for j, p in enumerate(names):
-            if p not in self.vary:
-                initial[:, j] = fixed.get(p, 0.5 * (float(ranges[p][0]) + float(ranges[p][1])))
-        self.initial_population = initial
-        self._set_sample(initial)
+        fixed = self._resolve_box(vary, fixed, max_dims=core._lib.NSGA2_MAX_DIMS)
+        self._start_from(self.population, fixed)
         self.rank = self.crowding = self.front_index = self.keys = self.diagnostics = self.state = None
 
     def _new_state(self, population, device):
         """The population on the device: the launch matrix is the population at full width"""
-        from ..engine import as_device
-        rows = as_device(population, device).clone()
+        rows = self._device_rows(population, device)
         return core.Nsga2State(rows[:, self.columns], self.lo, self.hi, self.objectives,
                                seed=0 if self.seed is None else self.seed, f=self.f, cr=self.cr, b_star=self.b_star,
                                n_carry=N_CARRY, columns=self.columns, rows=rows, device=device)
@@ -109,11 +86,7 @@ class NSGA2(MonteCarlo):
         n = self.population
         # (a view of its own per launch: what the engine remembers about a tensor object is not asked about rows that the
         # step kernel rewrites behind torch's back)
-        out = self.model.simulate_ensemble(state.rows.view(n, len(self.param_names)), objective_functions=True,
-                                           gw_constraint=self.constraints['gw'], save_discharge=False,
-                                           math_mode=self.math_mode)
-        table = out.objfn[:n]
-        payload = torch.cat([table, out.gw[:n].unsqueeze(1)], dim=1)
+        _, table, payload = self._launch(state.rows.view(n, len(self.param_names)))
         eligible = (table[:, GW_FLAG_COLUMN] > 0.0).to(torch.uint8).contiguous() if self.gw_constraint else None
         return table, payload, eligible
 
@@ -131,11 +104,8 @@ class NSGA2(MonteCarlo):
         every rank computes everything itself and rank 0 alone writes."""
         import torch
         from ..engine import default_device
-        world = sdist.rank_world()[1]
-        population = self.initial_population
-        if world > 1:       # (seed=None draws from NumPy's global stream: rank 0's population is THE population)
-            population = sdist.broadcast_matrix(population, src=0)
-        N, G = self.population, self.generations
+        population = self._population_of_all_ranks()
+        G = self.generations
         device = default_device()
         state = self._new_state(population, device)
         rows = []
@@ -147,26 +117,9 @@ class NSGA2(MonteCarlo):
         self.state = state
         self.diagnostics = torch.stack(rows).cpu().numpy()
         # ---- the MonteCarlo object every second stage and analysis takes: the final population, in tournament order
-        base = torch.from_numpy(np.ascontiguousarray(population[:1])).to(device)
-        full = base.repeat(N, 1)
-        full[:, self.columns] = state.x
-        n_obj = len(self.obj_fn_names)
-        carry = state.carry
-        self._set_sample(full.contiguous())
-        self.device_obj_fns, self.device_gw = carry[:, :n_obj].contiguous(), carry[:, N_CARRY - 1].contiguous()
-        host = carry.cpu().numpy()
-        self.obj_fns, self.gw_contributions = np.ascontiguousarray(host[:, :n_obj]), np.ascontiguousarray(host[:, -1])
+        self._adopt(self._full_rows(population, state.x), state.carry)
         self.keys = state.keys
         self.rank, self.crowding = state.rank.cpu().numpy(), state.crowding.cpu().numpy()
         self.front_index = np.nonzero(self.rank == 1)[0]
-
-        def write_files():
-            self._write_database(None, compression)
-            self.diagnostics_written = self._write_side(write, '.diagnostics', lambda path: core.write_diagnostics(
-                path, self.objective_names, self.diagnostics))
-        sdist.on_rank_zero(write_files)
-
-    @property
-    def diagnostics_file(self):
-        """`<out>/<catchment>.SMART.nsga2.diagnostics`: beside the sampling database, whatever its format."""
-        return self._side_file('.diagnostics')
+        self.diagnostics_written = self._write_files(compression, write, lambda path: core.write_diagnostics(
+            path, self.objective_names, self.diagnostics))

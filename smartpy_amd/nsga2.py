@@ -12,21 +12,16 @@ built: both need pow, which no library rounds correctly, and every output of the
 statement of the tests holds the kernels to it bit for bit.
 """
 import ctypes
-import math
 
 import numpy as np
 
-from . import _lib
+from . import _lib, generational
 from ._lib import SmartEngineError
-
-TWO32 = 1 << 32
 
 
 def cr_threshold(cr):
     """-> C = floor(CR 2^32): what a 32-bit word is compared with"""
-    if not 0.0 <= float(cr) <= 1.0:
-        raise SmartEngineError(-2, "nsga2: cr {} must be in [0, 1].".format(cr))
-    return int(math.floor(float(cr) * TWO32))
+    return generational.threshold('nsga2', 'cr', cr)
 
 
 def directions_of(objectives):
@@ -64,7 +59,7 @@ class _Population(object):
         self.part = torch.zeros((N,), dtype=torch.uint8, device=device)
 
 
-class Nsga2State(object):
+class Nsga2State(generational.BoxState):
     """N rows of d varying parameters on the device, and what the host keeps of them.
 
     Device tensors: two population buffers (`buffers`; `current` is the index of the one that holds the population: x [N, d],
@@ -83,14 +78,8 @@ class Nsga2State(object):
     def __init__(self, x, lo, hi, objectives, seed=0, f=0.5, cr=0.9, b_star=1e-6, n_carry=0, columns=None, ld=None,
                  rows=None, fill=float('nan'), device=None):
         import torch
-        from .engine import as_device, default_device
-        device = torch.device(device) if device is not None else (
-            x.device if isinstance(x, torch.Tensor) and x.is_cuda else default_device())
-        self.device = device
-        self.offspring = as_device(x, device).clone().contiguous()
-        if self.offspring.dim() != 2:
-            raise SmartEngineError(-2, "nsga2: the population must be [rows, dimensions], not {}."
-                                   .format(tuple(self.offspring.shape)))
+        self.offspring = self._place('nsga2', 'rows', x, device)
+        device = self.device
         N, d = self.offspring.shape
         self.score_columns, self.direction, self.target = directions_of(list(objectives))
         M = len(self.score_columns)
@@ -99,14 +88,8 @@ class Nsga2State(object):
         if not 1 <= d <= _lib.NSGA2_MAX_DIMS:
             raise SmartEngineError(-2, "nsga2: {} dimensions, between 1 and {}.".format(d, _lib.NSGA2_MAX_DIMS))
         self.n_rows, self.n_dims, self.n_objectives, self.n_carry = N, d, M, int(n_carry)
-        self.lo = np.ascontiguousarray(np.asarray(lo, dtype=np.float64).reshape(-1))
-        self.hi = np.ascontiguousarray(np.asarray(hi, dtype=np.float64).reshape(-1))
-        if self.lo.shape != (d,) or self.hi.shape != (d,):
-            raise SmartEngineError(-2, "nsga2: lo and hi must hold {} values.".format(d))
-        self.scale = np.ascontiguousarray(float(b_star) * (self.hi - self.lo))
+        self._set_box('nsga2', self.offspring, lo, hi, b_star, seed, columns, ld, rows, fill)
         self.f, self.C = float(f), cr_threshold(cr)
-        self.seed = int(seed) & (2 ** 64 - 1)
-        self.columns = np.ascontiguousarray(np.arange(d) if columns is None else columns, dtype=np.int32)
         self.buffers = [_Population(N, d, M, self.n_carry, device) for _ in range(2)]
         self.current = 0
         self.rank = torch.full((N,), _lib.NSGA2_RANK_OUT, dtype=torch.int32, device=device)
@@ -118,12 +101,6 @@ class Nsga2State(object):
         if need < 0:
             raise SmartEngineError(need, "nsga2: no workspace for {} rows and {} objectives.".format(N, M))
         self.workspace = torch.empty((need,), dtype=torch.uint8, device=device)
-        if rows is None:
-            ld = d if ld is None else int(ld)
-            rows = torch.full((N, ld), float(fill), dtype=torch.float64, device=device)
-            if ld >= d and int(self.columns.max()) < ld:
-                rows[:, torch.from_numpy(self.columns.astype(np.int64)).to(device)] = self.offspring
-        self.rows = rows
         self.parents, self.g = False, 1
 
     x = property(lambda self: self.buffers[self.current].x)
@@ -161,17 +138,13 @@ def nsga2_step(state, scores=None, carry_new=None, eligible=None, vary=True):
         score_ptr, ld_scores = scores.data_ptr(), scores.stride(0)
         if carry_new is None and nc > 0:
             raise SmartEngineError(-1, "nsga2_step: the state carries {} values per row: carry_new is needed.".format(nc))
-    if carry_new is not None:
-        if not (isinstance(carry_new, torch.Tensor) and carry_new.is_cuda and carry_new.dtype == torch.float64
-                and tuple(carry_new.shape) == (N, nc) and carry_new.is_contiguous()):
-            raise SmartEngineError(-2, "nsga2_step: carry_new must be a contiguous float64 device tensor [{}, {}]."
-                                   .format(N, nc))
+    generational.check_carry_new('nsga2_step', carry_new, N, nc)
     if eligible is not None:
         if not (isinstance(eligible, torch.Tensor) and eligible.is_cuda and eligible.dtype == torch.uint8
                 and tuple(eligible.shape) == (N,) and eligible.is_contiguous()):
             raise SmartEngineError(-2, "nsga2_step: eligible must be a contiguous uint8 device tensor [{}].".format(N))
     old, new = s.buffers[s.current], s.buffers[1 - s.current]
-    ld = s.rows.stride(0) if s.rows.dim() == 2 and s.rows.shape[0] > 1 else s.rows.shape[-1]
+    ld = s.ld
 
     def ptr(t):
         return None if t is None else t.data_ptr()
@@ -223,7 +196,4 @@ def diagnostics_header(names):
 def write_diagnostics(path, names, diagnostics):
     """diagnostics: rows of (generation, size of front 1, best key per objective); the first two as integers, the keys
     '%.6e'."""
-    with open(path, 'w', newline='', encoding='utf8') as f:
-        f.write(diagnostics_header(names))
-        for row in np.asarray(diagnostics, dtype=np.float64).reshape(-1, 2 + len(names)):
-            f.write(','.join(['%d' % int(row[0]), '%d' % int(row[1])] + ['%.6e' % v for v in row[2:]]) + '\n')
+    generational.write_diagnostics(path, diagnostics_header(names), 2, diagnostics)

@@ -1,4 +1,4 @@
-"""NSGA-II on the device: smart_nsga2_step_hip against the numpy statement of tests/nsga2_statement.py BIT FOR BIT -- the
+"""NSGA-II on the device: smart_nsga2_step_hip against the numpy statement of oracle/analyses/nsga2.py BIT FOR BIT -- the
 population (parameters, keys, payload, flags), ranks, crowding distances, origins, the two counters, offspring, `out` flags
 and launch rows after every one of 40 generations, inside buffers with guards; stress inputs (massive ties, a chain of
 fronts, one front cut by crowding alone, candidates that take no part, the first call); the rank-1 set against
@@ -11,8 +11,8 @@ rounded otherwise than numpy rounds it, so there is no margin to watch."""
 import numpy as np
 import pytest
 
-import nsga2_statement as st
-from nsga2_statement import MAX, MIN, TARGET, RANK_BEYOND, RANK_OUT, Population, nsga2_statement
+import oracle.analyses.nsga2 as st
+from oracle.analyses.nsga2 import MAX, MIN, TARGET, RANK_BEYOND, RANK_OUT, Population, nsga2_statement
 from support import EXTRA, GATE, Guarded, example_root, same_bits, settings_file
 
 pytestmark = pytest.mark.gpu

@@ -11,8 +11,9 @@ import re
 import numpy as np
 import pytest
 
-import nsga2_statement as st
-from nsga2_statement import MAX, MIN, TARGET, RANK_BEYOND, RANK_OUT, Population, nsga2_statement
+import cases_nsga2 as cases
+import oracle.analyses.nsga2 as st
+from oracle.analyses.nsga2 import MAX, MIN, TARGET, RANK_BEYOND, RANK_OUT, Population, nsga2_statement
 from smartpy_amd import _lib, nsga2
 from support import E_MODE, E_NO_DEVICE, E_NULL, E_SIZE, FAKE, example_root, refusal, same_bits, settings_file
 
@@ -185,11 +186,11 @@ def test_the_thresholds_are_the_recorded_ones():
     assert recorded and [float(v) for v in recorded.groups()] == [DISTANCE, GAP, ENDS]
 
 
-@pytest.mark.parametrize('seed', list(st.CONVERGENCE['seeds']))
+@pytest.mark.parametrize('seed', list(cases.CONVERGENCE['seeds']))
 def test_the_statement_converges_on_the_segment(seed):
     """Two objectives, the negated squared distances to two points of the unit box, d = 6, N = 128, 60 generations: the
     population ends on the segment between the points, spread along it, both ends reached."""
-    before, after, best = st.convergence_run(seed)
+    before, after, best = cases.convergence_run(seed)
     print('seed %d: distance %.6f -> %.6f, gap %.6f -> %.6f, ends %.6f' % (seed, before[0], after[0], before[1], after[1],
                                                                             after[2]))
     assert before[0] > 0.5

@@ -1,4 +1,4 @@
-"""Writes profiles/nsga2_statement.txt: what the numpy statement of smart_nsga2_step_hip (tests/nsga2_statement.py) reaches on
+"""Writes profiles/nsga2_statement.txt: what the numpy statement of smart_nsga2_step_hip (oracle/analyses/nsga2.py) reaches on
 the two-point problem over six seeds, and the thresholds tests/test_nsga2_host.py takes from it (the worst seed times two).
 No device needed.  `python tools/profile_nsga2_statement.py`."""
 import os
@@ -8,12 +8,12 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, 'tests')]
 
 import numpy as np                      # noqa: E402
-import nsga2_statement as st            # noqa: E402
+import cases_nsga2 as st                # noqa: E402
 
 
 def main():
     c = st.CONVERGENCE
-    lines = ['NSGA-II, the numpy statement (tests/nsga2_statement.py) on the two-point problem: two objectives, the negated',
+    lines = ['NSGA-II, the numpy statement (oracle/analyses/nsga2.py) on the two-point problem: two objectives, the negated',
              'squared distances to two points of the unit box; the Pareto set is the segment between them.',
              'd = %d, N = %d, %d generations, f = 0.5, CR = 0.9, b* = 1e-6, Philox draws, uniform initial population of the seed.'
              % (c['d'], c['N'], c['generations']),
