@@ -23,7 +23,7 @@ sys.path.insert(0, os.path.dirname(HERE))
 
 import smartpy_amd                                   # noqa: E402
 from smartpy_amd import distributed                  # noqa: E402
-from smartpy_amd.montecarlo import LHS, GLUE, Best, Sobol, NSGA2   # noqa: E402
+from smartpy_amd.montecarlo import LHS, GLUE, Best, Sobol, NSGA2, ParticleFilter   # noqa: E402
 
 EXTRA = {'aar': 1200, 'r-o_ratio': 0.45, 'r-o_split': (0.10, 0.15, 0.15, 0.30, 0.30)}
 
@@ -111,7 +111,18 @@ def main():
     nsga = NSGA2('Catchment', root, 'csv', 'csv', objectives=['NSE', 'PBias'], population=256, generations=30, seed=0)
     nsga.model.extra = EXTRA
     nsga.run(write=True)
+    # the STATES consistent with the flows up to the end of the record -- the start of a forecast: 256 particles from the
+    # final population, a launch per window of seven report steps from the particles' own states and one step call after it
+    # (weigh by the window's observations, resample where the effective sample size has fallen below half, perturb the states)
+    pf = ParticleFilter('Catchment', root, 'csv', 'csv', particles=256, assimilate_every=7, sigma=(0.1, 0.1), sampling=nsga,
+                        seed=0)
+    pf.model.extra = EXTRA
+    pf.run(write=True, verify=True)
     if rank == 0:
+        print('particle filter: %d windows, %d resampled, smallest effective sample size %.1f of %d, log-evidence %.1f; the '
+              'one-window-ahead forecast has a mean CRPS of %.4g -> %s'
+              % (len(pf.ess), pf.resampled.sum(), pf.ess.min(), pf.particles, pf.log_evidence,
+                 np.nanmean(pf.verification[0]), pf.file))
         front = nsga.obj_fns[nsga.front_index]
         print('NSGA-II: %d rows on the front after %d generations: NSE %.3f .. %.3f against PBias %.2f .. %.2f %% -> %s'
               % (len(nsga.front_index), nsga.generations, front[:, 0].min(), front[:, 0].max(), front[:, 5].min(),

@@ -975,6 +975,106 @@ int smart_error_model_draw_hip(int64_t n_samples, int64_t n_reports, int64_t n_r
                                double *out, int64_t out_ld, void *stream);
 
 /*
+ * One assimilation step of a bootstrap particle filter (Gordon et al. 1993; systematic resampling: Kitagawa 1996) AROUND the
+ * ensemble launch that ran N particles over window k of the report steps: the particles are weighed by the window's
+ * observations, the weights are turned into integers, and where the effective sample size falls below tau N the particles
+ * are resampled and moved.  1 <= N = n_particles <= SMART_PARTICLE_MAX_PARTICLES = 2^19, d = n_dims <=
+ * SMART_PARTICLE_MAX_DIMS varying parameters, k = step.  Four small kernels on `stream`; nothing is read back, nothing is
+ * allocated (the workspace is the caller's), no kernel waits on another workgroup, no floating-point atomics: the same call
+ * gives the same bits on every launch.  Which half of its double-buffered arrays is current is the caller's to keep: the
+ * *_in arrays are read, the *_out arrays written, and they must not overlap (a parent's row is read while a child's is
+ * written).
+ *
+ * A particle i has a row rows_in[i][0 .. ld) of the launch matrix (the d columns `columns` vary inside [lo, hi]; the others
+ * are the caller's in both halves), SMART_PARTICLE_STATES = 12 states states_in[i][0 .. 12) (SmartEnsemble.initial of the
+ * next window; columns 7 .. 18 of final_vars of the last) and a log-weight logw_in[i].
+ *
+ * WEIGH (phase SMART_PARTICLE_WEIGH).  With sim[t][i] = sim[t * ld_sim + i] the window's discharge where the launch left it,
+ * t < Rw = n_reports, and obs[t] (NaN: missing), over the observed t in ascending order, each operation rounded once:
+ *     sigma_t = sigma0 + sigma1 |obs_t|;   r = (sim_ti - obs_t) / sigma_t;   s = s + r r      from s = 0
+ *     l_i = -0.5 s;   logw'_i = logw_i + l_i,  or -inf where sim_ti is not finite at an observed t
+ * (what sim holds at a step that is not observed is never looked at).  logw' is written to logw_out.
+ * QUANTISE.  m' = the largest finite logw'; q_i = rint(2^22 exp(logw'_i - m')) as an integer, 0 where logw'_i is not finite
+ * (exp is the one operation here that is not correctly rounded: its last bit moves 2^22 e by far less than 1).  No finite
+ * logw' at all: the flag SMART_PARTICLE_FLAG_DEGENERATE, q_i = 2^22 for every particle, the particles are kept and logw_out
+ * = 0.  No observed t in the window: the flag SMART_PARTICLE_FLAG_NO_OBS; logw' = logw bit for bit and nothing is resampled.
+ * The same integers q0_i are made of logw (maximum m, sum Q0; all 0 where no logw is finite).  From here on everything is
+ * integers, so no order of summation can matter: Q = sum q_i <= 2^41, S2 = sum q_i^2 <= 2^63 (unsigned), C_i = the
+ * inclusive prefix sums of q.  q[N] (int64) is an output: as doubles, the weights of the analysis.
+ * With q_in (int64 [N], each in 0 .. 2^22) the window is not weighed: q = q_in, logw' = logw_in, DEGENERATE iff Q = 0 (q
+ * stays 0), and the evidence and the two maxima are NaN.  sim and obs are not read.
+ * DECIDE.  ess = fl(fl(double(Q) double(Q)) / double(S2)); resampled iff no flag is set and ess < fl(tau double(N)).
+ * RESAMPLE (phase SMART_PARTICLE_RESAMPLE), systematic.  With u = u53(w0, w1) of the Philox4x32-10 words of the counter
+ * (2^32 - 1, k, 0, 0) under the key (seed mod 2^32, seed div 2^32) -- u53 as for smart_demcz_step_hip --
+ *     rho = min(offset >= 0 ? offset : floor(fl(u double(Q))), Q - 1);    a_j = #{i : N C_i <= j Q + rho}     (parents[j])
+ * in unsigned 64-bit integers (every product stays below 2^60).  A particle with q = 0 has no child, particle i has
+ * floor(N q_i / Q) or that plus one.  Without resampling a_j = j.  counts[SMART_PARTICLE_DISTINCT] = the number of
+ * particles with a child.
+ * MOVE (phase SMART_PARTICLE_MOVE) of child j from its parent p = a_j, resampled or not.
+ *   Parameters: the jitter and the box of the generational samplers (smart_demcz_step_hip, with a difference of weight 0).
+ *     For a dimension c whose scale_c is not 0, with (w0, w1, w2, w3) the words of the counter (j, k, 2 + c, 0):
+ *         eps = scale_c (2 u53(w1, w2) - 1);   t = 0 + eps;   y = theta_p,c + t
+ *         if y < lo_c: y = 2 lo_c - y;   if y > hi_c: y = 2 hi_c - y
+ *     and where a y is still outside its [lo_c, hi_c] (or NaN) the child takes the parent's whole row.  A dimension whose
+ *     scale_c is 0 is copied.  rows_out[j][columns[c]] is written for every c < d; the other columns are not touched.
+ *   States, s < 12, with the words of the counter (j, k, 18 + s div 2, 0), (w0, w1) for an even s and (w2, w3) for an odd:
+ *         f = 2 u53(.,.);  f = f - 1;  f = noise_s f;  f = 1 + f;  x' = x_p,s f               0 <= noise_s < 1
+ *     then the six soil layers s = SMART_PARTICLE_FIRST_LAYER .. + 5 are held below their capacity (above it the model
+ *     overflows): cap = ((Z' / 6) / 1e3) area_m2, x' = x' > cap ? cap : x', Z' the child's value of column z_column of the
+ *     launch matrix (the parent's where that column does not vary).
+ *   logw_out[j] = 0 where the step resampled or is DEGENERATE, else logw'_j.
+ * THE HEADER, on the device: stats[4] (doubles) = ess, the evidence increment log(sum w_prev e^l) = (m' + ln(Q / 2^22)) -
+ * (m + ln(Q0 / 2^22)), m', m; counts[8] (int64) = resampled (0 / 1), Q, distinct parents, flags, rho, S2, Q0, 0.  The
+ * RESAMPLE and MOVE phases read it there.
+ * PHASES.  `phases` is a mask; a call with all three is the step.  A call without WEIGH uses what an earlier call with it
+ * left in the workspace, q, stats and counts (and is given the same q_in); MOVE without RESAMPLE reads parents[].
+ * lo, hi, scale (d values), noise (12) and columns (d) are HOST arrays (they travel as kernel arguments).
+ *
+ * Errors (all found before the device is touched; the first offending argument wins): SMART_E_NULL logw_in, logw_out, q,
+ * parents, stats, counts or workspace missing; SMART_E_SIZE n_particles outside 1 .. 2^19, n_dims outside 1 .. 16, step
+ * outside 0 .. 2^32 - 1, SMART_E_MODE phases outside 1 .. 7; weigh phase: SMART_E_SIZE tau not finite or < 0, offset >=
+ * 2^41, and without q_in SMART_E_NULL sim or obs missing, SMART_E_SIZE n_reports outside 1 .. 2^31 - 1, ld_sim < n_particles,
+ * sigma0 not finite or <= 0, sigma1 not finite or < 0; move phase: SMART_E_NULL rows_in, rows_out, states_in, states_out,
+ * lo, hi, scale, noise or columns missing, SMART_E_SIZE ld < n_dims, a column outside 0 .. ld - 1 or named twice, bounds that
+ * are not finite or lo > hi, z_column outside 0 .. ld - 1, a scale that is not finite or < 0, a noise outside [0, 1), area_m2
+ * not finite or <= 0; SMART_E_SIZE a workspace of fewer than smart_particle_workspace_bytes bytes; then SMART_E_NO_DEVICE
+ * without a HIP device.
+ */
+#define SMART_PARTICLE_MAX_PARTICLES 524288
+#define SMART_PARTICLE_MAX_DIMS 16
+#define SMART_PARTICLE_STATES 12
+#define SMART_PARTICLE_FIRST_LAYER 5
+#define SMART_PARTICLE_WEIGH 1
+#define SMART_PARTICLE_RESAMPLE 2
+#define SMART_PARTICLE_MOVE 4
+#define SMART_PARTICLE_FLAG_DEGENERATE 1
+#define SMART_PARTICLE_FLAG_NO_OBS 2
+#define SMART_PARTICLE_ESS 0
+#define SMART_PARTICLE_EVIDENCE 1
+#define SMART_PARTICLE_MAX 2
+#define SMART_PARTICLE_MAX_PRIOR 3
+#define SMART_PARTICLE_RESAMPLED 0
+#define SMART_PARTICLE_Q 1
+#define SMART_PARTICLE_DISTINCT 2
+#define SMART_PARTICLE_FLAGS 3
+#define SMART_PARTICLE_OFFSET 4
+#define SMART_PARTICLE_S2 5
+#define SMART_PARTICLE_Q_PRIOR 6
+int smart_particle_step_hip(int64_t n_particles, int32_t n_dims, uint64_t seed, int64_t step, int32_t phases,
+                            int64_t n_reports, const double *sim, int64_t ld_sim, const double *obs, double sigma0,
+                            double sigma1, double tau, const int64_t *q_in, int64_t offset, const double *rows_in,
+                            double *rows_out, int64_t ld, const int32_t *columns, int32_t z_column, double area_m2,
+                            const double *lo, const double *hi, const double *scale, const double *noise,
+                            const double *states_in, double *states_out, const double *logw_in, double *logw_out,
+                            int64_t *q, int32_t *parents, double *stats, int64_t *counts, void *workspace,
+                            int64_t workspace_bytes, void *stream);
+
+/* The workspace smart_particle_step_hip asks for, in bytes: six values per block of 256 particles for 2048 blocks, and the
+ * 32-bit prefix sums of the integers inside a block (96 KiB + 4 N rounded up to blocks).  SMART_E_SIZE (negative) for an
+ * n_particles the entry refuses.  Needs no device. */
+int64_t smart_particle_workspace_bytes(int64_t n_particles);
+
+/*
  * Sampling database, CSV flavour -- the rows MonteCarlo.save writes one by one (montecarlo.py:211-231): every value
  * cast to float32 and printed '%.6e', comma separated, one '\n'-terminated line per sample.  HOST pointers, no
  * device involved.  Appends n_rows lines of n_cols values (row-major float32 table: objective functions, parameters,

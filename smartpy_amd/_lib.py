@@ -45,6 +45,11 @@ DEMCZ_MAX_DIMS, DEMCZ_MAX_CARRY = 16, 16
 DEMCZ_SCORES = {'logp': 0, 'rmse': 1, 'rmse_sigma': 2}          # SMART_DEMCZ_SCORE_*
 NSGA2_MAX_ROWS, NSGA2_MAX_DIMS, NSGA2_MAX_OBJECTIVES, NSGA2_MAX_CARRY = 8192, 16, 4, 16
 NSGA2_RANK_BEYOND, NSGA2_RANK_OUT = 2 ** 31 - 2, 2 ** 31 - 1     # SMART_NSGA2_RANK_*
+PARTICLE_MAX_PARTICLES, PARTICLE_MAX_DIMS, PARTICLE_STATES, PARTICLE_FIRST_LAYER = 2 ** 19, 16, 12, 5
+PARTICLE_WEIGH, PARTICLE_RESAMPLE, PARTICLE_MOVE = 1, 2, 4        # SMART_PARTICLE_*: the phase mask
+PARTICLE_FLAG_DEGENERATE, PARTICLE_FLAG_NO_OBS = 1, 2
+PARTICLE_STATS = ['ESS', 'EVIDENCE', 'MAX', 'MAX_PRIOR']        # SMART_PARTICLE_*, the doubles of the header in order
+PARTICLE_COUNTS = ['RESAMPLED', 'Q', 'DISTINCT', 'FLAGS', 'OFFSET', 'S2', 'Q_PRIOR']     # ... and its integers
 ERROR_MODEL_SEGMENT = 64                                       # SMART_ERROR_MODEL_SEGMENT
 ERROR_MODEL_ROWS = ['LOGLIK', 'SSQ', 'LOGSIG']                  # SMART_ERROR_MODEL_*, in row order
 
@@ -143,6 +148,12 @@ SYMBOLS = {
                                             ctypes.c_int64, ctypes.c_int32, _dp, _dp, _dp, ctypes.c_double,
                                             ctypes.c_int64, _dp, ctypes.c_int64, _dp, _dp]),
     'smart_nsga2_workspace_bytes': (ctypes.c_int64, [ctypes.c_int64, ctypes.c_int32]),
+    'smart_particle_step_hip': (ctypes.c_int, [ctypes.c_int64, ctypes.c_int32, ctypes.c_uint64, ctypes.c_int64, ctypes.c_int32,
+                                               ctypes.c_int64, _dp, ctypes.c_int64, _dp, ctypes.c_double, ctypes.c_double,
+                                               ctypes.c_double, _dp, ctypes.c_int64, _dp, _dp, ctypes.c_int64, _dp,
+                                               ctypes.c_int32, ctypes.c_double, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp,
+                                               _dp, _dp, _dp, _dp, _dp, ctypes.c_int64, _dp]),
+    'smart_particle_workspace_bytes': (ctypes.c_int64, [ctypes.c_int64]),
     'smart_error_model_loglik_hip': (ctypes.c_int, [ctypes.c_int64, ctypes.c_int64, _dp, ctypes.c_int64, _dp, _dp,
                                                     ctypes.c_int64, _dp, _dp]),
     'smart_error_model_draw_hip': (ctypes.c_int, [ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, _dp, ctypes.c_int64, _dp,

@@ -66,6 +66,10 @@ UNITS = {
     # variation): every operation of the distance and of the offspring rounded once -- the numpy statement of the tests is
     # held to it bit for bit; NaNs honoured -- a NaN key loses every compare, which is how a row that takes no part is kept out
     'smart_nsga2.hip': ['-ffp-contract=off'],
+    # the step of the particle filter (window likelihood, integer weights, systematic resampling, jitter and state noise):
+    # every operation of the weights and of the move rounded once -- the numpy statement of the tests is held to it bit for
+    # bit; NaNs honoured -- a missing observation and a particle that is not finite are found by their compares
+    'smart_particle.hip': ['-ffp-contract=off'],
     # the residual error model (the AR(1) log-likelihood of a stored matrix, error realisations on top of it): every
     # operation rounded once, as the numpy statement of the tests rounds it; NaNs honoured -- a NaN at a step without an
     # observation is selected away, one at an observed step makes the sample invalid

@@ -877,6 +877,81 @@ int64_t smart_nsga2_workspace_bytes(int64_t n_rows, int32_t n_objectives)
     return c.ok() ? nsga2_workspace_bytes((long)n_rows) : c.rc;
 }
 
+// (the step of the particle filter, smart_particle.hip: the size the entry shares with its workspace query)
+static void particle_sizes(Check &c, int64_t n_particles)
+{
+    c.in_range("n_particles", n_particles, 1, SMART_PARTICLE_MAX_PARTICLES);
+}
+
+int smart_particle_step_hip(int64_t n_particles, int32_t n_dims, uint64_t seed, int64_t step, int32_t phases,
+                            int64_t n_reports, const double *sim, int64_t ld_sim, const double *obs, double sigma0,
+                            double sigma1, double tau, const int64_t *q_in, int64_t offset, const double *rows_in,
+                            double *rows_out, int64_t ld, const int32_t *columns, int32_t z_column, double area_m2,
+                            const double *lo, const double *hi, const double *scale, const double *noise,
+                            const double *states_in, double *states_out, const double *logw_in, double *logw_out,
+                            int64_t *q, int32_t *parents, double *stats, int64_t *counts, void *workspace,
+                            int64_t workspace_bytes, void *stream)
+{
+    Check c("smart_particle_step_hip");
+    c.required({NAMED(logw_in), NAMED(logw_out), NAMED(q), NAMED(parents), NAMED(stats), NAMED(counts), NAMED(workspace)});
+    particle_sizes(c, n_particles);
+    c.in_range("n_dims", n_dims, 1, SMART_PARTICLE_MAX_DIMS);
+    c.in_range("step", step, 0, kTwo32 - 1);
+    if (phases < 1 || phases > (SMART_PARTICLE_WEIGH | SMART_PARTICLE_RESAMPLE | SMART_PARTICLE_MOVE))
+        c.refuse(SMART_E_MODE, "phases '%d' unknown.", (int)phases);
+    if (phases & SMART_PARTICLE_WEIGH) { // ---- the weigh phase
+        if (!(tau >= 0.0 && std::isfinite(tau)))
+            c.refuse(SMART_E_SIZE, "tau %g must be finite and >= 0", tau);
+        if (offset >= (1ll << 41))
+            c.refuse(SMART_E_SIZE, "offset %lld must be below 2^41 (negative: drawn)", (long long)offset);
+        if (!q_in) {
+            c.wants("the weigh phase without q_in needs", {NAMED(sim), NAMED(obs)});
+            c.in_range("n_reports", n_reports, 1, kInt32Max);
+            c.ld_holds("ld_sim", ld_sim, n_particles);
+            if (!(sigma0 > 0.0 && std::isfinite(sigma0)))
+                c.refuse(SMART_E_SIZE, "sigma0 %g must be finite and > 0", sigma0);
+            if (!(sigma1 >= 0.0 && std::isfinite(sigma1)))
+                c.refuse(SMART_E_SIZE, "sigma1 %g must be finite and >= 0", sigma1);
+        }
+    }
+    if (phases & SMART_PARTICLE_MOVE) { // ---- the move phase
+        c.wants("the move phase needs", {NAMED(rows_in), NAMED(rows_out), NAMED(states_in), NAMED(states_out), NAMED(lo),
+                                         NAMED(hi), NAMED(scale), NAMED(noise), NAMED(columns)});
+        c.box_holds(n_dims, (long long)ld, columns, lo, hi);
+        c.in_range("z_column", z_column, 0, (long long)ld - 1);
+        for (int j = 0; c.ok() && j < n_dims; ++j)
+            if (!(scale[j] >= 0.0 && std::isfinite(scale[j])))
+                c.refuse(SMART_E_SIZE, "scale[%d] %g must be finite and >= 0", j, scale[j]);
+        for (int k = 0; c.ok() && k < SMART_PARTICLE_STATES; ++k)
+            if (!(noise[k] >= 0.0 && noise[k] < 1.0))
+                c.refuse(SMART_E_SIZE, "noise[%d] %g must be in [0, 1)", k, noise[k]);
+        if (!(area_m2 > 0.0 && std::isfinite(area_m2)))
+            c.refuse(SMART_E_SIZE, "area_m2 %g must be finite and > 0", area_m2);
+    }
+    if (c.ok())
+        c.workspace_fits(/*for_objfn=*/false, workspace, workspace_bytes, particle_workspace_bytes((long)n_particles));
+    if (int rc = c.ready())
+        return rc;
+    ParticleCall call{};
+    call.n_particles = (long)n_particles, call.n_dims = n_dims, call.seed = seed, call.step = (long)step, call.phases = phases;
+    call.n_reports = (long)n_reports, call.sim = sim, call.ld_sim = (long)ld_sim, call.obs = obs;
+    call.sigma0 = sigma0, call.sigma1 = sigma1, call.tau = tau, call.q_in = q_in, call.offset = (long long)offset;
+    call.rows_in = rows_in, call.rows_out = rows_out, call.ld = (long)ld, call.columns = columns, call.z_column = z_column;
+    call.area_m2 = area_m2, call.lo = lo, call.hi = hi, call.scale = scale, call.noise = noise;
+    call.states_in = states_in, call.states_out = states_out, call.logw_in = logw_in, call.logw_out = logw_out;
+    call.q = q, call.parents = parents, call.stats = stats, call.counts = counts, call.workspace = workspace;
+    if (int rc = launch_particle(call, (hipStream_t)stream))
+        return rc;
+    return launched();
+}
+
+int64_t smart_particle_workspace_bytes(int64_t n_particles)
+{
+    Check c(nullptr);
+    particle_sizes(c, n_particles);
+    return c.ok() ? particle_workspace_bytes((long)n_particles) : c.rc;
+}
+
 // ---- the residual error model (smart_error_model.hip): the rules the two entries share, in the entries' order
 static void error_model_sizes(Check &c, std::initializer_list<Count> counts, int64_t n_samples, int64_t ld, int64_t err_ld)
 {

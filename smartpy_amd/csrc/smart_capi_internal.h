@@ -220,6 +220,41 @@ struct Nsga2Call {
 long nsga2_workspace_bytes(long N);
 int launch_nsga2(const Nsga2Call &c, hipStream_t s); // SMART_OK, or the code of hip_fail (the flag of a peel batch is read)
 
+// ---- smart_particle.hip: the arguments of smart_particle_step_hip as the entry has checked them
+struct ParticleCall {
+    long n_particles;
+    int n_dims;
+    unsigned long long seed;
+    long step;
+    int phases;
+    long n_reports;
+    const double *sim;
+    long ld_sim;
+    const double *obs;
+    double sigma0, sigma1, tau;
+    const int64_t *q_in;
+    long long offset;
+    const double *rows_in;
+    double *rows_out;
+    long ld;
+    const int *columns; // host, n_dims
+    int z_column;
+    double area_m2;
+    const double *lo, *hi, *scale; // host, n_dims each
+    const double *noise;           // host, SMART_PARTICLE_STATES
+    const double *states_in;
+    double *states_out;
+    const double *logw_in;
+    double *logw_out;
+    int64_t *q;
+    int *parents;
+    double *stats;
+    int64_t *counts;
+    void *workspace;
+};
+long particle_workspace_bytes(long N);
+int launch_particle(const ParticleCall &c, hipStream_t s); // SMART_OK, or the code of hip_fail
+
 // ---- smart_error_model.hip
 void launch_error_model_loglik(long N, long R, const double *sim, long ld, const double *obs, const double *err, long err_ld,
                                double *out, hipStream_t s);

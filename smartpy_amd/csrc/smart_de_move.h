@@ -1,10 +1,11 @@
 // smart_de_move.h -- the differential-evolution move the generational samplers share (smart_demcz.hip: smart_demcz_propose,
-// smart_nsga2.hip: smart_nsga2_vary): the box of a call and the key of its draws as kernel arguments, the subspace
+// smart_nsga2.hip: smart_nsga2_vary; smart_particle.hip: smart_particle_resample, which moves a child from its parent's own
+// row with weight 0 and every jittered dimension marked as moved): the box of a call and the key of its draws as kernel arguments, the subspace
 // crossover, the move of one row with its one reflection at the box, and the row of the launch matrix.  What differs stays
 // in the two kernels: the base row, the two partner rows, the weight of their difference and where the fallback dimension
 // is drawn.  The draw layout (include/smart_amd.h) is ABI: counter (row, generation, 2 + j, 0) belongs to dimension j, word 0
 // against the crossover threshold, words 1 and 2 the jitter.
-// ARITHMETIC.  Both units are compiled with -ffp-contract=off and this header adds no pragma of its own: every operation
+// ARITHMETIC.  The three units are compiled with -ffp-contract=off and this header adds no pragma of its own: every operation
 // below is rounded once, in the order written, and each is correctly rounded.
 #pragma once
 
@@ -13,7 +14,8 @@
 
 namespace smart {
 
-static_assert(SMART_DEMCZ_MAX_DIMS == 16 && SMART_NSGA2_MAX_DIMS == 16, "one DeBox for both samplers");
+static_assert(SMART_DEMCZ_MAX_DIMS == 16 && SMART_NSGA2_MAX_DIMS == 16 && SMART_PARTICLE_MAX_DIMS == 16,
+              "one DeBox for every unit that moves rows");
 constexpr int kDeMaxDims = 16;
 
 // the box of a call, by value inside the kernel arguments: slots from n_dims on hold 0
